@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Headline benchmark of the VBQ hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--workload NAME] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (histograms, length table, models, and the rank indices on a
+fixed sample of rows) as DIR/<name>.npy, with DIR/manifest.json; the inputs are the same on every run with the same arguments.
 
 One "step" = one whole entropy-model build of the reference (quantizer.py:82-150) over one batch, as
 vbq_amd.pipeline.EntropyModelBuild runs it: [layout change] -> pass 1 (K1t: the 32-lambda solve with raw lengths as a
@@ -140,11 +143,28 @@ def make_inputs_with_table(rows, C, seed):
     return mu, sigma, gaussian_tables(scale)
 
 
-def empirical_tables(x_dev, rows_local, C, layout):
-    """ONE code book for all ranks: sqrt(mean x^2) per channel over every rank's rows (K3 moments on the device, the f64
-    sums all-reduced -- ipynb:374 computed globally), then the Gaussian table on the host."""
+def host_moments(x_h, dev):
+    """f64 [C, 2] = (sum x, sum x^2) per channel of a host array [rows, C], summed in a fixed order (NumPy's pairwise sums over
+    each channel's rows, block after block) and put on `dev`: the same bits on every run.  K3 adds its partial sums with
+    atomics, in whatever order the workgroups finish -- the last bits of the moments, and so possibly of the code book, can
+    change from run to run."""
+    import torch
+    rows, C = x_h.shape
+    m = np.zeros((C, 2))
+    block = max(1, (1 << 22) // C)
+    for r in range(0, rows, block):
+        b = np.ascontiguousarray(x_h[r:r + block].T, dtype=np.float64)      # [C, rows of the block]
+        m[:, 0] += b.sum(axis=1)
+        m[:, 1] += np.square(b).sum(axis=1)
+    return torch.from_numpy(m).to(dev)
+
+
+def empirical_tables(x_dev, rows_local, C, layout, x_host=None):
+    """ONE code book for all ranks: sqrt(mean x^2) per channel over every rank's rows (K3 moments on the device, or the
+    fixed-order sums of `x_host` [rows, C] when given; the f64 sums all-reduced -- ipynb:374 computed globally),
+    then the Gaussian table on the host.  bench.py passes `x_host`, so that the same arguments give the same inputs."""
     from vbq_amd import dist as vd, ops
-    m = ops.moments(x_dev, layout=layout)                      # f64 [C, 2] = (sum x, sum x^2)
+    m = ops.moments(x_dev, layout=layout) if x_host is None else host_moments(x_host, x_dev.device)
     return gaussian_tables(vd.global_empirical_std(m, rows_local))
 
 
@@ -391,6 +411,66 @@ def emit(full, path):
     print(json.dumps(headline(full, side)), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs writes at most this much
+DUMP_SEED = 20201                 # the samples of --dump-outputs: the same positions on every run
+DUMP_CHANNELS = 16                # [L, C, T] tables: every lambda, this many channels
+DUMP_INDEX_ELEMENTS = 1 << 22     # index planes: every lambda and channel, as many rows as fit this many elements
+
+
+def dump_sample(n, k, salt):
+    """Sorted positions of a fixed, seeded sample of k out of n (all n when k >= n)."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, k, replace=False))
+
+
+def _index_sample(idx, axis, rows):
+    """uint16 device index planes -> f32 host array of the sampled positions along `axis` (the exact values)."""
+    import torch
+    pos = torch.from_numpy(dump_sample(rows, max(1, DUMP_INDEX_ELEMENTS * rows // idx.numel()), 2)).to(idx.device)
+    return idx.view(torch.int16).index_select(axis, pos).cpu().numpy().view(np.uint16).astype(np.float32), len(pos)
+
+
+def build_outputs(build):
+    """What EntropyModelBuild.run leaves its caller after a step: both histograms, the length table and both model tables in
+    full, except the [L, C, T] ones on DUMP_CHANNELS sampled channels, and the rank indices [L, C, rows] on sampled rows."""
+    import torch
+    L, C, rows, T = build.L, build.C, build.rows, build.T
+    ch = dump_sample(C, DUMP_CHANNELS, 1)
+    sel = torch.from_numpy(ch).to(build.dev)
+    idx, n = _index_sample(build.idx, 2, rows)
+    arrays = {"indices": idx,
+              "rank_counts": build.counts.index_select(1, sel).cpu().numpy().astype(np.float64),
+              "level_counts": build.level_counts.cpu().numpy().astype(np.float64),
+              "level_len": build.level_len.cpu().numpy(),
+              "raw_models": build.raw_models.cpu().numpy()}
+    about = {"indices": f"rank indices [L, C, rows] = [{L}, {C}, {rows}] on {n} sampled rows",
+             "rank_counts": f"rank histogram [L, C, T] = [{L}, {C}, {T}] on channels {ch.tolist()}",
+             "level_counts": "bit-length histogram [L, C, N+1]", "level_len": "code-length table [L, C, N+1]",
+             "raw_models": "raw-length models [L, C, N+1]"}
+    if build.models is not None:
+        arrays["models"] = build.models.index_select(1, sel).cpu().numpy()
+        about["models"] = f"code-length models [L, C, T] = [{L}, {C}, {T}] on channels {ch.tolist()}"
+    return arrays, about
+
+
+def write_dump(out_dir, arrays, about, context):
+    """--dump-outputs: every array as <out_dir>/<name>.npy (float32 or float64) and manifest.json saying what each one is."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    manifest = dict(context, samples=f"fixed: numpy.random.default_rng([{DUMP_SEED}, salt]).choice(n, k, replace=False), "
+                                     "sorted (salt 1: channels, 2: rows)",
+                    arrays={k: {"shape": list(a.shape), "dtype": str(a.dtype), "what": about[k]} for k, a in arrays.items()})
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    print(f"bench.py: {len(arrays)} output arrays ({total / 1e6:.1f} MB) written to {out_dir}", file=sys.stderr)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` started by hand (no WORLD_SIZE in the environment): this process -- which has made no GPU
     call and has not imported torch -- starts the N ranks as child processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
@@ -464,8 +544,9 @@ def rd_curve_oracle(mu_w, sg_w, idx_w, tab_h, models_h, lambdas):
     return {"distortion": d, "rate": r, "lagrangian": d + np.asarray(lambdas) * r}
 
 
-def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detailed, lambdas=None, strong=False):
-    """Time `steps` alternations of one workload; returns the result dict (rank 0) or None."""
+def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detailed, lambdas=None, strong=False, dump=False):
+    """Time `steps` alternations of one workload; returns the result dict (rank 0) or None.  dump: write what the last timed
+    step computed to args.dump_outputs (rank 0)."""
     from vbq_amd import dist as vd, entropy, ops
     from vbq_amd.pipeline import EntropyModelBuild
     lambdas = LAMBDAS if lambdas is None else lambdas
@@ -484,11 +565,11 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
         mu_in, sg_in = torch.from_numpy(mu_h).to(dev), torch.from_numpy(sg_h).to(dev)
         mu = torch.empty((C, rows), dtype=torch.float32, device=dev)
         sg = torch.empty((C, rows), dtype=torch.float32, device=dev)
-        tab_h = empirical_tables(mu_in, rows, C, "bc")
+        tab_h = empirical_tables(mu_in, rows, C, "bc", x_host=mu_h)
     else:
         mu_in = sg_in = None
         mu, sg = torch.from_numpy(mu_h.reshape(1, rows)).to(dev), torch.from_numpy(sg_h.reshape(1, rows)).to(dev)
-        tab_h = empirical_tables(mu.reshape(rows), rows, 1, "bc")
+        tab_h = empirical_tables(mu.reshape(rows), rows, 1, "bc", x_host=mu_h)
     tab = torch.from_numpy(tab_h).to(dev)
     build = EntropyModelBuild(rows, C, lambdas, tab, N=N_BITS, add_n_smoothing=1, global_rows=global_rows,
                               distributed=world > 1, level_group=args.level_group, n_chunks=args.chunks)
@@ -574,6 +655,11 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
         except Exception as e:                     # the eager measurement above stands
             torch.cuda.synchronize()
             launch += f" (HIP graph capture failed: {type(e).__name__})"
+    if dump and rank == 0:                         # the buffers still hold the last timed step's results
+        torch.cuda.synchronize()
+        write_dump(args.dump_outputs, *build_outputs(build),
+                   {"workload": name, "rank": rank, "n_gpus": world, "scaling": "strong" if strong else "weak", "steps": steps,
+                    "warmup": warmup, "launch": launch, "step": "the last timed step"})
     k1_ms, k1_n = timers.total_ms("k1") / steps, timers.launches("k1") // steps
     k1h_ms = timers.total_ms("k1h") / steps
     k2_ms = timers.total_ms("k2") / steps
@@ -814,6 +900,9 @@ def main():
     ap.add_argument("--full-record", default=os.environ.get("VBQ_BENCH_FULL_RECORD", os.path.join(ROOT, "bench_full.json")),
                     help="where the full record goes (R-D curve arrays, per-workload and per-rank reports); stdout carries one "
                          "compact line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32 / f64; index planes and "
+                         "[L, C, T] tables on a fixed, seeded sample; at most 64 MB) and DIR/manifest.json")
     args = ap.parse_args()
     strong = args.scaling == "strong"
     if args.workload is None:
@@ -854,12 +943,12 @@ def main():
     args.cpu_group = dist.new_group(backend="gloo", timeout=__import__("datetime").timedelta(minutes=30)) if world > 1 else None
 
     if args.notebook:
-        out = run_notebook(args, torch, dev, cpu=not args.no_cpu_baseline)
+        out = run_notebook(args, torch, dev, cpu=not args.no_cpu_baseline, dump=bool(args.dump_outputs))
         emit(out, args.full_record)
         return
 
     res = run_workload(args.workload, args, torch, dist, dev, rank, world, args.steps, args.warmup,
-                       detailed=(world == 1 or not args.no_parity), strong=strong)
+                       detailed=(world == 1 or not args.no_parity), strong=strong, dump=bool(args.dump_outputs))
     out = None
     if rank == 0:
         host = res.pop("_host", None)
@@ -973,7 +1062,7 @@ def run_call_patterns(torch, dev, steps=10, warmup=3):
     E = rows * C
     mu_h, sg_h = make_inputs(rows, C, seed=1000)
     mu_bc, sg_bc = torch.from_numpy(mu_h).to(dev), torch.from_numpy(sg_h).to(dev)
-    tab_h = empirical_tables(mu_bc, rows, C, "bc")
+    tab_h = empirical_tables(mu_bc, rows, C, "bc", x_host=mu_h)
     tab = torch.from_numpy(tab_h).to(dev)
     mu, sg = ops.transpose(mu_bc), ops.transpose(sg_bc)
     th = CO.max_threads()
@@ -1461,8 +1550,9 @@ def run_api_methods(torch, dev, mu_h, sg_h, mu_bc, sg_bc, tab_h, steps=10, warmu
     return out
 
 
-def run_notebook(args, torch, dev, workload=None, steps=None, warmup=None, cpu=True):
-    """The C = 1 workloads in the notebook's own arithmetic: one K1n launch + one K2 launch per step."""
+def run_notebook(args, torch, dev, workload=None, steps=None, warmup=None, cpu=True, dump=False):
+    """The C = 1 workloads in the notebook's own arithmetic: one K1n launch + one K2 launch per step.  dump: write what the
+    last timed step computed to args.dump_outputs."""
     from vbq_amd import ops, embeddings as Emb
     name = workload or (args.workload if WORKLOADS[args.workload][1] == 1 else "embeddings_1e7")
     steps = steps or args.steps
@@ -1496,6 +1586,12 @@ def run_notebook(args, torch, dev, workload=None, steps=None, warmup=None, cpu=T
         step(i)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump:
+        ix, n = _index_sample(idx, 1, rows)
+        write_dump(args.dump_outputs, {"indices": ix, "rank_counts": counts.cpu().numpy().astype(np.float64)},
+                   {"indices": f"rank indices [L, rows] = [{L}, {rows}] on {n} sampled rows",
+                    "rank_counts": f"rank histogram [L, 1, T] = [{L}, 1, {T}]"},
+                   {"workload": name, "notebook": True, "n_gpus": 1, "steps": steps, "warmup": warmup, "step": "the last timed step"})
     k1_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     alg = rows * (8 + 2 * L)
     out = {"metric": "quantized latents/sec (32-beta sweep, notebook arithmetic)", "value": rows * L * steps / dt, "unit": "latents/s",

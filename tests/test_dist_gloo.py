@@ -34,6 +34,8 @@ def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
+    # the CPU path on every host: on a GPU host init_from_env would give rank r the device cuda:r, which a one-GPU host lacks
+    torch.cuda.is_available = lambda: False
     from vbq_amd import dist as vd
     r, w, dev = vd.init_from_env("gloo")
     assert (r, w) == (rank, world) and dev.type == "cpu"

@@ -172,6 +172,44 @@ def test_bench_inputs_and_rd_helpers():
     assert bench.sweep_name(bench.LAMBDAS).startswith("2**linspace(-8,7.5") and "post_process" in bench.sweep_name(bench.LAMBDAS_16)
 
 
+def test_bench_dump_outputs_and_fixed_moments(tmp_path):
+    """bench.py --dump-outputs on a stand-in build (CPU tensors of the headline's shapes): every array f32 / f64 with the exact
+    values at the same seeded positions on every call, 64 MB at most; and the code book's moments are the same bits on every
+    call and within 1e-15 of the exact sums."""
+    import json
+    import math
+    import types
+    import bench
+    L, C, rows, T = 32, 256, 36864, bench.T
+    g = torch.Generator().manual_seed(0)
+    b = types.SimpleNamespace(L=L, C=C, rows=rows, T=T, dev=torch.device("cpu"), models=torch.rand(L, C, T, generator=g),
+                              idx=torch.randint(0, T, (L, C, rows), generator=g, dtype=torch.int32).to(torch.uint16),
+                              counts=torch.randint(0, 1000, (L, C, T), generator=g, dtype=torch.int32),
+                              level_counts=torch.randint(0, 1 << 40, (L, C, N + 1), generator=g), level_len=torch.rand(L, C, N + 1, generator=g),
+                              raw_models=torch.rand(L, C, N + 1, generator=g))
+    arrays, about = bench.build_outputs(b)
+    again, _ = bench.build_outputs(b)
+    ch, r = bench.dump_sample(C, bench.DUMP_CHANNELS, 1), bench.dump_sample(rows, (1 << 22) // (L * C), 2)
+    assert len(ch) == 16 and len(r) == 512 and np.all(np.diff(r) > 0)
+    want = {"indices": b.idx.to(torch.int32).numpy()[:, :, r], "rank_counts": b.counts.numpy()[:, ch], "models": b.models.numpy()[:, ch],
+            "level_counts": b.level_counts.numpy(), "level_len": b.level_len.numpy(), "raw_models": b.raw_models.numpy()}
+    assert set(arrays) == set(want)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, want[k]) and np.array_equal(a, again[k]), k
+    out = tmp_path / "dump"
+    bench.write_dump(str(out), arrays, about, {"workload": "stand-in"})
+    assert sum(os.path.getsize(out / f"{k}.npy") for k in arrays) <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(np.load(out / "indices.npy"), arrays["indices"])
+    assert set(json.load(open(out / "manifest.json"))["arrays"]) == set(arrays)
+    with pytest.raises(SystemExit):                           # more than 64 MB is refused, not written
+        bench.write_dump(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)}, {"x": ""}, {})
+    mu, _ = bench.make_inputs(5000, 7, seed=1000)
+    m = bench.host_moments(mu, "cpu").numpy()
+    assert np.array_equal(m, bench.host_moments(mu.copy(), "cpu").numpy())
+    exact = np.array([math.fsum((mu[:, c].astype(np.float64) ** 2).tolist()) for c in range(7)])
+    assert np.all(np.abs(m[:, 1] - exact) <= 1e-15 * exact)
+
+
 def test_quantize_facade_table_cache_keys():
     """The facade's table cache (api._device_table): a NumPy table is recognised by a cheap key + a strided sample and then
     VERIFIED against what was uploaded (xxh3 digest, or np.array_equal with a kept copy when xxhash is missing) -- an ndarray has
