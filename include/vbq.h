@@ -497,6 +497,23 @@ int vbq_rans_encode_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int
 int vbq_rans_decode_u16(const uint16_t *d_words, const uint32_t *d_sizes, int64_t n_streams, int64_t n,
                         int32_t N, int32_t seg, const uint16_t *d_freq, uint16_t *d_idx, uint32_t *d_status,
                         void *stream);
+/* Packed payload of the byte-string container (vbq_amd/bitstream.py): the valid words of every segment, stream-major
+ * then segment-major, without the padding -- segment g = s * nseg + j occupies payload words [off[g], off[g] + size[g]),
+ * off = exclusive prefix sum of the sizes.  M = n_streams * nseg segments, nseg = ceil(n / seg), as above.
+ * vbq_rans_pack_u16: d_words / d_sizes as vbq_rans_encode_u16 wrote them -> d_payload u16, room for up to
+ * M * (seg + 2) words (the largest possible total); d_offsets int64 [M] receives off (it is also the scratch of the
+ * scan); *d_total (u64, device) the number of payload words.  Sizes above seg + 2 are clamped (memory safety only). */
+int vbq_rans_pack_u16(const uint16_t *d_words, const uint32_t *d_sizes, int64_t n_streams, int64_t n, int32_t seg,
+                      uint16_t *d_payload, int64_t *d_offsets, uint64_t *d_total, void *stream);
+/* vbq_rans_unpack_u16: the inverse, into the padded layout vbq_rans_decode_u16 reads.  The payload u16 [n_words] and the
+ * sizes u16 [M] (as a file stores them) are UNTRUSTED: no read leaves [0, n_words) and no write leaves d_words
+ * u16 [M][seg + 2] / d_sizes u32 [M].  d_offsets int64 [M] as above.  d_status (u32, device, may be NULL; OR-ed into, zero
+ * it first): bit 0 a size outside [2, seg + 2] (counted as 0), bit 4 sizes whose sum is not n_words.  A segment with a
+ * bad size or one that would end past n_words gets size 0 in d_sizes, so that the decoder rejects it as well; its words
+ * are not written.  The decoder only reads the first size[g] words of a segment: d_words need not be zeroed. */
+int vbq_rans_unpack_u16(const uint16_t *d_payload, int64_t n_words, const uint16_t *d_sizes_in, int64_t n_streams,
+                        int64_t n, int32_t seg, uint16_t *d_words, uint32_t *d_sizes, int64_t *d_offsets,
+                        uint32_t *d_status, void *stream);
 
 /* ----------------------------------------------------------------------------------
  * Packed counters for the histogram all-reduce: three 21-bit fields per int64 word.

@@ -4,6 +4,8 @@ The reference stops at ESTIMATING the rate as sum(-log2 freq) with add-n smoothe
 (quantizer.py:138-146, 226-228; utils.py:547).  This module turns the same per-(lambda, channel)
 histograms into integer frequency tables and the indices into a bitstream, and decodes it back.
 Format: include/vbq.h (vbq_rans_encode_u16).  Nothing here changes the quantization path.
+pack_device / unpack_device / encode_packed / decode_packed turn the padded per-segment layout into the contiguous payload of
+a compressed file (vbq_amd.bitstream) and back on the device (vbq_rans_pack_u16 / vbq_rans_unpack_u16).
 """
 from __future__ import annotations
 
@@ -62,6 +64,15 @@ def ideal_bits(counts, freq, prob_bits: int = PROB_BITS) -> float:
     return float(np.sum(c * (prob_bits - np.log2(np.asarray(freq, dtype=np.float64)))))
 
 
+def _raise_status(st: int):
+    """The OR-ed status word of vbq_rans_decode_u16 / vbq_rans_unpack_u16 -> VBQError (nothing when 0)."""
+    if st:
+        what = [m for b, m in ((1, "segment size out of range"), (2, "segment ran out of words"),
+                               (4, "left-over words / wrong final state"), (8, "invalid frequency table"),
+                               (16, "segment sizes do not add up to the payload length")) if st & b]
+        raise _lib.VBQError("rANS bitstream rejected: " + ", ".join(what))
+
+
 class RansCodec:
     """Encoder / decoder for u16 rank indices laid out as streams [S, n] (S = L*C planes of K1)."""
 
@@ -115,6 +126,82 @@ class RansCodec:
             what = [m for b, m in ((1, "segment size out of range"), (2, "segment ran out of words"),
                                    (4, "left-over words / wrong final state"), (8, "invalid frequency table")) if st & b]
             raise _lib.VBQError("rANS bitstream rejected: " + ", ".join(what))
+        return idx
+
+    # ------------------------------------------------------------ packed payload (vbq_amd.bitstream, vbq_rans_pack_u16)
+    def pack_device(self, words: torch.Tensor, sizes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The payload of `pack`, built on the device: -> (payload u16 [S * nseg * (segment+2)] whose first `total` words are
+        valid, total u64 [1], offsets int64 [S, nseg]), all device tensors; nothing is read back."""
+        words = ops._dev(words, torch.uint16, "words")
+        sizes = ops._dev(sizes, torch.uint32, "sizes")
+        S, nseg = sizes.shape
+        if tuple(words.shape) != (S, nseg, self.segment + 2):
+            raise ValueError(f"words {tuple(words.shape)} do not match sizes {tuple(sizes.shape)} and segment {self.segment}")
+        payload = torch.empty(S * nseg * (self.segment + 2), dtype=torch.uint16, device=words.device)
+        offsets = torch.empty((S, nseg), dtype=torch.int64, device=words.device)
+        total = torch.empty(1, dtype=torch.uint64, device=words.device)
+        self._pack(words, sizes, payload, offsets, total)
+        return payload, total, offsets
+
+    def _pack(self, words, sizes, payload, offsets, total):
+        S, nseg = sizes.shape
+        check(_lib.lib().vbq_rans_pack_u16(ops._ptr(words), ops._ptr(sizes), S, nseg * self.segment, self.segment,
+                                           ops._ptr(payload), ops._ptr(offsets), ops._ptr(total), ops._stream(words)),
+              "vbq_rans_pack_u16")
+
+    def unpack_device(self, payload: torch.Tensor, sizes: torch.Tensor, n: int, status: Optional[torch.Tensor] = None):
+        """vbq_rans_unpack_u16: untrusted payload u16 [n_words] + sizes u16 [S * nseg] -> (words [S, nseg, segment+2],
+        sizes u32 [S, nseg], status u32 [1]) in the layout `decode` reads.  Nothing is checked on the host here."""
+        payload = ops._dev(payload, torch.uint16, "payload")
+        sizes = ops._dev(sizes, torch.uint16, "sizes")
+        S = self.freq_host.shape[0]
+        nseg = (n + self.segment - 1) // self.segment
+        if sizes.numel() != S * nseg:
+            raise ValueError(f"expected {S * nseg} segment sizes for {S} streams of {n} symbols, got {sizes.numel()}")
+        dev = payload.device
+        words = torch.empty((S, nseg, self.segment + 2), dtype=torch.uint16, device=dev)
+        out_sizes = torch.empty((S, nseg), dtype=torch.uint32, device=dev)
+        offsets = torch.empty(S * nseg, dtype=torch.int64, device=dev)
+        if status is None:
+            status = torch.zeros(1, dtype=torch.uint32, device=dev)
+        check(_lib.lib().vbq_rans_unpack_u16(ops._ptr(payload), payload.numel(), ops._ptr(sizes), S, n, self.segment,
+                                             ops._ptr(words), ops._ptr(out_sizes), ops._ptr(offsets), ops._ptr(status),
+                                             ops._stream(payload)), "vbq_rans_unpack_u16")
+        return words, out_sizes, status
+
+    def encode_packed(self, idx: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+        """encode + pack on the device -> (sizes u32 [S, nseg], payload u16 [total]) on the host, in TWO device-to-host
+        copies: the total together with the sizes, then the payload."""
+        idx = ops._dev(idx, torch.uint16, "idx")
+        n = idx.shape[-1]
+        S = idx.numel() // max(n, 1)
+        if S != self.freq_host.shape[0]:
+            raise ValueError(f"{S} index streams but {self.freq_host.shape[0]} frequency rows")
+        nseg = (n + self.segment - 1) // self.segment
+        dev = idx.device
+        words = torch.empty((S, nseg, self.segment + 2), dtype=torch.uint16, device=dev)    # pack reads valid words only
+        aux = torch.empty(8 + 4 * S * nseg, dtype=torch.uint8, device=dev)                  # total u64, then sizes u32
+        total, sizes = aux[:8].view(torch.uint64), aux[8:].view(torch.uint32).view(S, nseg)
+        payload = torch.empty(S * nseg * (self.segment + 2), dtype=torch.uint16, device=dev)
+        offsets = torch.empty((S, nseg), dtype=torch.int64, device=dev)
+        check(_lib.lib().vbq_rans_encode_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(dev)),
+                                             ops._ptr(words), ops._ptr(sizes), ops._stream(idx)), "vbq_rans_encode_u16")
+        self._pack(words, sizes, payload, offsets, total)
+        h = aux.cpu().numpy()
+        n_words = int(h[:8].view(np.uint64)[0])
+        return h[8:].view(np.uint32).reshape(S, nseg), payload[:n_words].cpu().numpy()
+
+    def decode_packed(self, payload: torch.Tensor, sizes: torch.Tensor, n: int) -> torch.Tensor:
+        """unpack + the existing decoder, one status word for both (one synchronisation): u16 indices [S, n].
+        A damaged payload raises VBQError."""
+        status = torch.zeros(1, dtype=torch.uint32, device=payload.device)
+        words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
+        S = self.freq_host.shape[0]
+        idx = torch.empty((S, n), dtype=torch.uint16, device=payload.device)
+        check(_lib.lib().vbq_rans_decode_u16(ops._ptr(words), ops._ptr(out_sizes), S, n, self.N, self.segment,
+                                             ops._ptr(self._freq(payload.device)), ops._ptr(idx), ops._ptr(status),
+                                             ops._stream(payload)), "vbq_rans_decode_u16")
+        _raise_status(int(status.cpu().item()))
         return idx
 
     @staticmethod

@@ -170,6 +170,110 @@ k_rans_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict__ s
     if (bad && status) atomicOr(status, bad);
 }
 
+// ---- the byte-string container (vbq_amd/bitstream.py): padded segments [M][seg+2] <-> contiguous payload ----
+// Segment g (M = n_streams * nseg of them, stream-major) occupies payload words [off[g], off[g] + size[g]), off = exclusive
+// prefix sum of the sizes.  Two launches either way:
+//   k_scan_groups   ONE workgroup: thread t sums the sizes of group t (kGroup consecutive segments), the workgroup scans those
+//                   totals (wave64 shuffles + LDS) into exclusive group offsets -> offs[first segment of the group], and writes
+//                   the grand total.  Any number of groups: chunks of kScanThreads groups with a running carry.  (A separate
+//                   multi-workgroup pass for the group totals was one more launch: ~5 us more on an image's 512 - 9216
+//                   segments, where the single workgroup needs one chunk.)
+//   k_copy_segments one wave per segment: its offset = the group's offset + the sizes before it in the group (a 16-lane
+//                   shuffle sum, no LDS), then the 64 lanes copy its words (coalesced on both sides)
+// Unpacking reads UNTRUSTED sizes: one outside [2, seg + 2] counts as 0 (status bit 0), a segment that would read past n_words
+// is left zero-sized (the decoder then rejects it), and a total other than n_words sets status bit 4.
+constexpr int kGroup = 16;
+constexpr int kScanThreads = 1024;
+constexpr int kCopyThreads = 256;                                // 4 waves = 4 segments per workgroup
+
+template <bool kUntrusted, typename SizeT>
+__device__ __forceinline__ unsigned segment_size(const SizeT *sizes, long i, int seg, unsigned &bad) {
+    const unsigned k = sizes[i];
+    if (kUntrusted) {
+        if (k < 2u || k > (unsigned)seg + 2u) { bad = 1u; return 0u; }
+        return k;
+    }
+    return k < (unsigned)seg + 2u ? k : (unsigned)seg + 2u;     // (the encoder never writes more; clamped for memory safety)
+}
+
+template <bool kUntrusted, typename SizeT>
+__global__ void __launch_bounds__(kScanThreads)
+k_scan_groups(const SizeT *__restrict__ sizes, long M, int seg, long expect, int64_t *__restrict__ offs,
+              uint64_t *__restrict__ total, uint32_t *__restrict__ status) {
+    __shared__ long wsum[kScanThreads / 64];
+    const long G = (M + kGroup - 1) / kGroup;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned bad = 0;
+    long carry = 0;                                              // the same in every thread (it only reads wsum)
+    for (long base = 0; base < G; base += kScanThreads) {
+        const long gi = base + threadIdx.x;
+        long v = 0;
+        if (gi < G) {
+            const long a = gi * kGroup, b = a + kGroup < M ? a + kGroup : M;
+            for (long i = a; i < b; ++i) v += segment_size<kUntrusted>(sizes, i, seg, bad);
+        }
+        long incl = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long u = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += u;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        long before = carry, chunk = 0;
+        for (int w = 0; w < kScanThreads / 64; ++w) {
+            if (w < wave) before += wsum[w];
+            chunk += wsum[w];
+        }
+        if (gi < G) offs[gi * kGroup] = before + incl - v;
+        carry += chunk;
+        __syncthreads();                                         // wsum is rewritten by the next chunk
+    }
+    if (bad && status) atomicOr(status, 1u);
+    if (threadIdx.x == 0) {
+        if (total) *total = (uint64_t)carry;
+        if (expect >= 0 && carry != expect && status) atomicOr(status, 16u);
+    }
+}
+
+template <bool kUnpack, typename SizeT>
+__global__ void __launch_bounds__(kCopyThreads)
+k_copy_segments(const uint16_t *__restrict__ src, const SizeT *__restrict__ sizes, long M, int seg, long n_words,
+                int64_t *__restrict__ offs, uint16_t *__restrict__ dst, uint32_t *__restrict__ sizes_out) {
+    const int lane = threadIdx.x & 63;
+    const long g = (long)blockIdx.x * (kCopyThreads / 64) + (threadIdx.x >> 6);
+    if (g >= M) return;                                          // wave-uniform
+    const long g0 = g - g % kGroup;
+    const int r = (int)(g - g0);
+    unsigned bad = 0, kl = 0;
+    if (lane < kGroup && g0 + lane < M) kl = segment_size<kUnpack>(sizes, g0 + lane, seg, bad);
+    unsigned before = lane < r ? kl : 0u;
+#pragma unroll
+    for (int o = kGroup / 2; o >= 1; o >>= 1) before += __shfl_xor(before, o, 64);   // lanes 0..15: sum of the group's first r
+    before = __shfl(before, 0, 64);
+    const unsigned k = __shfl(kl, r, 64);
+    const long off = (long)offs[g0] + before;                    // offs[g0] = the group's offset (k_scan_groups)
+    if (lane == 0 && r != 0) offs[g] = off;                      // (segment g0's own entry already holds it)
+    const uint16_t *s;
+    uint16_t *d;
+    if (kUnpack) {
+        const bool fits = k != 0u && off + (long)k <= n_words;   // off >= 0: every read stays in [0, n_words)
+        if (lane == 0) sizes_out[g] = fits ? k : 0u;
+        if (!fits) return;
+        s = src + off;
+        d = dst + g * (long)(seg + 2);                           // k <= seg + 2: every write stays in segment g's buffer
+    } else {
+        s = src + g * (long)(seg + 2);
+        d = dst + off;
+    }
+    int j = lane;
+    for (; j + 192 < (int)k; j += 256) {                         // four loads in flight before the stores
+        const uint16_t a = s[j], b = s[j + 64], c = s[j + 128], e = s[j + 192];
+        d[j] = a; d[j + 64] = b; d[j + 128] = c; d[j + 192] = e;
+    }
+    for (; j < (int)k; j += 64) d[j] = s[j];
+}
+
 }  // namespace
 }  // namespace vbq
 
@@ -203,5 +307,55 @@ extern "C" int vbq_rans_decode_u16(const uint16_t *d_words, const uint32_t *d_si
                        dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream), d_words, d_sizes, (long)n, table_size(N),
                        (int)seg, (int)nseg, d_freq, d_idx, d_status);
     VBQ_CHECK_LAUNCH("rans_decode");
+    return VBQ_OK;
+}
+
+extern "C" int vbq_rans_pack_u16(const uint16_t *d_words, const uint32_t *d_sizes, int64_t n_streams, int64_t n, int32_t seg,
+                                 uint16_t *d_payload, int64_t *d_offsets, uint64_t *d_total, void *stream) {
+    using namespace vbq;
+    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && seg >= 1 && seg <= 65533 && n_streams <= 65535, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_pack_u16: bad sizes n_streams=%lld n=%lld seg=%d", (long long)n_streams, (long long)n, seg);
+    VBQ_REQUIRE(d_total, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_pack_u16: null d_total");
+    const int64_t M = n_streams * ((n + seg - 1) / seg);
+    VBQ_REQUIRE(M == 0 || (d_words && d_sizes && d_payload && d_offsets), VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_pack_u16: null pointer argument");
+    VBQ_REQUIRE((M + kCopyThreads / 64 - 1) / (kCopyThreads / 64) <= INT32_MAX, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_pack_u16: %lld segments are too many", (long long)M);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_groups<false, uint32_t>), dim3(1), dim3(kScanThreads), 0, st, d_sizes, (long)M,
+                       (int)seg, -1L, d_offsets, d_total, nullptr);
+    VBQ_CHECK_LAUNCH("rans_pack (scan)");
+    if (M > 0) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_copy_segments<false, uint32_t>),
+                           dim3((unsigned)((M + kCopyThreads / 64 - 1) / (kCopyThreads / 64))), dim3(kCopyThreads), 0, st,
+                           d_words, d_sizes, (long)M, (int)seg, 0L, d_offsets, d_payload, nullptr);
+        VBQ_CHECK_LAUNCH("rans_pack (copy)");
+    }
+    return VBQ_OK;
+}
+
+extern "C" int vbq_rans_unpack_u16(const uint16_t *d_payload, int64_t n_words, const uint16_t *d_sizes_in, int64_t n_streams,
+                                   int64_t n, int32_t seg, uint16_t *d_words, uint32_t *d_sizes, int64_t *d_offsets,
+                                   uint32_t *d_status, void *stream) {
+    using namespace vbq;
+    VBQ_REQUIRE(n_words >= 0 && n_streams >= 0 && n >= 0 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
+                VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_unpack_u16: bad sizes n_words=%lld n_streams=%lld n=%lld seg=%d",
+                (long long)n_words, (long long)n_streams, (long long)n, seg);
+    const int64_t M = n_streams * ((n + seg - 1) / seg);
+    VBQ_REQUIRE(M == 0 || (d_sizes_in && d_words && d_sizes && d_offsets), VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_unpack_u16: null pointer argument");
+    VBQ_REQUIRE(n_words == 0 || d_payload, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_unpack_u16: null d_payload");
+    VBQ_REQUIRE((M + kCopyThreads / 64 - 1) / (kCopyThreads / 64) <= INT32_MAX, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_unpack_u16: %lld segments are too many", (long long)M);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_groups<true, uint16_t>), dim3(1), dim3(kScanThreads), 0, st, d_sizes_in, (long)M,
+                       (int)seg, (long)n_words, d_offsets, nullptr, d_status);
+    VBQ_CHECK_LAUNCH("rans_unpack (scan)");
+    if (M > 0) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_copy_segments<true, uint16_t>),
+                           dim3((unsigned)((M + kCopyThreads / 64 - 1) / (kCopyThreads / 64))), dim3(kCopyThreads), 0, st,
+                           d_payload, d_sizes_in, (long)M, (int)seg, (long)n_words, d_offsets, d_words, d_sizes);
+        VBQ_CHECK_LAUNCH("rans_unpack (copy)");
+    }
     return VBQ_OK;
 }

@@ -627,6 +627,111 @@ class ChannelwisePriorCDFQuantizer:
         zhat = ops.gather(idx, self._sorted_dev(), C, N=self.max_bits_per_coord, layout="cb", out_layout="bc")
         return {lamb: (zhat[i].cpu().numpy() if return_np else zhat[i]) for i, lamb in enumerate(lambs)}
 
+    # ------------------------------------------------------------------ byte strings (vbq_amd.bitstream)
+    def _check_coder_bits(self):
+        if self.max_bits_per_coord > 10:
+            raise ValueError(f"max_bits_per_coord = {self.max_bits_per_coord}: the rANS coder supports at most 10")
+
+    def _lambda_key(self, lamb):
+        """The key of entropy_models equal to `lamb` as a float64 (KeyError otherwise, as compress_latents)."""
+        if self.entropy_models is None or not hasattr(self, "_code_counts"):
+            raise ValueError("build_entropy_models() first")
+        for k in self.lambs:
+            if float(k) == float(lamb):
+                return k
+        raise KeyError(lamb)
+
+    def _coder_tables(self, lamb, segment):
+        """(codec, digest) of one lambda.  The quantised frequencies and the digest are cached per lambda, keyed on the identity
+        of the `_code_counts` object a build installs (as _keyed_dev keys on identities): a rebuild of the entropy models -- or
+        build_code_points, which clears the device cache -- invalidates them."""
+        from . import bitstream
+        from .coder import RansCodec, quantize_frequencies
+        cc = self._code_counts
+        hit = self._dev_cache.get("_coder_tables")
+        if hit is None or hit[0] is not cc or hit[1] != self._add_n_smoothing:
+            hit = self._dev_cache["_coder_tables"] = (cc, self._add_n_smoothing, {})
+        per = hit[2]
+        ent = per.get(lamb)
+        if ent is None:
+            rows = cc.device_rows([lamb]) if isinstance(cc, DeviceModels) else None     # one lambda's rows, not the whole stack
+            counts = rows[0].cpu().numpy() if rows is not None else np.asarray(cc[lamb])
+            freq = quantize_frequencies(counts, add_n_smoothing=self._add_n_smoothing)    # [C, T]
+            ent = per[lamb] = {"freq": freq, "digest": bitstream.digest(self.code_points_by_channel, freq), "codecs": {}}
+        codec = ent["codecs"].get(segment)
+        if codec is None:
+            codec = ent["codecs"][segment] = RansCodec(ent["freq"], N=self.max_bits_per_coord, segment=segment)
+        return codec, ent["digest"]
+
+    def compress_latents_to_bytes(self, posterior_means, posterior_logvars, lamb, segment=1024) -> bytes:
+        """compress_latents at ONE lambda, entropy-coded into a self-describing byte string (format: vbq_amd.bitstream).
+        Same inputs and sigma = exp(logvar) ** 0.5 as compress_latents; the indices come from the same solve (the canonical
+        index of a repeated code point, as encode_batch).  Solve, encode and pack run on the device; two device-to-host
+        copies (the total with the segment sizes, then the payload)."""
+        from . import bitstream
+        self._check_coder_bits()
+        key = self._lambda_key(lamb)
+        C = self.num_channels
+        shape = tuple(int(d) for d in np.shape(posterior_means))
+        if tuple(np.shape(posterior_logvars)) != shape or not shape or shape[-1] != C:
+            raise ValueError(f"expected channel-last latents [..., {C}] of one shape, got {shape} / {tuple(np.shape(posterior_logvars))}")
+        if not 1 <= segment <= bitstream.MAX_SEGMENT:
+            raise ValueError(f"segment {segment} outside [1, {bitstream.MAX_SEGMENT}]")
+        codec, dig = self._coder_tables(key, int(segment))
+        m = posterior_means if isinstance(posterior_means, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_means))
+        lv = posterior_logvars if isinstance(posterior_logvars, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_logvars))
+        mu_cb, sg_cb = self._prep(m.reshape(-1, C), lv.reshape(-1, C), spread="logvar")
+        idx = self._solve_idx(mu_cb, sg_cb, [key], self._level_len_dev([key]))[0]          # [C, B]
+        if not self._strict:                  # code the canonical index of a run of equal values (see encode_batch)
+            canon = self._dev("canon", lambda: torch.from_numpy(self._canon))             # [C, T] int64
+            idx = torch.gather(canon, 1, idx.to(torch.int64)).to(torch.uint16)
+        sizes, payload = codec.encode_packed(idx)
+        h = bitstream.Header(N=self.max_bits_per_coord, C=C, shape=shape, lamb=float(key), segment=int(segment), digest=dig,
+                             n_words=int(payload.size))
+        return bitstream.write(h, sizes, payload)
+
+    def decompress_latents(self, data, return_np=True):
+        """Inverse of compress_latents_to_bytes: Z_hat shaped like the latents (NumPy, or a device tensor with
+        return_np=False), bit-identical to compress_latents(...)["Z_hat"][lamb].  ValueError for a malformed header or
+        a stream made with another quantizer / entropy model (digest), KeyError for a lambda this quantizer has no
+        model for, VBQError for a damaged payload."""
+        from . import bitstream
+        self._check_coder_bits()
+        h, _, _ = bitstream.parse(data)
+        if h.N != self.max_bits_per_coord or h.C != self.num_channels:
+            raise ValueError(f"stream is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
+                             f"C = {self.num_channels}")
+        key = self._lambda_key(h.lamb)
+        codec, dig = self._coder_tables(key, h.segment)
+        if dig != h.digest:
+            raise ValueError("stream was compressed with a different quantizer or entropy model (digest mismatch)")
+        start = h.nbytes                      # sizes, then payload: one upload
+        tail = np.frombuffer(memoryview(data).cast("B"), dtype="<u2", count=h.n_sizes + h.n_words, offset=start)
+        buf = torch.from_numpy(tail.copy()).to(self.device)
+        idx = codec.decode_packed(buf[h.n_sizes:], buf[: h.n_sizes], h.n_rows)          # [C, B]
+        zhat = ops.gather(idx[None], self._sorted_dev(), self.num_channels, N=self.max_bits_per_coord, layout="cb",
+                          out_layout="bc")                                                # [1, B, C]
+        zhat = zhat.reshape(h.shape)
+        return zhat.cpu().numpy() if return_np else zhat
+
+    def compress_to_bytes(self, X, vae, lamb, segment=1024) -> bytes:
+        """`vae.encode(X)`, then compress_latents_to_bytes."""
+        posterior_means, posterior_logvars = vae.encode(X)
+        return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment)
+
+    def decompress(self, data, vae, clip=True, return_np=True):
+        """decompress_latents, then `vae.decode` and the clip to [0, 1] of compress (quantizer.py:251-253).  The decoder
+        receives the latents as a device tensor; the image comes back as NumPy unless return_np=False."""
+        Z = self.decompress_latents(data, return_np=False)
+        X_hat = vae.decode(Z)
+        if isinstance(X_hat, torch.Tensor):
+            X_hat = X_hat.detach()
+            if clip:
+                X_hat = X_hat.clamp(0, 1)
+            return X_hat.cpu().numpy() if return_np else X_hat
+        X_hat = _to_numpy(X_hat)
+        return np.clip(X_hat, 0, 1) if clip else X_hat
+
     def compress(self, X, vae, lambs, clip=True):
         """quantizer.py:242-256.  With a torch VAE on the device nothing crosses PCIe here: the decoder gets the Z_hat tensor the
         kernels wrote (the reference -- and this method before round 5 -- went through NumPy: a device-to-host copy of L latent
