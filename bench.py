@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark of the VBQ hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--workload NAME] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line.  --full adds everything else listed below (the eager steps with per-kernel events in front of the graph replays, the
+oracle parity and R-D curve, the CPU baselines, the other workloads, the cost of the collectives at N > 1).
 
 --dump-outputs DIR writes what the last timed step computed (histograms, length table, models, and the rank indices on a
 fixed sample of rows) as DIR/<name>.npy, with DIR/manifest.json; the inputs are the same on every run with the same arguments.
@@ -29,10 +33,12 @@ this load -- after an idle gap the first ~50 ms of kernels run about 10 % slower
 
 Prints ONE compact JSON line (rank 0, the LAST line of stdout, below 4 KB: `headline`) and writes the full record --
 everything listed below in full -- to --full-record (default bench_full.json next to this file).  `python bench.py --gpus N`
-started by hand starts its own N ranks (`launch_ranks`); under torch.distributed.run it is one of them.
+started by hand starts its own N ranks (`launch_ranks`); under torch.distributed.run it is one of them.  What --full adds:
   roofline       the dominant kernel (pass 2's K1, k_quant_fast): ALGORITHMIC bytes -- 8 B read per element + 2 B written
                  per (element, lambda) -- over its event-timed launches against 8 TB/s (bound = "hbm").  The committed
-                 counters say what keeps it below that: VALU issue (`limited_by`, `valu_issue_frac`).
+                 counters say what keeps it below that: VALU issue (`limited_by`, `valu_issue_frac`).  With `stages_ms`, from
+                 K eager steps with per-stage events in front of the graph replays; a run without a graph (--no-graph,
+                 N > 1) times exactly those steps, so there a plain run has both too.
   rd_curve       rate (bits per latent from the entropy models, quantizer.py:226-228), distortion
                  sum((z - mu)^2 / (2 sigma^2)) / E and Lagrangian for every lambda of the sweep, on the whole tensor (f64
                  device reduction) and, on the parity sample, next to the oracle's (max_rel_diff <= 1e-5 asserted).
@@ -360,6 +366,8 @@ def headline(full, side_file=None):
     if roof.get("traffic_source"):                           # "<file> (committed ..., not this run)" -> file + tag
         line["roofline"]["traffic_source"] = str(roof["traffic_source"]).split(" ")[0] + " (committed pmc, not this run)"
     line["roofline"]["per_lambda_read_frac"] = [_sig(v, 3) for v in (roof.get("per_lambda_read_frac") or [])] or None
+    if not roof:                                             # a plain run replaying a graph times no kernel on its own
+        line["roofline"] = None
     cb = full.get("cpu_baseline")
     line["cpu_baseline"] = None if not cb else {"value": _sig(cb.get("value")), "unit": cb.get("unit"), "cores": cb.get("cores"),
                                                 "kind": cb.get("kind"), "sample": str(cb.get("sample", ""))[:200]}
@@ -369,8 +377,8 @@ def headline(full, side_file=None):
     line["stages_ms"] = {short: _sig(v, 4) for short, v in zip(("layout", "k1t", "k1", "k2"), st.values())} if st else None
     # HBM fraction of every stage's kernel on ITS algorithmic bytes (K1t: 8 B / element read; K1: 8 B / element + 2 B / pair;
     # K2: 2 B / pair read), event-timed in this run: all three recomputable from the line alone
-    line["stages_frac"] = {"k1t": _sig((full.get("roofline_k1h") or {}).get("frac"), 3), "k1": _sig(roof.get("frac"), 3),
-                           "k2": _sig((full.get("roofline_k2_histogram") or {}).get("frac"), 3)}
+    line["stages_frac"] = None if not roof else {"k1t": _sig((full.get("roofline_k1h") or {}).get("frac"), 3), "k1": _sig(roof.get("frac"), 3),
+                                                 "k2": _sig((full.get("roofline_k2_histogram") or {}).get("frac"), 3)}
     if full.get("allreduce"):
         ar = full["allreduce"]
         line["allreduce"] = {"payload_bytes": ar.get("rank_histogram_payload_bytes"), "packed_3x21": ar.get("packed_3x21"),
@@ -544,9 +552,12 @@ def rd_curve_oracle(mu_w, sg_w, idx_w, tab_h, models_h, lambdas):
     return {"distortion": d, "rate": r, "lagrangian": d + np.asarray(lambdas) * r}
 
 
-def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detailed, lambdas=None, strong=False, dump=False):
+def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detailed, lambdas=None, strong=False, dump=False,
+                 full=True):
     """Time `steps` alternations of one workload; returns the result dict (rank 0) or None.  dump: write what the last timed
-    step computed to args.dump_outputs (rank 0)."""
+    step computed to args.dump_outputs (rank 0).  full=False (a plain run): only what `ms_per_step` needs -- no region right
+    after the warm-up, no eager steps with per-stage events in front of the graph replays, no cost of the collectives -- and
+    no parity (`detailed` False)."""
     from vbq_amd import dist as vd, entropy, ops
     from vbq_amd.pipeline import EntropyModelBuild
     lambdas = LAMBDAS if lambdas is None else lambdas
@@ -606,25 +617,33 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
             dt = float(tt.item())
         return dt
 
+    def eager_region():
+        """The untimed clock ramp, then `steps` eager steps with every stage's events -> (seconds, what the ramp ran)."""
+        n = clock_ramp(torch, step, dist=dist if world > 1 else None, dev=dev)      # untimed, see clock_ramp
+        build.wait()
+        torch.cuda.synchronize()
+        timers.enabled = True
+        dt = timed(steps)
+        timers.enabled = False
+        return dt, f"{n} eager steps"
+
     for _ in range(warmup):
         step()
     build.wait()
-    cold_ms = timed(steps) / steps * 1e3     # the contract's letter -- W warm-up steps, then K steps -- kept for comparison
-    ramp_steps = clock_ramp(torch, step, dist=dist if world > 1 else None, dev=dev)      # untimed, see clock_ramp
-    build.wait()
-    torch.cuda.synchronize()
-    timers.enabled = True
-    dt = timed(steps)
-    timers.enabled = False
-    build.check()                      # the LUT assumption and the packed counters' overflow guard, outside the timed loop
-    eager_ms = dt / steps * 1e3
-    timed_regions_ms = [eager_ms]
-    launch = "eager launches, two streams" if len(build.chunks) > 1 else "eager launches"
+    cold_ms = eager_ms = dt = None
+    if full:
+        cold_ms = timed(steps) / steps * 1e3     # the contract's letter -- W warm-up steps, then K steps -- kept for comparison
     # The step only enqueues stream-ordered work (no allocation, no host synchronisation: the -log2 step is a table
     # lookup or a stream-ordered host callback), so the whole alternation replays from one captured HIP graph: ~20
-    # launches become one.  Per-kernel times above come from the eager steps (events cannot sit inside a graph); the
+    # launches become one.  Per-kernel times come from the eager steps (events cannot sit inside a graph); the
     # step time from the replays.
-    if args.graph and world == 1 and build.graph_safe:
+    use_graph = args.graph and world == 1 and build.graph_safe
+    if full or not use_graph:
+        dt, ramp = eager_region()
+        eager_ms = dt / steps * 1e3
+    timed_regions_ms = [eager_ms]
+    launch = "eager launches, two streams" if len(build.chunks) > 1 else "eager launches"
+    if use_graph:
         try:
             graph = torch.cuda.CUDAGraph()
             cs = torch.cuda.Stream()
@@ -637,7 +656,7 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
                 step()
             for _ in range(max(3, warmup)):
                 graph.replay()
-            clock_ramp(torch, graph.replay)            # untimed: capture left the device idle
+            ramp = f"{clock_ramp(torch, graph.replay)} graph replays"      # untimed: capture left the device idle
             # The timed region -- EXACTLY `steps` replays between two synchronisations -- is taken three times back to back and
             # the MEDIAN region is the one reported (all three are in the full record): one region of 13 ms is short enough
             # for a transient on the box to land in it (0.81 instead of 0.63 ms per step was seen once in this round).
@@ -651,10 +670,15 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
                 regions.append(time.perf_counter() - t0)
             dt = sorted(regions)[1]
             timed_regions_ms = [r / steps * 1e3 for r in regions]
-            launch = f"one HIP graph replay per step (eager: {eager_ms:.3f} ms)"
-        except Exception as e:                     # the eager measurement above stands
+            launch = "one HIP graph replay per step" + (f" (eager: {eager_ms:.3f} ms)" if eager_ms is not None else "")
+        except Exception as e:                     # the eager measurement stands (a plain run takes it now)
             torch.cuda.synchronize()
             launch += f" (HIP graph capture failed: {type(e).__name__})"
+            if eager_ms is None:
+                dt, ramp = eager_region()
+                eager_ms = dt / steps * 1e3
+                timed_regions_ms = [eager_ms]
+    build.check()                      # the LUT assumption and the packed counters' overflow guard, outside the timed loop
     if dump and rank == 0:                         # the buffers still hold the last timed step's results
         torch.cuda.synchronize()
         write_dump(args.dump_outputs, *build_outputs(build),
@@ -664,7 +688,6 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
     k1h_ms = timers.total_ms("k1h") / steps
     k2_ms = timers.total_ms("k2") / steps
     alg_bytes = E * (8 + 2 * L)                              # one K1 pass: 8 B in per element, 2 B out per solve
-    traffic, traffic_src, valu = committed_counters(name, rows, C, L)
     total_E = E * world if not strong else rows_total * C
     res = {
         "ms_per_step": dt / steps * 1e3,
@@ -675,47 +698,6 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
         "pairs_per_step": total_E * L,
         # the same time counting both solves of every pair (pass 1 solves for the bit-length histogram only)
         "solves_per_s_counting_both_passes": 2 * total_E * L * steps / dt,
-        "roofline": {"bound": "hbm", "limited_by": "valu issue", "kernel": "k_quant_fast (pass 2: corrected lengths -> rank indices)",
-                     "achieved": alg_bytes / (k1_ms * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                     "frac": alg_bytes / (k1_ms * 1e-3) / HBM_PEAK, "traffic": traffic,
-                     # `traffic` and `valu_issue_frac` are NOT measured in this run: they are the newest committed rocprofv3 --pmc
-                     # passes of this same workload (2 x FETCH_SIZE + WRITE_SIZE per launch), named here
-                     "traffic_source": (traffic_src + " (committed rocprofv3 --pmc passes, not this run)") if traffic_src else None,
-                     # the same achieved rate against the 6.29 TB/s a float4 copy measures on this chip
-                     "frac_of_measured_copy": alg_bytes / (k1_ms * 1e-3) / HBM_COPY_MEASURED,
-                     # what the exact dense argmin can reach with a perfect locate: VALU issue slots, not bytes
-                     "ceiling_frac": 0.35, "ceiling_source": "EXPERIMENTS.md, 'a bound for the dense formulation' (rounds 1-2 text) and 'K1's phase B, costed' (round 5)",
-                     # throughput against the north star's unfused per-lambda ceiling (8 B read per latent): [this kernel, whole step]
-                     "per_lambda_read_frac": [E * L / (k1_ms * 1e-3) / (HBM_PEAK / 8.0), E * L * steps / dt / (HBM_PEAK / 8.0)],
-                     # the index planes K1 writes and K2 reads back: intermediate bytes of the STEP that are in no result
-                     "step_intermediate_bytes": 4 * L * E,
-                     "step_floor_bytes": 16 * E + 8 * L * C * T,
-                     "algorithmic_bytes_per_pass": alg_bytes, "launches_per_pass": k1_n,
-                     "algorithmic_bytes_per_launch": alg_bytes / max(k1_n, 1), "avg_launch_ms": k1_ms / max(k1_n, 1),
-                     "pass_ms": k1_ms, "latents_per_s_kernel_only": E * L / (k1_ms * 1e-3),
-                     # what bounds the kernel: share of the SIMDs' issue cycles spent on its VALU instructions (committed
-                     # SQ counters); achieved / peak / frac are the HBM figures that issue rate moves
-                     "valu_issue_frac": (valu or {}).get("valu_issue_frac"), "valu": valu,
-                     "bound_note": "HBM roofline on algorithmic bytes; what limits the kernel below it is instruction issue (VALU) "
-                                   "-- counters in `valu`",
-                     # the north star's "HBM-read roofline" prices the UNFUSED per-lambda call, 8 B read per latent,
-                     # i.e. a ceiling of 1.0e12 latents/s at 8 TB/s (target 60 % = 6.0e11).  The fused kernels read every element
-                     # once per sweep, so this is a throughput ratio against that ceiling, not a bandwidth fraction.
-                     "per_lambda_read_roofline": {"bytes_read_per_latent": 8, "ceiling_latents_per_s": HBM_PEAK / 8.0,
-                                                  "kernel_frac": E * L / (k1_ms * 1e-3) / (HBM_PEAK / 8.0),
-                                                  "step_frac_per_gpu": E * L * steps / dt / (HBM_PEAK / 8.0)},
-                     "note": "K2 of the previous row chunk runs concurrently on a second stream" if k1_n > 1 else None},
-        "stages_ms": {"layout_change": timers.total_ms("layout") / steps if C > 1 else None,
-                      "pass1_k1t_solve_and_level_histogram": k1h_ms, "pass2_k1_solve": k1_ms,
-                      "pass2_k2_histogram (overlapped with k1)" if k1_n > 1 else "pass2_k2_histogram": k2_ms},
-        "roofline_k1h": {"bound": "hbm", "limited_by": "valu issue", "kernel": "k_level_counts_hull (pass 1, K1t: thresholds instead of a lambda loop; no per-element output)",
-                         "achieved": 8.0 * E / (k1h_ms * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": 8.0 * E / (k1h_ms * 1e-3) / HBM_PEAK, "algorithmic_bytes_per_launch": 8 * E,
-                         "avg_launch_ms": k1h_ms, "latents_per_s_kernel_only": E * L / (k1h_ms * 1e-3),
-                         "note": "reads 8 B per element and writes nothing per element: instruction- and LDS-bound by construction"},
-        "roofline_k2_histogram": {"bound": "hbm", "kernel": "k_hist_flat", "achieved": 2.0 * L * E / (k2_ms * 1e-3) / 1e9,
-                                  "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": 2.0 * L * E / (k2_ms * 1e-3) / HBM_PEAK,
-                                  "algorithmic_bytes_per_pass": 2 * L * E, "pass_ms": k2_ms},
         "config": {"workload": f"{name}: {desc}; {L}-point lambda sweep {sweep_name(lambdas)}; N={N_BITS} (2047 code points/"
                                f"channel); step = two-pass entropy-model build (quantizer.py:82-150): "
                                f"{'layout change + ' if C > 1 else ''}pass 1 (solve, raw lengths, bit-length histogram) + length table + "
@@ -727,12 +709,57 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
                                      f"(quantizer.py:82-150)" + ("; rows of one tensor split over the ranks" if strong else ""),
                    "elements_per_gpu": E, "lambdas": L, "parallelism": f"element-sharded x{world}",
                    "launch": launch, "untimed_clock_ramp_s": RAMP_S,
-                   "clock_ramp": f"{RAMP_S} s of untimed steps ({ramp_steps} eager steps here) in front of every timed region, after the "
+                   "clock_ramp": f"{RAMP_S} s of untimed steps in front of every timed region ({ramp} in front of the reported one), after the "
                                  f"{warmup} warm-up steps: the timed {steps} steps run at the clock the device sustains under this load",
                    "eager_ms_per_step_right_after_warmup": cold_ms,
                    "length_table": build.length_table_route, "models": build.models_route},
     }
-    if world > 1:
+    if k1_n:                                                 # the eager steps ran with their per-stage events
+        traffic, traffic_src, valu = committed_counters(name, rows, C, L)
+        res.update({
+            "roofline": {"bound": "hbm", "limited_by": "valu issue", "kernel": "k_quant_fast (pass 2: corrected lengths -> rank indices)",
+                         "achieved": alg_bytes / (k1_ms * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                         "frac": alg_bytes / (k1_ms * 1e-3) / HBM_PEAK, "traffic": traffic,
+                         # `traffic` and `valu_issue_frac` are NOT measured in this run: they are the newest committed rocprofv3 --pmc
+                         # passes of this same workload (2 x FETCH_SIZE + WRITE_SIZE per launch), named here
+                         "traffic_source": (traffic_src + " (committed rocprofv3 --pmc passes, not this run)") if traffic_src else None,
+                         # the same achieved rate against the 6.29 TB/s a float4 copy measures on this chip
+                         "frac_of_measured_copy": alg_bytes / (k1_ms * 1e-3) / HBM_COPY_MEASURED,
+                         # what the exact dense argmin can reach with a perfect locate: VALU issue slots, not bytes
+                         "ceiling_frac": 0.35, "ceiling_source": "EXPERIMENTS.md, 'a bound for the dense formulation' (rounds 1-2 text) and 'K1's phase B, costed' (round 5)",
+                         # throughput against the north star's unfused per-lambda ceiling (8 B read per latent): [this kernel, whole step]
+                         "per_lambda_read_frac": [E * L / (k1_ms * 1e-3) / (HBM_PEAK / 8.0), E * L * steps / dt / (HBM_PEAK / 8.0)],
+                         # the index planes K1 writes and K2 reads back: intermediate bytes of the STEP that are in no result
+                         "step_intermediate_bytes": 4 * L * E,
+                         "step_floor_bytes": 16 * E + 8 * L * C * T,
+                         "algorithmic_bytes_per_pass": alg_bytes, "launches_per_pass": k1_n,
+                         "algorithmic_bytes_per_launch": alg_bytes / max(k1_n, 1), "avg_launch_ms": k1_ms / max(k1_n, 1),
+                         "pass_ms": k1_ms, "latents_per_s_kernel_only": E * L / (k1_ms * 1e-3),
+                         # what bounds the kernel: share of the SIMDs' issue cycles spent on its VALU instructions (committed
+                         # SQ counters); achieved / peak / frac are the HBM figures that issue rate moves
+                         "valu_issue_frac": (valu or {}).get("valu_issue_frac"), "valu": valu,
+                         "bound_note": "HBM roofline on algorithmic bytes; what limits the kernel below it is instruction issue (VALU) "
+                                       "-- counters in `valu`",
+                         # the north star's "HBM-read roofline" prices the UNFUSED per-lambda call, 8 B read per latent,
+                         # i.e. a ceiling of 1.0e12 latents/s at 8 TB/s (target 60 % = 6.0e11).  The fused kernels read every element
+                         # once per sweep, so this is a throughput ratio against that ceiling, not a bandwidth fraction.
+                         "per_lambda_read_roofline": {"bytes_read_per_latent": 8, "ceiling_latents_per_s": HBM_PEAK / 8.0,
+                                                      "kernel_frac": E * L / (k1_ms * 1e-3) / (HBM_PEAK / 8.0),
+                                                      "step_frac_per_gpu": E * L * steps / dt / (HBM_PEAK / 8.0)},
+                         "note": "K2 of the previous row chunk runs concurrently on a second stream" if k1_n > 1 else None},
+            "stages_ms": {"layout_change": timers.total_ms("layout") / steps if C > 1 else None,
+                          "pass1_k1t_solve_and_level_histogram": k1h_ms, "pass2_k1_solve": k1_ms,
+                          "pass2_k2_histogram (overlapped with k1)" if k1_n > 1 else "pass2_k2_histogram": k2_ms},
+            "roofline_k1h": {"bound": "hbm", "limited_by": "valu issue", "kernel": "k_level_counts_hull (pass 1, K1t: thresholds instead of a lambda loop; no per-element output)",
+                             "achieved": 8.0 * E / (k1h_ms * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                             "frac": 8.0 * E / (k1h_ms * 1e-3) / HBM_PEAK, "algorithmic_bytes_per_launch": 8 * E,
+                             "avg_launch_ms": k1h_ms, "latents_per_s_kernel_only": E * L / (k1h_ms * 1e-3),
+                             "note": "reads 8 B per element and writes nothing per element: instruction- and LDS-bound by construction"},
+            "roofline_k2_histogram": {"bound": "hbm", "kernel": "k_hist_flat", "achieved": 2.0 * L * E / (k2_ms * 1e-3) / 1e9,
+                                      "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": 2.0 * L * E / (k2_ms * 1e-3) / HBM_PEAK,
+                                      "algorithmic_bytes_per_pass": 2 * L * E, "pass_ms": k2_ms},
+        })
+    if world > 1 and full:
         # what the collectives cost: the same steps without them, and the rank-histogram all-reduce in isolation
         build.collectives = False
         for _ in range(2):
@@ -787,7 +814,7 @@ def run_workload(name, args, torch, dist, dev, rank, world, steps, warmup, detai
         res["per_gpu"] = gathered
 
     if not detailed:
-        if rank == 0:                     # what the CPU baseline of the line needs (no index planes: nothing to cross-check against)
+        if rank == 0 and full:            # what the CPU baseline of the line needs (no index planes: nothing to cross-check against)
             torch.cuda.synchronize()
             res["_host"] = (mu_h, sg_h, tab_h, build.level_len.cpu().numpy(), None)
         del build
@@ -891,9 +918,12 @@ def main():
                                                              "stream); default 1: the overlap measured slower, profiles/r2_overlap_sweep.txt")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="time eager launches instead of replaying the step from a captured HIP graph (one GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the `workloads` section (the other BASELINE configs)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity block of the N > 1 line (the N = 1 line always has it)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline: per-stage times and rooflines, oracle parity and the "
+                         "R-D curve, the CPU baselines, the other workloads, the cost of the collectives (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: skip the `workloads` section (the other BASELINE configs)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity block of the N > 1 line (the N = 1 line always has it)")
     ap.add_argument("--notebook", action="store_true",
                     help="C = 1 workloads in the word-embedding notebook's arithmetic (K1n: f64 squared error, penalty "
                          "fl32(2 beta sigma^2) * length, ipynb:429-443): one K1n + K2 pass per step")
@@ -940,15 +970,16 @@ def main():
     # a second communicator for the small, latency-critical all-reduce of the bit-length histogram (see pipeline.py)
     args.level_group = dist.new_group() if world > 1 else None
     # ... and a gloo group to WAIT on without spinning (the ranks that idle while rank 0 times the CPU baseline)
-    args.cpu_group = dist.new_group(backend="gloo", timeout=__import__("datetime").timedelta(minutes=30)) if world > 1 else None
+    args.cpu_group = dist.new_group(backend="gloo", timeout=__import__("datetime").timedelta(minutes=30)) if world > 1 and args.full else None
 
     if args.notebook:
-        out = run_notebook(args, torch, dev, cpu=not args.no_cpu_baseline, dump=bool(args.dump_outputs))
+        out = run_notebook(args, torch, dev, cpu=args.full and not args.no_cpu_baseline, check=args.full, dump=bool(args.dump_outputs))
         emit(out, args.full_record)
         return
 
     res = run_workload(args.workload, args, torch, dist, dev, rank, world, args.steps, args.warmup,
-                       detailed=(world == 1 or not args.no_parity), strong=strong, dump=bool(args.dump_outputs))
+                       detailed=args.full and (world == 1 or not args.no_parity), strong=strong, dump=bool(args.dump_outputs),
+                       full=args.full)
     out = None
     if rank == 0:
         host = res.pop("_host", None)
@@ -966,13 +997,13 @@ def main():
             "dtype": "f32",
             "data": "synthetic",
             "config": res["config"],
-            "roofline": res["roofline"],
+            "roofline": res.get("roofline"),
             "pairs_per_step": res["pairs_per_step"],
             "timed_regions_ms_per_step": res["timed_regions_ms_per_step"],
             "solves_per_s_counting_both_passes": res["solves_per_s_counting_both_passes"],
-            "stages_ms": res["stages_ms"],
-            "roofline_k1h": res["roofline_k1h"],
-            "roofline_k2_histogram": res["roofline_k2_histogram"],
+            "stages_ms": res.get("stages_ms"),
+            "roofline_k1h": res.get("roofline_k1h"),
+            "roofline_k2_histogram": res.get("roofline_k2_histogram"),
         }
         for k in ("allreduce", "per_gpu", "rd_curve"):
             if k in res:
@@ -980,7 +1011,7 @@ def main():
         if "parity" in res:
             out["parity"] = res["parity"]
             out["parity_vs_oracle_on_sample"] = res["parity_ok"]
-        if not args.no_cpu_baseline and host is not None:
+        if args.full and not args.no_cpu_baseline and host is not None:
             # north_star: "next to the repo's CPU path timed on the same box's host cores in the same run" -- at EVERY N.  Rank 0
             # runs the bounded sample on its own rows after the timed regions; with N > 1 the other ranks sleep in a socket wait
             # meanwhile (a gloo barrier below: no spinning on the cores the sample uses).
@@ -1002,11 +1033,11 @@ def main():
         del host
     del res
     torch.cuda.empty_cache()
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and args.full and not args.no_cpu_baseline:
         dist.barrier(group=args.cpu_group)          # the other ranks wait here (blocked on a socket) while rank 0 times the CPU sample
 
     # the other BASELINE configurations, same step, same checks, fewer repetitions (every rank takes part when N > 1)
-    if not args.no_other_workloads:
+    if args.full and not args.no_other_workloads:
         others = {}
         few = max(3, min(args.steps, 5))
         if world == 1:
@@ -1550,9 +1581,9 @@ def run_api_methods(torch, dev, mu_h, sg_h, mu_bc, sg_bc, tab_h, steps=10, warmu
     return out
 
 
-def run_notebook(args, torch, dev, workload=None, steps=None, warmup=None, cpu=True, dump=False):
+def run_notebook(args, torch, dev, workload=None, steps=None, warmup=None, cpu=True, dump=False, check=True):
     """The C = 1 workloads in the notebook's own arithmetic: one K1n launch + one K2 launch per step.  dump: write what the
-    last timed step computed to args.dump_outputs."""
+    last timed step computed to args.dump_outputs.  check: the oracle's brute force on a sample (the CPU baseline with cpu)."""
     from vbq_amd import ops, embeddings as Emb
     name = workload or (args.workload if WORKLOADS[args.workload][1] == 1 else "embeddings_1e7")
     steps = steps or args.steps
@@ -1603,6 +1634,9 @@ def run_notebook(args, torch, dev, workload=None, steps=None, warmup=None, cpu=T
            "roofline": {"bound": "hbm", "limited_by": "valu issue", "kernel": "k_quant_notebook_hull", "achieved": alg / (k1_ms * 1e-3) / 1e9,
                         "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": alg / (k1_ms * 1e-3) / HBM_PEAK, "traffic": None,
                         "algorithmic_bytes_per_launch": alg, "avg_launch_ms": k1_ms}}
+    if not check:
+        out["cpu_baseline"] = out["parity_vs_oracle_on_sample"] = None
+        return out
     # the notebook's own brute force over all 2047 code points (C oracle, OpenMP), a bounded sample
     from oracle import c_oracle as CO, vbq_oracle as O
     th = CO.max_threads()

@@ -289,7 +289,7 @@ def _run_bench_two_ranks(extra, tmp_path, launcher="torchrun"):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     full = str(tmp_path / "bench_full.json")
-    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-other-workloads", "--full-record", full] + extra
+    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-other-workloads", "--full-record", full] + extra
     if launcher == "torchrun":                    # as the driver launches N > 1
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
@@ -372,6 +372,35 @@ def test_bench_two_ranks_strong_scaling_splits_one_tensor(tmp_path):
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["config"]["elements_per_gpu"] == 18432 * 32 and d["pairs_per_step"] == 36864 * 32 * 32
     assert d["parity_vs_oracle_on_sample"] is True and d["parity"]["counts_total"] is True
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_the_headline_only(tmp_path):
+    """A plain `bench.py --gpus 1` (no --full): the contract's keys from the graph replays, the dumped results of the last timed
+    step, and nothing that only --full measures (no CPU baseline, parity, other workloads or eager per-stage figures)."""
+    import json
+    import subprocess
+    if not torch.cuda.is_available():
+        pytest.fail("gpu-marked test run without a ROCm device")
+    full, dump = str(tmp_path / "bench_full.json"), tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--workload", "kodak24_c32", "--full-record", full, "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=540, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    assert line["n_gpus"] == 1 and line["steps"] == 5 and line["warmup"] == 2 and line["higher_is_better"] is True
+    assert line["unit"] == "latents/s" and line["dtype"] == "f32" and line["metric"].startswith("quantized latents/sec")
+    assert line["value"] == pytest.approx(36864 * 32 * 32 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["config"]["launch"] == "one HIP graph replay per step" and len(line["config"]["timed_regions_ms_per_step"]) == 3
+    assert line["cpu_baseline"] is None and line["parity_vs_oracle_on_sample"] is None and line["roofline"] is None
+    assert "workloads" not in line and line["stages_ms"] is None
+    d = json.load(open(full))
+    assert "rd_curve" not in d and "parity" not in d and "cpu_baseline_numpy" not in d
+    assert d["config"]["eager_ms_per_step_right_after_warmup"] is None
+    arrays = json.load(open(dump / "manifest.json"))["arrays"]
+    assert {"indices", "rank_counts", "level_counts", "level_len", "raw_models"} <= set(arrays)
+    assert np.all(np.load(dump / "level_counts.npy").sum(axis=-1) == 36864)          # every histogram row holds every row
+    assert np.all(np.load(dump / "rank_counts.npy").sum(axis=-1) == 36864)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -303,6 +303,23 @@ def test_bench_headline_line_is_compact_and_complete(tmp_path, capsys):
     assert len(json.dumps(l2)) < bench.LINE_LIMIT and "workloads" not in l2 and "roofline" in l2 and "cpu_baseline" in l2
 
 
+def test_bench_headline_of_a_plain_run(capsys):
+    """A plain run (no --full) replaying a graph has the contract's keys and nothing else measured: its line says so with
+    nulls -- no roofline or stage fractions made of missing timers, no CPU baseline, no parity verdict."""
+    import json
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r3_bench_full.json")))
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                  "vs_baseline", "dtype", "data", "config", "pairs_per_step", "solves_per_s_counting_both_passes")}
+    plain.update(roofline=None, stages_ms=None, roofline_k1h=None, roofline_k2_histogram=None, cpu_baseline=None,
+                 timed_regions_ms_per_step=[full["ms_per_step"]] * 3)
+    bench.emit(plain, None)
+    line = json.loads(capsys.readouterr().out.splitlines()[-1])
+    assert line["value"] == full["value"] and line["ms_per_step"] == full["ms_per_step"] and line["dtype"] == full["dtype"]
+    assert line["roofline"] is None and line["stages_frac"] is None and line["stages_ms"] is None
+    assert line["cpu_baseline"] is None and line["parity_vs_oracle_on_sample"] is None and "workloads" not in line
+
+
 def test_bench_self_launch_propagates_rank_failure():
     """`python bench.py --gpus 2` without WORLD_SIZE: the parent starts the ranks itself.  Without a ROCm device every rank
     exits with an error -- the parent must report it and exit non-zero (never hang, never print a JSON line)."""
