@@ -233,17 +233,32 @@ class BMSHJ2018Prior:
         stopping rule (all mid values exactly 0, or the smallest bracket <= tol)."""
         if method != "bisection":
             raise NotImplementedError
+        # The bracket doubling below never ends for an xi outside (0, 1) (or NaN) after the float32 cast: check on the host,
+        # before anything goes to the device.
+        xi32 = xi.detach().to(torch.float32) if isinstance(xi, torch.Tensor) else \
+            torch.from_numpy(np.asarray(xi, dtype=np.float32))
+        if not bool(torch.all((xi32 > 0) & (xi32 < 1))):
+            raise ValueError("inverse_cdf: every xi must be finite and lie in (0, 1) as a float32")
         xi_t = self._x(xi)
         params = self._params()
-        left = torch.full_like(xi_t, -1.0)
-        right = torch.full_like(xi_t, 1.0)
 
         def f(z):
             return ops.bmshj_cdf_pdf(params, z, cdf=True, pdf=False)[0] - xi_t
-        while not bool(torch.all(f(left) < 0)):
-            left = left * 2
-        while not bool(torch.all(f(right) > 0)):
-            right = right * 2
+
+        def bracket(z, side):
+            # double until every f(z) has the sign `side`; a channel whose CDF never crosses its xi (e.g. zero matrices
+            # after a float32 softplus) would take z to -inf / +inf and then spin there
+            while True:
+                miss = ~(f(z) * side > 0)
+                if not bool(miss.any()):
+                    return z
+                z = z * 2
+                if not bool(torch.isfinite(z).all()):
+                    c = int(torch.nonzero(miss.reshape(-1))[0]) % self._channels
+                    raise ValueError(f"inverse_cdf: the CDF of channel {c} does not cross its xi on "
+                                     f"[-3.4e38, 3.4e38]: no bracket")
+        left = bracket(torch.full_like(xi_t, -1.0), -1)
+        right = bracket(torch.full_like(xi_t, 1.0), 1)
         mid = torch.empty_like(xi_t)
         # The bisection steps are enqueued in chains of 48 with the stopping rule (:210-211) applied on the device between them
         # (vbq_bmshj_icdf_chain_f32): ONE host read per chain instead of one per step -- the loop was 40 synchronisations long.
