@@ -10,8 +10,8 @@
  *     allocated inside a call -- scratch comes from a caller-provided workspace.
  *   - return value: 0 = ok, negative = VBQ_ERR_*; vbq_last_error() gives the text of
  *     the calling thread's most recent failure.
- *   - no global state besides that thread-local error string (launch policies are per-call arguments; environment
- *     presets are read once and never written).
+ *   - no global state besides that thread-local error string (launch policies are per-call arguments, never environment
+ *     presets; the one variable read is the test-only VBQ_FAST_DEBUG, see "Launch policy").
  *
  * The reference (mandt-lab/vbq) has no FFI of its own: the boundary it offers is the
  * Python call surface listed in SURVEY.md 8(b).  Each entry point below names the
@@ -83,8 +83,10 @@ const char *vbq_last_error(void);
  * a few dozen workgroups) takes some of those slots, and a resident workgroup that finds its slot taken starts only after another
  * one has finished all its iterations -- up to twice the kernel time.  With n > 0 the grids of THAT CALL are sized to (slots - n), or
  * launched as short-lived workgroups when the (workgroups x channels) grid shape would give up more than a tenth of the chip.
- * n = 0: every slot.  n < 0: the default, 0 unless the environment variable VBQ_RESERVED_WORKGROUPS presets it (read once).  A
- * per-call argument: the library keeps no mutable launch state, two builds with different policies may run side by side. */
+ * n = 0: every slot; a negative n is taken as 0.  A per-call argument: the library keeps no mutable launch state, two builds
+ * with different policies may run side by side, and no environment variable changes which kernel or grid a call takes.  The one
+ * variable the library reads is VBQ_FAST_DEBUG (tests only, read once): 1 sends every solve of the fast kernels through the
+ * literal scan, 2 switches their near-tie flags off; the kernels and grids stay the same. */
 
 /* The launch shape a solve call would take on the current device -- nothing is launched: h_grid (HOST, int64 [3]) = { workgroups
  * per channel, channels, 1 when every workgroup is resident from start to end (0: short-lived workgroups) } for

@@ -143,3 +143,18 @@ def test_launch_policy_is_a_per_call_argument_not_process_state(built_lib):
     [t.join() for t in ts]
     assert not bad
     assert len({want[r] for r in want}) >= 3                   # the policies really differ in the grids they give
+
+
+def test_library_reads_no_environment_but_the_test_hook():
+    """Kernel and grid of a call follow from its arguments (include/vbq.h, "Launch policy"): the only environment variable
+    the native library reads is the test hook VBQ_FAST_DEBUG, in one place; the Python package has no host-stage switch."""
+    args = []
+    for d in ("vbq_amd/csrc", "include"):
+        for f in sorted(os.listdir(os.path.join(ROOT, d))):
+            args += re.findall(r"getenv\s*\(([^)]*)\)", open(os.path.join(ROOT, d, f), errors="replace").read())
+    assert {a.strip() for a in args} == {'"VBQ_FAST_DEBUG"'}, args
+    assert len(args) == 1, args
+    pkg = os.path.join(ROOT, "vbq_amd")
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            assert "VBQ_PYTHON_HOST_STAGE" not in open(os.path.join(pkg, f)).read(), f

@@ -1,4 +1,4 @@
-import os, sys
+import sys
 sys.path.insert(0, "/root/repo")
 import numpy as np, torch
 from bench import make_inputs, N_BITS, BETAS_50
@@ -21,4 +21,4 @@ for b in (BETAS_50[0], BETAS_50[10], BETAS_50[25], BETAS_50[40], BETAS_50[49]):
     i2, v2 = ops.quantize_notebook(m[:nn+1], s[:nn+1], cb, [b, BETAS_50[30]], N=N_BITS, want_values=True)
     want2 = CO.compress_coordinates(m_h[:nn+1, 0], s_h[:nn+1, 0], b, pts_h, lens_h, threads=CO.max_threads())
     ok2 = np.array_equal(i2[0].cpu().numpy().astype(np.int64), r2s[want2[1]]) and np.array_equal(v2[0].cpu().numpy(), want2[0])
-    print(f"{os.environ.get('VBQ_NO_PRUNED','0')} beta {b:10.4g}: {med*1e3:7.1f} us  {n/med/1e6:.1f} G/s  idx ok {ok}  pair+values ok {ok2}", flush=True)
+    print(f"beta {b:10.4g}: {med*1e3:7.1f} us  {n/med/1e6:.1f} G/s  idx ok {ok}  pair+values ok {ok2}", flush=True)

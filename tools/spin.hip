@@ -1,6 +1,6 @@
 // Developer tool: a kernel that only OCCUPIES workgroup slots -- the footprint of a collective's kernel (RCCL all-reduce:
 // a few dozen workgroups of 256-512 threads with >= 128 VGPRs, resident for the whole transfer) beside the resident grids
-// of K1t / K1 (tools/resident_vs_collective.py).
+// of K1t / K1 (tools/coresident_probe.py).
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC tools/spin.hip -o tools/bin/libspin.so
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -33,15 +33,8 @@ int num_cus() {
     }
     return cached[dev];
 }
-// Workgroup slots a resident grid leaves free for a kernel of another stream: a PER-CALL argument of the entry points that launch
-// resident grids (vbq_quantize_rows_f32, vbq_level_counts_f32, vbq_build_entropy_models_f32).  A negative argument takes the
-// default, which VBQ_RESERVED_WORKGROUPS presets (read once, never written afterwards: no mutable process state).
-int default_reserved_workgroups() {
-    static const int v = [] {
-        const char *e = getenv("VBQ_RESERVED_WORKGROUPS");
-        const int n = e ? atoi(e) : 0;
-        return n < 0 ? 0 : n;
-    }();
+int fast_debug() {
+    static const int v = [] { const char *e = getenv("VBQ_FAST_DEBUG"); return e ? atoi(e) : 0; }();
     return v;
 }
 int64_t resident_slots(int per_cu, int reserved) {

@@ -13,11 +13,13 @@ void set_error(const char *fmt, ...);
 // Compute units of the current device (hipDeviceProp_t::multiProcessorCount, cached per device): what the persistent
 // grids are sized by.  256 on MI355X; never hard-coded.
 int num_cus();
+// The `dbg` argument of the fast kernels: the test-only environment variable VBQ_FAST_DEBUG, read once (1 = every solve through
+// the literal scan, 2 = their flags / guard bands off, unset = 0).  The one environment input of the library.
+int fast_debug();
 // Workgroup slots of a resident grid with `per_cu` workgroups per CU, minus the `reserved` slots the CALLER leaves to a kernel of
 // another stream (the `reserved_workgroups` argument of the entry points: the distributed pipeline's overlapped all-reduce),
-// never below one per CU.  default_reserved_workgroups(): what a negative argument means -- VBQ_RESERVED_WORKGROUPS, read once.
+// never below one per CU.
 int64_t resident_slots(int per_cu, int reserved);
-int default_reserved_workgroups();
 
 #define VBQ_REQUIRE(cond, code, ...)            \
     do {                                        \

@@ -17,8 +17,6 @@
 //
 // The level of rank index q is N - ctz(q + 1) (slot (n, i) <-> rank (2i + 1) 2^(N-n) - 1), so no per-rank length table is
 // built or read.
-#include <stdlib.h>
-
 #include <atomic>
 
 #include <type_traits>
@@ -251,7 +249,7 @@ constexpr int kLdsCh = 16, kLdsRows = 256, kLdsPitch = kLdsRows, kLdsAhead = VBQ
 // against 51.0 us for the three outputs), two images and more in the LDS form (74.6 against 107 us; Kodak-24 x 32 Z_hat, real
 // indices, inside the facade: 1.23 -> 0.84 ms).
 constexpr int64_t kLdsMinLookupsZ = 9 << 14;         // lambdas x rows per channel table (Z_hat, with raw_num_bits riding along): from about six Kodak
-                                                     // images x 16 lambdas up (round 6, tools/image_lookup_modes.py: 2 / 4 images are 7-8 % faster with the table in L2)
+                                                     // images x 16 lambdas up (round 6, EXPERIMENTS.md: 2 / 4 images are 7-8 % faster with the table in L2)
 constexpr int64_t kLdsMinLookupsNb = 3 << 10;        // rows per (lambda, channel) table (num_bits)
 template <int N>
 __global__ void __launch_bounds__(1024)
@@ -348,15 +346,14 @@ int lookup_lds_passes(const uint16_t *idx, int64_t B, int32_t C, int32_t L, cons
     if constexpr (N > 10) {
         return VBQ_OK;
     } else {
-        static const int mode = [] { const char *e = getenv("VBQ_LOOKUP_LDS"); return e ? atoi(e) : -1; }();   // A/B: 0 never, 1 always
         const uintptr_t al = reinterpret_cast<uintptr_t>(out_z) | reinterpret_cast<uintptr_t>(out_nb);
-        if (mode == 0 || B % 4 != 0 || C % 4 != 0 || (al & 15) != 0 || (reinterpret_cast<uintptr_t>(idx) & 7) != 0) return VBQ_OK;
+        if (B % 4 != 0 || C % 4 != 0 || (al & 15) != 0 || (reinterpret_cast<uintptr_t>(idx) & 7) != 0) return VBQ_OK;
         constexpr int TP = table_size(N);
         const size_t lds = sizeof(float) * (size_t)(((kLdsCh * TP + 3) & ~3) + 2 * kLdsCh * kLdsPitch);
         const int groups = (C + kLdsCh - 1) / kLdsCh;
         // a staged table entry must be looked up often enough to pay for its staging: measured break-even (tools/gather_bench.py)
-        const bool want_z = out_z != nullptr && (mode == 1 || mode == 3 || (mode < 0 && (int64_t)L * B >= kLdsMinLookupsZ));
-        const bool want_nb = out_nb != nullptr && (mode == 1 || mode == 2 || (mode < 0 && B >= kLdsMinLookupsNb));
+        const bool want_z = out_z != nullptr && (int64_t)L * B >= kLdsMinLookupsZ;
+        const bool want_nb = out_nb != nullptr && B >= kLdsMinLookupsNb;
         if (!want_z && !want_nb) return VBQ_OK;
         // The LDS opt-in of the kernel, once per (device, N): 1 = granted, 2 = refused (a device or partition mode with less LDS
         // to opt into).  The passes are an optimisation: refused, or with a grid beyond the launch limits, the outputs stay with
@@ -420,8 +417,7 @@ int gather_latents(const uint16_t *idx, int64_t B, int32_t C, int32_t L, int32_t
     }
     const uintptr_t all = reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(out_z) | reinterpret_cast<uintptr_t>(out_raw) |
                           reinterpret_cast<uintptr_t>(out_nb) | reinterpret_cast<uintptr_t>(out_idx);
-    static const bool scalar_only = [] { const char *e = getenv("VBQ_GATHER_SCALAR"); return e && e[0] == '1'; }();   // A/B timing
-    const bool vec = !scalar_only && B % 8 == 0 && C % 4 == 0 && (all & 15) == 0;
+    const bool vec = B % 8 == 0 && C % 4 == 0 && (all & 15) == 0;
     const int64_t tiles = vec ? ((B + 63) / 64) * ((C + 63) / 64) : ((B + kGlRows - 1) / kGlRows) * ((C + kGlCh - 1) / kGlCh);
     VBQ_REQUIRE(tiles <= 0x7fffffffll && L <= 65535, VBQ_ERR_UNSUPPORTED, "vbq_gather_latents_u16: grid too large");
     const dim3 grid((unsigned)tiles, (unsigned)L);

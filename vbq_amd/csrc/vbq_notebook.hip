@@ -6,7 +6,6 @@
 // The notebook scores all 2047 points; only the two neighbours of mu on each bit level can
 // win (rounding is monotone, so a farther point of the same level never scores lower), so
 // the same 21-candidate descent as K1 is used, scanned in level-major order.
-#include <stdlib.h>
 #include <string.h>
 #include <math.h>
 
@@ -873,8 +872,7 @@ k_quant_notebook_hull(const float *__restrict__ means, const float *__restrict__
 // bucket apart, within 24 octaves).  Returns 1 when the sweep is not eligible (the caller takes the per-beta kernel).
 int launch_notebook_hull10(const float *means, const float *stds, int64_t n, const double *codebook, const double *betas,
                            int Lc, uint16_t *oi, float *ov, int vec_ok, int dbg, hipStream_t st) {
-    static const bool off = [] { const char *e = getenv("VBQ_NO_HULL"); return e && e[0] == '1'; }();
-    if (off || Lc < 1 || Lc > kMaxBetaChunk) return 1;
+    if (Lc < 1 || Lc > kMaxBetaChunk) return 1;
     NbSweep sw;
     int order[kMaxBetaChunk];
     float b[kMaxBetaChunk];
@@ -952,16 +950,14 @@ int launch_notebook(const float *means, const float *stds, int64_t n, const doub
         int64_t gx = ((n + 1) / 2 + 255) / 256;
         if (gx > 2048) gx = 2048;
         if (gx < 1) gx = 1;
-        static const bool plain = [] { const char *e = getenv("VBQ_PLAIN_KERNEL"); return e && e[0] == '1'; }();
-        static const int dbg = [] { const char *e = getenv("VBQ_FAST_DEBUG"); return e ? atoi(e) : 0; }();
-        bool fast_ok = !plain;                      // the tie certificate wants betas in a sane range
+        const int dbg = fast_debug();
+        bool fast_ok = true;                        // the tie certificate wants betas in a sane range
         for (int i = 0; i < Lc; ++i) fast_ok = fast_ok && (bc.beta[i] >= 1e-12 && bc.beta[i] <= 1e18);
-        static const bool no_pruned = [] { const char *e = getenv("VBQ_NO_PRUNED"); return e && e[0] == '1'; }();
         // The pruned descent stops once best <= w (n + 1): a bound on every deeper level's penalty that holds for w >= 0 only
         // (with a negative beta deeper levels carry SMALLER penalties and can still win): such calls take the literal kernel.
         bool nonneg = true;
         for (int i = 0; i < Lc; ++i) nonneg = nonneg && bc.beta[i] >= 0.0;
-        if (!plain && !no_pruned && nonneg && Lc <= 2) {  // one or two betas per call (the notebook's own pattern): pruned descent
+        if (nonneg && Lc <= 2) {  // one or two betas per call (the notebook's own pattern): pruned descent
             int64_t gp = gx;
             const int64_t capp = (int64_t)num_cus() * 6 * 2;
             if (gp > capp) gp = capp;

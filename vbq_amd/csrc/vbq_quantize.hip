@@ -18,8 +18,6 @@
 //   VBQ_MODE_F32: four separately rounded f32 ops per candidate, IEEE division,
 //   score = fl(s - fl(lambda*len)); candidates scanned in the reference order
 //   [L_0..L_N, R_1..R_N] with a strict '>' so the first maximum wins, as np/tf argmax do.
-#include <stdlib.h>
-
 #include "vbq_common.h"
 
 namespace vbq {
@@ -360,12 +358,6 @@ k_intervals(const float *__restrict__ z_cb, long n_rows, const float *__restrict
     }
 }
 
-// VBQ_PLAIN_KERNEL=1 routes everything through the literal 21-candidate kernels (A/B checks).
-inline bool force_plain_kernel() {
-    static const bool v = [] { const char *e = getenv("VBQ_PLAIN_KERNEL"); return e && e[0] == '1'; }();
-    return v;
-}
-
 // Rows [row_begin, row_end) of the full [n_rows x n_ch] arrays are processed; outputs keep the full arrays'
 // addressing (lambda planes E = n_rows * n_ch apart).  level_counts != NULL: counting mode of the fast kernel.
 template <int N, typename PenT>
@@ -428,7 +420,7 @@ int launch_quantize(const float *mu, const float *sg, int64_t n_rows, int32_t n_
             if (gx > cap) gx = cap;
             if (gx < 1) gx = 1;
             // The fast kernel's tie certificate needs lambda*len to be 0 or comfortably normal.
-            bool fast_ok = sizeof(PenT) == 4 && !force_plain_kernel();
+            bool fast_ok = sizeof(PenT) == 4;
             // (vbq_quantize_fast.hip: the equality mask needs every lambda*len >= 2^-39 for len >= 1)
             for (int i = 0; i < Lc; ++i) fast_ok = fast_ok && (lc.lam[i] >= 1.9e-12 && lc.lam[i] <= 1.8e19);
             if constexpr (sizeof(PenT) == 4 && N == 10) {
@@ -451,7 +443,7 @@ int launch_quantize(const float *mu, const float *sg, int64_t n_rows, int32_t n_
             }
             if constexpr (sizeof(PenT) == 4) {
                 // one to four lambdas, indices only: the descent with exact pruning (literal comparisons: any penalties)
-                if (!force_plain_kernel() && !lc_out && oi && !oz && !ob && wg_per_cu == 0) {
+                if (!lc_out && oi && !oz && !ob && wg_per_cu == 0) {
                     const int r = launch_quant_pruned<N>(mu_r, sg_r, n_per_ch, ch_stride, n_ch, table, l32, len_c, Lc, oi, E,
                                                          vec2_ok | (bc_to_cb ? 2 : 0), st);
                     if (r == VBQ_OK) continue;
@@ -548,7 +540,7 @@ int quantize_entry(const char *who, const float *d_mu, const float *d_sigma, int
                 workspace_bytes, need);
     if (row_begin == row_end) return VBQ_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int reserved = reserved_wgs < 0 ? default_reserved_workgroups() : reserved_wgs;
+    const int reserved = reserved_wgs < 0 ? 0 : reserved_wgs;
 #define VBQ_DISPATCH_N(NN)                                                                                         \
     case NN:                                                                                                       \
         return mode == VBQ_MODE_F32                                                                                \

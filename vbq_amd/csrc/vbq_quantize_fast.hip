@@ -29,7 +29,6 @@
 //          the flag is raised when it is below 2^-20 * S (tested as packed word <= bits(2^-19 * S)).
 //    A wave with any flagged lane re-solves those lanes for that lambda with the literal
 //    21-candidate scan (exact_rank_scan).  Both events have probability ~1e-6 per solve.
-#include <stdlib.h>
 #include <string.h>
 
 #include "vbq_common.h"
@@ -1403,7 +1402,6 @@ void quant_fast_grid(int64_t n_per_ch, int32_t n_ch, int wg_per_cu, int reserved
     // for 18 short-lived workgroups per channel and 394 us for the same resident grid without the rotation.
     // wg_per_cu < 4 leaves LDS and wave slots for a kernel of another stream (K2 overlapping this launch); 5 is taken as 4
     // (a fifth workgroup per CU would only wait for a slot: 444 us).
-    static const bool dynamic_env = [] { const char *e = getenv("VBQ_K1_DYNAMIC"); return e && e[0] == '1'; }();   // A/B switch
     const bool explicit_wgs = wg_per_cu >= 1 && wg_per_cu <= 5;
     const int fit = kFastNE == 4 ? 3 : 4;
     // Slots the caller reserves for a kernel of another stream (`reserved_workgroups` of the entry points: the overlapped
@@ -1413,15 +1411,11 @@ void quant_fast_grid(int64_t n_per_ch, int32_t n_ch, int wg_per_cu, int reserved
     // the grid is (workgroups per channel) x channels, so with many channels that costs whole rounds of n_ch slots: when more
     // than a tenth of the chip would be given up the launch falls back to short-lived workgroups, which lose 8 % alone but
     // only their share of the taken slots beside a collective.
-    bool dynamic_grid = dynamic_env;
-    if (!dynamic_grid && !explicit_wgs && reserved > 0) {
-        const int64_t all = (int64_t)num_cus() * fit;
-        const int64_t kept = (resident_slots(fit, reserved) / n_ch) * n_ch;
-        if (kept * 10 < all * 9) dynamic_grid = true;
-    }
+    const bool dynamic_grid = !explicit_wgs && reserved > 0 &&
+                              (resident_slots(fit, reserved) / n_ch) * n_ch * 10 < (int64_t)num_cus() * fit * 9;
     const int per_cu = explicit_wgs ? (wg_per_cu < fit ? wg_per_cu : fit) : (dynamic_grid ? 5 : fit);
-    int64_t cap = (dynamic_grid && !explicit_wgs ? (int64_t)num_cus() * per_cu * 4 : resident_slots(per_cu, reserved)) / n_ch;
-    const bool resident = !(dynamic_grid && !explicit_wgs) && (int64_t)n_ch <= (int64_t)num_cus() * per_cu;
+    int64_t cap = (dynamic_grid ? (int64_t)num_cus() * per_cu * 4 : resident_slots(per_cu, reserved)) / n_ch;
+    const bool resident = !dynamic_grid && (int64_t)n_ch <= (int64_t)num_cus() * per_cu;
     if (cap < 1) cap = 1;
     if (gx > cap) {
         const int64_t iters = gx;
@@ -1460,7 +1454,7 @@ int launch_quant_fast(const float *mu, const float *sg, int64_t n_per_ch, int64_
     quant_fast_grid(n_per_ch, n_ch, wg_per_cu, reserved, level_counts != nullptr, &gx, &resident);
     if (resident) vec_ok |= 4;
     const dim3 grid((unsigned)gx, (unsigned)n_ch), block(kFastThreads);
-    static const int dbg = [] { const char *e = getenv("VBQ_FAST_DEBUG"); return e ? atoi(e) : 0; }();
+    const int dbg = fast_debug();
     if (level_counts)
         hipLaunchKernelGGL((k_quant_fast<N, 2>), grid, block, 0, st, mu, sg, (long)n_per_ch, (long)ch_stride, (int)n_ch, table,
                            lam, len, (int)L, out_idx, out_zhat, out_bits, (long)E, vec_ok, dbg, level_counts);
@@ -1478,15 +1472,14 @@ int launch_quant_fast(const float *mu, const float *sg, int64_t n_per_ch, int64_
 template <int N>
 int launch_quant_pruned(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch, const float *table,
                         const Lambdas32 &lam, const float *len, int32_t L, uint16_t *out_idx, int64_t E, int vec_ok, hipStream_t st) {
-    static const bool off = [] { const char *e = getenv("VBQ_NO_PRUNED"); return e && e[0] == '1'; }();
-    if (off || L < 1 || L > kPrunedMaxL) return 1;
+    if (L < 1 || L > kPrunedMaxL) return 1;
     const int64_t npairs = (n_per_ch + 1) / 2;
     int64_t gx = (npairs + 255) / 256;
     int64_t cap = (int64_t)num_cus() * 4 / n_ch;               // the 4 workgroups per CU that are resident (one round: with the
                                                                 // priority rotation 71 us at lambda = 2^-8, two rounds 79, no rotation 74)
     if (cap < 1) cap = 1;
     if (gx > cap) gx = cap;
-    static const int dbg = [] { const char *e = getenv("VBQ_FAST_DEBUG"); return e ? atoi(e) : 0; }();
+    const int dbg = fast_debug();
     const dim3 grid((unsigned)gx, (unsigned)n_ch), block(256);
 #define VBQ_PRUNED_CASE(LLv)                                                                                          \
     case LLv:                                                                                                          \
@@ -1557,8 +1550,6 @@ int64_t level_counts_hull_grid(int64_t n_per_ch, int32_t n_ch, int reserved) {
     // (only with slots reserved: without a reservation the grid is floor(all / n_ch) workgroups per channel, whatever n_ch)
     if (reserved > 0 && (slots / n_ch) * n_ch * 10 < (int64_t)num_cus() * per_cu * 9)
         slots = (int64_t)num_cus() * (per_cu > 1 ? per_cu - 1 : 1);
-    static const int exp_per_cu = [] { const char *e = getenv("VBQ_HULL_WG_PER_CU"); return e ? atoi(e) : 0; }();   // A/B switch
-    if (exp_per_cu > 0 && exp_per_cu < per_cu) slots = (int64_t)num_cus() * exp_per_cu;
     int64_t cap = slots * rounds / n_ch;                    // VBQ_HULL_WAVES x 4 waves per CU resident
     if (cap < 1) cap = 1;
     if (gx > cap) {
@@ -1582,12 +1573,11 @@ int64_t level_counts_hull_grid(int64_t n_per_ch, int32_t n_ch, int reserved) {
 int launch_level_counts_hull10(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch,
                                const float *table, const double *lam, int32_t L, int vec_ok,
                                unsigned long long *level_counts, int reserved, hipStream_t st) {
-    static const bool off = [] { const char *e = getenv("VBQ_NO_HULL"); return e && e[0] == '1'; }();
-    if (off || L < 1 || L > 32) return 1;
+    if (L < 1 || L > 32) return 1;
     HullSweep sw;
     if (!build_hull_sweep(lam, L, sw)) return 1;
     const int64_t gx = level_counts_hull_grid(n_per_ch, n_ch, reserved);
-    static const int dbg = [] { const char *e = getenv("VBQ_FAST_DEBUG"); return e ? atoi(e) : 0; }();
+    const int dbg = fast_debug();
     Lambdas32 l32;
     for (int i = 0; i < kMaxLambdaChunk; ++i) l32.lam[i] = i < L ? (float)lam[i] : 0.0f;
     hipLaunchKernelGGL((k_level_counts_hull<10>), dim3((unsigned)gx, (unsigned)n_ch), dim3(kHullThreads), 0, st, mu, sg,
@@ -1600,8 +1590,7 @@ int launch_level_counts_hull10(const float *mu, const float *sg, int64_t n_per_c
 int launch_quant_hull_idx10(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch,
                             const float *table, const double *lam, int32_t L, int vec_ok, uint16_t *out_idx, int64_t E,
                             hipStream_t st) {
-    static const bool off = [] { const char *e = getenv("VBQ_NO_HULL"); return e && e[0] == '1'; }();
-    if (off || L < 16) return 1;                             // below that the thresholds cost more than the solves they replace
+    if (L < 16) return 1;                                    // below that the thresholds cost more than the solves they replace
                                                              // (Kodak-24: 0.25 against 0.27 ms at 16 lambdas, 0.29 against 0.43 at 32)
     // The emission addresses an index plane with a 32-bit BYTE offset from a scalar plane base (global_store_dword voff, v,
     // s[plane]): planes of 2^31 elements or more (a 16-lambda sweep of that size is 64 GB of indices: it fits) go to K1.
@@ -1614,7 +1603,7 @@ int launch_quant_hull_idx10(const float *mu, const float *sg, int64_t n_per_ch, 
     int64_t cap = (int64_t)num_cus() * VBQ_K1E_WAVES * rounds / n_ch;          // VBQ_K1E_WAVES workgroups per CU resident
     if (cap < 1) cap = 1;
     if (gx > cap) gx = cap;
-    static const int dbg = [] { const char *e = getenv("VBQ_FAST_DEBUG"); return e ? atoi(e) : 0; }();
+    const int dbg = fast_debug();
     Lambdas32 l32;
     for (int i = 0; i < kMaxLambdaChunk; ++i) l32.lam[i] = i < L ? (float)lam[i] : 0.0f;
     // all L planes within 4 GB: the emission addresses them through one buffer descriptor (32-bit scalar plane offsets)
@@ -1652,7 +1641,7 @@ extern "C" int vbq_solve_grid(int32_t kernel, int64_t n_rows, int32_t n_ch, int3
     VBQ_REQUIRE(kernel == VBQ_GRID_K1 || kernel == VBQ_GRID_K1T, VBQ_ERR_INVALID_ARGUMENT, "vbq_solve_grid: unknown kernel %d", kernel);
     VBQ_REQUIRE(workgroups_per_cu >= 0 && workgroups_per_cu <= 5, VBQ_ERR_INVALID_ARGUMENT, "vbq_solve_grid: workgroups_per_cu=%d not in 0..5",
                 workgroups_per_cu);
-    const int reserved = reserved_workgroups < 0 ? default_reserved_workgroups() : reserved_workgroups;
+    const int reserved = reserved_workgroups < 0 ? 0 : reserved_workgroups;
     if (kernel == VBQ_GRID_K1) {
         int64_t gx = 1;
         bool resident = false;

@@ -75,7 +75,7 @@ def quantize(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, lamb
     f32 mode and lambdas in the fast kernel's range only, VBQError otherwise).
     rows=(r0, r1): only that row range is solved (vbq_quantize_rows_f32; the output tensors are still full-size) --
     the host cuts a pass into chunks to overlap K2 with K1; workgroups_per_cu, reserved_workgroups (slots this call's
-    resident grid leaves to a kernel of another stream; None: the library's default): see include/vbq.h."""
+    resident grid leaves to a kernel of another stream; None: 0): see include/vbq.h."""
     to_planes = layout in ("bc->cb", LAYOUT_BC_TO_CB)
     layout = LAYOUT_BC if to_planes else _LAYOUTS[layout]
     mode = _MODES[mode]

@@ -234,10 +234,11 @@ class EntropyModelBuild:
     def __init__(self, rows: int, n_ch: int, lambdas: Sequence[float], table_lm: torch.Tensor, *, N: int = 10,
                  add_n_smoothing=1, global_rows: Optional[int] = None, distributed: bool = False, group=None,
                  level_group=None, n_chunks: Optional[int] = None, counts_dtype=None, keep_models: bool = True,
-                 buffers: Optional[dict] = None, reserved_workgroups: Optional[int] = None):
+                 buffers: Optional[dict] = None, reserved_workgroups: Optional[int] = None, python_host_stage: bool = False):
         """buffers: a dict the caller keeps between builds -- the index planes, the solve's workspace and the -log2 tables
         (device copies) of one shape are taken from it instead of being allocated / computed / uploaded again; every
-        OUTPUT tensor (histograms, length table, models) is new per object."""
+        OUTPUT tensor (histograms, length table, models) is new per object.  python_host_stage: the -log2 steps that cannot
+        be tabulated run as NumPy in Python even where the plain C form is available (tests compare the two)."""
         self.rows, self.C, self.N = int(rows), int(n_ch), int(N)
         self.lambdas = [float(l) for l in lambdas]
         self.L = len(self.lambdas)
@@ -300,9 +301,9 @@ class EntropyModelBuild:
 
         # The -log2 steps that cannot be tabulated: plain C on the runtime's callback thread with NumPy's own log2 loop
         # (NativeHostStage) when this interpreter lets us have it and the smoothing is a Python number (a NumPy float64 scalar
-        # would make `c += n` a float64 addition); otherwise -- or with VBQ_PYTHON_HOST_STAGE=1 -- NumPy itself on that thread.
+        # would make `c += n` a float64 addition); otherwise -- or with python_host_stage -- NumPy itself on that thread.
         loop = None
-        if type(add_n_smoothing) in (int, float) and T <= 8192 and _os.environ.get("VBQ_PYTHON_HOST_STAGE") != "1":
+        if type(add_n_smoothing) in (int, float) and T <= 8192 and not python_host_stage:
             loop = numpy_log2_f32_loop()
         self.host_stage_kind = None
         self._len_stage = None
