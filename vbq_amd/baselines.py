@@ -25,6 +25,19 @@ def _dev_f32(a):
     return t.to(torch.device("cuda", torch.cuda.current_device()), torch.float32).contiguous().reshape(-1)
 
 
+def _require_finite(samples, allow_inf):
+    """The reference raises on samples it cannot bin: scipy's vq.vq refuses NaN and +-inf ("array must not contain infs
+    or NaNs"); UniformQuantizer casts floor(NaN) to INT_MIN, which np.bincount / np.take refuse (+-inf clip to an edge
+    bin and are fine).  The kernels would put such a sample in bin 0 without a word, so refuse it before they run."""
+    if isinstance(samples, torch.Tensor):
+        bad = bool(torch.isnan(samples).any()) if allow_inf else not bool(torch.isfinite(samples).all())
+    else:
+        a = np.asarray(samples)
+        bad = bool(np.isnan(a).any()) if allow_inf else not bool(np.isfinite(a).all())
+    if bad:
+        raise ValueError("samples must not contain " + ("NaNs" if allow_inf else "infs or NaNs"))
+
+
 def _code_lengths(counts, n_samples, add_n_smoothing):
     """quantizer.py:281-288 / 314-321 on the bincount."""
     counts = np.asarray(counts)
@@ -51,6 +64,7 @@ class UniformQuantizer:
         return I, q, counts
 
     def fit(self, samples, add_n_smoothing=1.):
+        _require_finite(samples, allow_inf=True)
         s = np.asarray(samples)
         mn, mx = np.min(s), np.max(s)
         N = self.quantization_levels
@@ -62,6 +76,7 @@ class UniformQuantizer:
         self.code_lengths = _code_lengths(counts.cpu().numpy(), len(s), add_n_smoothing)
 
     def quantize(self, samples):
+        _require_finite(samples, allow_inf=True)
         shape = np.shape(samples)
         I, q, _ = self._run(samples, False)
         I = I.cpu().numpy().reshape(shape)
@@ -95,6 +110,7 @@ class KmeansQuantizer:
         self.code_lengths = _code_lengths(counts, len(s), add_n_smoothing)
 
     def quantize(self, samples):
+        _require_finite(samples, allow_inf=False)
         shape = np.shape(samples)
         I, q, _ = self._vq(samples, False)
         I = I.cpu().numpy().reshape(shape)

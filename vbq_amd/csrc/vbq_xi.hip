@@ -5,7 +5,8 @@
 //                    budget n the two n-bit grid points around xi -- the literal bit-by-bit truncation loop, operation
 //                    for operation (x - offset may round; the loop's subtractions are then exact)
 //   k_xi_select      utils.encode_vectorized after the callables (:291-303): the better endpoint per budget (first
-//                    maximum), the rate term lamb * n, the best budget (first maximum), and the gathers
+//                    maximum), the rate term lamb * n, the best budget (first maximum), and the gathers; both maxima
+//                    follow np.argmax on NaN (the first NaN wins)
 // Golden vectors g3 / g4 (the reference's own functions run in the build container) pin both.   gfx950 / ROCm only.
 #include "vbq_common.h"
 
@@ -59,10 +60,12 @@ k_xi_select(const double *__restrict__ F, const double *__restrict__ ends, const
         for (int n = 0; n <= N; ++n) {
             const long o = (long)n * K + k;
             const double fl = F[o], fr = F[plane + o];
-            const bool pick_r = fr > fl;                      // np.argmax over the pair: the first maximum
+            // np.argmax over the pair: the first maximum, where a NaN beats every number (the first NaN wins)
+            const bool pick_r = !isnan(fl) && (isnan(fr) || fr > fl);
             const double fm = pick_r ? fr : fl;
             const double reg = __dsub_rn(fm, __dmul_rn(lamb, (double)n));
-            if (n == 0 || reg > best) { best = reg; best_n = n; best_off = (pick_r ? plane : 0) + o; }
+            // np.argmax over n, the same rule: once a NaN is the best it stays the best
+            if (n == 0 || (!isnan(best) && (isnan(reg) || reg > best))) { best = reg; best_n = n; best_off = (pick_r ? plane : 0) + o; }
         }
         z_hat[k] = unsq[best_off];
         xi_hat[k] = ends[best_off];
