@@ -516,6 +516,28 @@ int vbq_rans_pack_u16(const uint16_t *d_words, const uint32_t *d_sizes, int64_t 
 int vbq_rans_unpack_u16(const uint16_t *d_payload, int64_t n_words, const uint16_t *d_sizes_in, int64_t n_streams,
                         int64_t n, int32_t seg, uint16_t *d_words, uint32_t *d_sizes, int64_t *d_offsets,
                         uint32_t *d_status, void *stream);
+/* Row-wise decode of ONE packed stream (the embedding container of vbq_amd/bitstream.py, magic "VBQe").  These two
+ * entry points were added without an ABI version bump: nothing that existed before changed.
+ * vbq_rans_segment_offsets_u16: d_offsets int64 [M] = the exclusive prefix sum of the UNTRUSTED sizes u16 [M], at every
+ * segment.  d_status as vbq_rans_unpack_u16: bit 0 a size outside [2, seg + 2] (counted as 0), bit 4 a sum other than
+ * n_words. */
+int vbq_rans_segment_offsets_u16(const uint16_t *d_sizes, int64_t M, int32_t seg, int64_t n_words, int64_t *d_offsets,
+                                 uint32_t *d_status, void *stream);
+/* vbq_rans_decode_values_f32: decodes the stream of n symbols (nseg = ceil(n / seg) segments) straight from the payload
+ * u16 [n_words] (segment g at words [d_offsets[g], d_offsets[g] + d_sizes[g])) and writes d_values[symbol] as f32 --
+ * d_freq u16 [T] and d_values f32 [T], T = 2^(N+1) - 1.  Entries of d_freq may be 0 (a table fitted to the data it codes);
+ * every entry must be <= 2^15 - 1 and the row must sum to 2^15.
+ *   d_segments == NULL: every segment, into d_out f32 [n] in stream order (n_sel is not read beyond n_sel >= 0).
+ *   otherwise:          the n_sel listed segment ids (any order, repeats allowed), segment d_segments[i] into
+ *                       d_out[i * seg ...]; d_out holds n_sel * seg values, the last segment writes only its valid length.
+ * Everything but the table sizes is UNTRUSTED: no read leaves [off, off + size) or [0, n_words), no write leaves d_out,
+ * every decoded symbol is below T.  d_status (u32, device, may be NULL; OR-ed into, zero it first): bits 0 - 3 as
+ * vbq_rans_decode_u16 (a segment whose words do not lie in [0, n_words) counts as bit 0; an entry above 2^15 - 1 as bit 3),
+ * bit 5 (32) a listed segment id outside [0, nseg).  Segments with bits 0 / 3 / 5 decode to zeros; with bits 1 / 2 the
+ * output of that segment is meaningless. */
+int vbq_rans_decode_values_f32(const uint16_t *d_payload, int64_t n_words, const uint16_t *d_sizes, const int64_t *d_offsets,
+                               int64_t n, int32_t seg, int32_t N, const uint16_t *d_freq, const float *d_values,
+                               const int64_t *d_segments, int64_t n_sel, float *d_out, uint32_t *d_status, void *stream);
 
 /* ----------------------------------------------------------------------------------
  * Packed counters for the histogram all-reduce: three 21-bit fields per int64 word.

@@ -7,7 +7,8 @@ ROCm device the ops raise.
     vbq_amd.quantize(mu, sigma, lmbda, table=...)          one-call surface (api.py)
     vbq_amd.ChannelwisePriorCDFQuantizer                   img-compression/quantizer.py:13-256
     vbq_amd.utils                                          img-compression/utils.py solvers
-    vbq_amd.embeddings                                     word-embeddings notebook cells 25-30
+    vbq_amd.embeddings                                     word-embeddings notebook cells 25-30; compress_to_bytes / decompress /
+                                                           CompressedEmbeddings: the quantized matrix as rANS-coded bytes, rows on demand
     vbq_amd.priors                                         vae_models.py:14-43, learned_prior.py:6-334
     vbq_amd.dist                                           element-axis sharding + histogram all-reduce
     vbq_amd.LazyArray / vbq_amd.device_tensor              what compress_latents / compress hand out per lambda: ndarray-like views

@@ -3,7 +3,8 @@
 Host-only: writing and strictly validating the header.  The payload is what `RansCodec.pack` returns for the coder's
 streams (one per channel, each holding the B = prod(shape) / C latents of that channel, cut into segments of `segment`
 symbols); the device builds it with vbq_rans_pack_u16 and takes it apart with vbq_rans_unpack_u16 (include/vbq.h).
-ChannelwisePriorCDFQuantizer.compress_latents_to_bytes / decompress_latents are the users.
+ChannelwisePriorCDFQuantizer.compress_latents_to_bytes / decompress_latents are the users.  A second format (magic b"VBQe",
+further down) holds one compressed word-embedding matrix: vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings.
 
 Layout, every field little-endian (version 1):
 
@@ -163,3 +164,172 @@ def parse(data) -> Tuple[Header, np.ndarray, int]:
     sizes = np.frombuffer(mv, dtype="<u2", count=h.n_sizes, offset=hlen)
     _check_sizes(sizes, segment, n_words)
     return h, sizes, hlen + 2 * h.n_sizes
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Second format: ONE compressed word-embedding matrix at ONE beta (vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings).
+#
+# One rANS stream holds every coordinate in row-major order (rows = slices along axis 0), cut into segments of `segment`
+# symbols; by default a segment is a whole number of rows, so that looking up a row decodes only the segment that holds it.
+# The frequency table is fitted to the matrix itself (coder.exact_frequencies: unused symbols get 0), so the file stores
+# only the K symbols with a nonzero frequency.  Layout, every field little-endian (version 1):
+#
+#     offset  size      field
+#     0       4         magic b"VBQe"
+#     4       1         version = 1
+#     5       1         N = max_bits_per_coord (1..10)
+#     6       2         reserved = 0
+#     8       4         segment, symbols per rANS segment (u32, 1..65533)
+#     12      4         K, symbols with a nonzero frequency (u32, 2..T)
+#     16      8         beta (f64, finite, >= 0)
+#     24      8         n_words, payload length in 16-bit words (u64)
+#     32      4         empirical_std (f32, informational: the scale of the code book)
+#     36      4         ndim of the matrix shape (u32, 1..64)
+#     40      8 * ndim  shape (u64 each, every entry >= 1)
+#     ...     8 * K     the sparse table, one 8-byte record per symbol: rank (u16, strictly increasing, < T), frequency
+#                       (u16, 1..2^15 - 1, summing to 2^15), value (f32, finite, non-decreasing with rank)
+#     ...     2 * nseg  segment sizes (u16, each in [2, segment + 2]), nseg = ceil(prod(shape) / segment)
+#     ...     2*n_words payload (u16): the valid words of every segment in order; sum(sizes) == n_words
+#
+# Every part before the sizes is a multiple of 8 bytes long.  `parse_embeddings` raises ValueError with a specific message
+# on anything malformed, never struct.error or IndexError.
+# ---------------------------------------------------------------------------------------------------------------------------
+EMB_MAGIC = b"VBQe"
+EMB_VERSION = 1
+MAX_NDIM = 64
+_EMB_FIXED = struct.Struct("<4sBBHIIdQfI")   # the 40 bytes before the shape
+assert _EMB_FIXED.size == 40
+TABLE_DTYPE = np.dtype([("rank", "<u2"), ("freq", "<u2"), ("value", "<f4")])
+assert TABLE_DTYPE.itemsize == 8
+PROB_ONE = 1 << 15                           # the coder's probability scale (coder.PROB_BITS)
+
+
+@dataclass(frozen=True)
+class EmbeddingHeader:
+    N: int
+    shape: Tuple[int, ...]
+    segment: int
+    beta: float
+    empirical_std: float
+    n_words: int
+    K: int
+
+    @property
+    def n(self) -> int:
+        """Coordinates in the matrix: the length of the one stream."""
+        return math.prod(self.shape)
+
+    @property
+    def row_length(self) -> int:
+        return math.prod(self.shape[1:])
+
+    @property
+    def nseg(self) -> int:
+        return (self.n + self.segment - 1) // self.segment
+
+    @property
+    def nbytes(self) -> int:
+        """Length of the header and the sparse table (where the sizes start)."""
+        return _EMB_FIXED.size + 8 * len(self.shape) + TABLE_DTYPE.itemsize * self.K
+
+
+def _check_emb_fields(N, shape, segment, beta, n_words, K):
+    if not 1 <= N <= MAX_N:
+        raise ValueError(f"N = {N} outside [1, {MAX_N}]")
+    if not 1 <= len(shape) <= MAX_NDIM:
+        raise ValueError(f"matrix shape with {len(shape)} dimensions")
+    if any(d < 1 for d in shape):
+        raise ValueError(f"empty matrix shape {tuple(shape)}")
+    if math.prod(shape) >= 2 ** 62:
+        raise ValueError(f"matrix shape {tuple(shape)} is too large")
+    if not 1 <= segment <= MAX_SEGMENT:
+        raise ValueError(f"segment {segment} outside [1, {MAX_SEGMENT}]")
+    if not (math.isfinite(beta) and beta >= 0):
+        raise ValueError(f"beta {beta} is not finite and >= 0")
+    if n_words < 0:
+        raise ValueError("negative payload length")
+    T = 2 ** (N + 1) - 1
+    if not 2 <= K <= T:
+        raise ValueError(f"K = {K} symbols outside [2, {T}]")
+
+
+def _check_table(table: np.ndarray, N: int):
+    T = 2 ** (N + 1) - 1
+    r = table["rank"].astype(np.int64)
+    f = table["freq"].astype(np.int64)
+    v = table["value"]
+    if np.any(np.diff(r) <= 0):
+        raise ValueError("table ranks are not strictly increasing")
+    if r.size and int(r[-1]) >= T:
+        raise ValueError(f"table rank {int(r[-1])} >= T = {T}")
+    if np.any(f == 0):
+        raise ValueError("table frequency 0 (only symbols with a nonzero frequency are stored)")
+    if np.any(f >= PROB_ONE):
+        raise ValueError(f"table frequency above {PROB_ONE - 1}")
+    if int(f.sum()) != PROB_ONE:
+        raise ValueError(f"table frequencies sum to {int(f.sum())}, not {PROB_ONE}")
+    if not np.all(np.isfinite(v)):
+        raise ValueError("non-finite table value")
+    if np.any(np.diff(v) < 0):
+        raise ValueError("table values decrease with rank")
+
+
+def write_embeddings(header: EmbeddingHeader, table, sizes, payload) -> bytes:
+    """header + table (TABLE_DTYPE [K]) + sizes (any integer array of nseg entries) + payload (u16 [n_words]) -> bytes.
+    Validates as `parse_embeddings` does."""
+    h = header
+    shape = tuple(int(d) for d in h.shape)
+    _check_emb_fields(h.N, shape, h.segment, float(h.beta), h.n_words, h.K)
+    table = np.asarray(table)
+    if table.dtype != TABLE_DTYPE or table.shape != (h.K,):
+        raise ValueError(f"table must be {TABLE_DTYPE} [{h.K}], got {table.dtype} {table.shape}")
+    _check_table(table, h.N)
+    sizes = np.asarray(sizes).reshape(-1)
+    if sizes.size != h.nseg:
+        raise ValueError(f"{sizes.size} segment sizes, the shape needs {h.nseg}")
+    _check_sizes(sizes, h.segment, h.n_words)
+    payload = np.ascontiguousarray(payload, dtype="<u2").reshape(-1)
+    if payload.size != h.n_words:
+        raise ValueError(f"payload of {payload.size} words, the header says {h.n_words}")
+    head = _EMB_FIXED.pack(EMB_MAGIC, EMB_VERSION, h.N, 0, h.segment, h.K, float(h.beta), h.n_words,
+                           float(h.empirical_std), len(shape))
+    return b"".join([head, np.asarray(shape, dtype="<u8").tobytes(), np.ascontiguousarray(table).tobytes(),
+                     sizes.astype("<u2").tobytes(), payload.tobytes()])
+
+
+def parse_embeddings(data) -> Tuple[EmbeddingHeader, np.ndarray, np.ndarray, int]:
+    """bytes -> (header, table TABLE_DTYPE [K], sizes u16 [nseg], byte offset of the payload); the table and the sizes are
+    read-only views into `data`.  ValueError on anything malformed."""
+    mv = memoryview(data).cast("B")
+    if len(mv) < _EMB_FIXED.size:
+        raise ValueError(f"truncated: {len(mv)} bytes, the fixed header alone is {_EMB_FIXED.size}")
+    magic, version, N, reserved, segment, K, beta, n_words, std, ndim = _EMB_FIXED.unpack_from(mv, 0)
+    if magic == MAGIC:
+        raise ValueError("a latent bitstream (magic b'VBQb'), not a compressed embedding matrix")
+    if magic != EMB_MAGIC:
+        raise ValueError(f"not a VBQ embedding bitstream (magic {magic!r})")
+    if version != EMB_VERSION:
+        raise ValueError(f"unknown embedding bitstream version {version}")
+    if reserved != 0:
+        raise ValueError(f"reserved header bytes are {reserved}, not 0")
+    if not 1 <= ndim <= MAX_NDIM:
+        raise ValueError(f"matrix shape with {ndim} dimensions")
+    hlen = _EMB_FIXED.size + 8 * ndim
+    if len(mv) < hlen:
+        raise ValueError(f"truncated in the matrix shape: {len(mv)} bytes, the header is {hlen}")
+    shape = tuple(int(d) for d in np.frombuffer(mv, dtype="<u8", count=ndim, offset=_EMB_FIXED.size))
+    _check_emb_fields(N, shape, segment, beta, n_words, K)
+    h = EmbeddingHeader(N=N, shape=shape, segment=segment, beta=float(beta), empirical_std=float(std), n_words=n_words, K=K)
+    if len(mv) < h.nbytes:
+        raise ValueError(f"truncated in the symbol table: {len(mv)} bytes, header and table need {h.nbytes}")
+    table = np.frombuffer(mv, dtype=TABLE_DTYPE, count=K, offset=hlen)
+    _check_table(table, N)
+    need = h.nbytes + 2 * h.nseg + 2 * n_words
+    if len(mv) < need:
+        raise ValueError(f"truncated: {len(mv)} bytes, header, table, {h.nseg} segment sizes and {n_words} payload words "
+                         f"need {need}")
+    if len(mv) > need:
+        raise ValueError(f"{len(mv) - need} trailing bytes after the payload")
+    sizes = np.frombuffer(mv, dtype="<u2", count=h.nseg, offset=h.nbytes)
+    _check_sizes(sizes, segment, n_words)
+    return h, table, sizes, h.nbytes + 2 * h.nseg

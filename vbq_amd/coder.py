@@ -58,6 +58,49 @@ def quantize_frequencies(counts, add_n_smoothing=1, prob_bits: int = PROB_BITS) 
     return out.reshape(lead + (T,)).astype(np.uint16)
 
 
+def exact_frequencies(counts, prob_bits: int = PROB_BITS) -> np.ndarray:
+    """Counts [T] of the very data a table will code -> uint16 frequencies [T] summing to 2**prob_bits.  Unlike
+    `quantize_frequencies` (a model that must code unseen symbols), a symbol that does not occur gets 0: an embedding
+    matrix is coded with the table fitted to it.  Every nonzero count gets >= 1, no entry exceeds 2**prob_bits - 1 (the
+    encoder divides by f < 2^15): when a single symbol occurs, its neighbour (the next symbol, or the previous one for the
+    last) gets 1.  Deterministic largest-remainder rounding; the leftover slots go to the largest remainders, ties to the
+    lower symbol, and a surplus is taken from the largest entries."""
+    c = np.asarray(counts.cpu().numpy() if isinstance(counts, torch.Tensor) else counts).reshape(-1)
+    if c.size and (c.dtype.kind not in "iu" and not np.all(np.isfinite(c)) or np.any(c < 0)):
+        raise ValueError("counts must be finite and >= 0")
+    c = c.astype(np.int64)
+    T, M = c.size, 1 << prob_bits
+    if T < 2 or T > M:
+        raise ValueError(f"{T} symbols: need 2..{M}")
+    used = np.flatnonzero(c)
+    if used.size == 0:
+        raise ValueError("no symbol occurs: nothing to fit a table to")
+    f = np.zeros(T, dtype=np.int64)
+    if used.size == 1:
+        s = int(used[0])
+        f[s] = M - 1
+        f[s + 1 if s + 1 < T else s - 1] = 1
+        return f.astype(np.uint16)
+    cu = c[used]
+    ideal = cu.astype(np.float64) * (M / float(cu.sum()))
+    fu = np.maximum(1, np.floor(ideal).astype(np.int64))
+    diff = M - int(fu.sum())
+    if diff > 0:                                        # at most len(used) - 1 slots: one to each of the largest remainders
+        order = np.argsort(-(ideal - np.floor(ideal)), kind="stable")
+        fu[order[:diff]] += 1
+    while diff < 0:                                     # the floor of 1 overshot: take from the largest entries, never below 1
+        order = np.argsort(-fu, kind="stable")
+        for j in order:
+            if diff == 0:
+                break
+            take = min(-diff, int(fu[j]) - 1, max(1, int(fu[j]) // 64))
+            fu[j] -= take
+            diff += take
+    f[used] = fu
+    assert int(f.sum()) == M and int(f.max()) < M and np.all((f > 0) == (c > 0))
+    return f.astype(np.uint16)
+
+
 def ideal_bits(counts, freq, prob_bits: int = PROB_BITS) -> float:
     """Cross-entropy of the data under the quantised table: sum counts * -log2(freq / 2^PB)."""
     c = np.asarray(counts.cpu().numpy() if isinstance(counts, torch.Tensor) else counts, dtype=np.float64)
@@ -69,19 +112,25 @@ def _raise_status(st: int):
     if st:
         what = [m for b, m in ((1, "segment size out of range"), (2, "segment ran out of words"),
                                (4, "left-over words / wrong final state"), (8, "invalid frequency table"),
-                               (16, "segment sizes do not add up to the payload length")) if st & b]
+                               (16, "segment sizes do not add up to the payload length"),
+                               (32, "segment id out of range")) if st & b]
         raise _lib.VBQError("rANS bitstream rejected: " + ", ".join(what))
 
 
 class RansCodec:
     """Encoder / decoder for u16 rank indices laid out as streams [S, n] (S = L*C planes of K1)."""
 
-    def __init__(self, freq, N: int = 10, segment: int = DEFAULT_SEGMENT):
+    def __init__(self, freq, N: int = 10, segment: int = DEFAULT_SEGMENT, *, allow_zero: bool = False):
+        """allow_zero=True accepts zero entries (`exact_frequencies`: a table fitted to the data it codes).  Such a table
+        codes only symbols whose entry is nonzero; every entry must then stay below 2**15."""
         f = freq if isinstance(freq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(freq, dtype=np.uint16)))
         T = ops.table_size(N)
         self.freq_host = f.cpu().reshape(-1, T)
         sums = self.freq_host.to(torch.int64).sum(dim=1)
-        if not bool(torch.all(sums == (1 << PROB_BITS))) or int(self.freq_host.to(torch.int64).min()) < 1:
+        if allow_zero:
+            if not bool(torch.all(sums == (1 << PROB_BITS))) or int(self.freq_host.to(torch.int64).max()) >= (1 << PROB_BITS):
+                raise ValueError("every frequency row must sum to 2**15 with every entry below 2**15")
+        elif not bool(torch.all(sums == (1 << PROB_BITS))) or int(self.freq_host.to(torch.int64).min()) < 1:
             raise ValueError("every frequency row must be >= 1 and sum to 2**15")
         self.N, self.segment, self.T = N, int(segment), T
         self._freq_dev: Optional[torch.Tensor] = None

@@ -359,3 +359,169 @@ extern "C" int vbq_rans_unpack_u16(const uint16_t *d_payload, int64_t n_words, c
     }
     return VBQ_OK;
 }
+
+namespace vbq {
+namespace {
+
+// ---- row-wise decode of the embedding container (vbq_amd/bitstream.py, VBQe): ONE stream read straight from its packed
+// payload into f32 values, without the padded layout of vbq_rans_unpack_u16 and without a u16 index array.
+//   k_fill_offsets        after k_scan_groups<true, uint16_t>: every segment's exclusive offset, not only the group starts (one
+//                         thread per segment adds the <= 15 sizes before it in its group to the group's offset)
+//   k_rans_decode_values  one lane per segment as k_rans_decode; the decoded rank indexes a value table in LDS.  The frequency
+//                         table may hold zeros (a model fitted to the data it codes: coder.exact_frequencies); the slot search
+//                         then still ends on the one symbol whose slot range holds the slot, as every empty range is skipped.
+constexpr int kFillThreads = 256;
+constexpr int kValThreads = 64;                                  // one wave: the table staging scans with wave shuffles alone
+
+__global__ void __launch_bounds__(kFillThreads)
+k_fill_offsets(const uint16_t *__restrict__ sizes, long M, int seg, int64_t *__restrict__ offs) {
+    const long g = (long)blockIdx.x * kFillThreads + threadIdx.x;
+    if (g >= M) return;
+    const long g0 = g - g % kGroup;
+    if (g == g0) return;                                         // the group's own entry: written by k_scan_groups
+    unsigned bad = 0;                                            // (reported by the scan already)
+    long off = (long)offs[g0];
+    for (long i = g0; i < g; ++i) off += segment_size<true>(sizes, i, seg, bad);
+    offs[g] = off;
+}
+
+// Untrusted input as k_rans_decode, plus: a segment whose words [off, off + size) do not lie inside [0, n_words) counts as a bad
+// size (bit 0), an entry of the frequency table above 2^15 - 1 makes the table invalid (bit 3), a listed segment id outside
+// [0, nseg) sets bit 5 (32).  Segments with bits 0 / 3 / 5 decode to zeros.
+__global__ void __launch_bounds__(kValThreads)
+k_rans_decode_values(const uint16_t *__restrict__ payload, long n_words, const uint16_t *__restrict__ sizes,
+                     const int64_t *__restrict__ offs, long n, int T, int seg, long nseg, const uint16_t *__restrict__ freq,
+                     const float *__restrict__ values, const int64_t *__restrict__ segs, long count, float *__restrict__ out,
+                     uint32_t *__restrict__ status) {
+    __shared__ uint32_t fc_l[2048];
+    __shared__ uint16_t c_l[2048 + 2];
+    __shared__ uint16_t start[(1 << kPB) / 16];                  // start[b] = the symbol whose slot range holds slot 16 b
+    __shared__ float val_l[2048];
+    const int lane = threadIdx.x;
+    const int per = (T + kValThreads - 1) / kValThreads;
+    const int i0 = min(T, lane * per), i1 = min(T, (lane + 1) * per);
+    unsigned sum = 0;
+    bool big = false;
+    for (int i = i0; i < i1; ++i) {
+        const unsigned f = freq[i];
+        fc_l[i] = f;
+        val_l[i] = values[i];
+        sum += f;
+        big |= f >= (1u << kPB);
+    }
+    unsigned incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+    }
+    const bool table_ok = __shfl(incl, 63, 64) == (1u << kPB) && !__any(big);
+    if (table_ok) {                                              // every partial sum <= 2^15: c fits in 16 bits
+        unsigned run = incl - sum;
+        for (int i = i0; i < i1; ++i) {
+            const unsigned f = fc_l[i];
+            fc_l[i] = f | (run << 16);
+            c_l[i] = (uint16_t)run;
+            for (unsigned b = (run + 15u) >> 4; 16u * b < run + f; ++b) start[b] = (uint16_t)i;   // the ranges tile [0, 2^15)
+            run += f;
+        }
+        if (lane == 63) c_l[T] = (uint16_t)(1u << kPB);          // > every slot: ends the walk below T
+    }
+    __syncthreads();
+    const long t = (long)blockIdx.x * kValThreads + lane;
+    if (t >= count) return;
+    const long g = segs ? segs[t] : t;
+    float *dst = out + t * (long)seg;
+    if (g < 0 || g >= nseg) {                                    // (only a listed id can be out of range)
+        for (int j = 0; j < seg; ++j) dst[j] = 0.0f;
+        if (status) atomicOr(status, 32u);
+        return;
+    }
+    const long a = g * (long)seg;
+    const int len = (int)(a + seg < n ? seg : n - a);
+    unsigned bad = table_ok ? 0u : 8u;
+    const unsigned k0 = sizes[g];
+    const long off = offs[g];
+    if (k0 < 2u || k0 > (unsigned)seg + 2u || off < 0 || off > n_words - (long)k0) bad |= 1u;
+    if (bad) {
+        for (int j = 0; j < len; ++j) dst[j] = 0.0f;
+        if (status) atomicOr(status, bad);
+        return;
+    }
+    const uint16_t *in = payload + off;                          // reads stay in [off, off + k0) within [0, n_words)
+    int k = (int)k0;
+    unsigned x = ((unsigned)in[k - 1] << 16) | in[k - 2];
+    k -= 2;
+    bool starved = false;
+    auto get = [&]() -> float {                                  // one value; after a starved stream: the value of symbol 0
+        if (starved) return val_l[0];
+        const unsigned slot = x & ((1u << kPB) - 1u);
+        unsigned sym = start[slot >> 4];                         // last symbol with cum <= slot
+        while (c_l[sym + 1] <= slot) ++sym;
+        const unsigned fc = fc_l[sym];
+        x = (fc & 0xffffu) * (x >> kPB) + slot - (fc >> 16);
+        if (x < kRansL) {
+            if (k == 0) { bad |= 2u; starved = true; }
+            else x = (x << 16) | in[--k];
+        }
+        return val_l[sym];
+    };
+    int j = 0;
+    // four values per 16-byte store where every segment's slot starts 16-byte aligned
+    if (seg % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
+        for (; j + 4 <= len; j += 4) {
+            float4 v;
+            v.x = get(); v.y = get(); v.z = get(); v.w = get();
+            *reinterpret_cast<float4 *>(dst + j) = v;
+        }
+    }
+    for (; j < len; ++j) dst[j] = get();
+    if (!bad && (k != 0 || x != kRansL)) bad |= 4u;
+    if (bad && status) atomicOr(status, bad);
+}
+
+}  // namespace
+}  // namespace vbq
+
+extern "C" int vbq_rans_segment_offsets_u16(const uint16_t *d_sizes, int64_t M, int32_t seg, int64_t n_words,
+                                            int64_t *d_offsets, uint32_t *d_status, void *stream) {
+    using namespace vbq;
+    VBQ_REQUIRE(M >= 0 && n_words >= 0 && seg >= 1 && seg <= 65533, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_segment_offsets_u16: bad sizes M=%lld seg=%d n_words=%lld", (long long)M, seg, (long long)n_words);
+    VBQ_REQUIRE(M == 0 || (d_sizes && d_offsets), VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_segment_offsets_u16: null pointer argument");
+    VBQ_REQUIRE((M + kFillThreads - 1) / kFillThreads <= INT32_MAX, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_segment_offsets_u16: %lld segments are too many", (long long)M);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_groups<true, uint16_t>), dim3(1), dim3(kScanThreads), 0, st, d_sizes, (long)M,
+                       (int)seg, (long)n_words, d_offsets, nullptr, d_status);
+    VBQ_CHECK_LAUNCH("rans_segment_offsets (scan)");
+    if (M > 1) {
+        hipLaunchKernelGGL(k_fill_offsets, dim3((unsigned)((M + kFillThreads - 1) / kFillThreads)), dim3(kFillThreads), 0, st,
+                           d_sizes, (long)M, (int)seg, d_offsets);
+        VBQ_CHECK_LAUNCH("rans_segment_offsets (fill)");
+    }
+    return VBQ_OK;
+}
+
+extern "C" int vbq_rans_decode_values_f32(const uint16_t *d_payload, int64_t n_words, const uint16_t *d_sizes,
+                                          const int64_t *d_offsets, int64_t n, int32_t seg, int32_t N, const uint16_t *d_freq,
+                                          const float *d_values, const int64_t *d_segments, int64_t n_sel, float *d_out,
+                                          uint32_t *d_status, void *stream) {
+    using namespace vbq;
+    VBQ_REQUIRE(n_words >= 0 && n >= 0 && seg >= 1 && seg <= 65533 && N >= 1 && N <= 10 && n_sel >= 0,
+                VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_decode_values_f32: bad sizes n_words=%lld n=%lld seg=%d N=%d n_sel=%lld",
+                (long long)n_words, (long long)n, seg, N, (long long)n_sel);
+    const int64_t nseg = (n + seg - 1) / seg;
+    const int64_t count = d_segments ? n_sel : nseg;
+    if (count == 0) return VBQ_OK;
+    VBQ_REQUIRE(d_sizes && d_offsets && d_freq && d_values && d_out, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_decode_values_f32: null pointer argument");
+    VBQ_REQUIRE(n_words == 0 || d_payload, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_decode_values_f32: null d_payload");
+    VBQ_REQUIRE((count + kValThreads - 1) / kValThreads <= INT32_MAX, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_decode_values_f32: %lld segments are too many", (long long)count);
+    hipLaunchKernelGGL(k_rans_decode_values, dim3((unsigned)((count + kValThreads - 1) / kValThreads)), dim3(kValThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), d_payload, (long)n_words, d_sizes, d_offsets, (long)n,
+                       table_size(N), (int)seg, (long)nseg, d_freq, d_values, d_segments, (long)count, d_out, d_status);
+    VBQ_CHECK_LAUNCH("rans_decode_values");
+    return VBQ_OK;
+}

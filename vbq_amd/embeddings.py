@@ -7,15 +7,17 @@
     empirical_entropy(values)                    ipynb:452-455   (K2 histogram when indices are given)
     prediction_ranks(emb, analogies_id)          ipynb:199-209   (fused f32 MFMA GEMM + count, vbq_ranks.hip)
     test_beta / test_betas / quantize_coordinates / test_quantization   ipynb:464-473, cells 32, 36-37
+    compress_to_bytes / decompress / CompressedEmbeddings    (ours) the quantized matrix as a real byte string (rANS,
+                                                             vbq_amd.bitstream "VBQe") and row-wise lookups from it
 """
 from __future__ import annotations
 
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from ._lib import VBQError
 
 
@@ -205,3 +207,156 @@ def test_beta(means, stds, beta, codepoints, analogies_id=None):
     else:
         ranks = prediction_ranks(compressed.reshape(np.shape(means)), analogies_id)
     return analogy_metrics(ranks) + (bits,)
+
+
+# ------------------------------------------------------------------------ compressed byte string (vbq_amd.bitstream, "VBQe")
+_LOOKUP_SYMBOLS = 1024                       # the default segment: a whole number of rows near this many symbols
+_Q75 = 0.6744897501960817                    # norm.ppf(0.75): the level-1 code points of make_code_book are -/+ std * this
+
+
+def default_segment(row_length: int) -> int:
+    """A whole number of rows near 1024 symbols (so that a row lookup decodes exactly one segment), or 1024 for rows
+    longer than the format's largest segment."""
+    from .bitstream import MAX_SEGMENT
+    D = int(row_length)
+    return max(1, _LOOKUP_SYMBOLS // D) * D if D <= MAX_SEGMENT else _LOOKUP_SYMBOLS
+
+
+def compress_to_bytes(means, stds, beta, codepoints, *, segment=None) -> bytes:
+    """The matrix `compress_coordinates(means, stds, beta, codepoints=codepoints)` as a self-describing byte string:
+    K1n's rank indices, one K2 histogram, ONE device-to-host copy of the counts, a table fitted to them
+    (coder.exact_frequencies), then rANS encode + pack on the device.  `decompress` / `CompressedEmbeddings` read it.
+    Rows are the slices along axis 0; `segment` (symbols per rANS segment) defaults to `default_segment(row length)`."""
+    from . import bitstream as bs, coder, tables
+    cp = np.asarray(codepoints, dtype=np.float64).reshape(-1)
+    N = int(np.log2(cp.size + 1)) - 1
+    if not 1 <= N <= bs.MAX_N or cp.size != tables.table_size(N):
+        raise ValueError(f"a code book of {cp.size} points: need 2^(N+1) - 1 of them with N in 1..{bs.MAX_N}")
+    beta = float(beta)
+    if not (np.isfinite(beta) and beta >= 0):
+        raise ValueError(f"beta {beta} is not finite and >= 0")
+    shape = tuple(int(d) for d in np.shape(means)) or (1,)
+    n = int(np.prod(shape))
+    if n == 0:
+        raise ValueError("an empty matrix has no compressed form")
+    seg = default_segment(int(np.prod(shape[1:]))) if segment is None else int(segment)
+    if not 1 <= seg <= bs.MAX_SEGMENT:
+        raise ValueError(f"segment {seg} outside [1, {bs.MAX_SEGMENT}]")
+    idx, _ = compress_coordinates_sweep(means, stds, [beta], cp, want_values=False)
+    idx = idx.reshape(1, n)
+    counts = ops.histogram(idx, 1, N=N).cpu().numpy().reshape(-1)
+    freq = coder.exact_frequencies(counts)
+    sizes, payload = coder.RansCodec(freq, N=N, segment=seg, allow_zero=True).encode_packed(idx)
+    ranks = np.flatnonzero(freq)
+    table = np.empty(ranks.size, dtype=bs.TABLE_DTYPE)
+    table["rank"] = ranks
+    table["freq"] = freq[ranks]
+    table["value"] = tables.level_major_to_sorted(cp).astype(np.float32)[ranks]   # what K1n writes: (float) code point
+    h = bs.EmbeddingHeader(N=N, shape=shape, segment=seg, beta=beta, empirical_std=float(np.float32(cp[2] / _Q75)),
+                           n_words=int(payload.size), K=int(ranks.size))
+    return bs.write_embeddings(h, table, sizes, payload)
+
+
+class CompressedEmbeddings:
+    """A compressed embedding matrix ("VBQe" bytes) on the device.  The header and table are validated on the host; the
+    payload, sizes and segment offsets are uploaded and checked ONCE here, so a damaged size raises at load time.  Then
+    `rows(ids)` decodes only the segments that hold the requested rows (one launch) and `tensor()` the whole matrix."""
+
+    def __init__(self, data, device=None):
+        from . import bitstream as bs, coder
+        h, table, _, _ = bs.parse_embeddings(data)
+        raw = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
+        self.header = h
+        self.nbytes = int(raw.size)
+        self.device = torch.device(device) if device is not None else _device()
+        T = 2 ** (h.N + 1) - 1
+        # ONE upload: dense freq u16 [T] (+ 2 bytes: the values stay 4-byte aligned), values f32 [T], sizes u16 [nseg],
+        # payload u16 [n_words] (the last two straight from the file)
+        fb, vb = 2 * T + 2, 4 * T
+        host = np.zeros(fb + vb + raw.size - h.nbytes, np.uint8)
+        host[:2 * T].view(np.uint16)[table["rank"]] = table["freq"]
+        host[fb:fb + vb].view(np.float32)[table["rank"]] = table["value"]
+        host[fb + vb:] = raw[h.nbytes:]
+        dev = torch.from_numpy(host).to(self.device)
+        self._freq = dev[:2 * T].view(torch.uint16)
+        self._values = dev[fb:fb + vb].view(torch.float32)
+        self._sizes = dev[fb + vb:fb + vb + 2 * h.nseg].view(torch.uint16)
+        self._payload = dev[fb + vb + 2 * h.nseg:].view(torch.uint16)
+        self._offsets = torch.empty(h.nseg, dtype=torch.int64, device=self.device)
+        status = torch.zeros(1, dtype=torch.uint32, device=self.device)
+        _lib.check(_lib.lib().vbq_rans_segment_offsets_u16(ops._ptr(self._sizes), h.nseg, h.segment, h.n_words,
+                                                            ops._ptr(self._offsets), ops._ptr(status), ops._stream(dev)),
+                   "vbq_rans_segment_offsets_u16")
+        coder._raise_status(int(status.cpu().item()))
+
+    @property
+    def shape(self):
+        return self.header.shape
+
+    @property
+    def beta(self) -> float:
+        return self.header.beta
+
+    @property
+    def bits_per_coordinate(self) -> float:
+        """The whole byte string (header and table included) in bits per coordinate."""
+        return 8.0 * self.nbytes / self.header.n
+
+    def _decode(self, segments: Optional[torch.Tensor], out: torch.Tensor):
+        from . import coder
+        h = self.header
+        status = torch.zeros(1, dtype=torch.uint32, device=self.device)
+        _lib.check(_lib.lib().vbq_rans_decode_values_f32(
+            ops._ptr(self._payload), h.n_words, ops._ptr(self._sizes), ops._ptr(self._offsets), h.n, h.segment, h.N,
+            ops._ptr(self._freq), ops._ptr(self._values), ops._ptr(segments), 0 if segments is None else segments.numel(),
+            ops._ptr(out), ops._ptr(status), ops._stream(out)), "vbq_rans_decode_values_f32")
+        coder._raise_status(int(status.cpu().item()))
+
+    def tensor(self) -> torch.Tensor:
+        """The whole matrix, f32 on the device, shaped like the compressed array."""
+        out = torch.empty(self.header.n, dtype=torch.float32, device=self.device)
+        self._decode(None, out)
+        return out.view(self.header.shape)
+
+    def rows(self, ids) -> torch.Tensor:
+        """Rows `ids` (any order, repeats allowed) -> f32 device tensor [len(ids), *shape[1:]].  IndexError outside [0, V)."""
+        h = self.header
+        V, D, seg = h.shape[0], h.row_length, h.segment
+        ids = np.asarray(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids)
+        if ids.ndim != 1:
+            raise ValueError(f"ids must be one-dimensional, got shape {ids.shape}")
+        if ids.size and ids.dtype.kind not in "iu":
+            raise IndexError(f"row ids must be integers, got {ids.dtype}")
+        ids = ids.astype(np.int64)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= V):
+            raise IndexError(f"row {int(ids[(ids < 0) | (ids >= V)][0])} outside [0, {V})")
+        out_shape = (ids.size,) + tuple(h.shape[1:])
+        if ids.size == 0:
+            return torch.empty(out_shape, dtype=torch.float32, device=self.device)
+        first = ids * D // seg
+        if seg % D == 0:                                            # whole rows per segment (the default): gather rows
+            uniq, slot = np.unique(first, return_inverse=True)
+            per = seg // D
+            dev = torch.from_numpy(np.concatenate([uniq, slot.reshape(-1) * per + ids * D % seg // D])).to(self.device)
+            buf = torch.empty(uniq.size * seg, dtype=torch.float32, device=self.device)
+            self._decode(dev[:uniq.size], buf)
+            return buf.view(uniq.size * per, D).index_select(0, dev[uniq.size:]).view(out_shape)
+        last = (ids * D + D - 1) // seg                             # rows straddle segments: gather coordinates
+        cand = first[:, None] + np.arange(int((last - first).max()) + 1)[None, :]
+        uniq = np.unique(cand[cand <= last[:, None]])
+        dev = torch.from_numpy(np.concatenate([uniq, ids])).to(self.device)
+        segs, rid = dev[:uniq.size], dev[uniq.size:]
+        buf = torch.empty(uniq.size * seg, dtype=torch.float32, device=self.device)
+        self._decode(segs, buf)
+        slot_of = torch.zeros(h.nseg, dtype=torch.int64, device=self.device)
+        slot_of[segs] = torch.arange(uniq.size, dtype=torch.int64, device=self.device)
+        e = rid[:, None] * D + torch.arange(D, dtype=torch.int64, device=self.device)[None, :]
+        return buf[(slot_of[e // seg] * seg + e % seg).reshape(-1)].view(out_shape)
+
+
+def decompress(data, return_np: bool = True):
+    """`compress_to_bytes` inverted: the quantized matrix (f32, bit for bit what compress_coordinates returns), as a NumPy
+    array or (return_np=False) a device tensor.  A damaged byte string raises ValueError (header, table, sizes) or
+    VBQError (payload)."""
+    t = CompressedEmbeddings(data).tensor()
+    return t.cpu().numpy() if return_np else t
