@@ -491,6 +491,13 @@ int vbq_bmshj_nll_grad_f32(const float *d_params, const float *d_x_cb, int64_t n
  * ---------------------------------------------------------------------------------- */
 int vbq_rans_encode_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t seg,
                         const uint16_t *d_freq, uint16_t *d_words, uint32_t *d_sizes, void *stream);
+/* vbq_rans_sizes_u16: the d_sizes of vbq_rans_encode_u16 for the same arguments, entry by entry, without the words -- the
+ * same state machine, renormalisation and final-state flush, storing only u32 [n_streams][nseg] (no d_words buffer of
+ * n_streams * nseg * (seg + 2) u16): the exact coded length of every segment.  d_freq may hold entries of 0 for symbols
+ * that do not occur (a table fitted to the data it codes, as vbq_rans_decode_values_f32 reads); an index outside the
+ * table is read safely, as in the encoder.  Added without an ABI version bump: nothing that existed before changed. */
+int vbq_rans_sizes_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t seg, const uint16_t *d_freq,
+                       uint32_t *d_sizes, void *stream);
 /* Decoding treats words / sizes as UNTRUSTED: no read leaves a segment's seg + 2 words, every decoded index is
  * below T, and d_status (u32, device, may be NULL; OR-ed into, zero it first) reports what was wrong --
  * bit 0 a segment size outside [2, seg + 2], bit 1 a segment that ran out of words, bit 2 words left over or a

@@ -5,6 +5,8 @@ streams (one per channel, each holding the B = prod(shape) / C latents of that c
 symbols); the device builds it with vbq_rans_pack_u16 and takes it apart with vbq_rans_unpack_u16 (include/vbq.h).
 ChannelwisePriorCDFQuantizer.compress_latents_to_bytes / decompress_latents are the users.  A second format (magic b"VBQe",
 further down) holds one compressed word-embedding matrix: vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings.
+latent_nbytes / embeddings_nbytes give the exact length of either file without building it, and smallest_rate_within is the
+byte-budget rule of the rate-control calls (coded_nbytes / *_to_budget on the quantizer and in vbq_amd.embeddings).
 
 Layout, every field little-endian (version 1):
 
@@ -132,6 +134,15 @@ def write(header: Header, sizes, payload) -> bytes:
         raise ValueError(f"payload of {payload.size} words, the header says {h.n_words}")
     head = _FIXED.pack(MAGIC, VERSION, h.N, len(shape), 0, h.C, h.segment, float(h.lamb), h.n_words, h.digest)
     return b"".join([head, np.asarray(shape, dtype="<u8").tobytes(), sizes.astype("<u2").tobytes(), payload.tobytes()])
+
+
+def latent_nbytes(shape, C, segment, n_words) -> int:
+    """len(write(...)) of a latent tensor of `shape` (channel-last, C channels) in segments of `segment` symbols with a payload
+    of n_words 16-bit words, without building the file.  ValueError for fields `write` rejects."""
+    shape = tuple(int(d) for d in shape)
+    h = Header(N=MAX_N, C=int(C), shape=shape, lamb=0.0, segment=int(segment), digest=bytes(16), n_words=int(n_words))
+    _check_fields(h.N, h.C, shape, h.lamb, h.segment, h.digest, h.n_words)
+    return h.nbytes + 2 * h.n_sizes + 2 * h.n_words
 
 
 def parse(data) -> Tuple[Header, np.ndarray, int]:
@@ -295,6 +306,43 @@ def write_embeddings(header: EmbeddingHeader, table, sizes, payload) -> bytes:
                            float(h.empirical_std), len(shape))
     return b"".join([head, np.asarray(shape, dtype="<u8").tobytes(), np.ascontiguousarray(table).tobytes(),
                      sizes.astype("<u2").tobytes(), payload.tobytes()])
+
+
+def embeddings_nbytes(shape, segment, K, n_words) -> int:
+    """len(write_embeddings(...)) of a matrix of `shape` in segments of `segment` symbols, with K symbols in the table and a
+    payload of n_words 16-bit words, without building the file.  ValueError for fields `write_embeddings` rejects."""
+    shape = tuple(int(d) for d in shape)
+    h = EmbeddingHeader(N=MAX_N, shape=shape, segment=int(segment), beta=0.0, empirical_std=0.0, n_words=int(n_words), K=int(K))
+    _check_emb_fields(h.N, shape, h.segment, h.beta, h.n_words, h.K)
+    return h.nbytes + 2 * h.nseg + 2 * h.n_words
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Rate control: the file of a byte budget.  One model serves every rate; a caller measures the exact length at each candidate
+# rate (lambda or beta) and keeps the numerically SMALLEST candidate whose file fits.  The rule does not assume the length falls
+# as the rate grows -- it usually does, not always -- so it is well defined on any set of candidates.
+# ---------------------------------------------------------------------------------------------------------------------------
+def check_budget(max_bytes) -> int:
+    """max_bytes as an int: an integer >= 1 (bool and floats are rejected, TypeError; values below 1, ValueError)."""
+    if isinstance(max_bytes, (bool, np.bool_)) or not isinstance(max_bytes, (int, np.integer)):
+        raise TypeError(f"max_bytes must be an integer, got {type(max_bytes).__name__}")
+    if max_bytes < 1:
+        raise ValueError(f"max_bytes = {max_bytes}: a budget needs at least one byte")
+    return int(max_bytes)
+
+
+def smallest_rate_within(nbytes, max_bytes, name: str = "lambda"):
+    """The numerically smallest key of `nbytes` (a mapping rate -> exact file length) whose length is <= max_bytes.  ValueError
+    naming the smallest achievable length and its rate when none fits."""
+    budget = check_budget(max_bytes)
+    items = [(float(r), int(b), r) for r, b in nbytes.items()]
+    if not items:
+        raise ValueError(f"no candidate {name} to choose from")
+    fits = [it for it in items if it[1] <= budget]
+    if fits:
+        return min(fits, key=lambda it: it[0])[2]
+    _, least, rate = min(items, key=lambda it: (it[1], it[0]))
+    raise ValueError(f"no {name} fits in {budget} bytes: the smallest file is {least} bytes, at {name} = {float(rate)!r}")
 
 
 def parse_embeddings(data) -> Tuple[EmbeddingHeader, np.ndarray, np.ndarray, int]:

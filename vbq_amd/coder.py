@@ -155,6 +155,20 @@ class RansCodec:
                                              ops._ptr(words), ops._ptr(sizes), ops._stream(idx)), "vbq_rans_encode_u16")
         return words, sizes
 
+    def sizes(self, idx: torch.Tensor) -> torch.Tensor:
+        """The sizes `encode` returns -- u32 [S, nseg], 16-bit words per segment -- without the words (vbq_rans_sizes_u16): the
+        exact coded length of every segment at 4 bytes of output per segment instead of a padded word buffer."""
+        idx = ops._dev(idx, torch.uint16, "idx")
+        n = idx.shape[-1]
+        S = idx.numel() // max(n, 1)
+        if S != self.freq_host.shape[0]:
+            raise ValueError(f"{S} index streams but {self.freq_host.shape[0]} frequency rows")
+        nseg = (n + self.segment - 1) // self.segment
+        sizes = torch.zeros((S, nseg), dtype=torch.uint32, device=idx.device)
+        check(_lib.lib().vbq_rans_sizes_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(idx.device)),
+                                            ops._ptr(sizes), ops._stream(idx)), "vbq_rans_sizes_u16")
+        return sizes
+
     def decode(self, words: torch.Tensor, sizes: torch.Tensor, n: int) -> torch.Tensor:
         """words / sizes are untrusted (they may come from a file): shapes are checked here, segment sizes and
         word counts in the kernel; a damaged stream raises VBQError instead of returning garbage."""

@@ -95,6 +95,46 @@ k_rans_encode(const uint16_t *__restrict__ idx, long n, int T, int seg, int nseg
     sizes[s * nseg + g] = (uint32_t)k;
 }
 
+// The sizes k_rans_encode writes, without the words: the same state machine, renormalisation and final-state flush over the same
+// symbols in the same order (the same 16-byte loads where the layout allows them), storing only the count k of every segment --
+// the exact coded length without a (seg + 2)-word buffer per segment.  (The encoder keeps its own copy of these lines: moving its
+// body into a helper shared by both kernels, templated on the word stores, changed the register allocation of k_rans_encode --
+// one more v_mov on every renormalisation -- and its ISA is pinned; tests/test_gpu_budget.py pins the two kernels' sizes to each
+// other and to the C checker element by element.)
+__global__ void __launch_bounds__(kRansThreads)
+k_rans_sizes(const uint16_t *__restrict__ idx, long n, int T, int seg, int nseg, const uint16_t *__restrict__ freq,
+             uint32_t *__restrict__ sizes) {
+    __shared__ uint32_t fc_l[2048];
+    const long s = blockIdx.y;                                   // stream
+    stage_tables(freq + s * T, T, fc_l, nullptr);
+    const int g = blockIdx.x * kRansThreads + threadIdx.x;       // segment within the stream
+    if (g >= nseg) return;
+    const long a = (long)g * seg;
+    const long b = a + seg < n ? a + seg : n;
+    const uint16_t *src = idx + s * n;
+    unsigned x = kRansL;
+    int k = 0;
+    auto put = [&](unsigned sym) {
+        const unsigned fc = fc_l[sym < (unsigned)T ? sym : 0u];  // (an index outside the table: memory-safe, as in the encoder)
+        const unsigned f = fc & 0xffffu, c = fc >> 16;
+        if (x >= (f << (32 - kPB))) { ++k; x >>= 16; }
+        unsigned q, r;
+        divmod_small(x, f, q, r);
+        x = (q << kPB) + r + c;
+    };
+    long i = b;
+    const bool vec = ((seg | n) % 8 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
+    if (vec) {
+        for (; i - 8 >= a; i -= 8) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(src + i - 8);
+            put(v.w >> 16); put(v.w & 0xffffu); put(v.z >> 16); put(v.z & 0xffffu);
+            put(v.y >> 16); put(v.y & 0xffffu); put(v.x >> 16); put(v.x & 0xffffu);
+        }
+    }
+    for (--i; i >= a; --i) put(src[i]);
+    sizes[s * nseg + g] = (uint32_t)(k + 2);                     // + the final state's two words
+}
+
 // Untrusted input: the segment sizes and words may come from a damaged or foreign file.  Every read is kept
 // inside the segment's (seg + 2)-word buffer and every decoded symbol below T; what is wrong is reported in
 // *status (bit 0: a segment size outside [2, seg + 2]; bit 1: a segment ran out of words; bit 2: words left
@@ -290,6 +330,24 @@ extern "C" int vbq_rans_encode_u16(const uint16_t *d_idx, int64_t n_streams, int
                        dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream), d_idx, (long)n, table_size(N), (int)seg,
                        (int)nseg, d_freq, d_words, d_sizes);
     VBQ_CHECK_LAUNCH("rans_encode");
+    return VBQ_OK;
+}
+
+extern "C" int vbq_rans_sizes_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t seg,
+                                  const uint16_t *d_freq, uint32_t *d_sizes, void *stream) {
+    using namespace vbq;
+    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && N >= 1 && N <= 10 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
+                VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_sizes_u16: bad sizes n_streams=%lld n=%lld N=%d seg=%d",
+                (long long)n_streams, (long long)n, N, seg);
+    if (n_streams == 0 || n == 0) return VBQ_OK;
+    VBQ_REQUIRE(d_idx && d_freq && d_sizes, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_sizes_u16: null pointer argument");
+    const int64_t nseg = (n + seg - 1) / seg;
+    VBQ_REQUIRE(nseg <= INT32_MAX, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_sizes_u16: %lld segments per stream are too many",
+                (long long)nseg);
+    hipLaunchKernelGGL(k_rans_sizes, dim3((unsigned)((nseg + kRansThreads - 1) / kRansThreads), (unsigned)n_streams),
+                       dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream), d_idx, (long)n, table_size(N), (int)seg,
+                       (int)nseg, d_freq, d_sizes);
+    VBQ_CHECK_LAUNCH("rans_sizes");
     return VBQ_OK;
 }
 

@@ -9,6 +9,7 @@
     test_beta / test_betas / quantize_coordinates / test_quantization   ipynb:464-473, cells 32, 36-37
     compress_to_bytes / decompress / CompressedEmbeddings    (ours) the quantized matrix as a real byte string (rANS,
                                                              vbq_amd.bitstream "VBQe") and row-wise lookups from it
+    coded_nbytes / compress_to_budget                        (ours) the exact file length at every beta; the file of a byte budget
 """
 from __future__ import annotations
 
@@ -222,19 +223,13 @@ def default_segment(row_length: int) -> int:
     return max(1, _LOOKUP_SYMBOLS // D) * D if D <= MAX_SEGMENT else _LOOKUP_SYMBOLS
 
 
-def compress_to_bytes(means, stds, beta, codepoints, *, segment=None) -> bytes:
-    """The matrix `compress_coordinates(means, stds, beta, codepoints=codepoints)` as a self-describing byte string:
-    K1n's rank indices, one K2 histogram, ONE device-to-host copy of the counts, a table fitted to them
-    (coder.exact_frequencies), then rANS encode + pack on the device.  `decompress` / `CompressedEmbeddings` read it.
-    Rows are the slices along axis 0; `segment` (symbols per rANS segment) defaults to `default_segment(row length)`."""
-    from . import bitstream as bs, coder, tables
+def _file_args(means, codepoints, segment):
+    """(code book f64 [T], N, shape, n coordinates, segment) of a compressed file, validated."""
+    from . import bitstream as bs, tables
     cp = np.asarray(codepoints, dtype=np.float64).reshape(-1)
     N = int(np.log2(cp.size + 1)) - 1
     if not 1 <= N <= bs.MAX_N or cp.size != tables.table_size(N):
         raise ValueError(f"a code book of {cp.size} points: need 2^(N+1) - 1 of them with N in 1..{bs.MAX_N}")
-    beta = float(beta)
-    if not (np.isfinite(beta) and beta >= 0):
-        raise ValueError(f"beta {beta} is not finite and >= 0")
     shape = tuple(int(d) for d in np.shape(means)) or (1,)
     n = int(np.prod(shape))
     if n == 0:
@@ -242,6 +237,24 @@ def compress_to_bytes(means, stds, beta, codepoints, *, segment=None) -> bytes:
     seg = default_segment(int(np.prod(shape[1:]))) if segment is None else int(segment)
     if not 1 <= seg <= bs.MAX_SEGMENT:
         raise ValueError(f"segment {seg} outside [1, {bs.MAX_SEGMENT}]")
+    return cp, N, shape, n, seg
+
+
+def _check_beta(beta) -> float:
+    beta = float(beta)
+    if not (np.isfinite(beta) and beta >= 0):
+        raise ValueError(f"beta {beta} is not finite and >= 0")
+    return beta
+
+
+def compress_to_bytes(means, stds, beta, codepoints, *, segment=None) -> bytes:
+    """The matrix `compress_coordinates(means, stds, beta, codepoints=codepoints)` as a self-describing byte string:
+    K1n's rank indices, one K2 histogram, ONE device-to-host copy of the counts, a table fitted to them
+    (coder.exact_frequencies), then rANS encode + pack on the device.  `decompress` / `CompressedEmbeddings` read it.
+    Rows are the slices along axis 0; `segment` (symbols per rANS segment) defaults to `default_segment(row length)`."""
+    from . import bitstream as bs, coder, tables
+    cp, N, shape, n, seg = _file_args(means, codepoints, segment)
+    beta = _check_beta(beta)
     idx, _ = compress_coordinates_sweep(means, stds, [beta], cp, want_values=False)
     idx = idx.reshape(1, n)
     counts = ops.histogram(idx, 1, N=N).cpu().numpy().reshape(-1)
@@ -255,6 +268,50 @@ def compress_to_bytes(means, stds, beta, codepoints, *, segment=None) -> bytes:
     h = bs.EmbeddingHeader(N=N, shape=shape, segment=seg, beta=beta, empirical_std=float(np.float32(cp[2] / _Q75)),
                            n_words=int(payload.size), K=int(ranks.size))
     return bs.write_embeddings(h, table, sizes, payload)
+
+
+# ------------------------------------------------------------------------ rate control: exact file lengths, byte budgets
+NOTEBOOK_BETAS = [float(b) for b in np.exp(np.linspace(np.log(0.01), np.log(1e5), 50))]    # ipynb cell 32
+SWEEP_SCRATCH_BYTES = 1 << 30                # coded_nbytes: the u16 indices of one chunk of betas stay below this
+
+
+def coded_nbytes(means, stds, betas, codepoints, *, segment=None) -> np.ndarray:
+    """int64 [len(betas)]: len(compress_to_bytes(means, stds, beta, codepoints, segment=segment)) for every beta, exact,
+    without building a file.  Per chunk of betas (the index scratch stays below SWEEP_SCRATCH_BYTES): one K1n sweep, one K2
+    histogram and ONE copy of the counts, the tables fitted to them (coder.exact_frequencies), one vbq_rans_sizes_u16
+    launch with one stream and one table per beta (segment sizes only, no words), one copy of the totals."""
+    from . import bitstream as bs, coder
+    cp, N, shape, n, seg = _file_args(means, codepoints, segment)
+    betas = [_check_beta(b) for b in betas]
+    out = np.empty(len(betas), dtype=np.int64)
+    if not betas:
+        return out
+    m, s = _dev(means), _dev(stds)                                        # uploaded once for every chunk
+    per = int(min(max(1, SWEEP_SCRATCH_BYTES // (2 * n)), 65535))        # (65535: the coder's limit on streams per launch)
+    for lo in range(0, len(betas), per):
+        chunk = betas[lo:lo + per]
+        idx, _ = compress_coordinates_sweep(m, s, chunk, cp, want_values=False)
+        idx = idx.reshape(len(chunk), n)
+        counts = ops.histogram(idx, 1, N=N).cpu().numpy().reshape(len(chunk), -1)
+        freq = np.stack([coder.exact_frequencies(c) for c in counts])   # host: tools/budget_bench.py times it
+        sizes = coder.RansCodec(freq, N=N, segment=seg, allow_zero=True).sizes(idx)
+        words = sizes.view(torch.int32).sum(dim=1, dtype=torch.int64).cpu().numpy()
+        K = np.count_nonzero(freq, axis=1)
+        out[lo:lo + len(chunk)] = [bs.embeddings_nbytes(shape, seg, int(k), int(w)) for k, w in zip(K, words)]
+    return out
+
+
+def compress_to_budget(means, stds, codepoints, max_bytes, *, betas=None, segment=None) -> bytes:
+    """The file of the numerically SMALLEST beta of `betas` (default: the notebook's grid NOTEBOOK_BETAS) whose exact length is
+    <= max_bytes (an integer >= 1), byte for byte compress_to_bytes at that beta; the header says which beta it is.  A larger
+    beta usually, but not always, gives a smaller file: the rule takes no monotonicity for granted.  ValueError naming the
+    smallest achievable length and its beta when nothing fits."""
+    from . import bitstream as bs
+    bs.check_budget(max_bytes)
+    betas = NOTEBOOK_BETAS if betas is None else [_check_beta(b) for b in betas]
+    nbytes = coded_nbytes(means, stds, betas, codepoints, segment=segment)
+    beta = bs.smallest_rate_within(dict(zip(betas, nbytes.tolist())), max_bytes, "beta")
+    return compress_to_bytes(means, stds, beta, codepoints, segment=segment)
 
 
 class CompressedEmbeddings:

@@ -663,6 +663,33 @@ class ChannelwisePriorCDFQuantizer:
             codec = ent["codecs"][segment] = RansCodec(ent["freq"], N=self.max_bits_per_coord, segment=segment)
         return codec, ent["digest"]
 
+    def _file_shape(self, posterior_means, posterior_logvars, segment):
+        """The latent shape of a file (channel-last, one shape for both inputs); ValueError otherwise or for a bad segment."""
+        from . import bitstream
+        C = self.num_channels
+        shape = tuple(int(d) for d in np.shape(posterior_means))
+        if tuple(np.shape(posterior_logvars)) != shape or not shape or shape[-1] != C:
+            raise ValueError(f"expected channel-last latents [..., {C}] of one shape, got {shape} / {tuple(np.shape(posterior_logvars))}")
+        if not 1 <= segment <= bitstream.MAX_SEGMENT:
+            raise ValueError(f"segment {segment} outside [1, {bitstream.MAX_SEGMENT}]")
+        return shape
+
+    def _file_indices(self, posterior_means, posterior_logvars, keys):
+        """The u16 indices [L, C, B] a file codes: one solve of every lambda of `keys` with sigma = exp(logvar) ** 0.5, and the
+        canonical index of a run of equal code points when the table has any (see encode_batch)."""
+        C = self.num_channels
+        m = posterior_means if isinstance(posterior_means, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_means))
+        lv = posterior_logvars if isinstance(posterior_logvars, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_logvars))
+        mu_cb, sg_cb = self._prep(m.reshape(-1, C), lv.reshape(-1, C), spread="logvar")
+        idx = self._solve_idx(mu_cb, sg_cb, keys, self._level_len_dev(keys))                  # [L, C, B]
+        if not self._strict:
+            # one lambda at a time, in place: the int64 gather index and result stay [C, B] (16 lambdas of Kodak-24 at once
+            # would be two 1.2 GB temporaries)
+            canon = self._dev("canon", lambda: torch.from_numpy(self._canon))                 # [C, T] int64
+            for l in range(idx.shape[0]):
+                idx[l] = torch.gather(canon, 1, idx[l].to(torch.int64)).to(torch.uint16)
+        return idx
+
     def compress_latents_to_bytes(self, posterior_means, posterior_logvars, lamb, segment=1024) -> bytes:
         """compress_latents at ONE lambda, entropy-coded into a self-describing byte string (format: vbq_amd.bitstream).
         Same inputs and sigma = exp(logvar) ** 0.5 as compress_latents; the indices come from the same solve (the canonical
@@ -672,19 +699,9 @@ class ChannelwisePriorCDFQuantizer:
         self._check_coder_bits()
         key = self._lambda_key(lamb)
         C = self.num_channels
-        shape = tuple(int(d) for d in np.shape(posterior_means))
-        if tuple(np.shape(posterior_logvars)) != shape or not shape or shape[-1] != C:
-            raise ValueError(f"expected channel-last latents [..., {C}] of one shape, got {shape} / {tuple(np.shape(posterior_logvars))}")
-        if not 1 <= segment <= bitstream.MAX_SEGMENT:
-            raise ValueError(f"segment {segment} outside [1, {bitstream.MAX_SEGMENT}]")
+        shape = self._file_shape(posterior_means, posterior_logvars, segment)
         codec, dig = self._coder_tables(key, int(segment))
-        m = posterior_means if isinstance(posterior_means, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_means))
-        lv = posterior_logvars if isinstance(posterior_logvars, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_logvars))
-        mu_cb, sg_cb = self._prep(m.reshape(-1, C), lv.reshape(-1, C), spread="logvar")
-        idx = self._solve_idx(mu_cb, sg_cb, [key], self._level_len_dev([key]))[0]          # [C, B]
-        if not self._strict:                  # code the canonical index of a run of equal values (see encode_batch)
-            canon = self._dev("canon", lambda: torch.from_numpy(self._canon))             # [C, T] int64
-            idx = torch.gather(canon, 1, idx.to(torch.int64)).to(torch.uint16)
+        idx = self._file_indices(posterior_means, posterior_logvars, [key])[0]                 # [C, B]
         sizes, payload = codec.encode_packed(idx)
         h = bitstream.Header(N=self.max_bits_per_coord, C=C, shape=shape, lamb=float(key), segment=int(segment), digest=dig,
                              n_words=int(payload.size))
@@ -718,6 +735,65 @@ class ChannelwisePriorCDFQuantizer:
         """`vae.encode(X)`, then compress_latents_to_bytes."""
         posterior_means, posterior_logvars = vae.encode(X)
         return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment)
+
+    # ------------------------------------------------------------------ rate control: exact lengths, byte budgets
+    def _rate_keys(self, lambs):
+        """The entropy-model keys of `lambs` (all of self.lambs when None), in order, each once; KeyError for an unknown one."""
+        if self.entropy_models is None or not hasattr(self, "_code_counts"):
+            raise ValueError("build_entropy_models() first")
+        return list(dict.fromkeys(self.lambs if lambs is None else [self._lambda_key(l) for l in lambs]))
+
+    def _coder_stack(self, keys, segment):
+        """One codec over the L x C streams of `keys` (the per-lambda tables of _coder_tables, stacked).  Cached in a slot of its
+        own, invalidated as _coder_tables is (a rebuild of the models) and holding the last few (lambdas, segment) asked for."""
+        from .coder import RansCodec
+        for k in keys:
+            self._coder_tables(k, segment)                                                    # refreshes the per-lambda cache
+        per = self._dev_cache["_coder_tables"][2]
+        hit = self._dev_cache.get("_coder_stacks")
+        if hit is None or hit[0] is not self._code_counts or hit[1] != self._add_n_smoothing:
+            hit = self._dev_cache["_coder_stacks"] = (self._code_counts, self._add_n_smoothing, {})
+        stacks = hit[2]
+        tag = (tuple(float(k) for k in keys), segment)
+        codec = stacks.get(tag)
+        if codec is None:
+            if len(stacks) >= 8:
+                stacks.clear()
+            codec = stacks[tag] = RansCodec(np.concatenate([per[k]["freq"] for k in keys]), N=self.max_bits_per_coord,
+                                            segment=segment)
+        return codec
+
+    def coded_nbytes(self, posterior_means, posterior_logvars, lambs=None, segment=1024) -> dict:
+        """{lambda: len(compress_latents_to_bytes(posterior_means, posterior_logvars, lambda, segment))} for every key of
+        entropy_models in `lambs` (default: all of self.lambs), exact, without building a file: ONE solve of every lambda, one
+        vbq_rans_sizes_u16 launch over the L x C streams (segment sizes only, no words), one copy of the L totals.  Inputs and
+        errors as compress_latents_to_bytes (KeyError for a lambda without a model)."""
+        from . import bitstream
+        self._check_coder_bits()
+        keys = self._rate_keys(lambs)
+        C = self.num_channels
+        shape = self._file_shape(posterior_means, posterior_logvars, segment)
+        codec = self._coder_stack(keys, int(segment))
+        idx = self._file_indices(posterior_means, posterior_logvars, keys)                     # [L, C, B]
+        sizes = codec.sizes(idx)                                                               # u32 [L * C, nseg]
+        words = sizes.view(torch.int32).view(len(keys), -1).sum(dim=1, dtype=torch.int64).cpu().numpy()
+        return {k: bitstream.latent_nbytes(shape, C, int(segment), int(w)) for k, w in zip(keys, words)}
+
+    def compress_latents_to_budget(self, posterior_means, posterior_logvars, max_bytes, lambs=None, segment=1024) -> bytes:
+        """The file of the numerically SMALLEST lambda of `lambs` (default: all of self.lambs) whose exact length is <= max_bytes
+        (an integer >= 1), byte for byte compress_latents_to_bytes at that lambda; the header says which lambda it is.  A larger
+        lambda usually, but not always, gives a smaller file: the rule takes no monotonicity for granted.  ValueError naming
+        the smallest achievable length and its lambda when nothing fits."""
+        from . import bitstream
+        bitstream.check_budget(max_bytes)
+        nbytes = self.coded_nbytes(posterior_means, posterior_logvars, lambs, segment=segment)
+        lamb = bitstream.smallest_rate_within(nbytes, max_bytes, "lambda")
+        return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment)
+
+    def compress_to_budget(self, X, vae, max_bytes, lambs=None, segment=1024) -> bytes:
+        """`vae.encode(X)`, then compress_latents_to_budget."""
+        posterior_means, posterior_logvars = vae.encode(X)
+        return self.compress_latents_to_budget(posterior_means, posterior_logvars, max_bytes, lambs=lambs, segment=segment)
 
     def decompress(self, data, vae, clip=True, return_np=True):
         """decompress_latents, then `vae.decode` and the clip to [0, 1] of compress (quantizer.py:251-253).  The decoder
