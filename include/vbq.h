@@ -233,6 +233,10 @@ void vbq_host_stage_run(void *stage);
  *   d_len   f32 [M][n_elems], or [n_lambda][M][n_elems] when len_per_lambda != 0
  *           (the 4-D stack of utils.py:393-394).
  *   d_out_j   optional i32 [n_lambda][n_elems] winning candidate (first maximum);
+ *   NaN scores (+-inf candidates against an infinite mu or sigma, lambda = 0 times an infinite length):
+ *     VBQ_MODE_F64_SCORE follows np.argmax, the reference's NumPy backend: the first NaN wins.
+ *     VBQ_MODE_F32 keeps its strict '>' scan: a NaN score never replaces the running best, so a NaN after
+ *     candidate 0 is never taken and a NaN at candidate 0 keeps j = 0.
  *   d_out_zhat / d_out_bits   optional f32 [n_lambda][n_elems]   (utils.py:414-415).
  * ---------------------------------------------------------------------------------- */
 int vbq_argmax_candidates_f32(const float *d_P, const float *d_len, int32_t len_per_lambda,

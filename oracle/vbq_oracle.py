@@ -180,6 +180,8 @@ def rd_solve(P: np.ndarray, Lens: np.ndarray, mu: np.ndarray, sigma: np.ndarray,
         win = np.zeros(best.shape, dtype=np.int64)
         for j in range(1, M):                                     # first maximum wins (:401)
             upd = scores[j] > best
+            if mode == "f64":                                     # np.argmax: the first NaN wins
+                upd |= np.isnan(scores[j]) & ~np.isnan(best)
             best = np.where(upd, scores[j], best)
             win = np.where(upd, j, win)
         Zs.append(np.take_along_axis(P, win[None], axis=0)[0])

@@ -33,7 +33,8 @@ k_argmax_candidates(const float *__restrict__ P, const float *__restrict__ len, 
                     bool up;
                     if (F64) {
                         const double sc = __dsub_rn((double)d, __dmul_rn(lc.lam[l], (double)ln));
-                        up = j == 0 || sc > bestd[l];
+                        // np.argmax: a NaN beats every number and the first NaN stays the best
+                        up = j == 0 || (!isnan(bestd[l]) && (isnan(sc) || sc > bestd[l]));
                         bestd[l] = up ? sc : bestd[l];
                     } else {
                         const float sc = __fsub_rn(d, __fmul_rn((float)lc.lam[l], ln));
