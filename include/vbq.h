@@ -269,6 +269,22 @@ int vbq_xi_select_f64(const double *d_F, const double *d_endpoints, const double
  *   d_codebook_lm   f64 [T] level-major (ipynb:383-389), non-decreasing in xi.
  *   h_betas         HOST doubles [n_beta].
  *   d_out_idx       u16 [n_beta][n] rank index;  d_out_val optional f32 [n_beta][n].
+ *   Non-finite and out-of-range inputs follow NumPy, nothing is special-cased away from it
+ *   (tests/test_gpu_notebook_variants.py, against the reference pinned in
+ *   tests/test_notebook_f64.py): np.argmin returns the first NaN, and slot 0 (the root)
+ *   costs err_0 + w * 0 with w = fl32(fl32(2 beta) * fl32(sigma^2)), so the root is the
+ *   answer for a NaN mean, for an infinite mean (every cost inf or NaN) and for every w
+ *   that is NaN or +-inf (sigma NaN or inf, sigma^2 overflowing f32, 0 * inf).  sigma = 0
+ *   or a sigma^2 that underflows gives w = 0: the nearest code point, the first in
+ *   level-major order among equals.  The sign of sigma does not matter.  A negative beta is
+ *   scored on all 2^(N+1)-1 points (the neighbours of the mean are not enough there: a
+ *   cost near -|w| N can round every point of a level onto the same value, and the first
+ *   of them wins); such calls cost about a hundred times a non-negative one.  For
+ *   beta >= 0 the kernels score the two neighbours of the mean per level, which equals the
+ *   full scan as long as |mean| stays below about 2^50 code-book spacings (1e12 scales at
+ *   N = 10; beyond that c - mean rounds neighbouring points onto each other and the first
+ *   of them would win; from about 2^53 scales on every point ties and the root wins,
+ *   which the kernels reproduce again: +-3e38 is tested).
  * ---------------------------------------------------------------------------------- */
 int vbq_quantize_notebook_f64(const float *d_means, const float *d_stds, int64_t n,
                               const double *d_codebook_lm, const double *h_betas, int32_t n_beta,

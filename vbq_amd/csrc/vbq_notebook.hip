@@ -62,6 +62,25 @@ __device__ __forceinline__ void search_and_score_d(const double *tb, double z, E
     e.G = g;
 }
 
+// Every code point, as ipynb:436-440 scores them: for a NEGATIVE penalty weight.  There the deepest levels win with costs
+// of about -|w| N, whose rounding can swallow the whole difference between the squared errors of neighbouring points
+// (|w| N > 2^53 times that difference: sigma of 1e4 scales and beta of -1e4 are enough); every point of the level that
+// rounds onto the minimum then ties, and the first of them in the scan wins -- which need not be a neighbour of the mean.
+// With w >= 0 a level only wins with a cost below err_0, which is too small to swallow a code-book spacing.
+template <int N>
+__device__ __noinline__ void all_points_scan_nb(const double *tb, double z, double w, int &lvl, uint32_t &pos) {
+    double best = 0.0;
+    int j = 0;
+    lvl = 0; pos = 0;
+    for (int n = 0; n <= N; ++n) {
+        const double pen = __dmul_rn(w, (double)n);      // level 0: w * 0, NaN for w = -inf: no later cost compares below it
+        for (int i = 0; i < (1 << n); ++i, ++j) {
+            const double cost = __dadd_rn(sq_err(tb[j], z), pen);
+            if (j == 0 || cost < best) { best = cost; lvl = n; pos = (uint32_t)i; }
+        }
+    }
+}
+
 template <int N>
 __global__ void __launch_bounds__(256)
 k_quant_notebook(const float *__restrict__ means, const float *__restrict__ stds, long n,
@@ -102,7 +121,10 @@ k_quant_notebook(const float *__restrict__ means, const float *__restrict__ stds
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const double w = (double)__fmul_rn(tb2, var[k]);
-                double best = el[k].a[0];     // length 0: no penalty (w * 0 == 0, x + 0 == x)
+                // length 0: the penalty w * 0 is formed all the same -- it is 0 for a finite w, and NaN for w = +-inf or NaN,
+                // where np.argmin returns the first NaN, slot 0.  Without it w = -inf (negative beta, sigma^2 = inf) would
+                // let level 1 win with a cost of -inf.
+                double best = __dadd_rn(el[k].a[0], __dmul_rn(w, 0.0));
                 int lvl = 0;
                 bool right = false;
 #pragma unroll
@@ -120,7 +142,8 @@ k_quant_notebook(const float *__restrict__ means, const float *__restrict__ stds
                 const uint32_t m = 1u << lvl;
                 const uint32_t r = g < m - 1 ? g : m - 1;
                 const uint32_t lft = g > 0 ? g - 1 : 0;
-                const uint32_t pos = right ? r : lft;
+                uint32_t pos = right ? r : lft;
+                if (w < 0.0) all_points_scan_nb<N>(tb, (double)m2[k], w, lvl, pos);     // negative beta: see above
                 idx[k] = ((2 * pos + 1) << (N - lvl)) - 1;
                 if (out_val) val[k] = (float)tb[(1 << lvl) - 1 + pos];
             }
@@ -283,8 +306,13 @@ k_quant_notebook_fast(const float *__restrict__ means, const float *__restrict__
             bool any_flag = false;
 #pragma unroll
             for (int k = 0; k < NE; ++k) {
-                const int n1 = __builtin_ctz(~ne[k]);
-                const uint32_t pk = scratch[(n1 * NE + k) * 256 + threadIdx.x];
+                // A mean or a weight that is not finite: the reference's answer is slot 0, the root (a NaN cost at slot 0 -- w * 0
+                // for w = inf or NaN, any cost of a NaN mean -- is np.argmin's first NaN; an infinite mean costs inf
+                // everywhere).  The sign mask is meaningless there (S - cost is inf - inf or NaN, of either sign, and with
+                // every sign set ctz would point past the last level).
+                const bool root = !(fabs(w[k]) <= 1.7976931348623157e308) || !(fabsf(m2[k]) <= 3.4028234663852886e38f);
+                const int n1 = root ? 0 : min(__builtin_ctz(~ne[k]), N);
+                const uint32_t pk = root ? (0x3ffu << 21) | ((1u << N) - 1u) : scratch[(n1 * NE + k) * 256 + threadIdx.x];
                 // errL - errR < ~ulp64(S) = 2^-52 S could let fl64(errL + pen) round onto fl64(errR + pen): flag below 2^-46 S
                 const uint32_t thr = __float_as_uint(__fmul_rn((float)S[k], 1.4210854715202004e-14f));
                 flagged[k] = (((pk & 0x7fe00000u) <= thr) && dbg != 2) || dbg == 1;
