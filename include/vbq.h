@@ -651,6 +651,41 @@ int vbq_ssim_scale_f64(const double *d_im1, const double *d_im2, int32_t B, int3
                        double *d_out_cs, void *d_workspace, size_t workspace_bytes, void *stream);
 int vbq_downsample2_f64(const double *d_in, int32_t B, int32_t H, int32_t W, int32_t C, double *d_out, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Fixed bit budgets (img-compression/utils.py:106-208), float64 as there.  Both entry points take the per-level score
+ * table d_fhat [N+1][E]: fhat(e, n) = the best score of element e when it gets exactly n bits (the better of the two n-bit
+ * neighbours; level 0 = the zero-bit value).  The caller builds it; squash / unsquash / f stay where the caller evaluates them.
+ *   vbq_budget_dp_f64        utils.encode_mode_dp (:106-160) for n_rows rows of K coordinates, E = n_rows * K, element
+ *                            e = row * K + k: the allocation of EXACTLY `budget` bits over the K coordinates of a row, at most
+ *                            N per coordinate, that maximises the sum of the scores.
+ *                              T[0][n] = fhat(0, n) for n <= N, -inf for n > N
+ *                              T[k][n] = max over m = 0..min(n, N) of fhat(k, m) + T[k-1][n-m]     (one rounded add each)
+ *                            the first maximum in ascending m wins (np.argmax, :137); d_out_obj[row] = T[K-1][budget];
+ *                            d_out_bits [n_rows][K] follows the back-pointers and coordinate 0 takes the remainder (:156), so a
+ *                            row's bits sum to `budget`.  budget == N is the reference's call; budget up to K * N generalises
+ *                            it.  A row without any finite allocation has objective -inf and its remainder may exceed N.
+ *                            Entries of d_fhat are finite or -inf.  A row that holds a NaN or +inf is outside the contract:
+ *                            it is still processed memory-safely, gets bits in [0, N], and sets bit 0 of d_status (u32, may
+ *                            be NULL, OR-ed into; zero it first).
+ *                            Returns VBQ_ERR_INVALID_ARGUMENT for budget < 0, budget > K * N, N > 52, K < 1 or null pointers
+ *                            (checked before any device work); n_rows == 0 returns 0.  One workgroup per row; the
+ *                            back-pointers (one byte per (k, n)) stay in LDS when K * (budget+1) bytes fit there beside the
+ *                            value rows.  Otherwise they go to d_workspace, one slice of K * (budget+1) bytes per resident
+ *                            workgroup: vbq_budget_dp_workspace_bytes gives the size that keeps the chip busy (0 when none is
+ *                            needed); any workspace that holds at least one slice is accepted, and the rows are then
+ *                            processed in as many rounds as it takes.
+ *   vbq_budget_patience_f64  the per-coordinate scan of utils.encode_mode (:186-203): g_0 = fhat_0, g_b = fhat_b - lamb * b
+ *                            for b = 1..N; a strictly greater g becomes the best and resets the counter, `patience` (>= 1)
+ *                            consecutive non-improvements end the scan.  d_out_bits [E] = the best b, d_out_g [E] = its g
+ *                            (the caller folds it: obj = np.add.accumulate(g)[-1]).
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+size_t vbq_budget_dp_workspace_bytes(int64_t n_rows, int32_t K, int32_t N, int32_t budget);
+int vbq_budget_dp_f64(const double *d_fhat, int64_t n_rows, int32_t K, int32_t N, int32_t budget, int32_t *d_out_bits,
+                      double *d_out_obj, uint32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
+int vbq_budget_patience_f64(const double *d_fhat, int64_t E, int32_t N, double lamb, int32_t patience, int32_t *d_out_bits,
+                            double *d_out_g, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -615,3 +615,44 @@ def bmshj_nll_grad(params: torch.Tensor, x_cb: torch.Tensor, out: Optional[torch
     check(_lib.lib().vbq_bmshj_nll_grad_f32(_ptr(params), _ptr(x_cb), n, Cc, _ptr(out), _stream(x_cb)),
           "vbq_bmshj_nll_grad_f32")
     return out
+
+
+def budget_dp(fhat: torch.Tensor, K: int, budget: int, *, status: Optional[torch.Tensor] = None,
+              workspace: Optional[torch.Tensor] = None):
+    """vbq_budget_dp_f64: the allocation of exactly `budget` bits over the K coordinates of every row that maximises the summed
+    score (utils.py:106-160).  fhat: f64 [N+1, rows * K] (or [N+1, rows, K]) = score of element row * K + k with exactly n bits.
+    Returns (bits int32 [rows, K], objective f64 [rows]).  `status` (uint32 [1], zeroed by the caller) gets bit 0 set when a row
+    held a NaN or +inf; `workspace` (uint8) replaces the one this call would allocate and may be smaller (more rounds)."""
+    fhat = _dev(fhat, torch.float64, "fhat")
+    N, K, budget = fhat.shape[0] - 1, int(K), int(budget)
+    E = fhat[0].numel() if fhat.shape[0] else 0
+    if K < 1 or E % K:
+        raise ValueError(f"fhat holds {E} elements per level, not a multiple of K={K}")
+    rows = E // K
+    bits = torch.empty((rows, K), dtype=torch.int32, device=fhat.device)
+    obj = torch.empty(rows, dtype=torch.float64, device=fhat.device)
+    if status is not None:
+        status = _dev(status, torch.uint32, "status")
+    h = _lib.lib()
+    if workspace is None:
+        wsb = h.vbq_budget_dp_workspace_bytes(rows, K, N, budget)
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=fhat.device) if wsb else None
+    else:
+        workspace = _dev(workspace, torch.uint8, "workspace")
+    wsb = workspace.numel() if workspace is not None else 0
+    check(h.vbq_budget_dp_f64(_ptr(fhat), rows, K, N, budget, _ptr(bits), _ptr(obj), _ptr(status), _ptr(workspace), wsb,
+                              _stream(fhat)), "vbq_budget_dp_f64")
+    return bits, obj
+
+
+def budget_patience(fhat: torch.Tensor, lamb: float, patience: int = 3):
+    """vbq_budget_patience_f64: per element the scan of utils.encode_mode (utils.py:186-203) over g_b = fhat_b - lamb * b.
+    fhat: f64 [N+1, E].  Returns (bits int32 [E], g f64 [E])."""
+    fhat = _dev(fhat, torch.float64, "fhat")
+    N = fhat.shape[0] - 1
+    E = fhat[0].numel() if fhat.shape[0] else 0
+    bits = torch.empty(E, dtype=torch.int32, device=fhat.device)
+    g = torch.empty(E, dtype=torch.float64, device=fhat.device)
+    check(_lib.lib().vbq_budget_patience_f64(_ptr(fhat), E, N, float(lamb), int(patience), _ptr(bits), _ptr(g), _stream(fhat)),
+          "vbq_budget_patience_f64")
+    return bits, g

@@ -1,0 +1,104 @@
+"""quantize_rows_to_budget(mu, sigma, total_bits): every row of a matrix quantized to EXACTLY total_bits raw bits.
+
+Where quantize() picks a lambda and takes whatever rate falls out, and compress_to_budget searches lambda for a file size "at
+most" a budget of the whole tensor, this solves the constrained problem per row: the allocation of total_bits over the K
+coordinates, at most N each, with the largest Gaussian score (the budget DP of img-compression/utils.py:106-160, batched:
+vbq_budget_dp_f64).  Rows of equal cost are fixed-size records, addressable without an entropy coder.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import VBQError
+from .api import _device_table
+from .tables import table_size
+
+
+def level_candidates(mu_t: torch.Tensor, sg_t: torch.Tensor, tab_lm: torch.Tensor, N: int):
+    """Per level n = 0..N and element (r, k): the better of the two n-bit neighbours of mu (vbq_n_bit_intervals_f32) under the
+    score -0.5 * ((c - mu) / sigma)**2, float64 on the upcast float32 values; the right neighbour only when strictly better;
+    level 0 is the root table[..., 0].  Returns (scores f64 [N+1, R, K], values f32 [N+1, R, K])."""
+    R, K = mu_t.shape
+    C = tab_lm.shape[0]
+    z_cb = ops.transpose(mu_t) if C > 1 else mu_t.reshape(1, R * K)                  # [K, R] planes, or one plane of R*K
+    B = z_cb.shape[1]
+    left = torch.empty((C, N + 1, B), dtype=torch.float32, device=mu_t.device)
+    right = torch.empty_like(left)
+    _lib.check(_lib.lib().vbq_n_bit_intervals_f32(ops._ptr(z_cb), B, C, ops._ptr(tab_lm), N, ops._ptr(left), ops._ptr(right),
+                                                  ops._stream(z_cb)), "vbq_n_bit_intervals_f32")
+    if C > 1:
+        left, right = left.permute(1, 2, 0), right.permute(1, 2, 0)                 # [N+1, R, K]
+    else:
+        left, right = left.reshape(N + 1, R, K), right.reshape(N + 1, R, K)
+    mu64, sg64 = mu_t.to(torch.float64), sg_t.to(torch.float64)
+
+    def score(c):
+        t = (c.to(torch.float64) - mu64) / sg64
+        return -0.5 * (t * t)
+    s_l, s_r = score(left), score(right)
+    take_r = s_r > s_l
+    scores = torch.where(take_r, s_r, s_l).contiguous()
+    values = torch.where(take_r, right, left).contiguous()
+    root = tab_lm[:, 0].expand(R, K) if C > 1 else tab_lm[0, 0].expand(R, K)
+    values[0] = root
+    scores[0] = score(root)
+    return scores, values
+
+
+def quantize_rows_to_budget(mu, sigma, total_bits, *, table, N: int = 10):
+    """Quantize every row of mu [R, K] to exactly total_bits raw bits, at most N per coordinate.
+
+    mu, sigma  : f32 [R, K], torch (device) or NumPy.
+    total_bits : an int, or an int array [R] with one budget per row (rows are grouped by budget, one launch per distinct value);
+                 0 <= total_bits <= K * N.
+    table      : level-major f32 code points, one code book [T] or one per column [K, T], T = 2**(N+1) - 1, monotone in xi.
+    Returns device tensors (idx, num_bits, objective): idx uint16 [R, K] = the rank index of the chosen code point (the lower
+    bound of its value in the sorted table, as quantize() gives it: feeds RansCodec, ops.histogram and ops.gather unchanged),
+    num_bits int32 [R, K] = its bit length (every row sums to its budget), objective f64 [R] = the row's summed score
+    -0.5 * ((c - mu) / sigma)**2 in float64, accumulated over ascending k.  The best allocation is exact: no other allocation
+    of the same total has a larger objective.  Raises VBQError when a score is NaN or +inf (sigma <= 0, non-finite inputs)."""
+    if not torch.cuda.is_available():
+        raise VBQError("no ROCm device visible: vbq_amd.quantize_rows_to_budget has no CPU implementation")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mu_t = (torch.from_numpy(np.ascontiguousarray(mu)) if not isinstance(mu, torch.Tensor) else mu).to(dev, torch.float32)
+    sg_t = (torch.from_numpy(np.ascontiguousarray(sigma)) if not isinstance(sigma, torch.Tensor) else sigma).to(dev, torch.float32)
+    if mu_t.dim() != 2 or mu_t.shape != sg_t.shape:
+        raise ValueError(f"mu and sigma must be [R, K] of one shape, got {tuple(mu_t.shape)} and {tuple(sg_t.shape)}")
+    R, K = mu_t.shape
+    if K < 1:
+        raise ValueError("K must be at least 1")
+    T = table_size(N)
+    shape = tuple(table.shape)
+    if shape not in ((T,), (1, T), (K, T)):
+        raise ValueError(f"table must be [{T}] or [{K}, {T}] for N={N}, got {shape}")
+    C = K if shape == (K, T) else 1
+    tab_lm, tab_sorted = _device_table(table, C, N, dev, True)
+    budgets = torch.as_tensor(np.asarray(total_bits.cpu() if isinstance(total_bits, torch.Tensor) else total_bits)).reshape(-1)
+    if budgets.dtype.is_floating_point or budgets.numel() not in (1, R):
+        raise ValueError("total_bits must be an int or an int array with one entry per row")
+    budgets = budgets.to(torch.int64)
+    mu_t, sg_t = mu_t.contiguous(), sg_t.contiguous()
+    num_bits = torch.empty((R, K), dtype=torch.int32, device=dev)
+    objective = torch.empty(R, dtype=torch.float64, device=dev)
+    if R == 0:
+        return torch.empty((0, K), dtype=torch.uint16, device=dev), num_bits, objective
+    scores, values = level_candidates(mu_t, sg_t, tab_lm, N)
+    status = torch.zeros(1, dtype=torch.uint32, device=dev)
+    if budgets.numel() == 1:
+        num_bits, objective = ops.budget_dp(scores, K, int(budgets[0]), status=status)
+    else:
+        for b in torch.unique(budgets).tolist():
+            rows = torch.nonzero(budgets == b).reshape(-1).to(dev)
+            nb, ob = ops.budget_dp(scores[:, rows].contiguous(), K, int(b), status=status)
+            num_bits[rows] = nb
+            objective[rows] = ob
+    chosen = torch.gather(values, 0, num_bits.to(torch.int64)[None])[0]              # [R, K] f32: the code point itself
+    if C > 1:
+        idx = torch.searchsorted(tab_sorted, chosen.t().contiguous()).t()
+    else:
+        idx = torch.searchsorted(tab_sorted[0], chosen)
+    if int(status.cpu().item()) & 1:
+        raise VBQError("quantize_rows_to_budget: a score is NaN or +inf (non-finite mu, or sigma that is not positive)")
+    return idx.to(torch.uint16).contiguous(), num_bits, objective

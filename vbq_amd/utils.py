@@ -138,6 +138,98 @@ def encode_vectorized(fun, z, lamb, squash, unsquash, max_bits_per_coord=16):
     return dict(z_hat=z_hat.cpu().numpy(), score=np.sum(f_z.cpu().numpy()), num_bits=nb.cpu().numpy(), xi_hat=xi_hat.cpu().numpy())
 
 
+def truncate_float_to_n_bits(x, n):
+    """utils.py:60-78 (host scalar): the value of the first n binary places of x in [0, 1], and those places as a string."""
+    rem = float(x)
+    bits = []
+    for i in range(1, n + 1):
+        place = 2.0 ** (-i)
+        take = not rem < place
+        bits.append("1" if take else "0")
+        if take:
+            rem -= place
+    return x - rem, "".join(bits)
+
+
+def get_n_bit_interval(x, n):
+    """utils.py:27-57 (host scalar): the two neighbours of x on the grid (i + 1/2) * 2**-n, i = 0 .. 2**n - 1; both are the
+    rim point when x lies outside the grid, and both are 0.5 for n = 0."""
+    if n == 0:
+        return [0.5, 0.5]
+    width = 2 ** (-n)
+    half = width / 2
+    if x < half:
+        return (half, half)
+    if x > 1 - half:
+        return (1 - half, 1 - half)
+    left = truncate_float_to_n_bits(x - half, n)[0] + half
+    return (left, left + width)
+
+
+def encode_mode_1d(f, mode, nbits, squash, unsquash):
+    """utils.py:88-103 (host scalars): the better of the two nbits-bit neighbours of squash(mode), mapped back through unsquash and
+    scored by f; the right one only when strictly better.  Returns (mode_hat, f(mode_hat))."""
+    left, right = get_n_bit_interval(squash(mode), nbits)
+    mode_hat = unsquash(left)
+    f_hat = f(mode_hat)
+    if right != left:
+        cand = unsquash(right)
+        f_cand = f(cand)
+        if f_cand > f_hat:
+            mode_hat, f_hat = cand, f_cand
+    return mode_hat, f_hat
+
+
+def _level_tables(f, mode, N, squash, unsquash, zero_bit_mode_hat):
+    """What encode_mode_1d answers for every coordinate k and every bit count n = 1..N, with the zero-bit value on level 0:
+    (scores, values), float64 [N+1, K] each.  The grid neighbours come from the GPU (vbq_xi_intervals_f64); the caller's
+    per-coordinate callables are called with scalars, as the reference calls them."""
+    K = len(f)
+    xi = np.array([squash[k](mode[k]) for k in range(K)], dtype=np.float64)
+    left, right = np.empty((N + 1, K)), np.empty((N + 1, K))
+    get_all_N_bit_intervals(xi, N, left, right)
+    scores, values = np.empty((N + 1, K)), np.empty((N + 1, K))
+    for k in range(K):
+        values[0, k] = zero_bit_mode_hat[k]
+        scores[0, k] = f[k](zero_bit_mode_hat[k])
+        for n in range(1, N + 1):
+            v = unsquash[k](left[n, k])
+            s = f[k](v)
+            if right[n, k] != left[n, k]:
+                v_r = unsquash[k](right[n, k])
+                s_r = f[k](v_r)
+                if s_r > s:
+                    v, s = v_r, s_r
+            values[n, k], scores[n, k] = v, s
+    return scores, values
+
+
+def encode_mode_dp(f, mode, nbits, squash, unsquash, zero_bit_mode_hat):
+    """utils.py:106-160: spend exactly `nbits` bits over the K coordinates (at most nbits each) so that the sum of f[k] at the
+    quantised modes is largest.  f, squash, unsquash: length-K lists of scalar functions.  The allocation is the budget DP kernel
+    (vbq_budget_dp_f64); returns the reference's (mode_hat, obj, num_bits)."""
+    dev = _device()
+    K, N = len(f), int(nbits)
+    scores, values = _level_tables(f, mode, N, squash, unsquash, zero_bit_mode_hat)
+    bits, obj = ops.budget_dp(torch.from_numpy(scores).to(dev), K, N)
+    num_bits = bits[0].cpu().numpy().astype(np.int64)
+    return values[num_bits, np.arange(K)], obj.cpu().numpy()[0], num_bits
+
+
+def encode_mode(f, mode, lamb, squash, unsquash, zero_bit_mode_hat, max_bits_per_coord=32):
+    """utils.py:163-208: per coordinate the bit count b that maximises f[k](mode_hat_k(b)) - lamb * b, scanned upwards until three
+    counts in a row bring no improvement (vbq_budget_patience_f64).  Returns the reference's (mode_hat, obj, num_bits); obj is
+    the reference's running sum over k."""
+    dev = _device()
+    K, N = len(f), int(max_bits_per_coord)
+    scores, values = _level_tables(f, mode, N, squash, unsquash, zero_bit_mode_hat)
+    bits, g = ops.budget_patience(torch.from_numpy(scores).to(dev), float(lamb), patience=3)
+    num_bits = bits.cpu().numpy().astype(np.int64)
+    mode_hat = np.empty_like(np.asarray(mode))
+    mode_hat[...] = values[num_bits, np.arange(K)]
+    return mode_hat, np.add.accumulate(g.cpu().numpy())[-1], num_bits
+
+
 def convert_to_db(d):
     """utils.py:497-499 (BMSHJ ICLR 2018, p. 8)."""
     return -10 * np.log10(1 - d)
