@@ -140,30 +140,38 @@ class RansCodec:
             self._freq_dev = self.freq_host.to(device).contiguous()
         return self._freq_dev
 
-    def encode(self, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """idx: u16 device tensor [..., n] with prod(leading dims) == number of frequency rows.
-        Returns (words u16 [S, nseg, segment+2], sizes u32 [S, nseg])."""
+    def _streams(self, idx):
+        """The checked index tensor and its geometry -> (idx, S, n, nseg)."""
         idx = ops._dev(idx, torch.uint16, "idx")
         n = idx.shape[-1]
         S = idx.numel() // max(n, 1)
         if S != self.freq_host.shape[0]:
             raise ValueError(f"{S} index streams but {self.freq_host.shape[0]} frequency rows")
-        nseg = (n + self.segment - 1) // self.segment
-        words = torch.zeros((S, nseg, self.segment + 2), dtype=torch.uint16, device=idx.device)
-        sizes = torch.zeros((S, nseg), dtype=torch.uint32, device=idx.device)
+        return idx, S, n, (n + self.segment - 1) // self.segment
+
+    def _encode(self, idx, S, n, words, sizes):
         check(_lib.lib().vbq_rans_encode_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(idx.device)),
                                              ops._ptr(words), ops._ptr(sizes), ops._stream(idx)), "vbq_rans_encode_u16")
+
+    def _decode(self, words, sizes, n, idx, status):
+        """status: u32 [1] the decoder ORs its flags into (read it with _raise_status)."""
+        check(_lib.lib().vbq_rans_decode_u16(ops._ptr(words), ops._ptr(sizes), idx.shape[0], n, self.N, self.segment,
+                                             ops._ptr(self._freq(idx.device)), ops._ptr(idx), ops._ptr(status),
+                                             ops._stream(idx)), "vbq_rans_decode_u16")
+
+    def encode(self, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """idx: u16 device tensor [..., n] with prod(leading dims) == number of frequency rows.
+        Returns (words u16 [S, nseg, segment+2], sizes u32 [S, nseg])."""
+        idx, S, n, nseg = self._streams(idx)
+        words = torch.zeros((S, nseg, self.segment + 2), dtype=torch.uint16, device=idx.device)
+        sizes = torch.zeros((S, nseg), dtype=torch.uint32, device=idx.device)
+        self._encode(idx, S, n, words, sizes)
         return words, sizes
 
     def sizes(self, idx: torch.Tensor) -> torch.Tensor:
         """The sizes `encode` returns -- u32 [S, nseg], 16-bit words per segment -- without the words (vbq_rans_sizes_u16): the
         exact coded length of every segment at 4 bytes of output per segment instead of a padded word buffer."""
-        idx = ops._dev(idx, torch.uint16, "idx")
-        n = idx.shape[-1]
-        S = idx.numel() // max(n, 1)
-        if S != self.freq_host.shape[0]:
-            raise ValueError(f"{S} index streams but {self.freq_host.shape[0]} frequency rows")
-        nseg = (n + self.segment - 1) // self.segment
+        idx, S, n, nseg = self._streams(idx)
         sizes = torch.zeros((S, nseg), dtype=torch.uint32, device=idx.device)
         check(_lib.lib().vbq_rans_sizes_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(idx.device)),
                                             ops._ptr(sizes), ops._stream(idx)), "vbq_rans_sizes_u16")
@@ -181,14 +189,8 @@ class RansCodec:
                              f"stream, got {tuple(words.shape)} and {tuple(sizes.shape)}")
         idx = torch.empty((S, n), dtype=torch.uint16, device=words.device)
         status = torch.zeros(1, dtype=torch.uint32, device=words.device)
-        check(_lib.lib().vbq_rans_decode_u16(ops._ptr(words), ops._ptr(sizes), S, n, self.N, self.segment,
-                                             ops._ptr(self._freq(words.device)), ops._ptr(idx), ops._ptr(status),
-                                             ops._stream(words)), "vbq_rans_decode_u16")
-        st = int(status.cpu().item())
-        if st:
-            what = [m for b, m in ((1, "segment size out of range"), (2, "segment ran out of words"),
-                                   (4, "left-over words / wrong final state"), (8, "invalid frequency table")) if st & b]
-            raise _lib.VBQError("rANS bitstream rejected: " + ", ".join(what))
+        self._decode(words, sizes, n, idx, status)
+        _raise_status(int(status.cpu().item()))
         return idx
 
     # ------------------------------------------------------------ packed payload (vbq_amd.bitstream, vbq_rans_pack_u16)
@@ -235,20 +237,14 @@ class RansCodec:
     def encode_packed(self, idx: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
         """encode + pack on the device -> (sizes u32 [S, nseg], payload u16 [total]) on the host, in TWO device-to-host
         copies: the total together with the sizes, then the payload."""
-        idx = ops._dev(idx, torch.uint16, "idx")
-        n = idx.shape[-1]
-        S = idx.numel() // max(n, 1)
-        if S != self.freq_host.shape[0]:
-            raise ValueError(f"{S} index streams but {self.freq_host.shape[0]} frequency rows")
-        nseg = (n + self.segment - 1) // self.segment
+        idx, S, n, nseg = self._streams(idx)
         dev = idx.device
         words = torch.empty((S, nseg, self.segment + 2), dtype=torch.uint16, device=dev)    # pack reads valid words only
         aux = torch.empty(8 + 4 * S * nseg, dtype=torch.uint8, device=dev)                  # total u64, then sizes u32
         total, sizes = aux[:8].view(torch.uint64), aux[8:].view(torch.uint32).view(S, nseg)
         payload = torch.empty(S * nseg * (self.segment + 2), dtype=torch.uint16, device=dev)
         offsets = torch.empty((S, nseg), dtype=torch.int64, device=dev)
-        check(_lib.lib().vbq_rans_encode_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(dev)),
-                                             ops._ptr(words), ops._ptr(sizes), ops._stream(idx)), "vbq_rans_encode_u16")
+        self._encode(idx, S, n, words, sizes)
         self._pack(words, sizes, payload, offsets, total)
         h = aux.cpu().numpy()
         n_words = int(h[:8].view(np.uint64)[0])
@@ -259,11 +255,8 @@ class RansCodec:
         A damaged payload raises VBQError."""
         status = torch.zeros(1, dtype=torch.uint32, device=payload.device)
         words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
-        S = self.freq_host.shape[0]
-        idx = torch.empty((S, n), dtype=torch.uint16, device=payload.device)
-        check(_lib.lib().vbq_rans_decode_u16(ops._ptr(words), ops._ptr(out_sizes), S, n, self.N, self.segment,
-                                             ops._ptr(self._freq(payload.device)), ops._ptr(idx), ops._ptr(status),
-                                             ops._stream(payload)), "vbq_rans_decode_u16")
+        idx = torch.empty((self.freq_host.shape[0], n), dtype=torch.uint16, device=payload.device)
+        self._decode(words, out_sizes, n, idx, status)
         _raise_status(int(status.cpu().item()))
         return idx
 

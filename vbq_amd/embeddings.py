@@ -19,21 +19,12 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import VBQError
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise VBQError("no ROCm device visible: vbq_amd.embeddings has no CPU implementation")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _dev(a, dtype=torch.float32):
     from .lazy import device_tensor
     t = device_tensor(a)                     # a result of this package that still lives on the device: no round trip
-    if t is None:
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-    return t.to(_device(), dtype).contiguous()
+    return ops.upload(a if t is None else t, ops.current_device("vbq_amd.embeddings"), dtype)
 
 
 _STAGER = None
@@ -325,7 +316,7 @@ class CompressedEmbeddings:
         raw = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
         self.header = h
         self.nbytes = int(raw.size)
-        self.device = torch.device(device) if device is not None else _device()
+        self.device = torch.device(device) if device is not None else ops.current_device("vbq_amd.embeddings")
         T = 2 ** (h.N + 1) - 1
         # ONE upload: dense freq u16 [T] (+ 2 bytes: the values stay 4-byte aligned), values f32 [T], sizes u16 [nseg],
         # payload u16 [n_words] (the last two straight from the file)

@@ -15,12 +15,6 @@ from ._lib import VBQError, check
 float_type = "float64"
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise VBQError("no ROCm device visible: vbq_amd.metrics has no CPU implementation")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _on_device(x):
     return isinstance(x, torch.Tensor) and x.is_cuda
 
@@ -46,7 +40,7 @@ def _as_f64_device(a):
             return a.to(torch.float64).contiguous()
         u = a.contiguous()
     else:
-        dev = _device()
+        dev = ops.current_device("vbq_amd.metrics")
         if a.dtype != np.uint8:
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
         u = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -59,7 +53,7 @@ def mse(img1, img2):
     """img_comparison_metrics.py:6-16: mean squared difference over (H, W, C), float64 [B]."""
     a, b = _check_pair(img1, img2)
     if _is_u8(a) and _is_u8(b):
-        ta, tb = (x.contiguous() if _on_device(x) else torch.from_numpy(np.ascontiguousarray(x)).to(_device()) for x in (a, b))
+        ta, tb = (x.contiguous() if _on_device(x) else torch.from_numpy(np.ascontiguousarray(x)).to(ops.current_device("vbq_amd.metrics")) for x in (a, b))
         out = torch.empty(a.shape[0], dtype=torch.int64, device=ta.device)
         n = int(np.prod(tuple(a.shape[1:])))
         check(_lib.lib().vbq_image_sqerr_u8(ops._ptr(ta), ops._ptr(tb), a.shape[0], n, ops._ptr(out), ops._stream(ta)),
@@ -128,5 +122,5 @@ def ms_ssim(img1, img2, max_val=255, filter_size=11, filter_sigma=1.5, k1=0.01, 
 
 
 def convert_to_db(d):
-    """utils.py:497-499."""
+    """utils.py:497-499 (BMSHJ ICLR 2018, p. 8)."""
     return -10 * np.log10(1 - d)

@@ -6,17 +6,15 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import LAYOUT_BC, LAYOUT_BC_TO_CB, LAYOUT_CB, MODE_F32, MODE_F64_SCORE, VBQError, check
+from .tables import table_size
 
 _LAYOUTS = {"bc": LAYOUT_BC, "cb": LAYOUT_CB, LAYOUT_BC: LAYOUT_BC, LAYOUT_CB: LAYOUT_CB}
 _MODES = {"f32": MODE_F32, "f64": MODE_F64_SCORE, MODE_F32: MODE_F32, MODE_F64_SCORE: MODE_F64_SCORE}
-
-
-def table_size(N: int) -> int:
-    return 2 ** (N + 1) - 1
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -28,6 +26,19 @@ def raw_stream(device: torch.device) -> int:
     if _raw_stream is not None:
         return _raw_stream(device.index if device.index is not None else torch.cuda.current_device())
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def current_device(who: str) -> torch.device:
+    """The current ROCm device; VBQError in the name of `who` (a module or class that computes nowhere else) without one."""
+    if not torch.cuda.is_available():
+        raise VBQError(f"no ROCm device visible: {who} has no CPU implementation")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def upload(a, device, dtype) -> torch.Tensor:
+    """A tensor, NumPy array or sequence -> contiguous tensor of `dtype` on `device`."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+    return t.to(device, dtype).contiguous()
 
 
 def _stream(t: torch.Tensor):
@@ -62,6 +73,68 @@ def _rows_channels(shape, layout):
     return (shape[0], shape[1]) if layout == LAYOUT_BC else (shape[1], shape[0])
 
 
+# The argument checks the entry points share.  Each is the inline code it replaced: attribute reads and comparisons only.
+def _pair(mu, sigma):
+    mu = _dev(mu, torch.float32, "mu")
+    sigma = _dev(sigma, torch.float32, "sigma")
+    if mu.shape != sigma.shape:
+        raise ValueError(f"mu {tuple(mu.shape)} and sigma {tuple(sigma.shape)} differ in shape")
+    return mu, sigma
+
+
+def _pair_bc(means_bc, spread_bc):
+    means_bc = _dev(means_bc, torch.float32, "means")
+    spread_bc = _dev(spread_bc, torch.float32, "spread")
+    if means_bc.dim() != 2 or means_bc.shape != spread_bc.shape:
+        raise ValueError(f"expected two [rows, C] tensors, got {tuple(means_bc.shape)} / {tuple(spread_bc.shape)}")
+    return means_bc, spread_bc
+
+
+def _table(t, Cc, T, name):
+    t = _dev(t, torch.float32, name)
+    if t.numel() != Cc * T:
+        raise ValueError(f"{name} has {t.numel()} entries, expected C*T = {Cc}*{T}")
+    return t
+
+
+def _per_lambda(t, shape, name):
+    """An f32 table with one slice per lambda (level_len [L, C, N+1], models [L, C, T]); otherwise e.g.
+    "level_len shape (2, 2, 4) != (2, 2, 5)"."""
+    t = _dev(t, torch.float32, name)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} shape {tuple(t.shape)} != {shape}")
+    return t
+
+
+def _workspace(given, nbytes, device, floor=0):
+    ws = given if given is not None else torch.empty(max(nbytes, floor), dtype=torch.uint8, device=device)
+    if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
+        raise ValueError(f"workspace must be a device tensor of at least {nbytes} bytes")
+    return ws
+
+
+def _out(given, shape, dtype, device, name, want=True):
+    """The caller's output tensor, checked (its pointer goes to the library), or a new one (None when not wanted)."""
+    if given is not None:
+        if tuple(given.shape) != shape or given.dtype != dtype or not given.is_cuda or not given.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous {dtype} device tensor of shape {shape}")
+        return given
+    return torch.empty(shape, dtype=dtype, device=device) if want else None
+
+
+def _solve_inputs(mu, sigma, table_lm, lambdas, N, level_len, layout):
+    """What K1 and K1t / K1h take alike -> (mu, sigma, rows, C, table_lm, L, level_len)."""
+    mu, sigma = _pair(mu, sigma)
+    rows, Cc = _rows_channels(mu.shape, layout)
+    table_lm = _table(table_lm, Cc, table_size(N), "table_lm")
+    L = len(lambdas)
+    if L < 1:
+        raise ValueError("need at least one lambda")
+    if level_len is not None:
+        level_len = _per_lambda(level_len, (L, Cc, N + 1), "level_len")
+    return mu, sigma, rows, Cc, table_lm, L, level_len
+
+
 def quantize(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, lambdas: Sequence[float], *,
              N: int = 10, level_len: Optional[torch.Tensor] = None, layout="bc", mode="f32",
              want_zhat: bool = False, want_bits: bool = False, out_idx: Optional[torch.Tensor] = None,
@@ -80,43 +153,18 @@ def quantize(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, lamb
     layout = LAYOUT_BC if to_planes else _LAYOUTS[layout]
     mode = _MODES[mode]
     rows_range = rows
-    mu = _dev(mu, torch.float32, "mu")
-    sigma = _dev(sigma, torch.float32, "sigma")
-    if mu.shape != sigma.shape:
-        raise ValueError(f"mu {tuple(mu.shape)} and sigma {tuple(sigma.shape)} differ in shape")
-    rows, Cc = _rows_channels(mu.shape, layout)
-    T = table_size(N)
-    table_lm = _dev(table_lm, torch.float32, "table_lm")
-    if table_lm.numel() != Cc * T:
-        raise ValueError(f"table_lm has {table_lm.numel()} entries, expected C*T = {Cc}*{T}")
-    L = len(lambdas)
-    if L < 1:
-        raise ValueError("need at least one lambda")
-    if level_len is not None:
-        level_len = _dev(level_len, torch.float32, "level_len")
-        if tuple(level_len.shape) != (L, Cc, N + 1):
-            raise ValueError(f"level_len shape {tuple(level_len.shape)} != {(L, Cc, N + 1)}")
+    mu, sigma, rows, Cc, table_lm, L, level_len = _solve_inputs(mu, sigma, table_lm, lambdas, N, level_len, layout)
     h = _lib.lib()
     if to_planes and mu.dim() == 2 and Cc > 1:
         layout, oshape = LAYOUT_BC_TO_CB, (L, Cc, rows)
     else:
         oshape = (L,) + tuple(mu.shape)
-
-    def _out(given, dtype, want, name):
-        if given is not None:
-            if tuple(given.shape) != oshape or given.dtype != dtype or not given.is_cuda or not given.is_contiguous():
-                raise ValueError(f"{name}: expected a contiguous {dtype} device tensor of shape {oshape}")
-            return given
-        return torch.empty(oshape, dtype=dtype, device=mu.device) if want else None
-
-    idx = _out(out_idx, torch.uint16, True, "out_idx")
-    zhat = _out(out_zhat, torch.float32, want_zhat, "out_zhat")
-    bits = _out(out_bits, torch.float32, want_bits, "out_bits")
+    idx = _out(out_idx, oshape, torch.uint16, mu.device, "out_idx")
+    zhat = _out(out_zhat, oshape, torch.float32, mu.device, "out_zhat", want_zhat)
+    bits = _out(out_bits, oshape, torch.float32, mu.device, "out_bits", want_bits)
     want_zhat, want_bits = zhat is not None, bits is not None
     wsb = h.vbq_quantize_workspace_bytes(Cc, L, N)
-    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=mu.device)
-    if ws.numel() * ws.element_size() < wsb or not ws.is_cuda:
-        raise ValueError(f"workspace must be a device tensor of at least {wsb} bytes")
+    ws = _workspace(workspace, wsb, mu.device)
     if mu.numel() == 0:
         out = (idx,) + ((zhat,) if want_zhat else ()) + ((bits,) if want_bits else ())
         return out if len(out) > 1 else idx
@@ -141,10 +189,7 @@ def quantize(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, lamb
 def check_inputs(mu: torch.Tensor, sigma: torch.Tensor):
     """vbq_check_inputs_f32: raise ValueError when mu holds NaN / infinity or sigma holds NaN / infinity / values <= 0 --
     the inputs vbq_quantize_f32 does not define an answer for (synchronises: one 8-byte read)."""
-    mu = _dev(mu, torch.float32, "mu")
-    sigma = _dev(sigma, torch.float32, "sigma")
-    if mu.shape != sigma.shape:
-        raise ValueError(f"mu {tuple(mu.shape)} and sigma {tuple(sigma.shape)} differ in shape")
+    mu, sigma = _pair(mu, sigma)
     bad = torch.zeros(2, dtype=torch.uint32, device=mu.device)
     check(_lib.lib().vbq_check_inputs_f32(_ptr(mu), _ptr(sigma), mu.numel(), _ptr(bad), _stream(mu)), "vbq_check_inputs_f32")
     b = bad.cpu().numpy()
@@ -159,33 +204,16 @@ def level_counts(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, 
     winners' bit levels, in one kernel with no per-element output.  Returns int64 [L, C, N+1] (added into `out`)."""
     to_planes = layout in ("bc->cb", LAYOUT_BC_TO_CB)
     layout = LAYOUT_BC if to_planes else _LAYOUTS[layout]
-    mu = _dev(mu, torch.float32, "mu")
-    sigma = _dev(sigma, torch.float32, "sigma")
-    if mu.shape != sigma.shape:
-        raise ValueError(f"mu {tuple(mu.shape)} and sigma {tuple(sigma.shape)} differ in shape")
-    rows, Cc = _rows_channels(mu.shape, layout)
-    T = table_size(N)
-    table_lm = _dev(table_lm, torch.float32, "table_lm")
-    if table_lm.numel() != Cc * T:
-        raise ValueError(f"table_lm has {table_lm.numel()} entries, expected C*T = {Cc}*{T}")
-    L = len(lambdas)
-    if L < 1:
-        raise ValueError("need at least one lambda")
-    if level_len is not None:
-        level_len = _dev(level_len, torch.float32, "level_len")
-        if tuple(level_len.shape) != (L, Cc, N + 1):
-            raise ValueError(f"level_len shape {tuple(level_len.shape)} != {(L, Cc, N + 1)}")
+    mu, sigma, rows, Cc, table_lm, L, level_len = _solve_inputs(mu, sigma, table_lm, lambdas, N, level_len, layout)
     if to_planes and mu.dim() == 2 and Cc > 1:
         layout = LAYOUT_BC_TO_CB
     if out is None:
         out = torch.zeros((L, Cc, N + 1), dtype=torch.int64, device=mu.device)
-    elif tuple(out.shape) != (L, Cc, N + 1) or out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError(f"out: expected a contiguous int64 device tensor of shape {(L, Cc, N + 1)}")
+    else:
+        _out(out, (L, Cc, N + 1), torch.int64, mu.device, "out")
     h = _lib.lib()
     wsb = h.vbq_quantize_workspace_bytes(Cc, L, N)
-    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=mu.device)
-    if ws.numel() * ws.element_size() < wsb or not ws.is_cuda:
-        raise ValueError(f"workspace must be a device tensor of at least {wsb} bytes")
+    ws = _workspace(workspace, wsb, mu.device)
     if mu.numel():
         check(h.vbq_level_counts_f32(_ptr(mu), _ptr(sigma), rows, Cc, layout, _ptr(table_lm), _ptr(level_len),
                                      _doubles(lambdas), L, N, _ptr(out), _ptr(ws), wsb,
@@ -195,20 +223,22 @@ def level_counts(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, 
 
 
 def code_lengths_from_counts(counts: torch.Tensor, lut: torch.Tensor, *, level_period: int = 0, want_len: bool = True,
-                             want_model: bool = False):
-    """vbq_code_lengths_from_counts: f32 tensors shaped like `counts` -- (level +) lut[count] and / or lut[count]."""
+                             want_model: bool = False, out_len: Optional[torch.Tensor] = None,
+                             out_model: Optional[torch.Tensor] = None):
+    """vbq_code_lengths_from_counts: f32 tensors shaped like `counts` -- (level +) lut[count] and / or lut[count].
+    out_len / out_model: the caller's tensors, written instead of new ones (giving one asks for that result)."""
     if counts.dtype not in (torch.int64, torch.int32):
         raise ValueError("counts must be int64 or int32")
     counts = _dev(counts, counts.dtype, "counts")
     lut = _dev(lut, torch.float32, "lut")
-    out_len = torch.empty(counts.shape, dtype=torch.float32, device=counts.device) if want_len else None
-    out_model = torch.empty(counts.shape, dtype=torch.float32, device=counts.device) if want_model else None
+    out_len = _out(out_len, tuple(counts.shape), torch.float32, counts.device, "out_len", want_len)
+    out_model = _out(out_model, tuple(counts.shape), torch.float32, counts.device, "out_model", want_model)
     check(_lib.lib().vbq_code_lengths_from_counts(_ptr(counts), int(counts.dtype == torch.int32), counts.numel(), _ptr(lut),
                                                   lut.numel(), int(level_period), _ptr(out_len), _ptr(out_model),
                                                   _stream(counts)), "vbq_code_lengths_from_counts")
-    if want_len and want_model:
+    if out_len is not None and out_model is not None:
         return out_len, out_model
-    return out_len if want_len else out_model
+    return out_len if out_len is not None else out_model
 
 
 def quantize_notebook(means: torch.Tensor, stds: torch.Tensor, codebook_lm: torch.Tensor, betas: Sequence[float], *,
@@ -223,12 +253,7 @@ def quantize_notebook(means: torch.Tensor, stds: torch.Tensor, codebook_lm: torc
         raise ValueError(f"codebook has {codebook_lm.numel()} entries, expected {table_size(N)}")
     nb = len(betas)
     n = means.numel()
-    if out_idx is not None:
-        if tuple(out_idx.shape) != (nb,) + tuple(means.shape) or out_idx.dtype != torch.uint16 or not out_idx.is_contiguous():
-            raise ValueError(f"out_idx: expected a contiguous uint16 tensor of shape {(nb,) + tuple(means.shape)}")
-        idx = out_idx
-    else:
-        idx = torch.empty((nb,) + tuple(means.shape), dtype=torch.uint16, device=means.device)
+    idx = _out(out_idx, (nb,) + tuple(means.shape), torch.uint16, means.device, "out_idx")
     val = torch.empty((nb,) + tuple(means.shape), dtype=torch.float32, device=means.device) if want_values else None
     check(_lib.lib().vbq_quantize_notebook_f64(_ptr(means), _ptr(stds), n, _ptr(codebook_lm), _doubles(betas), nb, N,
                                                _ptr(idx), _ptr(val), _stream(means)), "vbq_quantize_notebook_f64")
@@ -255,9 +280,7 @@ def histogram(idx: torch.Tensor, n_ch: int, *, N: int = 10, layout="bc", out: Op
             raise ValueError("out must be int64 or int32")
         if not out.is_contiguous():
             raise ValueError("out must be contiguous (counts are accumulated in place)")
-        out = _dev(out, out.dtype, "out")
-        if tuple(out.shape) != (L, n_ch, T):
-            raise ValueError(f"out shape {tuple(out.shape)} != {(L, n_ch, T)}")
+        out = _out(_dev(out, out.dtype, "out"), (L, n_ch, T), out.dtype, idx.device, "out")
     h = _lib.lib()
     if rows_range is not None:
         check(h.vbq_histogram_rows_u16(_ptr(idx), rows, n_ch, layout, L, N, _ptr(out), int(out.dtype == torch.int32),
@@ -278,14 +301,14 @@ def histogram_models(idx: torch.Tensor, n_ch: int, counts: torch.Tensor, *, N: i
         raise ValueError(f"idx must be planes [L, {n_ch}, rows], got {tuple(idx.shape)}")
     L, _, rows = idx.shape
     T = table_size(N)
-    if counts.dtype not in (torch.int64, torch.int32) or tuple(counts.shape) != (L, n_ch, T) or not counts.is_cuda or not counts.is_contiguous():
+    if counts.dtype not in (torch.int64, torch.int32):
         raise ValueError(f"counts: expected a contiguous int32 / int64 device tensor of shape {(L, n_ch, T)}")
+    _out(counts, (L, n_ch, T), counts.dtype, idx.device, "counts")
     if (lut is None) != (models is None):
         raise ValueError("lut and models go together")
     if models is not None:
         lut = _dev(lut, torch.float32, "lut")
-        if models.dtype != torch.float32 or tuple(models.shape) != (L, n_ch, T) or not models.is_cuda or not models.is_contiguous():
-            raise ValueError(f"models: expected a contiguous f32 device tensor of shape {(L, n_ch, T)}")
+        _out(models, (L, n_ch, T), torch.float32, idx.device, "models")
     check(_lib.lib().vbq_histogram_models_u16(_ptr(idx), rows, n_ch, L, N, _ptr(counts), int(counts.dtype == torch.int32), _ptr(lut),
                                               lut.numel() if lut is not None else 0, _ptr(models), _stream(idx)),
           "vbq_histogram_models_u16")
@@ -391,21 +414,13 @@ def prep_planes(means_bc: torch.Tensor, spread_bc: torch.Tensor, *, spread: str 
     """vbq_prep_planes_f32: channel-last [rows, C] means and spreads -> channel-major planes [C, rows] in ONE launch.
     spread: what `spread_bc` holds -- 'sigma', 'variance' (sigma = sqrt(.)) or 'logvar' (sigma = sqrt(exp(.)), the
     `tf.exp(posterior_logvars) ** 0.5` of quantizer.py:197,202 inside the launch)."""
-    means_bc = _dev(means_bc, torch.float32, "means")
-    spread_bc = _dev(spread_bc, torch.float32, "spread")
-    if means_bc.dim() != 2 or means_bc.shape != spread_bc.shape:
-        raise ValueError(f"expected two [rows, C] tensors, got {tuple(means_bc.shape)} / {tuple(spread_bc.shape)}")
+    means_bc, spread_bc = _pair_bc(means_bc, spread_bc)
     r, c = means_bc.shape
-    outs = []
-    for o, name in ((out_mu, "out_mu"), (out_sigma, "out_sigma")):
-        if o is None:
-            o = torch.empty((c, r), dtype=torch.float32, device=means_bc.device)
-        elif tuple(o.shape) != (c, r) or o.dtype != torch.float32 or not o.is_contiguous() or not o.is_cuda:
-            raise ValueError(f"{name} must be a contiguous f32 device tensor of shape {(c, r)}")
-        outs.append(o)
-    check(_lib.lib().vbq_prep_planes_f32(_ptr(means_bc), _ptr(spread_bc), _spread_kind(spread), r, c, _ptr(outs[0]),
-                                         _ptr(outs[1]), _stream(means_bc)), "vbq_prep_planes_f32")
-    return outs[0], outs[1]
+    out_mu = _out(out_mu, (c, r), torch.float32, means_bc.device, "out_mu")
+    out_sigma = _out(out_sigma, (c, r), torch.float32, means_bc.device, "out_sigma")
+    check(_lib.lib().vbq_prep_planes_f32(_ptr(means_bc), _ptr(spread_bc), _spread_kind(spread), r, c, _ptr(out_mu),
+                                         _ptr(out_sigma), _stream(means_bc)), "vbq_prep_planes_f32")
+    return out_mu, out_sigma
 
 
 def gather_latents(idx_planes: torch.Tensor, *, N: int = 10, table_sorted: Optional[torch.Tensor] = None,
@@ -419,17 +434,11 @@ def gather_latents(idx_planes: torch.Tensor, *, N: int = 10, table_sorted: Optio
     L, Cc, B = idx_planes.shape
     T = table_size(N)
     if want_zhat:
-        table_sorted = _dev(table_sorted, torch.float32, "table_sorted")
-        if table_sorted.numel() != Cc * T:
-            raise ValueError(f"table_sorted has {table_sorted.numel()} entries, expected {Cc}*{T}")
+        table_sorted = _table(table_sorted, Cc, T, "table_sorted")
     if level_len is not None:
-        level_len = _dev(level_len, torch.float32, "level_len")
-        if tuple(level_len.shape) != (L, Cc, N + 1):
-            raise ValueError(f"level_len shape {tuple(level_len.shape)} != {(L, Cc, N + 1)}")
+        level_len = _per_lambda(level_len, (L, Cc, N + 1), "level_len")
     if want_num_bits:
-        models = _dev(models, torch.float32, "models")
-        if tuple(models.shape) != (L, Cc, T):
-            raise ValueError(f"models shape {tuple(models.shape)} != {(L, Cc, T)}")
+        models = _per_lambda(models, (L, Cc, T), "models")
     dev = idx_planes.device
     z = torch.empty((L, B, Cc), dtype=torch.float32, device=dev) if want_zhat else None
     raw = torch.empty((L, B, Cc), dtype=torch.int32 if level_len is None else torch.float32, device=dev) if want_raw_bits else None
@@ -448,10 +457,7 @@ def compress_latents(means_bc: torch.Tensor, spread_bc: torch.Tensor, table_lm: 
     """vbq_compress_latents_f32: the per-image call of quantizer.py:190-240 in one C call (planes, solve, fused lookups).
     means / spreads channel-last [B, C] (spread: 'sigma' | 'variance' | 'logvar', see prep_planes); returns
     (Z_hat f32, raw_num_bits int32 | f32, num_bits f32 | None), [L, B, C]."""
-    means_bc = _dev(means_bc, torch.float32, "means")
-    spread_bc = _dev(spread_bc, torch.float32, "spread")
-    if means_bc.dim() != 2 or means_bc.shape != spread_bc.shape:
-        raise ValueError(f"expected two [rows, C] tensors, got {tuple(means_bc.shape)} / {tuple(spread_bc.shape)}")
+    means_bc, spread_bc = _pair_bc(means_bc, spread_bc)
     B, Cc = means_bc.shape
     L = len(lambdas)
     T = table_size(N)
@@ -462,19 +468,13 @@ def compress_latents(means_bc: torch.Tensor, spread_bc: torch.Tensor, table_lm: 
     if table_lm.numel() != Cc * T or table_sorted.numel() != Cc * T:
         raise ValueError(f"tables must hold C*T = {Cc}*{T} entries")
     if level_len is not None:
-        level_len = _dev(level_len, torch.float32, "level_len")
-        if tuple(level_len.shape) != (L, Cc, N + 1):
-            raise ValueError(f"level_len shape {tuple(level_len.shape)} != {(L, Cc, N + 1)}")
+        level_len = _per_lambda(level_len, (L, Cc, N + 1), "level_len")
     if models is not None:
-        models = _dev(models, torch.float32, "models")
-        if tuple(models.shape) != (L, Cc, T):
-            raise ValueError(f"models shape {tuple(models.shape)} != {(L, Cc, T)}")
+        models = _per_lambda(models, (L, Cc, T), "models")
     dev = means_bc.device
     h = _lib.lib()
     wsb = h.vbq_compress_latents_workspace_bytes(B, Cc, L, N)
-    ws = workspace if workspace is not None else torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
-    if ws.numel() * ws.element_size() < wsb or not ws.is_cuda:
-        raise ValueError(f"workspace must be a device tensor of at least {wsb} bytes")
+    ws = _workspace(workspace, wsb, dev, floor=256)
     z = torch.empty((L, B, Cc), dtype=torch.float32, device=dev)
     raw = torch.empty((L, B, Cc), dtype=torch.int32 if level_len is None else torch.float32, device=dev)
     nb = torch.empty((L, B, Cc), dtype=torch.float32, device=dev) if models is not None else None
@@ -492,10 +492,7 @@ def transpose(x: torch.Tensor, out: Optional[torch.Tensor] = None):
     if x.dim() != 2:
         raise ValueError("transpose expects a 2-D tensor")
     r, c = x.shape
-    if out is None:
-        out = torch.empty((c, r), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (c, r) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous f32 tensor of shape {(c, r)}")
+    out = _out(out, (c, r), torch.float32, x.device, "out")
     check(_lib.lib().vbq_transpose_f32(_ptr(x), r, c, _ptr(out), _stream(x)), "vbq_transpose_f32")
     return out
 
@@ -538,10 +535,7 @@ def transpose_planes(x: torch.Tensor, out: Optional[torch.Tensor] = None):
         raise ValueError("transpose_planes expects a 3-D tensor of 2- or 4-byte elements")
     x = x.contiguous()
     b, r, c = x.shape
-    if out is None:
-        out = torch.empty((b, c, r), dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != (b, c, r) or out.dtype != x.dtype or not out.is_contiguous() or not out.is_cuda:
-        raise ValueError(f"out must be a contiguous {x.dtype} device tensor of shape {(b, c, r)}")
+    out = _out(out, (b, c, r), x.dtype, x.device, "out")
     check(_lib.lib().vbq_transpose_planes(_ptr(x), b, r, c, x.element_size(), _ptr(out), _stream(x)), "vbq_transpose_planes")
     return out
 

@@ -412,12 +412,9 @@ class EntropyModelBuild:
 
     def lengths(self):
         """quantizer.py:105-112 and the "n + overhead" of :171-175 -> (level_len, raw_models), device f32 [L, C, N+1]."""
-        N1 = self.N + 1
         if self.lut1 is not None:
-            ops_out = ops._lib.lib().vbq_code_lengths_from_counts
-            ops._lib.check(ops_out(ops._ptr(self.level_counts), 0, self.level_counts.numel(), ops._ptr(self.lut1),
-                                   self.lut1.numel(), N1, ops._ptr(self.level_len), ops._ptr(self.raw_models),
-                                   ops._stream(self.level_counts)), "vbq_code_lengths_from_counts")
+            ops.code_lengths_from_counts(self.level_counts, self.lut1, level_period=self.N + 1, out_len=self.level_len,
+                                         out_model=self.raw_models)
         else:                          # the [L, C, N+1] table through a stream-ordered host stage (no synchronisation)
             self._len_stage.enqueue()
         return self.level_len, self.raw_models
@@ -494,9 +491,7 @@ class EntropyModelBuild:
         if self.lut2 is None:                              # not tabulated: NumPy on the counts, stream-ordered
             self._model_stages[slot].enqueue()
         else:
-            ops._lib.check(ops._lib.lib().vbq_code_lengths_from_counts(
-                ops._ptr(counts), int(counts.dtype == torch.int32), counts.numel(), ops._ptr(self.lut2),
-                self.lut2.numel(), 0, None, ops._ptr(self.models), ops._stream(counts)), "vbq_code_lengths_from_counts")
+            ops.code_lengths_from_counts(counts, self.lut2, want_len=False, out_model=self.models)
         self._models_pending[slot] = False
 
     def finish_models(self):

@@ -25,12 +25,7 @@ import torch
 
 from . import entropy as _entropy
 from . import ops
-from ._lib import VBQError
-
-
-def n_bit_binary_floats(n: int):
-    """utils.py:23-24."""
-    return [i * 2 ** (-n) + 2 ** (-n - 1) for i in range(2 ** n)]
+from .tables import n_bit_binary_floats
 
 
 def _to_numpy(a):
@@ -39,12 +34,6 @@ def _to_numpy(a):
     if hasattr(a, "numpy") and not isinstance(a, np.ndarray):      # e.g. a TF eager tensor
         return np.asarray(a.numpy())
     return np.asarray(a)
-
-
-def _default_device():
-    if not torch.cuda.is_available():
-        raise VBQError("no ROCm device visible: the VBQ quantizer has no CPU implementation")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 class DeviceModels(MutableMapping):
@@ -236,7 +225,7 @@ class ChannelwisePriorCDFQuantizer:
     @property
     def device(self):
         if self._device is None:
-            self._device = _default_device()
+            self._device = ops.current_device("the VBQ quantizer")
         return self._device
 
     def _dev(self, name: str, builder):

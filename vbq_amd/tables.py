@@ -11,6 +11,11 @@ def table_size(N: int) -> int:
     return 2 ** (N + 1) - 1
 
 
+def n_bit_binary_floats(n: int):
+    """utils.py:23-24."""
+    return [i * 2 ** (-n) + 2 ** (-n - 1) for i in range(2 ** n)]
+
+
 def dyadic_xi(N: int) -> np.ndarray:
     """All xi of levels 0..N, level-major (utils.py:23-24 stacked as in quantizer.py:30)."""
     return np.concatenate([(np.arange(2 ** n, dtype=np.float64) + 0.5) / 2 ** n for n in range(N + 1)])

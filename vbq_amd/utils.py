@@ -13,11 +13,8 @@ import torch
 
 from . import ops
 from ._lib import VBQError
-
-
-def n_bit_binary_floats(n):
-    """utils.py:23-24."""
-    return [i * 2 ** (-n) + 2 ** (-n - 1) for i in range(2 ** n)]
+from .metrics import convert_to_db          # utils.py:497-499
+from .tables import n_bit_binary_floats     # noqa: F401  (utils.py:23-24; part of this module's surface)
 
 
 class NormalNegHalfSqErr:
@@ -42,14 +39,7 @@ def curry_normal_logpdf(loc, scale, ignore_const=False, backend=np):
 
 
 def _dev_f32(a, device):
-    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-    return t.to(device, torch.float32).contiguous()
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise VBQError("no ROCm device visible: vbq_amd.utils has no CPU implementation")
-    return torch.device("cuda", torch.cuda.current_device())
+    return ops.upload(a, device, torch.float32)
 
 
 def _mode(code_lengths, lambs):
@@ -65,7 +55,7 @@ def batch_quantize_indep_dims(Z_shape, code_points, code_lengths, fun, lambs, ba
     """utils.py:363-423.  code_points: K x M, or M x B x K; code_lengths likewise, or L x M x B x K."""
     if not isinstance(fun, NormalNegHalfSqErr):
         raise TypeError("fun must be created by vbq_amd.utils.curry_normal_logpdf (Gaussian distortion)")
-    dev = _device()
+    dev = ops.current_device("vbq_amd.utils")
     B, K = Z_shape
     mode = mode or _mode(code_lengths, lambs)
     P = _dev_f32(code_points, dev)
@@ -100,7 +90,7 @@ def get_all_N_bit_intervals(x, N, left_endpoints, right_endpoints):
     """utils.py:215-260 (the numba kernel), same in-place signature: fills the two (N+1) x K float64 arrays with the
     n-bit grid points around every x[k].  Runs on the GPU (vbq_xi_intervals_f64)."""
     from . import _lib, ops
-    dev = _device()
+    dev = ops.current_device("vbq_amd.utils")
     xd = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64))).to(dev)
     K = xd.numel()
     ld = torch.empty((N + 1, K), dtype=torch.float64, device=dev)
@@ -116,7 +106,7 @@ def encode_vectorized(fun, z, lamb, squash, unsquash, max_bits_per_coord=16):
     evaluated where the caller defined them; the interval search before them and the selection after them run on the GPU
     in the reference's float64.  Returns the reference's dict (z_hat, score, num_bits, xi_hat)."""
     from . import _lib, ops
-    dev = _device()
+    dev = ops.current_device("vbq_amd.utils")
     z = np.asarray(z)
     K, N = len(z), int(max_bits_per_coord)
     xi = np.asarray(squash(z), dtype=np.float64)
@@ -208,7 +198,7 @@ def encode_mode_dp(f, mode, nbits, squash, unsquash, zero_bit_mode_hat):
     """utils.py:106-160: spend exactly `nbits` bits over the K coordinates (at most nbits each) so that the sum of f[k] at the
     quantised modes is largest.  f, squash, unsquash: length-K lists of scalar functions.  The allocation is the budget DP kernel
     (vbq_budget_dp_f64); returns the reference's (mode_hat, obj, num_bits)."""
-    dev = _device()
+    dev = ops.current_device("vbq_amd.utils")
     K, N = len(f), int(nbits)
     scores, values = _level_tables(f, mode, N, squash, unsquash, zero_bit_mode_hat)
     bits, obj = ops.budget_dp(torch.from_numpy(scores).to(dev), K, N)
@@ -220,7 +210,7 @@ def encode_mode(f, mode, lamb, squash, unsquash, zero_bit_mode_hat, max_bits_per
     """utils.py:163-208: per coordinate the bit count b that maximises f[k](mode_hat_k(b)) - lamb * b, scanned upwards until three
     counts in a row bring no improvement (vbq_budget_patience_f64).  Returns the reference's (mode_hat, obj, num_bits); obj is
     the reference's running sum over k."""
-    dev = _device()
+    dev = ops.current_device("vbq_amd.utils")
     K, N = len(f), int(max_bits_per_coord)
     scores, values = _level_tables(f, mode, N, squash, unsquash, zero_bit_mode_hat)
     bits, g = ops.budget_patience(torch.from_numpy(scores).to(dev), float(lamb), patience=3)
@@ -228,11 +218,6 @@ def encode_mode(f, mode, lamb, squash, unsquash, zero_bit_mode_hat, max_bits_per
     mode_hat = np.empty_like(np.asarray(mode))
     mode_hat[...] = values[num_bits, np.arange(K)]
     return mode_hat, np.add.accumulate(g.cpu().numpy())[-1], num_bits
-
-
-def convert_to_db(d):
-    """utils.py:497-499 (BMSHJ ICLR 2018, p. 8)."""
-    return -10 * np.log10(1 - d)
 
 
 def _quality_by_mode(x, x_yc, x_hats, x_hats_yc):
