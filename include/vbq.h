@@ -567,6 +567,44 @@ int vbq_rans_decode_values_f32(const uint16_t *d_payload, int64_t n_words, const
                                const int64_t *d_segments, int64_t n_sel, float *d_out, uint32_t *d_status, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Wave-interleaved rANS: the coder of the compact latent file (vbq_amd/bitstream.py, magic "VBQc").  These three entry
+ * points were added without an ABI version bump: nothing that existed before changed.
+ *
+ * Coder constants as above (32-bit state, start state 2^16, 16-bit words, 15 probability bits; c = exclusive cumulative
+ * frequency).  The n_streams * n symbols of d_idx u16 [n_streams][n], in that order, are cut every `part` symbols
+ * (1 <= part <= 2^24; the last part may be shorter): P = ceil(n_streams * n / part) parts, each coded by 64 lanes.  A part
+ * may start and end inside a stream.  Inside a part a RUN is a maximal stretch within one stream; it uses that stream's
+ * frequency row and takes ceil(len / 64) steps; in step t lane l owns the run's symbol 64 t + l when that is < len and
+ * idles otherwise.  The 64 lane states carry on from run to run.  The words of a part, in the order the decoder reads them:
+ *   1. 128 words: the states of lanes 0 .. 63, low half then high half of each;
+ *   2. for every run in order and every step in order: each active lane decodes (slot = x & 32767, x = f (x >> 15) + slot
+ *      - c), then each active lane whose state is below 2^16 takes one word, in ascending lane order (x = x << 16 | w).
+ *   At the end every word has been taken and every lane's state is 2^16.
+ * The encoder is the exact inverse: runs last to first, steps last to first; a lane with x >= f << 17 emits x & 0xffff and
+ * shifts x >>= 16 before x = (x / f << 15) + x % f + c.  A part of m symbols takes 128 .. m + 128 words.
+ *
+ * vbq_rans_il_sizes_u16:  d_sizes u32 [P], the words of every part (the encoder's state machine, counting only).
+ * vbq_rans_il_encode_u16: writes part p to d_payload words [d_offsets[p], d_offsets[p] + d_sizes[p]), backwards from the
+ *   end, so that no padded buffer and no pack pass is needed.  d_sizes as vbq_rans_il_sizes_u16 gave them for the same
+ *   arguments, d_offsets int64 [P] their exclusive prefix sum, n_words the length of d_payload (no write leaves it; a part
+ *   that does not fit is skipped).
+ * vbq_rans_il_decode_u16: d_payload u16 [n_words], d_sizes and d_offsets (the exclusive prefix sum of d_sizes) are
+ *   UNTRUSTED: no read leaves a part's [off, off + size), which is itself checked against [0, n_words); every index written
+ *   to d_idx u16 [n_streams][n] is below T.  d_status (u32, device, may be NULL; OR-ed into, zero it first): bit 0 a part
+ *   size outside [128, m + 128], bit 1 a part ran out of words, bit 2 words left over or a final state other than 2^16,
+ *   bit 3 a frequency row that does not sum to 2^15 or holds an entry above 2^15 - 1, bit 4 the sizes do not add up to
+ *   n_words (a part outside the payload, or the last part not ending at n_words).  A part with any bit decodes to zeros.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_il_sizes_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t part,
+                          const uint16_t *d_freq, uint32_t *d_sizes, void *stream);
+int vbq_rans_il_encode_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t part,
+                           const uint16_t *d_freq, const uint32_t *d_sizes, const int64_t *d_offsets, uint16_t *d_payload,
+                           int64_t n_words, void *stream);
+int vbq_rans_il_decode_u16(const uint16_t *d_payload, int64_t n_words, const uint32_t *d_sizes, const int64_t *d_offsets,
+                           int64_t n_streams, int64_t n, int32_t N, int32_t part, const uint16_t *d_freq, uint16_t *d_idx,
+                           uint32_t *d_status, void *stream);
+
+/* ----------------------------------------------------------------------------------
  * Packed counters for the histogram all-reduce: three 21-bit fields per int64 word.
  * An integer SUM all-reduce of the words adds the fields independently while every GLOBAL count is
  * below 2^21, at 2.67 instead of 4 bytes per bin on the wire.  n bins <-> (n + 2) / 3 words.

@@ -7,6 +7,9 @@ ChannelwisePriorCDFQuantizer.compress_latents_to_bytes / decompress_latents are 
 further down) holds one compressed word-embedding matrix: vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings.
 latent_nbytes / embeddings_nbytes give the exact length of either file without building it, and smallest_rate_within is the
 byte-budget rule of the rate-control calls (coded_nbytes / *_to_budget on the quantizer and in vbq_amd.embeddings).
+A third format (magic b"VBQc", after `parse`) holds the same latent tensor in the wave-interleaved layout, whose fixed cost
+is 256 bytes per part instead of 6 bytes and the word rounding per 1024 symbols: write_compact / parse_compact /
+compact_nbytes, chosen with layout="interleaved" on the quantizer's calls.
 
 Layout, every field little-endian (version 1):
 
@@ -86,7 +89,7 @@ def digest(sorted_table, freq) -> bytes:
     return h.digest()
 
 
-def _check_fields(N, C, shape, lamb, segment, dig, n_words):
+def _check_fields(N, C, shape, lamb, segment, dig, n_words, unit="segment", limit=MAX_SEGMENT):
     if not 1 <= N <= MAX_N:
         raise ValueError(f"N = {N} outside [1, {MAX_N}]")
     if C < 1:
@@ -103,8 +106,8 @@ def _check_fields(N, C, shape, lamb, segment, dig, n_words):
         raise ValueError(f"latent shape {tuple(shape)} is too large")
     if not math.isfinite(lamb):
         raise ValueError(f"non-finite lambda {lamb}")
-    if not 1 <= segment <= MAX_SEGMENT:
-        raise ValueError(f"segment {segment} outside [1, {MAX_SEGMENT}]")
+    if not 1 <= segment <= limit:
+        raise ValueError(f"{unit} {segment} outside [1, {limit}]")
     if len(dig) != 16:
         raise ValueError("digest must be 16 bytes")
     if n_words < 0:
@@ -175,6 +178,142 @@ def parse(data) -> Tuple[Header, np.ndarray, int]:
     sizes = np.frombuffer(mv, dtype="<u2", count=h.n_sizes, offset=hlen)
     _check_sizes(sizes, segment, n_words)
     return h, sizes, hlen + 2 * h.n_sizes
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The compact latent file: the tensor of the first format, coded by the wave-interleaved coder (format of the payload:
+# include/vbq.h, vbq_rans_il_encode_u16; RansCodec.encode_interleaved / decode_interleaved).  The C * B rank indices in
+# channel-major order (channel c holds its B = prod(shape) / C latents in row order, the [C, B] planes the first format
+# codes) are cut every `part` symbols into P = ceil(C * B / part) parts; a part of m symbols takes 128 .. m + 128 words.
+# Layout, every field little-endian (version 1):
+#
+#     offset  size      field
+#     0       4         magic b"VBQc"
+#     4       1         version = 1
+#     5       1         N = max_bits_per_coord (1..10)
+#     6       1         ndim of the latent shape (>= 1)
+#     7       1         reserved = 0
+#     8       4         C, the number of channels (u32)
+#     12      4         part, symbols per part (u32, 1..2^24)
+#     16      8         lambda (f64, finite)
+#     24      8         n_words, payload length in 16-bit words (u64)
+#     32      16        digest, as in the first format
+#     48      8 * ndim  latent shape (u64 each, channel last)
+#     48+8nd  4 * P     part sizes in words (u32, part p in [128, m_p + 128], m_p = part but for a shorter last part)
+#     ...     0 or 4    padding: 4 zero bytes when P is odd, so that the payload starts 8-byte aligned
+#     ...     2*n_words payload (u16): the parts in order; sum(sizes) == n_words
+#
+# `parse` rejects such a file by its magic and `parse_compact` rejects a file of the first format; strictness as `parse`.
+# ---------------------------------------------------------------------------------------------------------------------------
+COMPACT_MAGIC = b"VBQc"
+COMPACT_VERSION = 1
+MAX_PART = 1 << 24                           # the coder's limit (vbq_rans_il_encode_u16)
+PART_STATE_WORDS = 128                       # the 64 lane states every part begins with
+
+
+@dataclass(frozen=True)
+class CompactHeader:
+    N: int
+    C: int
+    shape: Tuple[int, ...]
+    lamb: float
+    part: int
+    digest: bytes
+    n_words: int
+
+    @property
+    def n_rows(self) -> int:
+        """Symbols per channel."""
+        return math.prod(self.shape) // self.C
+
+    @property
+    def n_parts(self) -> int:
+        return (math.prod(self.shape) + self.part - 1) // self.part
+
+    @property
+    def nbytes(self) -> int:
+        """Length of the header itself (where the sizes start)."""
+        return _FIXED.size + 8 * len(self.shape)
+
+    @property
+    def sizes_nbytes(self) -> int:
+        """Length of the size block, padding included."""
+        return 4 * self.n_parts + 4 * (self.n_parts & 1)
+
+
+def _check_part_sizes(sizes: np.ndarray, n_symbols: int, part: int, n_words: int):
+    s = sizes.astype(np.int64)
+    limit = np.full(s.size, part + PART_STATE_WORDS, dtype=np.int64)
+    if s.size:
+        limit[-1] = n_symbols - (s.size - 1) * part + PART_STATE_WORDS
+    wrong = (s < PART_STATE_WORDS) | (s > limit)
+    if wrong.any():
+        bad = int(np.flatnonzero(wrong)[0])
+        raise ValueError(f"part size {int(s[bad])} at position {bad} outside [{PART_STATE_WORDS}, {int(limit[bad])}]")
+    total = int(s.sum())
+    if total != n_words:
+        raise ValueError(f"part sizes add up to {total} words, the header says {n_words}")
+
+
+def write_compact(header: CompactHeader, sizes, payload) -> bytes:
+    """header + sizes (any integer array of P entries) + payload (u16 [n_words]) -> bytes.  Validates as `parse_compact` does."""
+    h = header
+    shape = tuple(int(d) for d in h.shape)
+    _check_fields(h.N, h.C, shape, float(h.lamb), h.part, h.digest, h.n_words, "part", MAX_PART)
+    sizes = np.asarray(sizes).reshape(-1)
+    if sizes.size != h.n_parts:
+        raise ValueError(f"{sizes.size} part sizes, the shape needs {h.n_parts}")
+    _check_part_sizes(sizes, math.prod(shape), h.part, h.n_words)
+    payload = np.ascontiguousarray(payload, dtype="<u2").reshape(-1)
+    if payload.size != h.n_words:
+        raise ValueError(f"payload of {payload.size} words, the header says {h.n_words}")
+    head = _FIXED.pack(COMPACT_MAGIC, COMPACT_VERSION, h.N, len(shape), 0, h.C, h.part, float(h.lamb), h.n_words, h.digest)
+    return b"".join([head, np.asarray(shape, dtype="<u8").tobytes(), sizes.astype("<u4").tobytes(),
+                     bytes(4 * (h.n_parts & 1)), payload.tobytes()])
+
+
+def compact_nbytes(shape, C, part, n_words) -> int:
+    """len(write_compact(...)) of a latent tensor of `shape` (channel-last, C channels) in parts of `part` symbols with a
+    payload of n_words 16-bit words, without building the file.  ValueError for fields `write_compact` rejects."""
+    shape = tuple(int(d) for d in shape)
+    h = CompactHeader(N=MAX_N, C=int(C), shape=shape, lamb=0.0, part=int(part), digest=bytes(16), n_words=int(n_words))
+    _check_fields(h.N, h.C, shape, h.lamb, h.part, h.digest, h.n_words, "part", MAX_PART)
+    return h.nbytes + h.sizes_nbytes + 2 * h.n_words
+
+
+def parse_compact(data) -> Tuple[CompactHeader, np.ndarray, int]:
+    """bytes -> (header, sizes u32 [P] (a read-only view into `data`), byte offset of the payload).
+    ValueError on anything malformed."""
+    mv = memoryview(data).cast("B")
+    if len(mv) < _FIXED.size:
+        raise ValueError(f"truncated: {len(mv)} bytes, the fixed header alone is {_FIXED.size}")
+    magic, version, N, ndim, reserved, C, part, lamb, n_words, dig = _FIXED.unpack_from(mv, 0)
+    if magic == MAGIC:
+        raise ValueError("a latent bitstream in segments (magic b'VBQb'), not a compact one")
+    if magic != COMPACT_MAGIC:
+        raise ValueError(f"not a compact VBQ bitstream (magic {magic!r})")
+    if version != COMPACT_VERSION:
+        raise ValueError(f"unknown compact bitstream version {version}")
+    if reserved != 0:
+        raise ValueError(f"reserved header byte is {reserved}, not 0")
+    if ndim < 1:
+        raise ValueError("latent shape with 0 dimensions")
+    hlen = _FIXED.size + 8 * ndim
+    if len(mv) < hlen:
+        raise ValueError(f"truncated in the latent shape: {len(mv)} bytes, the header is {hlen}")
+    shape = tuple(int(d) for d in np.frombuffer(mv, dtype="<u8", count=ndim, offset=_FIXED.size))
+    _check_fields(N, C, shape, lamb, part, dig, n_words, "part", MAX_PART)
+    h = CompactHeader(N=N, C=C, shape=shape, lamb=float(lamb), part=part, digest=bytes(dig), n_words=n_words)
+    need = hlen + h.sizes_nbytes + 2 * n_words
+    if len(mv) < need:
+        raise ValueError(f"truncated: {len(mv)} bytes, header, {h.n_parts} part sizes and {n_words} payload words need {need}")
+    if len(mv) > need:
+        raise ValueError(f"{len(mv) - need} trailing bytes after the payload")
+    sizes = np.frombuffer(mv, dtype="<u4", count=h.n_parts, offset=hlen)
+    if h.n_parts & 1 and any(mv[hlen + 4 * h.n_parts: hlen + h.sizes_nbytes]):
+        raise ValueError("padding after the part sizes is not zero")
+    _check_part_sizes(sizes, math.prod(shape), part, n_words)
+    return h, sizes, hlen + h.sizes_nbytes
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ from ._lib import check
 
 PROB_BITS = 15
 DEFAULT_SEGMENT = 1024
+MAX_PART = 1 << 24                           # symbols per part of the interleaved layout (vbq_rans_il_*_u16)
 
 
 def quantize_frequencies(counts, add_n_smoothing=1, prob_bits: int = PROB_BITS) -> np.ndarray:
@@ -257,6 +258,63 @@ class RansCodec:
         words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
         idx = torch.empty((self.freq_host.shape[0], n), dtype=torch.uint16, device=payload.device)
         self._decode(words, out_sizes, n, idx, status)
+        _raise_status(int(status.cpu().item()))
+        return idx
+
+    # ------------------------------------------------------------ wave-interleaved layout (bitstream VBQc, vbq_rans_il_*_u16)
+    # The S * n symbols in stream-major order are cut every `part` symbols; 64 lanes code a part together (format:
+    # include/vbq.h).  `segment` plays no role here.
+    def _parts(self, n_symbols: int, part) -> int:
+        part = int(part)
+        if not 1 <= part <= MAX_PART:
+            raise ValueError(f"part {part} outside [1, {MAX_PART}]")
+        return (n_symbols + part - 1) // part
+
+    def sizes_interleaved(self, idx: torch.Tensor, part: int) -> torch.Tensor:
+        """Words of every part of the interleaved layout -- u32 [P] on the device, P = ceil(S * n / part) -- without the
+        words (vbq_rans_il_sizes_u16): the exact coded length."""
+        idx, S, n, _ = self._streams(idx)
+        sizes = torch.zeros(self._parts(S * n, part), dtype=torch.uint32, device=idx.device)
+        check(_lib.lib().vbq_rans_il_sizes_u16(ops._ptr(idx), S, n, self.N, int(part), ops._ptr(self._freq(idx.device)),
+                                               ops._ptr(sizes), ops._stream(idx)), "vbq_rans_il_sizes_u16")
+        return sizes
+
+    def encode_interleaved(self, idx: torch.Tensor, part: int) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (sizes u32 [P], payload u16 [n_words]) on the host.  The sizes kernel first, their exclusive scan on the device,
+        then the encoder writes every part straight to its place in the payload (no padded buffer, no pack pass).  Two
+        device-to-host copies: the sizes (they say how long the payload is), then the payload."""
+        idx, S, n, _ = self._streams(idx)
+        sizes = self.sizes_interleaved(idx, part)
+        s64 = sizes.view(torch.int32).to(torch.int64)                                       # (a size is at most 2^24 + 128)
+        offsets = torch.cumsum(s64, 0) - s64
+        sizes_h = sizes.cpu().numpy()
+        n_words = int(sizes_h.sum(dtype=np.int64))
+        payload = torch.empty(n_words, dtype=torch.uint16, device=idx.device)
+        check(_lib.lib().vbq_rans_il_encode_u16(ops._ptr(idx), S, n, self.N, int(part), ops._ptr(self._freq(idx.device)),
+                                                ops._ptr(sizes), ops._ptr(offsets), ops._ptr(payload), n_words,
+                                                ops._stream(idx)), "vbq_rans_il_encode_u16")
+        return sizes_h, payload.cpu().numpy()
+
+    def _decode_interleaved(self, payload, sizes, n, part, idx, status):
+        """One launch of the untrusted decoder; status: u32 [1] it ORs its flags into (read it with _raise_status)."""
+        s64 = sizes.view(torch.int32).to(torch.int64) & 0xffffffff
+        offsets = torch.cumsum(s64, 0) - s64
+        check(_lib.lib().vbq_rans_il_decode_u16(ops._ptr(payload), payload.numel(), ops._ptr(sizes), ops._ptr(offsets),
+                                                idx.shape[0], n, self.N, int(part), ops._ptr(self._freq(idx.device)),
+                                                ops._ptr(idx), ops._ptr(status), ops._stream(idx)), "vbq_rans_il_decode_u16")
+
+    def decode_interleaved(self, payload: torch.Tensor, sizes: torch.Tensor, n: int, part: int) -> torch.Tensor:
+        """payload u16 [n_words] and sizes u32 [P] (device tensors, untrusted: they may come from a file) -> u16 indices
+        [S, n].  Shapes are checked here, everything else in the kernel; a damaged stream raises VBQError."""
+        payload = ops._dev(payload, torch.uint16, "payload").reshape(-1)
+        sizes = ops._dev(sizes, torch.uint32, "sizes").reshape(-1)
+        S = self.freq_host.shape[0]
+        P = self._parts(S * int(n), part)
+        if sizes.numel() != P:
+            raise ValueError(f"expected {P} part sizes for {S} streams of {n} symbols in parts of {part}, got {sizes.numel()}")
+        idx = torch.empty((S, int(n)), dtype=torch.uint16, device=payload.device)
+        status = torch.zeros(1, dtype=torch.uint32, device=payload.device)
+        self._decode_interleaved(payload, sizes, int(n), part, idx, status)
         _raise_status(int(status.cpu().item()))
         return idx
 

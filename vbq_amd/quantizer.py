@@ -652,14 +652,20 @@ class ChannelwisePriorCDFQuantizer:
             codec = ent["codecs"][segment] = RansCodec(ent["freq"], N=self.max_bits_per_coord, segment=segment)
         return codec, ent["digest"]
 
-    def _file_shape(self, posterior_means, posterior_logvars, segment):
-        """The latent shape of a file (channel-last, one shape for both inputs); ValueError otherwise or for a bad segment."""
+    def _file_shape(self, posterior_means, posterior_logvars, segment, layout="segments", part=1 << 17):
+        """The latent shape of a file (channel-last, one shape for both inputs); ValueError otherwise, for a bad segment (layout
+        "segments") or part (layout "interleaved"), or for an unknown layout."""
         from . import bitstream
         C = self.num_channels
         shape = tuple(int(d) for d in np.shape(posterior_means))
         if tuple(np.shape(posterior_logvars)) != shape or not shape or shape[-1] != C:
             raise ValueError(f"expected channel-last latents [..., {C}] of one shape, got {shape} / {tuple(np.shape(posterior_logvars))}")
-        if not 1 <= segment <= bitstream.MAX_SEGMENT:
+        if layout not in ("segments", "interleaved"):
+            raise ValueError(f"layout {layout!r}: expected 'segments' or 'interleaved'")
+        if layout == "interleaved":
+            if not 1 <= part <= bitstream.MAX_PART:
+                raise ValueError(f"part {part} outside [1, {bitstream.MAX_PART}]")
+        elif not 1 <= segment <= bitstream.MAX_SEGMENT:
             raise ValueError(f"segment {segment} outside [1, {bitstream.MAX_SEGMENT}]")
         return shape
 
@@ -679,16 +685,27 @@ class ChannelwisePriorCDFQuantizer:
                 idx[l] = torch.gather(canon, 1, idx[l].to(torch.int64)).to(torch.uint16)
         return idx
 
-    def compress_latents_to_bytes(self, posterior_means, posterior_logvars, lamb, segment=1024) -> bytes:
+    def compress_latents_to_bytes(self, posterior_means, posterior_logvars, lamb, segment=1024, layout="segments",
+                                  part=1 << 17) -> bytes:
         """compress_latents at ONE lambda, entropy-coded into a self-describing byte string (format: vbq_amd.bitstream).
         Same inputs and sigma = exp(logvar) ** 0.5 as compress_latents; the indices come from the same solve (the canonical
         index of a repeated code point, as encode_batch).  Solve, encode and pack run on the device; two device-to-host
-        copies (the total with the segment sizes, then the payload)."""
+        copies (the total with the segment sizes, then the payload).
+        layout="interleaved" writes the compact file instead (magic b"VBQc": the wave-interleaved coder in parts of `part`
+        symbols, `segment` unused): the same indices and tables in fewer bytes -- 256 bytes of fixed cost per part where the
+        default layout pays 6 bytes and the word rounding per segment.  decompress_latents reads either."""
         from . import bitstream
         self._check_coder_bits()
         key = self._lambda_key(lamb)
         C = self.num_channels
-        shape = self._file_shape(posterior_means, posterior_logvars, segment)
+        shape = self._file_shape(posterior_means, posterior_logvars, segment, layout, part)
+        if layout == "interleaved":
+            codec, dig = self._coder_tables(key, 1024)                                         # (the tables; its segment plays no role)
+            idx = self._file_indices(posterior_means, posterior_logvars, [key])[0]             # [C, B]
+            sizes, payload = codec.encode_interleaved(idx, int(part))
+            h = bitstream.CompactHeader(N=self.max_bits_per_coord, C=C, shape=shape, lamb=float(key), part=int(part), digest=dig,
+                                        n_words=int(payload.size))
+            return bitstream.write_compact(h, sizes, payload)
         codec, dig = self._coder_tables(key, int(segment))
         idx = self._file_indices(posterior_means, posterior_logvars, [key])[0]                 # [C, B]
         sizes, payload = codec.encode_packed(idx)
@@ -703,27 +720,36 @@ class ChannelwisePriorCDFQuantizer:
         model for, VBQError for a damaged payload."""
         from . import bitstream
         self._check_coder_bits()
-        h, _, _ = bitstream.parse(data)
+        mv = memoryview(data).cast("B")
+        compact = bytes(mv[:4]) == bitstream.COMPACT_MAGIC
+        h, _, _ = bitstream.parse_compact(data) if compact else bitstream.parse(data)
         if h.N != self.max_bits_per_coord or h.C != self.num_channels:
             raise ValueError(f"stream is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
                              f"C = {self.num_channels}")
         key = self._lambda_key(h.lamb)
-        codec, dig = self._coder_tables(key, h.segment)
+        codec, dig = self._coder_tables(key, 1024 if compact else h.segment)
         if dig != h.digest:
             raise ValueError("stream was compressed with a different quantizer or entropy model (digest mismatch)")
         start = h.nbytes                      # sizes, then payload: one upload
-        tail = np.frombuffer(memoryview(data).cast("B"), dtype="<u2", count=h.n_sizes + h.n_words, offset=start)
-        buf = torch.from_numpy(tail.copy()).to(self.device)
-        idx = codec.decode_packed(buf[h.n_sizes:], buf[: h.n_sizes], h.n_rows)          # [C, B]
+        if compact:
+            n16 = h.sizes_nbytes // 2
+            tail = np.frombuffer(mv, dtype="<u2", count=n16 + h.n_words, offset=start)
+            buf = torch.from_numpy(tail.copy()).to(self.device)
+            sizes = buf[: 2 * h.n_parts].view(torch.uint32)                             # (the header is a multiple of 8 bytes)
+            idx = codec.decode_interleaved(buf[n16:], sizes, h.n_rows, h.part)          # [C, B]
+        else:
+            tail = np.frombuffer(mv, dtype="<u2", count=h.n_sizes + h.n_words, offset=start)
+            buf = torch.from_numpy(tail.copy()).to(self.device)
+            idx = codec.decode_packed(buf[h.n_sizes:], buf[: h.n_sizes], h.n_rows)      # [C, B]
         zhat = ops.gather(idx[None], self._sorted_dev(), self.num_channels, N=self.max_bits_per_coord, layout="cb",
                           out_layout="bc")                                                # [1, B, C]
         zhat = zhat.reshape(h.shape)
         return zhat.cpu().numpy() if return_np else zhat
 
-    def compress_to_bytes(self, X, vae, lamb, segment=1024) -> bytes:
+    def compress_to_bytes(self, X, vae, lamb, segment=1024, layout="segments", part=1 << 17) -> bytes:
         """`vae.encode(X)`, then compress_latents_to_bytes."""
         posterior_means, posterior_logvars = vae.encode(X)
-        return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment)
+        return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment, layout=layout, part=part)
 
     # ------------------------------------------------------------------ rate control: exact lengths, byte budgets
     def _rate_keys(self, lambs):
@@ -752,37 +778,46 @@ class ChannelwisePriorCDFQuantizer:
                                             segment=segment)
         return codec
 
-    def coded_nbytes(self, posterior_means, posterior_logvars, lambs=None, segment=1024) -> dict:
+    def coded_nbytes(self, posterior_means, posterior_logvars, lambs=None, segment=1024, layout="segments", part=1 << 17) -> dict:
         """{lambda: len(compress_latents_to_bytes(posterior_means, posterior_logvars, lambda, segment))} for every key of
         entropy_models in `lambs` (default: all of self.lambs), exact, without building a file: ONE solve of every lambda, one
         vbq_rans_sizes_u16 launch over the L x C streams (segment sizes only, no words), one copy of the L totals.  Inputs and
-        errors as compress_latents_to_bytes (KeyError for a lambda without a model)."""
+        errors as compress_latents_to_bytes (KeyError for a lambda without a model).  layout="interleaved": the lengths of the
+        compact files -- one vbq_rans_il_sizes_u16 launch per lambda (a part never holds symbols of two lambdas)."""
         from . import bitstream
         self._check_coder_bits()
         keys = self._rate_keys(lambs)
         C = self.num_channels
-        shape = self._file_shape(posterior_means, posterior_logvars, segment)
+        shape = self._file_shape(posterior_means, posterior_logvars, segment, layout, part)
+        if layout == "interleaved":
+            idx = self._file_indices(posterior_means, posterior_logvars, keys)                 # [L, C, B]
+            totals = [self._coder_tables(k, 1024)[0].sizes_interleaved(idx[l], int(part)).view(torch.int32).sum(dtype=torch.int64)
+                      for l, k in enumerate(keys)]
+            words = torch.stack(totals).cpu().numpy()
+            return {k: bitstream.compact_nbytes(shape, C, int(part), int(w)) for k, w in zip(keys, words)}
         codec = self._coder_stack(keys, int(segment))
         idx = self._file_indices(posterior_means, posterior_logvars, keys)                     # [L, C, B]
         sizes = codec.sizes(idx)                                                               # u32 [L * C, nseg]
         words = sizes.view(torch.int32).view(len(keys), -1).sum(dim=1, dtype=torch.int64).cpu().numpy()
         return {k: bitstream.latent_nbytes(shape, C, int(segment), int(w)) for k, w in zip(keys, words)}
 
-    def compress_latents_to_budget(self, posterior_means, posterior_logvars, max_bytes, lambs=None, segment=1024) -> bytes:
+    def compress_latents_to_budget(self, posterior_means, posterior_logvars, max_bytes, lambs=None, segment=1024,
+                                   layout="segments", part=1 << 17) -> bytes:
         """The file of the numerically SMALLEST lambda of `lambs` (default: all of self.lambs) whose exact length is <= max_bytes
         (an integer >= 1), byte for byte compress_latents_to_bytes at that lambda; the header says which lambda it is.  A larger
         lambda usually, but not always, gives a smaller file: the rule takes no monotonicity for granted.  ValueError naming
         the smallest achievable length and its lambda when nothing fits."""
         from . import bitstream
         bitstream.check_budget(max_bytes)
-        nbytes = self.coded_nbytes(posterior_means, posterior_logvars, lambs, segment=segment)
+        nbytes = self.coded_nbytes(posterior_means, posterior_logvars, lambs, segment=segment, layout=layout, part=part)
         lamb = bitstream.smallest_rate_within(nbytes, max_bytes, "lambda")
-        return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment)
+        return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment, layout=layout, part=part)
 
-    def compress_to_budget(self, X, vae, max_bytes, lambs=None, segment=1024) -> bytes:
+    def compress_to_budget(self, X, vae, max_bytes, lambs=None, segment=1024, layout="segments", part=1 << 17) -> bytes:
         """`vae.encode(X)`, then compress_latents_to_budget."""
         posterior_means, posterior_logvars = vae.encode(X)
-        return self.compress_latents_to_budget(posterior_means, posterior_logvars, max_bytes, lambs=lambs, segment=segment)
+        return self.compress_latents_to_budget(posterior_means, posterior_logvars, max_bytes, lambs=lambs, segment=segment,
+                                               layout=layout, part=part)
 
     def decompress(self, data, vae, clip=True, return_np=True):
         """decompress_latents, then `vae.decode` and the clip to [0, 1] of compress (quantizer.py:251-253).  The decoder
