@@ -1,38 +1,47 @@
-"""Self-describing byte format for ONE latent tensor coded at ONE lambda (a compressed file).
+"""Self-describing byte formats for ONE tensor coded at ONE rate (a compressed file).
 
-Host-only: writing and strictly validating the header.  The payload is what `RansCodec.pack` returns for the coder's
-streams (one per channel, each holding the B = prod(shape) / C latents of that channel, cut into segments of `segment`
-symbols); the device builds it with vbq_rans_pack_u16 and takes it apart with vbq_rans_unpack_u16 (include/vbq.h).
-ChannelwisePriorCDFQuantizer.compress_latents_to_bytes / decompress_latents are the users.  A second format (magic b"VBQe",
-further down) holds one compressed word-embedding matrix: vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings.
-latent_nbytes / embeddings_nbytes give the exact length of either file without building it, and smallest_rate_within is the
-byte-budget rule of the rate-control calls (coded_nbytes / *_to_budget on the quantizer and in vbq_amd.embeddings).
-A third format (magic b"VBQc", after `parse`) holds the same latent tensor in the wave-interleaved layout, whose fixed cost
-is 256 bytes per part instead of 6 bytes and the word rounding per 1024 symbols: write_compact / parse_compact /
-compact_nbytes, chosen with layout="interleaved" on the quantizer's calls.
+Host-only: writing and strictly validating the headers.  Two formats hold one latent tensor at one lambda, coded per channel
+(channel c holds its B = prod(shape) / C latents in row order: the [C, B] planes of rank indices):
 
-Layout, every field little-endian (version 1):
+    b"VBQb"  segments: every channel is a stream cut into segments of `segment` symbols, each an independent rANS stream; the
+             payload is what `RansCodec.pack` returns, built on the device by vbq_rans_pack_u16 and taken apart by
+             vbq_rans_unpack_u16 (include/vbq.h).  Fixed cost: 6 bytes and the word rounding per segment.
+    b"VBQc"  compact: the C * B indices in channel-major order are cut every `part` symbols into P = ceil(C * B / part) parts
+             coded by the wave-interleaved coder (include/vbq.h, vbq_rans_il_encode_u16; RansCodec.encode_interleaved /
+             decode_interleaved); a part of m symbols takes 128 .. m + 128 words.  Fixed cost: 256 bytes per part.
+
+ChannelwisePriorCDFQuantizer.compress_latents_to_bytes (layout="segments" / "interleaved") writes them and decompress_latents
+reads either through `parse_latent`.  A third format (magic b"VBQe", further down) holds one compressed word-embedding matrix:
+vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings.  latent_nbytes / compact_nbytes / embeddings_nbytes give the
+exact length of a file without building it, and smallest_rate_within is the byte-budget rule of the rate-control calls
+(coded_nbytes / *_to_budget on the quantizer and in vbq_amd.embeddings).
+
+Layout of the two latent files, every field little-endian (version 1); `unit` is the segment or the part:
 
     offset  size      field
-    0       4         magic b"VBQb"
+    0       4         magic b"VBQb" / b"VBQc"
     4       1         version = 1
     5       1         N = max_bits_per_coord (1..10)
     6       1         ndim of the latent shape (>= 1)
     7       1         reserved = 0
     8       4         C, the number of channels (u32)
-    12      4         segment, symbols per rANS segment (u32, 1..65533)
+    12      4         symbols per unit (u32): segment in 1..65533 / part in 1..2^24
     16      8         lambda (f64, finite)
     24      8         n_words, payload length in 16-bit words (u64)
     32      16        digest: blake2b-128 of the sorted code-point table (f32 [C, T]) and the quantised frequency
                       table (u16 [C, T]) of this lambda -- exactly what decoding depends on
     48      8 * ndim  latent shape (u64 each, channel last: shape[-1] == C, every entry >= 1)
-    48+8nd  2 * C*nseg segment sizes (u16, each in [2, segment + 2]), nseg = ceil(prod(shape) / C / segment),
-                      stream-major (channel), then segment
-    ...     2*n_words payload (u16): the valid words of every segment in the same order; sum(sizes) == n_words
+    then the size block, words per unit:
+      VBQb  2 * C*nseg  segment sizes (u16, each in [2, segment + 2]), nseg = ceil(B / segment), stream-major (channel),
+                        then segment
+      VBQc  4 * P       part sizes (u32, part p in [128, m_p + 128], m_p = part but for a shorter last part), then 4 zero
+                        bytes of padding when P is odd, so that the payload starts 8-byte aligned
+    ...     2*n_words payload (u16): the valid words of every unit in the same order; sum(sizes) == n_words
 
-The header is a multiple of 8 bytes long, so the sizes and the payload can be viewed as u16 in place.  `parse` raises
-ValueError with a specific message on anything malformed -- never struct.error or IndexError -- and checks every size
-with vectorised NumPy before anything reaches the device (the unpack kernel's own checks are the second line of defence).
+The header is a multiple of 8 bytes long, so the sizes and the payload can be viewed in place.  The parsers raise ValueError
+with a specific message on anything malformed -- never struct.error or IndexError -- and check every size with vectorised
+NumPy before anything reaches the device (the kernels' own checks are the second line of defence).  `parse` rejects a compact
+file by its magic and `parse_compact` rejects a file in segments.
 """
 from __future__ import annotations
 
@@ -40,45 +49,20 @@ import hashlib
 import math
 import struct
 from dataclasses import dataclass
-from typing import Tuple
+from typing import ClassVar, Tuple
 
 import numpy as np
 
 MAGIC = b"VBQb"
 VERSION = 1
+COMPACT_MAGIC = b"VBQc"
+COMPACT_VERSION = 1
 MAX_N = 10                                   # the coder's limit (vbq_rans_encode_u16)
 MAX_SEGMENT = 65533                          # seg + 2 must fit in a u16 size
+MAX_PART = 1 << 24                           # the coder's limit (vbq_rans_il_encode_u16)
+PART_STATE_WORDS = 128                       # the 64 lane states every part begins with
 _FIXED = struct.Struct("<4sBBBBIIdQ16s")     # the 48 bytes before the shape
 assert _FIXED.size == 48
-
-
-@dataclass(frozen=True)
-class Header:
-    N: int
-    C: int
-    shape: Tuple[int, ...]
-    lamb: float
-    segment: int
-    digest: bytes
-    n_words: int
-
-    @property
-    def n_rows(self) -> int:
-        """Symbols per stream: the latents of one channel."""
-        return math.prod(self.shape) // self.C
-
-    @property
-    def nseg(self) -> int:
-        return (self.n_rows + self.segment - 1) // self.segment
-
-    @property
-    def n_sizes(self) -> int:
-        return self.C * self.nseg
-
-    @property
-    def nbytes(self) -> int:
-        """Length of the header itself (where the sizes start)."""
-        return _FIXED.size + 8 * len(self.shape)
 
 
 def digest(sorted_table, freq) -> bytes:
@@ -89,146 +73,79 @@ def digest(sorted_table, freq) -> bytes:
     return h.digest()
 
 
-def _check_fields(N, C, shape, lamb, segment, dig, n_words, unit="segment", limit=MAX_SEGMENT):
-    if not 1 <= N <= MAX_N:
-        raise ValueError(f"N = {N} outside [1, {MAX_N}]")
-    if C < 1:
-        raise ValueError("zero channels")
-    if not 1 <= len(shape) <= 255:
-        raise ValueError(f"latent shape with {len(shape)} dimensions")
-    if any(d < 1 for d in shape):
-        raise ValueError(f"empty latent shape {tuple(shape)}")
-    if shape[-1] != C:
-        raise ValueError(f"latent shape {tuple(shape)} is not channel-last for C = {C}")
-    if math.prod(shape) % C:
-        raise ValueError(f"latent shape {tuple(shape)}: {math.prod(shape)} elements are not a multiple of C = {C}")
-    if math.prod(shape) >= 2 ** 62:
-        raise ValueError(f"latent shape {tuple(shape)} is too large")
-    if not math.isfinite(lamb):
-        raise ValueError(f"non-finite lambda {lamb}")
+def check_segment(segment, unit="segment", limit=MAX_SEGMENT):
+    """ValueError unless 1 <= segment <= limit: the one statement of the range of a segment (and, through check_part, a part)."""
     if not 1 <= segment <= limit:
         raise ValueError(f"{unit} {segment} outside [1, {limit}]")
-    if len(dig) != 16:
-        raise ValueError("digest must be 16 bytes")
-    if n_words < 0:
-        raise ValueError("negative payload length")
 
 
-def _check_sizes(sizes: np.ndarray, segment: int, n_words: int):
-    if sizes.size and (int(sizes.min()) < 2 or int(sizes.max()) > segment + 2):
-        bad = int(np.flatnonzero((sizes < 2) | (sizes > segment + 2))[0])
-        raise ValueError(f"segment size {int(sizes[bad])} at position {bad} outside [2, {segment + 2}]")
-    total = int(sizes.sum(dtype=np.int64))
+def check_part(part):
+    check_segment(part, "part", MAX_PART)
+
+
+# ---- what the three formats share: the checks of the size block and of the file's length
+def _check_sizes(sizes: np.ndarray, unit: str, lo: int, hi, n_words: int):
+    """Every size in [lo, hi] (hi: one bound, or one per size) and their sum n_words."""
+    s = sizes.astype(np.int64)
+    wrong = (s < lo) | (s > hi)
+    if wrong.any():
+        bad = int(np.flatnonzero(wrong)[0])
+        raise ValueError(f"{unit} size {int(s[bad])} at position {bad} outside [{lo}, {int(np.broadcast_to(hi, s.shape)[bad])}]")
+    total = int(s.sum())
     if total != n_words:
-        raise ValueError(f"segment sizes add up to {total} words, the header says {n_words}")
+        raise ValueError(f"{unit} sizes add up to {total} words, the header says {n_words}")
 
 
-def write(header: Header, sizes, payload) -> bytes:
-    """header + sizes (any integer array of C * nseg entries) + payload (u16 [n_words]) -> bytes.  Validates as `parse` does."""
-    h = header
-    shape = tuple(int(d) for d in h.shape)
-    _check_fields(h.N, h.C, shape, float(h.lamb), h.segment, h.digest, h.n_words)
+def _flat_sizes(sizes, count: int, unit: str) -> np.ndarray:
+    """A writer's sizes as a flat array of `count` entries."""
     sizes = np.asarray(sizes).reshape(-1)
-    if sizes.size != h.n_sizes:
-        raise ValueError(f"{sizes.size} segment sizes, the shape needs {h.n_sizes}")
-    _check_sizes(sizes, h.segment, h.n_words)
+    if sizes.size != count:
+        raise ValueError(f"{sizes.size} {unit} sizes, the shape needs {count}")
+    return sizes
+
+
+def _checked_payload(payload, n_words: int) -> np.ndarray:
     payload = np.ascontiguousarray(payload, dtype="<u2").reshape(-1)
-    if payload.size != h.n_words:
-        raise ValueError(f"payload of {payload.size} words, the header says {h.n_words}")
-    head = _FIXED.pack(MAGIC, VERSION, h.N, len(shape), 0, h.C, h.segment, float(h.lamb), h.n_words, h.digest)
-    return b"".join([head, np.asarray(shape, dtype="<u8").tobytes(), sizes.astype("<u2").tobytes(), payload.tobytes()])
+    if payload.size != n_words:
+        raise ValueError(f"payload of {payload.size} words, the header says {n_words}")
+    return payload
 
 
-def latent_nbytes(shape, C, segment, n_words) -> int:
-    """len(write(...)) of a latent tensor of `shape` (channel-last, C channels) in segments of `segment` symbols with a payload
-    of n_words 16-bit words, without building the file.  ValueError for fields `write` rejects."""
-    shape = tuple(int(d) for d in shape)
-    h = Header(N=MAX_N, C=int(C), shape=shape, lamb=0.0, segment=int(segment), digest=bytes(16), n_words=int(n_words))
-    _check_fields(h.N, h.C, shape, h.lamb, h.segment, h.digest, h.n_words)
-    return h.nbytes + 2 * h.n_sizes + 2 * h.n_words
+def _unpack_fixed(mv, fixed: struct.Struct):
+    if len(mv) < fixed.size:
+        raise ValueError(f"truncated: {len(mv)} bytes, the fixed header alone is {fixed.size}")
+    return fixed.unpack_from(mv, 0)
 
 
-def parse(data) -> Tuple[Header, np.ndarray, int]:
-    """bytes -> (header, sizes u16 [C * nseg] (a read-only view into `data`), byte offset of the payload).
-    ValueError on anything malformed."""
-    mv = memoryview(data).cast("B")
-    if len(mv) < _FIXED.size:
-        raise ValueError(f"truncated: {len(mv)} bytes, the fixed header alone is {_FIXED.size}")
-    magic, version, N, ndim, reserved, C, segment, lamb, n_words, dig = _FIXED.unpack_from(mv, 0)
-    if magic != MAGIC:
-        raise ValueError(f"not a VBQ bitstream (magic {magic!r})")
-    if version != VERSION:
-        raise ValueError(f"unknown bitstream version {version}")
-    if reserved != 0:
-        raise ValueError(f"reserved header byte is {reserved}, not 0")
-    if ndim < 1:
-        raise ValueError("latent shape with 0 dimensions")
-    hlen = _FIXED.size + 8 * ndim
+def _read_shape(mv, fixed: struct.Struct, ndim: int, what: str) -> Tuple[int, ...]:
+    hlen = fixed.size + 8 * ndim
     if len(mv) < hlen:
-        raise ValueError(f"truncated in the latent shape: {len(mv)} bytes, the header is {hlen}")
-    shape = tuple(int(d) for d in np.frombuffer(mv, dtype="<u8", count=ndim, offset=_FIXED.size))
-    _check_fields(N, C, shape, lamb, segment, dig, n_words)
-    h = Header(N=N, C=C, shape=shape, lamb=float(lamb), segment=segment, digest=bytes(dig), n_words=n_words)
-    need = hlen + 2 * h.n_sizes + 2 * n_words
-    if len(mv) < need:
-        raise ValueError(f"truncated: {len(mv)} bytes, header, {h.n_sizes} segment sizes and {n_words} payload words "
-                         f"need {need}")
-    if len(mv) > need:
-        raise ValueError(f"{len(mv) - need} trailing bytes after the payload")
-    sizes = np.frombuffer(mv, dtype="<u2", count=h.n_sizes, offset=hlen)
-    _check_sizes(sizes, segment, n_words)
-    return h, sizes, hlen + 2 * h.n_sizes
+        raise ValueError(f"truncated in the {what} shape: {len(mv)} bytes, the header is {hlen}")
+    return tuple(int(d) for d in np.frombuffer(mv, dtype="<u8", count=ndim, offset=fixed.size))
 
 
-# ---------------------------------------------------------------------------------------------------------------------------
-# The compact latent file: the tensor of the first format, coded by the wave-interleaved coder (format of the payload:
-# include/vbq.h, vbq_rans_il_encode_u16; RansCodec.encode_interleaved / decode_interleaved).  The C * B rank indices in
-# channel-major order (channel c holds its B = prod(shape) / C latents in row order, the [C, B] planes the first format
-# codes) are cut every `part` symbols into P = ceil(C * B / part) parts; a part of m symbols takes 128 .. m + 128 words.
-# Layout, every field little-endian (version 1):
-#
-#     offset  size      field
-#     0       4         magic b"VBQc"
-#     4       1         version = 1
-#     5       1         N = max_bits_per_coord (1..10)
-#     6       1         ndim of the latent shape (>= 1)
-#     7       1         reserved = 0
-#     8       4         C, the number of channels (u32)
-#     12      4         part, symbols per part (u32, 1..2^24)
-#     16      8         lambda (f64, finite)
-#     24      8         n_words, payload length in 16-bit words (u64)
-#     32      16        digest, as in the first format
-#     48      8 * ndim  latent shape (u64 each, channel last)
-#     48+8nd  4 * P     part sizes in words (u32, part p in [128, m_p + 128], m_p = part but for a shorter last part)
-#     ...     0 or 4    padding: 4 zero bytes when P is odd, so that the payload starts 8-byte aligned
-#     ...     2*n_words payload (u16): the parts in order; sum(sizes) == n_words
-#
-# `parse` rejects such a file by its magic and `parse_compact` rejects a file of the first format; strictness as `parse`.
-# ---------------------------------------------------------------------------------------------------------------------------
-COMPACT_MAGIC = b"VBQc"
-COMPACT_VERSION = 1
-MAX_PART = 1 << 24                           # the coder's limit (vbq_rans_il_encode_u16)
-PART_STATE_WORDS = 128                       # the 64 lane states every part begins with
+def _check_length(nbytes: int, need: int, parts: str):
+    if nbytes < need:
+        raise ValueError(f"truncated: {nbytes} bytes, {parts} need {need}")
+    if nbytes > need:
+        raise ValueError(f"{nbytes - need} trailing bytes after the payload")
 
 
+# ---- the two latent files
 @dataclass(frozen=True)
-class CompactHeader:
+class _LatentHeader:
+    """What the two latent headers share; a subclass adds its unit field (`segment` / `part`) and states what differs."""
     N: int
     C: int
     shape: Tuple[int, ...]
     lamb: float
-    part: int
     digest: bytes
     n_words: int
 
     @property
     def n_rows(self) -> int:
-        """Symbols per channel."""
+        """Symbols per stream: the latents of one channel."""
         return math.prod(self.shape) // self.C
-
-    @property
-    def n_parts(self) -> int:
-        return (math.prod(self.shape) + self.part - 1) // self.part
 
     @property
     def nbytes(self) -> int:
@@ -236,84 +153,167 @@ class CompactHeader:
         return _FIXED.size + 8 * len(self.shape)
 
     @property
+    def unit(self) -> int:
+        return getattr(self, self.UNIT)
+
+    def check(self):
+        N, C, shape, lamb = self.N, self.C, tuple(int(d) for d in self.shape), float(self.lamb)
+        if not 1 <= N <= MAX_N:
+            raise ValueError(f"N = {N} outside [1, {MAX_N}]")
+        if C < 1:
+            raise ValueError("zero channels")
+        if not 1 <= len(shape) <= 255:
+            raise ValueError(f"latent shape with {len(shape)} dimensions")
+        if any(d < 1 for d in shape):
+            raise ValueError(f"empty latent shape {shape}")
+        if shape[-1] != C:
+            raise ValueError(f"latent shape {shape} is not channel-last for C = {C}")
+        if math.prod(shape) % C:
+            raise ValueError(f"latent shape {shape}: {math.prod(shape)} elements are not a multiple of C = {C}")
+        if math.prod(shape) >= 2 ** 62:
+            raise ValueError(f"latent shape {shape} is too large")
+        if not math.isfinite(lamb):
+            raise ValueError(f"non-finite lambda {lamb}")
+        check_segment(self.unit, self.UNIT, self.LIMIT)
+        if len(self.digest) != 16:
+            raise ValueError("digest must be 16 bytes")
+        if self.n_words < 0:
+            raise ValueError("negative payload length")
+
+
+@dataclass(frozen=True)
+class Header(_LatentHeader):
+    segment: int
+    MAGIC: ClassVar = MAGIC
+    VERSION: ClassVar = VERSION
+    KIND: ClassVar = ""                      # "not a VBQ bitstream", "unknown bitstream version"
+    FOREIGN: ClassVar = {}
+    UNIT: ClassVar = "segment"
+    LIMIT: ClassVar = MAX_SEGMENT
+    SIZE_DTYPE: ClassVar = "<u2"
+
+    @property
+    def nseg(self) -> int:
+        return (self.n_rows + self.segment - 1) // self.segment
+
+    @property
+    def n_sizes(self) -> int:
+        return self.C * self.nseg
+
+    @property
+    def sizes_nbytes(self) -> int:
+        return 2 * self.n_sizes
+
+    def size_range(self):
+        return 2, self.segment + 2
+
+
+@dataclass(frozen=True)
+class CompactHeader(_LatentHeader):
+    part: int
+    MAGIC: ClassVar = COMPACT_MAGIC
+    VERSION: ClassVar = COMPACT_VERSION
+    KIND: ClassVar = "compact "
+    FOREIGN: ClassVar = {Header.MAGIC: "a latent bitstream in segments (magic b'VBQb'), not a compact one"}
+    UNIT: ClassVar = "part"
+    LIMIT: ClassVar = MAX_PART
+    SIZE_DTYPE: ClassVar = "<u4"
+
+    @property
+    def n_parts(self) -> int:
+        return (math.prod(self.shape) + self.part - 1) // self.part
+
+    n_sizes = n_parts
+
+    @property
     def sizes_nbytes(self) -> int:
         """Length of the size block, padding included."""
         return 4 * self.n_parts + 4 * (self.n_parts & 1)
 
+    def size_range(self):
+        hi = np.full(self.n_parts, self.part + PART_STATE_WORDS, dtype=np.int64)
+        hi[-1] = math.prod(self.shape) - (self.n_parts - 1) * self.part + PART_STATE_WORDS
+        return PART_STATE_WORDS, hi
 
-def _check_part_sizes(sizes: np.ndarray, n_symbols: int, part: int, n_words: int):
-    s = sizes.astype(np.int64)
-    limit = np.full(s.size, part + PART_STATE_WORDS, dtype=np.int64)
-    if s.size:
-        limit[-1] = n_symbols - (s.size - 1) * part + PART_STATE_WORDS
-    wrong = (s < PART_STATE_WORDS) | (s > limit)
-    if wrong.any():
-        bad = int(np.flatnonzero(wrong)[0])
-        raise ValueError(f"part size {int(s[bad])} at position {bad} outside [{PART_STATE_WORDS}, {int(limit[bad])}]")
-    total = int(s.sum())
-    if total != n_words:
-        raise ValueError(f"part sizes add up to {total} words, the header says {n_words}")
+
+def _write_latent(h: _LatentHeader, sizes, payload) -> bytes:
+    h.check()
+    sizes = _flat_sizes(sizes, h.n_sizes, h.UNIT)
+    _check_sizes(sizes, h.UNIT, *h.size_range(), h.n_words)
+    payload = _checked_payload(payload, h.n_words)
+    head = _FIXED.pack(h.MAGIC, h.VERSION, h.N, len(h.shape), 0, h.C, h.unit, float(h.lamb), h.n_words, h.digest)
+    block = sizes.astype(h.SIZE_DTYPE).tobytes()
+    return b"".join([head, np.asarray(h.shape, dtype="<u8").tobytes(), block, bytes(h.sizes_nbytes - len(block)),
+                     payload.tobytes()])
+
+
+def _latent_nbytes(cls, shape, C, unit, n_words) -> int:
+    h = cls(N=MAX_N, C=int(C), shape=tuple(int(d) for d in shape), lamb=0.0, digest=bytes(16), n_words=int(n_words),
+            **{cls.UNIT: int(unit)})
+    h.check()
+    return h.nbytes + h.sizes_nbytes + 2 * h.n_words
+
+
+def _parse_latent(data, cls):
+    mv = memoryview(data).cast("B")
+    magic, version, N, ndim, reserved, C, unit, lamb, n_words, dig = _unpack_fixed(mv, _FIXED)
+    if magic != cls.MAGIC:
+        raise ValueError(cls.FOREIGN.get(magic) or f"not a {cls.KIND}VBQ bitstream (magic {magic!r})")
+    if version != cls.VERSION:
+        raise ValueError(f"unknown {cls.KIND}bitstream version {version}")
+    if reserved != 0:
+        raise ValueError(f"reserved header byte is {reserved}, not 0")
+    if ndim < 1:
+        raise ValueError("latent shape with 0 dimensions")
+    shape = _read_shape(mv, _FIXED, ndim, "latent")
+    h = cls(N=N, C=C, shape=shape, lamb=float(lamb), digest=bytes(dig), n_words=n_words, **{cls.UNIT: unit})
+    h.check()
+    start = h.nbytes + h.sizes_nbytes                                # of the payload
+    _check_length(len(mv), start + 2 * n_words, f"header, {h.n_sizes} {cls.UNIT} sizes and {n_words} payload words")
+    sizes = np.frombuffer(mv, dtype=cls.SIZE_DTYPE, count=h.n_sizes, offset=h.nbytes)
+    if any(mv[h.nbytes + sizes.nbytes: start]):
+        raise ValueError(f"padding after the {cls.UNIT} sizes is not zero")
+    _check_sizes(sizes, cls.UNIT, *h.size_range(), n_words)
+    return h, sizes, start
+
+
+def write(header: Header, sizes, payload) -> bytes:
+    """header + sizes (any integer array of C * nseg entries) + payload (u16 [n_words]) -> bytes.  Validates as `parse` does."""
+    return _write_latent(header, sizes, payload)
 
 
 def write_compact(header: CompactHeader, sizes, payload) -> bytes:
     """header + sizes (any integer array of P entries) + payload (u16 [n_words]) -> bytes.  Validates as `parse_compact` does."""
-    h = header
-    shape = tuple(int(d) for d in h.shape)
-    _check_fields(h.N, h.C, shape, float(h.lamb), h.part, h.digest, h.n_words, "part", MAX_PART)
-    sizes = np.asarray(sizes).reshape(-1)
-    if sizes.size != h.n_parts:
-        raise ValueError(f"{sizes.size} part sizes, the shape needs {h.n_parts}")
-    _check_part_sizes(sizes, math.prod(shape), h.part, h.n_words)
-    payload = np.ascontiguousarray(payload, dtype="<u2").reshape(-1)
-    if payload.size != h.n_words:
-        raise ValueError(f"payload of {payload.size} words, the header says {h.n_words}")
-    head = _FIXED.pack(COMPACT_MAGIC, COMPACT_VERSION, h.N, len(shape), 0, h.C, h.part, float(h.lamb), h.n_words, h.digest)
-    return b"".join([head, np.asarray(shape, dtype="<u8").tobytes(), sizes.astype("<u4").tobytes(),
-                     bytes(4 * (h.n_parts & 1)), payload.tobytes()])
+    return _write_latent(header, sizes, payload)
+
+
+def latent_nbytes(shape, C, segment, n_words) -> int:
+    """len(write(...)) of a latent tensor of `shape` (channel-last, C channels) in segments of `segment` symbols with a payload
+    of n_words 16-bit words, without building the file.  ValueError for fields `write` rejects."""
+    return _latent_nbytes(Header, shape, C, segment, n_words)
 
 
 def compact_nbytes(shape, C, part, n_words) -> int:
-    """len(write_compact(...)) of a latent tensor of `shape` (channel-last, C channels) in parts of `part` symbols with a
-    payload of n_words 16-bit words, without building the file.  ValueError for fields `write_compact` rejects."""
-    shape = tuple(int(d) for d in shape)
-    h = CompactHeader(N=MAX_N, C=int(C), shape=shape, lamb=0.0, part=int(part), digest=bytes(16), n_words=int(n_words))
-    _check_fields(h.N, h.C, shape, h.lamb, h.part, h.digest, h.n_words, "part", MAX_PART)
-    return h.nbytes + h.sizes_nbytes + 2 * h.n_words
+    """The same for `write_compact`, in parts of `part` symbols."""
+    return _latent_nbytes(CompactHeader, shape, C, part, n_words)
+
+
+def parse(data) -> Tuple[Header, np.ndarray, int]:
+    """bytes -> (header, sizes u16 [C * nseg] (a read-only view into `data`), byte offset of the payload).
+    ValueError on anything malformed."""
+    return _parse_latent(data, Header)
 
 
 def parse_compact(data) -> Tuple[CompactHeader, np.ndarray, int]:
     """bytes -> (header, sizes u32 [P] (a read-only view into `data`), byte offset of the payload).
     ValueError on anything malformed."""
-    mv = memoryview(data).cast("B")
-    if len(mv) < _FIXED.size:
-        raise ValueError(f"truncated: {len(mv)} bytes, the fixed header alone is {_FIXED.size}")
-    magic, version, N, ndim, reserved, C, part, lamb, n_words, dig = _FIXED.unpack_from(mv, 0)
-    if magic == MAGIC:
-        raise ValueError("a latent bitstream in segments (magic b'VBQb'), not a compact one")
-    if magic != COMPACT_MAGIC:
-        raise ValueError(f"not a compact VBQ bitstream (magic {magic!r})")
-    if version != COMPACT_VERSION:
-        raise ValueError(f"unknown compact bitstream version {version}")
-    if reserved != 0:
-        raise ValueError(f"reserved header byte is {reserved}, not 0")
-    if ndim < 1:
-        raise ValueError("latent shape with 0 dimensions")
-    hlen = _FIXED.size + 8 * ndim
-    if len(mv) < hlen:
-        raise ValueError(f"truncated in the latent shape: {len(mv)} bytes, the header is {hlen}")
-    shape = tuple(int(d) for d in np.frombuffer(mv, dtype="<u8", count=ndim, offset=_FIXED.size))
-    _check_fields(N, C, shape, lamb, part, dig, n_words, "part", MAX_PART)
-    h = CompactHeader(N=N, C=C, shape=shape, lamb=float(lamb), part=part, digest=bytes(dig), n_words=n_words)
-    need = hlen + h.sizes_nbytes + 2 * n_words
-    if len(mv) < need:
-        raise ValueError(f"truncated: {len(mv)} bytes, header, {h.n_parts} part sizes and {n_words} payload words need {need}")
-    if len(mv) > need:
-        raise ValueError(f"{len(mv) - need} trailing bytes after the payload")
-    sizes = np.frombuffer(mv, dtype="<u4", count=h.n_parts, offset=hlen)
-    if h.n_parts & 1 and any(mv[hlen + 4 * h.n_parts: hlen + h.sizes_nbytes]):
-        raise ValueError("padding after the part sizes is not zero")
-    _check_part_sizes(sizes, math.prod(shape), part, n_words)
-    return h, sizes, hlen + h.sizes_nbytes
+    return _parse_latent(data, CompactHeader)
+
+
+def parse_latent(data):
+    """What `parse_compact` returns for a compact file, and what `parse` returns -- or raises -- for everything else."""
+    compact = bytes(memoryview(data).cast("B")[:4]) == COMPACT_MAGIC
+    return _parse_latent(data, CompactHeader if compact else Header)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -392,8 +392,7 @@ def _check_emb_fields(N, shape, segment, beta, n_words, K):
         raise ValueError(f"empty matrix shape {tuple(shape)}")
     if math.prod(shape) >= 2 ** 62:
         raise ValueError(f"matrix shape {tuple(shape)} is too large")
-    if not 1 <= segment <= MAX_SEGMENT:
-        raise ValueError(f"segment {segment} outside [1, {MAX_SEGMENT}]")
+    check_segment(segment)
     if not (math.isfinite(beta) and beta >= 0):
         raise ValueError(f"beta {beta} is not finite and >= 0")
     if n_words < 0:
@@ -434,13 +433,9 @@ def write_embeddings(header: EmbeddingHeader, table, sizes, payload) -> bytes:
     if table.dtype != TABLE_DTYPE or table.shape != (h.K,):
         raise ValueError(f"table must be {TABLE_DTYPE} [{h.K}], got {table.dtype} {table.shape}")
     _check_table(table, h.N)
-    sizes = np.asarray(sizes).reshape(-1)
-    if sizes.size != h.nseg:
-        raise ValueError(f"{sizes.size} segment sizes, the shape needs {h.nseg}")
-    _check_sizes(sizes, h.segment, h.n_words)
-    payload = np.ascontiguousarray(payload, dtype="<u2").reshape(-1)
-    if payload.size != h.n_words:
-        raise ValueError(f"payload of {payload.size} words, the header says {h.n_words}")
+    sizes = _flat_sizes(sizes, h.nseg, "segment")
+    _check_sizes(sizes, "segment", 2, h.segment + 2, h.n_words)
+    payload = _checked_payload(payload, h.n_words)
     head = _EMB_FIXED.pack(EMB_MAGIC, EMB_VERSION, h.N, 0, h.segment, h.K, float(h.beta), h.n_words,
                            float(h.empirical_std), len(shape))
     return b"".join([head, np.asarray(shape, dtype="<u8").tobytes(), np.ascontiguousarray(table).tobytes(),
@@ -488,9 +483,7 @@ def parse_embeddings(data) -> Tuple[EmbeddingHeader, np.ndarray, np.ndarray, int
     """bytes -> (header, table TABLE_DTYPE [K], sizes u16 [nseg], byte offset of the payload); the table and the sizes are
     read-only views into `data`.  ValueError on anything malformed."""
     mv = memoryview(data).cast("B")
-    if len(mv) < _EMB_FIXED.size:
-        raise ValueError(f"truncated: {len(mv)} bytes, the fixed header alone is {_EMB_FIXED.size}")
-    magic, version, N, reserved, segment, K, beta, n_words, std, ndim = _EMB_FIXED.unpack_from(mv, 0)
+    magic, version, N, reserved, segment, K, beta, n_words, std, ndim = _unpack_fixed(mv, _EMB_FIXED)
     if magic == MAGIC:
         raise ValueError("a latent bitstream (magic b'VBQb'), not a compressed embedding matrix")
     if magic != EMB_MAGIC:
@@ -501,22 +494,15 @@ def parse_embeddings(data) -> Tuple[EmbeddingHeader, np.ndarray, np.ndarray, int
         raise ValueError(f"reserved header bytes are {reserved}, not 0")
     if not 1 <= ndim <= MAX_NDIM:
         raise ValueError(f"matrix shape with {ndim} dimensions")
-    hlen = _EMB_FIXED.size + 8 * ndim
-    if len(mv) < hlen:
-        raise ValueError(f"truncated in the matrix shape: {len(mv)} bytes, the header is {hlen}")
-    shape = tuple(int(d) for d in np.frombuffer(mv, dtype="<u8", count=ndim, offset=_EMB_FIXED.size))
+    shape = _read_shape(mv, _EMB_FIXED, ndim, "matrix")
     _check_emb_fields(N, shape, segment, beta, n_words, K)
     h = EmbeddingHeader(N=N, shape=shape, segment=segment, beta=float(beta), empirical_std=float(std), n_words=n_words, K=K)
     if len(mv) < h.nbytes:
         raise ValueError(f"truncated in the symbol table: {len(mv)} bytes, header and table need {h.nbytes}")
-    table = np.frombuffer(mv, dtype=TABLE_DTYPE, count=K, offset=hlen)
+    table = np.frombuffer(mv, dtype=TABLE_DTYPE, count=K, offset=_EMB_FIXED.size + 8 * ndim)
     _check_table(table, N)
-    need = h.nbytes + 2 * h.nseg + 2 * n_words
-    if len(mv) < need:
-        raise ValueError(f"truncated: {len(mv)} bytes, header, table, {h.nseg} segment sizes and {n_words} payload words "
-                         f"need {need}")
-    if len(mv) > need:
-        raise ValueError(f"{len(mv) - need} trailing bytes after the payload")
+    _check_length(len(mv), h.nbytes + 2 * h.nseg + 2 * n_words,
+                  f"header, table, {h.nseg} segment sizes and {n_words} payload words")
     sizes = np.frombuffer(mv, dtype="<u2", count=h.nseg, offset=h.nbytes)
-    _check_sizes(sizes, segment, n_words)
+    _check_sizes(sizes, "segment", 2, segment + 2, n_words)
     return h, table, sizes, h.nbytes + 2 * h.nseg

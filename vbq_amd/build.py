@@ -70,7 +70,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     """One object per .hip source (rebuilt only when it or a header changed, in parallel), one link."""
     from concurrent.futures import ThreadPoolExecutor
     srcs = hip_sources()
-    headers = [os.path.join(CSRC, "vbq_common.h"), os.path.join(INCLUDE, "vbq.h")]
+    headers = [os.path.join(CSRC, "vbq_common.h"), os.path.join(CSRC, "vbq_rans_common.h"), os.path.join(INCLUDE, "vbq.h")]
     extra = extra_flags()
     objdir = os.path.join(LIBDIR, "obj")
     flags_tag = os.path.join(objdir, "flags.txt")

@@ -16,10 +16,10 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
+from .bitstream import MAX_PART, check_part  # the format's limits live with the format
 
 PROB_BITS = 15
 DEFAULT_SEGMENT = 1024
-MAX_PART = 1 << 24                           # symbols per part of the interleaved layout (vbq_rans_il_*_u16)
 
 
 def quantize_frequencies(counts, add_n_smoothing=1, prob_bits: int = PROB_BITS) -> np.ndarray:
@@ -121,9 +121,10 @@ def _raise_status(st: int):
 class RansCodec:
     """Encoder / decoder for u16 rank indices laid out as streams [S, n] (S = L*C planes of K1)."""
 
-    def __init__(self, freq, N: int = 10, segment: int = DEFAULT_SEGMENT, *, allow_zero: bool = False):
+    def __init__(self, freq, N: int = 10, segment: Optional[int] = DEFAULT_SEGMENT, *, allow_zero: bool = False):
         """allow_zero=True accepts zero entries (`exact_frequencies`: a table fitted to the data it codes).  Such a table
-        codes only symbols whose entry is nonzero; every entry must then stay below 2**15."""
+        codes only symbols whose entry is nonzero; every entry must then stay below 2**15.  segment=None: a codec for the
+        interleaved layout alone (the calls that cut streams into segments then raise ValueError)."""
         f = freq if isinstance(freq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(freq, dtype=np.uint16)))
         T = ops.table_size(N)
         self.freq_host = f.cpu().reshape(-1, T)
@@ -133,7 +134,7 @@ class RansCodec:
                 raise ValueError("every frequency row must sum to 2**15 with every entry below 2**15")
         elif not bool(torch.all(sums == (1 << PROB_BITS))) or int(self.freq_host.to(torch.int64).min()) < 1:
             raise ValueError("every frequency row must be >= 1 and sum to 2**15")
-        self.N, self.segment, self.T = N, int(segment), T
+        self.N, self.segment, self.T = N, None if segment is None else int(segment), T
         self._freq_dev: Optional[torch.Tensor] = None
 
     def _freq(self, device):
@@ -141,14 +142,29 @@ class RansCodec:
             self._freq_dev = self.freq_host.to(device).contiguous()
         return self._freq_dev
 
-    def _streams(self, idx):
-        """The checked index tensor and its geometry -> (idx, S, n, nseg)."""
+    def _streams(self, idx, segments: bool = True):
+        """The checked index tensor and its geometry -> (idx, S, n, nseg); nseg is None with segments=False (the interleaved
+        layout, which has none)."""
         idx = ops._dev(idx, torch.uint16, "idx")
         n = idx.shape[-1]
         S = idx.numel() // max(n, 1)
         if S != self.freq_host.shape[0]:
             raise ValueError(f"{S} index streams but {self.freq_host.shape[0]} frequency rows")
-        return idx, S, n, (n + self.segment - 1) // self.segment
+        return idx, S, n, self._nseg(n) if segments else None
+
+    def _nseg(self, n: int) -> int:
+        if self.segment is None:
+            raise ValueError("this codec was made without a segment: it serves the interleaved layout only")
+        return (n + self.segment - 1) // self.segment
+
+    def _decoded(self, device, n: int, launch) -> torch.Tensor:
+        """The tail of every decode: idx u16 [S, n] and a zeroed status word, launch(idx, status) -- one or more launches
+        that OR their flags into the word --, then ONE synchronisation to read it; VBQError when a flag is set."""
+        idx = torch.empty((self.freq_host.shape[0], n), dtype=torch.uint16, device=device)
+        status = torch.zeros(1, dtype=torch.uint32, device=device)
+        launch(idx, status)
+        _raise_status(int(status.cpu().item()))
+        return idx
 
     def _encode(self, idx, S, n, words, sizes):
         check(_lib.lib().vbq_rans_encode_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(idx.device)),
@@ -184,15 +200,11 @@ class RansCodec:
         words = ops._dev(words, torch.uint16, "words")
         sizes = ops._dev(sizes, torch.uint32, "sizes")
         S = self.freq_host.shape[0]
-        nseg = (n + self.segment - 1) // self.segment
+        nseg = self._nseg(n)
         if words.numel() != S * nseg * (self.segment + 2) or sizes.numel() != S * nseg:
             raise ValueError(f"expected words [{S}, {nseg}, {self.segment + 2}] and sizes [{S}, {nseg}] for {n} symbols per "
                              f"stream, got {tuple(words.shape)} and {tuple(sizes.shape)}")
-        idx = torch.empty((S, n), dtype=torch.uint16, device=words.device)
-        status = torch.zeros(1, dtype=torch.uint32, device=words.device)
-        self._decode(words, sizes, n, idx, status)
-        _raise_status(int(status.cpu().item()))
-        return idx
+        return self._decoded(words.device, n, lambda idx, status: self._decode(words, sizes, n, idx, status))
 
     # ------------------------------------------------------------ packed payload (vbq_amd.bitstream, vbq_rans_pack_u16)
     def pack_device(self, words: torch.Tensor, sizes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -221,7 +233,7 @@ class RansCodec:
         payload = ops._dev(payload, torch.uint16, "payload")
         sizes = ops._dev(sizes, torch.uint16, "sizes")
         S = self.freq_host.shape[0]
-        nseg = (n + self.segment - 1) // self.segment
+        nseg = self._nseg(n)
         if sizes.numel() != S * nseg:
             raise ValueError(f"expected {S * nseg} segment sizes for {S} streams of {n} symbols, got {sizes.numel()}")
         dev = payload.device
@@ -254,26 +266,23 @@ class RansCodec:
     def decode_packed(self, payload: torch.Tensor, sizes: torch.Tensor, n: int) -> torch.Tensor:
         """unpack + the existing decoder, one status word for both (one synchronisation): u16 indices [S, n].
         A damaged payload raises VBQError."""
-        status = torch.zeros(1, dtype=torch.uint32, device=payload.device)
-        words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
-        idx = torch.empty((self.freq_host.shape[0], n), dtype=torch.uint16, device=payload.device)
-        self._decode(words, out_sizes, n, idx, status)
-        _raise_status(int(status.cpu().item()))
-        return idx
+        def launch(idx, status):
+            words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
+            self._decode(words, out_sizes, n, idx, status)
+        return self._decoded(payload.device, n, launch)
 
     # ------------------------------------------------------------ wave-interleaved layout (bitstream VBQc, vbq_rans_il_*_u16)
     # The S * n symbols in stream-major order are cut every `part` symbols; 64 lanes code a part together (format:
-    # include/vbq.h).  `segment` plays no role here.
+    # include/vbq.h).  `segment` plays no role here: it may be None.
     def _parts(self, n_symbols: int, part) -> int:
         part = int(part)
-        if not 1 <= part <= MAX_PART:
-            raise ValueError(f"part {part} outside [1, {MAX_PART}]")
+        check_part(part)
         return (n_symbols + part - 1) // part
 
     def sizes_interleaved(self, idx: torch.Tensor, part: int) -> torch.Tensor:
         """Words of every part of the interleaved layout -- u32 [P] on the device, P = ceil(S * n / part) -- without the
         words (vbq_rans_il_sizes_u16): the exact coded length."""
-        idx, S, n, _ = self._streams(idx)
+        idx, S, n, _ = self._streams(idx, segments=False)
         sizes = torch.zeros(self._parts(S * n, part), dtype=torch.uint32, device=idx.device)
         check(_lib.lib().vbq_rans_il_sizes_u16(ops._ptr(idx), S, n, self.N, int(part), ops._ptr(self._freq(idx.device)),
                                                ops._ptr(sizes), ops._stream(idx)), "vbq_rans_il_sizes_u16")
@@ -283,7 +292,7 @@ class RansCodec:
         """-> (sizes u32 [P], payload u16 [n_words]) on the host.  The sizes kernel first, their exclusive scan on the device,
         then the encoder writes every part straight to its place in the payload (no padded buffer, no pack pass).  Two
         device-to-host copies: the sizes (they say how long the payload is), then the payload."""
-        idx, S, n, _ = self._streams(idx)
+        idx, S, n, _ = self._streams(idx, segments=False)
         sizes = self.sizes_interleaved(idx, part)
         s64 = sizes.view(torch.int32).to(torch.int64)                                       # (a size is at most 2^24 + 128)
         offsets = torch.cumsum(s64, 0) - s64
@@ -312,11 +321,8 @@ class RansCodec:
         P = self._parts(S * int(n), part)
         if sizes.numel() != P:
             raise ValueError(f"expected {P} part sizes for {S} streams of {n} symbols in parts of {part}, got {sizes.numel()}")
-        idx = torch.empty((S, int(n)), dtype=torch.uint16, device=payload.device)
-        status = torch.zeros(1, dtype=torch.uint32, device=payload.device)
-        self._decode_interleaved(payload, sizes, int(n), part, idx, status)
-        _raise_status(int(status.cpu().item()))
-        return idx
+        return self._decoded(payload.device, int(n),
+                             lambda idx, status: self._decode_interleaved(payload, sizes, int(n), part, idx, status))
 
     @staticmethod
     def compressed_bits(sizes: torch.Tensor) -> int:

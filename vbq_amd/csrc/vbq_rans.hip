@@ -10,13 +10,11 @@
 // segment and consuming words backwards -- reproduces them first-to-last.  One thread per
 // segment; the 64 segments of a workgroup belong to one stream and share its frequency /
 // cumulative tables in LDS.  oracle/vbq_oracle.c (rans_* functions) is the bit-exact checker.
-#include "vbq_common.h"
+#include "vbq_rans_common.h"
 
 namespace vbq {
 namespace {
 
-constexpr int kPB = 15;
-constexpr unsigned kRansL = 1u << 16;
 constexpr int kRansThreads = 64;
 
 // Frequencies and exclusive cumulative frequencies of one stream into LDS, as ONE u32 table fc[sym] = f | c << 16 (f >= 1,
@@ -44,17 +42,6 @@ __device__ __forceinline__ void stage_tables(const uint16_t *__restrict__ freq, 
     __syncthreads();
 }
 
-// x / f and x % f for 1 <= f < 2^15 and x < f 2^17 (the encoder's invariant after renormalisation) without the ~35-instruction
-// expansion of a 32-bit division: the quotient is below 2^17, a float estimate of it is off by at most one, and the remainder says
-// which way (exact by construction: the result is verified, not trusted).
-__device__ __forceinline__ void divmod_small(unsigned x, unsigned f, unsigned &q, unsigned &r) {
-    q = (unsigned)(__uint2float_rn(x) * __builtin_amdgcn_rcpf(__uint2float_rn(f)));
-    int rr = (int)(x - q * f);
-    if (rr < 0) { rr += (int)f; --q; }
-    if (rr >= (int)f) { rr -= (int)f; ++q; }
-    r = (unsigned)rr;
-}
-
 // One thread per segment; a lane walks its segment from the last symbol to the first.  Symbols come in 16-byte groups of eight
 // where the layout allows it (segment length and stream length multiples of eight: one load per eight symbols instead of eight
 // dependent 2-byte loads from a line other lanes do not share).
@@ -76,9 +63,7 @@ k_rans_encode(const uint16_t *__restrict__ idx, long n, int T, int seg, int nseg
         const unsigned fc = fc_l[sym < (unsigned)T ? sym : 0u];  // (an index outside the table: memory-safe; vbq_index_max_u16 tells beforehand)
         const unsigned f = fc & 0xffffu, c = fc >> 16;
         if (x >= (f << (32 - kPB))) { out[k++] = (uint16_t)(x & 0xffffu); x >>= 16; }
-        unsigned q, r;
-        divmod_small(x, f, q, r);
-        x = (q << kPB) + r + c;
+        x = rans_push(x, f, c);
     };
     long i = b;
     const bool vec = ((seg | n) % 8 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
@@ -118,9 +103,7 @@ k_rans_sizes(const uint16_t *__restrict__ idx, long n, int T, int seg, int nseg,
         const unsigned fc = fc_l[sym < (unsigned)T ? sym : 0u];  // (an index outside the table: memory-safe, as in the encoder)
         const unsigned f = fc & 0xffffu, c = fc >> 16;
         if (x >= (f << (32 - kPB))) { ++k; x >>= 16; }
-        unsigned q, r;
-        divmod_small(x, f, q, r);
-        x = (q << kPB) + r + c;
+        x = rans_push(x, f, c);
     };
     long i = b;
     const bool vec = ((seg | n) % 8 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
@@ -182,11 +165,7 @@ k_rans_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict__ s
     bool starved = false;
     auto get = [&]() -> unsigned {                               // one symbol; after a starved stream: zeros
         if (starved) return 0u;
-        const unsigned slot = x & ((1u << kPB) - 1u);
-        unsigned lo = start[slot >> 4];                          // last symbol with cum <= slot
-        while (c_l[lo + 1] <= slot) ++lo;                        // c_l[T] = 2^15 > slot ends the walk below T
-        const unsigned fc = fc_l[lo];
-        x = (fc & 0xffffu) * (x >> kPB) + slot - (fc >> 16);
+        const unsigned lo = rans_pop(x, start, c_l, fc_l);
         if (x < kRansL) {
             if (k == 0) { bad |= 2u; starved = true; }           // a valid stream never renormalises past its first word
             else x = (x << 16) | in[--k];
@@ -314,15 +293,22 @@ k_copy_segments(const uint16_t *__restrict__ src, const SizeT *__restrict__ size
     for (; j < (int)k; j += 64) d[j] = s[j];
 }
 
+// The sizes every entry point over (n_streams, n, N, seg) accepts (pack / unpack / the value decoder take other arguments and
+// word their own messages).
+int check_seg(const char *who, int64_t n_streams, int64_t n, int32_t N, int32_t seg) {
+    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && N >= 1 && N <= 10 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
+                VBQ_ERR_INVALID_ARGUMENT, "%s: bad sizes n_streams=%lld n=%lld N=%d seg=%d", who, (long long)n_streams,
+                (long long)n, N, seg);
+    return VBQ_OK;
+}
+
 }  // namespace
 }  // namespace vbq
 
 extern "C" int vbq_rans_encode_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t seg,
                                    const uint16_t *d_freq, uint16_t *d_words, uint32_t *d_sizes, void *stream) {
     using namespace vbq;
-    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && N >= 1 && N <= 10 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
-                VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_encode_u16: bad sizes n_streams=%lld n=%lld N=%d seg=%d",
-                (long long)n_streams, (long long)n, N, seg);
+    if (int r = check_seg("vbq_rans_encode_u16", n_streams, n, N, seg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_idx && d_freq && d_words && d_sizes, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_encode_u16: null pointer argument");
     const int64_t nseg = (n + seg - 1) / seg;
@@ -336,9 +322,7 @@ extern "C" int vbq_rans_encode_u16(const uint16_t *d_idx, int64_t n_streams, int
 extern "C" int vbq_rans_sizes_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t seg,
                                   const uint16_t *d_freq, uint32_t *d_sizes, void *stream) {
     using namespace vbq;
-    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && N >= 1 && N <= 10 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
-                VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_sizes_u16: bad sizes n_streams=%lld n=%lld N=%d seg=%d",
-                (long long)n_streams, (long long)n, N, seg);
+    if (int r = check_seg("vbq_rans_sizes_u16", n_streams, n, N, seg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_idx && d_freq && d_sizes, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_sizes_u16: null pointer argument");
     const int64_t nseg = (n + seg - 1) / seg;
@@ -355,9 +339,7 @@ extern "C" int vbq_rans_decode_u16(const uint16_t *d_words, const uint32_t *d_si
                                    int32_t N, int32_t seg, const uint16_t *d_freq, uint16_t *d_idx, uint32_t *d_status,
                                    void *stream) {
     using namespace vbq;
-    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && N >= 1 && N <= 10 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
-                VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_decode_u16: bad sizes n_streams=%lld n=%lld N=%d seg=%d",
-                (long long)n_streams, (long long)n, N, seg);
+    if (int r = check_seg("vbq_rans_decode_u16", n_streams, n, N, seg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_idx && d_freq && d_words && d_sizes, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_decode_u16: null pointer argument");
     const int64_t nseg = (n + seg - 1) / seg;
@@ -513,11 +495,7 @@ k_rans_decode_values(const uint16_t *__restrict__ payload, long n_words, const u
     bool starved = false;
     auto get = [&]() -> float {                                  // one value; after a starved stream: the value of symbol 0
         if (starved) return val_l[0];
-        const unsigned slot = x & ((1u << kPB) - 1u);
-        unsigned sym = start[slot >> 4];                         // last symbol with cum <= slot
-        while (c_l[sym + 1] <= slot) ++sym;
-        const unsigned fc = fc_l[sym];
-        x = (fc & 0xffffu) * (x >> kPB) + slot - (fc >> 16);
+        const unsigned sym = rans_pop(x, start, c_l, fc_l);
         if (x < kRansL) {
             if (k == 0) { bad |= 2u; starved = true; }
             else x = (x << 16) | in[--k];

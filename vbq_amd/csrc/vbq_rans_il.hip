@@ -11,13 +11,11 @@
 //   k_il_encode<false>  the encoder's state machine counting words only -> sizes u32 [P]
 //   k_il_encode<true>   the same, writing the words backwards from off + size so that the part ends exactly at off
 //   k_il_decode         untrusted words / sizes / offsets -> indices; what is wrong is reported in *status
-#include "vbq_common.h"
+#include "vbq_rans_common.h"
 
 namespace vbq {
 namespace {
 
-constexpr int kPB = 15;
-constexpr unsigned kRansL = 1u << 16;
 constexpr int kLanes = 64;                                       // the lane count of the FORMAT (and of the workgroup)
 constexpr int kStateWords = 2 * kLanes;
 
@@ -85,16 +83,6 @@ __device__ __forceinline__ bool stage_tables_il(const uint16_t *__restrict__ fre
     return ok;
 }
 
-// x / f and x % f for 1 <= f < 2^15 and x < f 2^17 (the encoder's invariant after renormalisation), as divmod_small of
-// vbq_rans.hip: a float estimate of the quotient (below 2^17) is off by at most one, and the remainder says which way.
-__device__ __forceinline__ void divmod_il(unsigned x, unsigned f, unsigned &q, unsigned &r) {
-    q = (unsigned)(__uint2float_rn(x) * __builtin_amdgcn_rcpf(__uint2float_rn(f)));
-    int rr = (int)(x - q * f);
-    if (rr < 0) { rr += (int)f; --q; }
-    if (rr >= (int)f) { rr -= (int)f; ++q; }
-    r = (unsigned)rr;
-}
-
 // One wave per part.  Runs last to first, steps last to first; in a step every active lane renormalises (emitting at most
 // one word) and encodes its symbol.  The words of a step go to [wp - cnt, wp) in ascending lane order: a lane's place is
 // the number of emitting lanes below it (a wave ballot).  kWrite = false counts only.
@@ -143,11 +131,7 @@ k_il_encode(const uint16_t *__restrict__ idx, long n, long total, int T, int par
             }
             count += (unsigned)cnt;
             if (emit) x >>= 16;
-            if (active) {
-                unsigned q, r;
-                divmod_il(x, f, q, r);
-                x = (q << kPB) + r + c;
-            }
+            if (active) x = rans_push(x, f, c);
         }
     }
     if (kWrite) {
@@ -199,13 +183,7 @@ k_il_decode(const uint16_t *__restrict__ payload, long n_words, const uint32_t *
             for (int t = 0; t * kLanes < len; ++t) {
                 const bool active = t * kLanes + lane < len;
                 unsigned sym = 0;
-                if (active) {
-                    const unsigned slot = x & ((1u << kPB) - 1u);
-                    sym = start[slot >> 4];                      // last symbol with c <= slot
-                    while (c_l[sym + 1] <= slot) ++sym;          // c_l[T] = 2^15 > slot ends the walk below T
-                    const unsigned fc = fc_l[sym];
-                    x = (fc & 0xffffu) * (x >> kPB) + slot - (fc >> 16);
-                }
+                if (active) sym = rans_pop(x, start, c_l, fc_l);
                 const bool need = active && x < kRansL;
                 const unsigned long long m = __ballot(need);
                 const int cnt = __popcll(m);

@@ -226,8 +226,7 @@ def _file_args(means, codepoints, segment):
     if n == 0:
         raise ValueError("an empty matrix has no compressed form")
     seg = default_segment(int(np.prod(shape[1:]))) if segment is None else int(segment)
-    if not 1 <= seg <= bs.MAX_SEGMENT:
-        raise ValueError(f"segment {seg} outside [1, {bs.MAX_SEGMENT}]")
+    bs.check_segment(seg)
     return cp, N, shape, n, seg
 
 

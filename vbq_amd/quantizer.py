@@ -17,12 +17,14 @@ There is no CPU path: without the HIP extension and a ROCm device the methods ra
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from collections.abc import MutableMapping
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
+from . import bitstream
 from . import entropy as _entropy
 from . import ops
 from .tables import n_bit_binary_floats
@@ -34,6 +36,30 @@ def _to_numpy(a):
     if hasattr(a, "numpy") and not isinstance(a, np.ndarray):      # e.g. a TF eager tensor
         return np.asarray(a.numpy())
     return np.asarray(a)
+
+
+# What the two latent files (vbq_amd.bitstream) do their own way.  `unit` is the segment / part length of the file; idx is u16
+# [C, B] (`encode`) or [L, C, B] (`words`); buf (`decode`) is the file from its sizes on, as u16 on the device.
+_Layout = namedtuple("_Layout", "unit header write nbytes check segment encode words decode")
+_LAYOUTS = {
+    "segments": _Layout(
+        "segment", bitstream.Header, bitstream.write, bitstream.latent_nbytes, bitstream.check_segment,
+        segment=lambda unit: unit,                               # of the codec
+        encode=lambda codec, idx, unit: codec.encode_packed(idx),
+        # payload words per lambda, on the device: ONE sizes launch over the L x C streams
+        words=lambda q, keys, idx, unit: q._coder_stack(keys, unit).sizes(idx).view(torch.int32).view(len(keys), -1)
+                                          .sum(dim=1, dtype=torch.int64),
+        decode=lambda codec, buf, h: codec.decode_packed(buf[h.n_sizes:], buf[: h.n_sizes], h.n_rows)),
+    "interleaved": _Layout(
+        "part", bitstream.CompactHeader, bitstream.write_compact, bitstream.compact_nbytes, bitstream.check_part,
+        segment=lambda unit: None,                               # the interleaved coder has no segments
+        encode=lambda codec, idx, unit: codec.encode_interleaved(idx, unit),
+        # one sizes launch per lambda: a part never holds symbols of two lambdas
+        words=lambda q, keys, idx, unit: torch.stack([
+            q._coder_tables(k)[0].sizes_interleaved(idx[l], unit).view(torch.int32).sum(dtype=torch.int64) for l, k in enumerate(keys)]),
+        decode=lambda codec, buf, h: codec.decode_interleaved(buf[h.sizes_nbytes // 2:], buf[: 2 * h.n_parts].view(torch.uint32),
+                                                              h.n_rows, h.part)),    # (the header is a multiple of 8 bytes)
+}
 
 
 class DeviceModels(MutableMapping):
@@ -374,11 +400,13 @@ class ChannelwisePriorCDFQuantizer:
         return ops.compress_latents(means_bc, spread_bc, self._table_dev(), self._sorted_dev(), [float(l) for l in lambs], N=N,
                                     spread=spread, level_len=level_len, models=models, workspace=ws)
 
+    def _f32_dev(self, a) -> torch.Tensor:
+        """A NumPy array (or anything _to_numpy takes) or a tensor as an f32 tensor on the device."""
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(_to_numpy(a))
+        return t.to(self.device, torch.float32)
+
     def _batch_dev(self, batch_means, batch_stds):
-        mu = torch.as_tensor(_to_numpy(batch_means) if not isinstance(batch_means, torch.Tensor) else batch_means)
-        sg = torch.as_tensor(_to_numpy(batch_stds) if not isinstance(batch_stds, torch.Tensor) else batch_stds)
-        mu = mu.to(self.device, torch.float32)
-        sg = sg.to(self.device, torch.float32)
+        mu, sg = self._f32_dev(batch_means), self._f32_dev(batch_stds)
         if mu.dim() != 2 or mu.shape[1] != self.num_channels or mu.shape != sg.shape:
             raise ValueError(f"expected means/stds of shape [B, {self.num_channels}], got {tuple(mu.shape)} / {tuple(sg.shape)}")
         return mu, sg
@@ -400,9 +428,7 @@ class ChannelwisePriorCDFQuantizer:
     # ------------------------------------------------------------------ entropy models (quantizer.py:82-150)
     def _encode(self, X, vae):
         posterior_means, posterior_logvars = vae.encode(X)
-        m = posterior_means if isinstance(posterior_means, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_means))
-        lv = posterior_logvars if isinstance(posterior_logvars, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_logvars))
-        return m.to(self.device, torch.float32), lv.to(self.device, torch.float32)
+        return self._f32_dev(posterior_means), self._f32_dev(posterior_logvars)
 
     def build_entropy_models(self, X, vae, lambs, add_n_smoothing):
         means, logvars = self._encode(X, vae)
@@ -519,9 +545,7 @@ class ChannelwisePriorCDFQuantizer:
         lambs = list(lambs)
         C = self.num_channels
         shape = tuple(np.shape(posterior_means))
-        m = posterior_means if isinstance(posterior_means, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_means))
-        lv = posterior_logvars if isinstance(posterior_logvars, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_logvars))
-        m, lv = m.to(self.device, torch.float32), lv.to(self.device, torch.float32)
+        m, lv = self._f32_dev(posterior_means), self._f32_dev(posterior_logvars)
         assert lv.shape[-1] == C                                                     # quantizer.py:195
         # sigma = exp(logvar) ** 0.5 (quantizer.py:197,202) is taken inside the planes kernel
         zhat, raw_bits, num_bits = self._latents_call(m.reshape(-1, C), lv.reshape(-1, C), lambs, spread="logvar",
@@ -583,12 +607,15 @@ class ChannelwisePriorCDFQuantizer:
                 self._models_dev(lambs).data_ptr(), None if ws is None else (ws.data_ptr(), ws.numel()))
 
     # ------------------------------------------------------------------ real bits
+    def _need_entropy_models(self):
+        if self.entropy_models is None or not hasattr(self, "_code_counts"):
+            raise ValueError("build_entropy_models() first")
+
     def codec(self, lambs, segment=1024):
         """rANS codec whose frequency tables are the histograms behind entropy_models[lamb]
         (one table per (lambda, channel)); see vbq_amd.coder."""
         from .coder import RansCodec, quantize_frequencies
-        if self.entropy_models is None or not hasattr(self, "_code_counts"):
-            raise ValueError("build_entropy_models() first")
+        self._need_entropy_models()
         counts = np.stack([self._code_counts[lamb] for lamb in lambs])              # [L, C, T]
         freq = quantize_frequencies(counts, add_n_smoothing=self._add_n_smoothing)
         return RansCodec(freq.reshape(-1, self.quantization_levels), N=self.max_bits_per_coord, segment=segment)
@@ -623,18 +650,17 @@ class ChannelwisePriorCDFQuantizer:
 
     def _lambda_key(self, lamb):
         """The key of entropy_models equal to `lamb` as a float64 (KeyError otherwise, as compress_latents)."""
-        if self.entropy_models is None or not hasattr(self, "_code_counts"):
-            raise ValueError("build_entropy_models() first")
+        self._need_entropy_models()
         for k in self.lambs:
             if float(k) == float(lamb):
                 return k
         raise KeyError(lamb)
 
-    def _coder_tables(self, lamb, segment):
-        """(codec, digest) of one lambda.  The quantised frequencies and the digest are cached per lambda, keyed on the identity
-        of the `_code_counts` object a build installs (as _keyed_dev keys on identities): a rebuild of the entropy models -- or
-        build_code_points, which clears the device cache -- invalidates them."""
-        from . import bitstream
+    def _coder_tables(self, lamb, segment=None):
+        """(codec, digest) of one lambda; segment=None: a codec without one, for the interleaved layout.  The quantised
+        frequencies and the digest are cached per lambda, keyed on the identity of the `_code_counts` object a build installs
+        (as _keyed_dev keys on identities): a rebuild of the entropy models -- or build_code_points, which clears the device
+        cache -- invalidates them.  The codecs are cached under their lambda, per segment."""
         from .coder import RansCodec, quantize_frequencies
         cc = self._code_counts
         hit = self._dev_cache.get("_coder_tables")
@@ -652,29 +678,25 @@ class ChannelwisePriorCDFQuantizer:
             codec = ent["codecs"][segment] = RansCodec(ent["freq"], N=self.max_bits_per_coord, segment=segment)
         return codec, ent["digest"]
 
-    def _file_shape(self, posterior_means, posterior_logvars, segment, layout="segments", part=1 << 17):
-        """The latent shape of a file (channel-last, one shape for both inputs); ValueError otherwise, for a bad segment (layout
-        "segments") or part (layout "interleaved"), or for an unknown layout."""
-        from . import bitstream
+    def _file_layout(self, posterior_means, posterior_logvars, layout, segment, part):
+        """(latent shape, layout, its segment or part) of a file: the shape channel-last and one for both inputs; ValueError
+        otherwise, for an unknown layout, or for a bad segment (layout "segments") or part (layout "interleaved")."""
         C = self.num_channels
         shape = tuple(int(d) for d in np.shape(posterior_means))
         if tuple(np.shape(posterior_logvars)) != shape or not shape or shape[-1] != C:
             raise ValueError(f"expected channel-last latents [..., {C}] of one shape, got {shape} / {tuple(np.shape(posterior_logvars))}")
-        if layout not in ("segments", "interleaved"):
+        lay = _LAYOUTS.get(layout) if isinstance(layout, str) else None
+        if lay is None:
             raise ValueError(f"layout {layout!r}: expected 'segments' or 'interleaved'")
-        if layout == "interleaved":
-            if not 1 <= part <= bitstream.MAX_PART:
-                raise ValueError(f"part {part} outside [1, {bitstream.MAX_PART}]")
-        elif not 1 <= segment <= bitstream.MAX_SEGMENT:
-            raise ValueError(f"segment {segment} outside [1, {bitstream.MAX_SEGMENT}]")
-        return shape
+        unit = part if lay.unit == "part" else segment
+        lay.check(unit)
+        return shape, lay, int(unit)
 
     def _file_indices(self, posterior_means, posterior_logvars, keys):
         """The u16 indices [L, C, B] a file codes: one solve of every lambda of `keys` with sigma = exp(logvar) ** 0.5, and the
         canonical index of a run of equal code points when the table has any (see encode_batch)."""
         C = self.num_channels
-        m = posterior_means if isinstance(posterior_means, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_means))
-        lv = posterior_logvars if isinstance(posterior_logvars, torch.Tensor) else torch.from_numpy(_to_numpy(posterior_logvars))
+        m, lv = self._f32_dev(posterior_means), self._f32_dev(posterior_logvars)
         mu_cb, sg_cb = self._prep(m.reshape(-1, C), lv.reshape(-1, C), spread="logvar")
         idx = self._solve_idx(mu_cb, sg_cb, keys, self._level_len_dev(keys))                  # [L, C, B]
         if not self._strict:
@@ -694,53 +716,33 @@ class ChannelwisePriorCDFQuantizer:
         layout="interleaved" writes the compact file instead (magic b"VBQc": the wave-interleaved coder in parts of `part`
         symbols, `segment` unused): the same indices and tables in fewer bytes -- 256 bytes of fixed cost per part where the
         default layout pays 6 bytes and the word rounding per segment.  decompress_latents reads either."""
-        from . import bitstream
         self._check_coder_bits()
         key = self._lambda_key(lamb)
-        C = self.num_channels
-        shape = self._file_shape(posterior_means, posterior_logvars, segment, layout, part)
-        if layout == "interleaved":
-            codec, dig = self._coder_tables(key, 1024)                                         # (the tables; its segment plays no role)
-            idx = self._file_indices(posterior_means, posterior_logvars, [key])[0]             # [C, B]
-            sizes, payload = codec.encode_interleaved(idx, int(part))
-            h = bitstream.CompactHeader(N=self.max_bits_per_coord, C=C, shape=shape, lamb=float(key), part=int(part), digest=dig,
-                                        n_words=int(payload.size))
-            return bitstream.write_compact(h, sizes, payload)
-        codec, dig = self._coder_tables(key, int(segment))
+        shape, lay, unit = self._file_layout(posterior_means, posterior_logvars, layout, segment, part)
+        codec, dig = self._coder_tables(key, lay.segment(unit))
         idx = self._file_indices(posterior_means, posterior_logvars, [key])[0]                 # [C, B]
-        sizes, payload = codec.encode_packed(idx)
-        h = bitstream.Header(N=self.max_bits_per_coord, C=C, shape=shape, lamb=float(key), segment=int(segment), digest=dig,
-                             n_words=int(payload.size))
-        return bitstream.write(h, sizes, payload)
+        sizes, payload = lay.encode(codec, idx, unit)
+        h = lay.header(N=self.max_bits_per_coord, C=self.num_channels, shape=shape, lamb=float(key), digest=dig,
+                       n_words=int(payload.size), **{lay.unit: unit})
+        return lay.write(h, sizes, payload)
 
     def decompress_latents(self, data, return_np=True):
         """Inverse of compress_latents_to_bytes: Z_hat shaped like the latents (NumPy, or a device tensor with
         return_np=False), bit-identical to compress_latents(...)["Z_hat"][lamb].  ValueError for a malformed header or
         a stream made with another quantizer / entropy model (digest), KeyError for a lambda this quantizer has no
         model for, VBQError for a damaged payload."""
-        from . import bitstream
         self._check_coder_bits()
-        mv = memoryview(data).cast("B")
-        compact = bytes(mv[:4]) == bitstream.COMPACT_MAGIC
-        h, _, _ = bitstream.parse_compact(data) if compact else bitstream.parse(data)
+        h, _, _ = bitstream.parse_latent(data)
+        lay = next(l for l in _LAYOUTS.values() if l.header is type(h))
         if h.N != self.max_bits_per_coord or h.C != self.num_channels:
             raise ValueError(f"stream is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
                              f"C = {self.num_channels}")
         key = self._lambda_key(h.lamb)
-        codec, dig = self._coder_tables(key, 1024 if compact else h.segment)
+        codec, dig = self._coder_tables(key, lay.segment(h.unit))
         if dig != h.digest:
             raise ValueError("stream was compressed with a different quantizer or entropy model (digest mismatch)")
-        start = h.nbytes                      # sizes, then payload: one upload
-        if compact:
-            n16 = h.sizes_nbytes // 2
-            tail = np.frombuffer(mv, dtype="<u2", count=n16 + h.n_words, offset=start)
-            buf = torch.from_numpy(tail.copy()).to(self.device)
-            sizes = buf[: 2 * h.n_parts].view(torch.uint32)                             # (the header is a multiple of 8 bytes)
-            idx = codec.decode_interleaved(buf[n16:], sizes, h.n_rows, h.part)          # [C, B]
-        else:
-            tail = np.frombuffer(mv, dtype="<u2", count=h.n_sizes + h.n_words, offset=start)
-            buf = torch.from_numpy(tail.copy()).to(self.device)
-            idx = codec.decode_packed(buf[h.n_sizes:], buf[: h.n_sizes], h.n_rows)      # [C, B]
+        tail = np.frombuffer(memoryview(data).cast("B"), dtype="<u2", count=h.sizes_nbytes // 2 + h.n_words, offset=h.nbytes)
+        idx = lay.decode(codec, torch.from_numpy(tail.copy()).to(self.device), h)           # sizes, then payload: one upload
         zhat = ops.gather(idx[None], self._sorted_dev(), self.num_channels, N=self.max_bits_per_coord, layout="cb",
                           out_layout="bc")                                                # [1, B, C]
         zhat = zhat.reshape(h.shape)
@@ -754,8 +756,7 @@ class ChannelwisePriorCDFQuantizer:
     # ------------------------------------------------------------------ rate control: exact lengths, byte budgets
     def _rate_keys(self, lambs):
         """The entropy-model keys of `lambs` (all of self.lambs when None), in order, each once; KeyError for an unknown one."""
-        if self.entropy_models is None or not hasattr(self, "_code_counts"):
-            raise ValueError("build_entropy_models() first")
+        self._need_entropy_models()
         return list(dict.fromkeys(self.lambs if lambs is None else [self._lambda_key(l) for l in lambs]))
 
     def _coder_stack(self, keys, segment):
@@ -784,22 +785,12 @@ class ChannelwisePriorCDFQuantizer:
         vbq_rans_sizes_u16 launch over the L x C streams (segment sizes only, no words), one copy of the L totals.  Inputs and
         errors as compress_latents_to_bytes (KeyError for a lambda without a model).  layout="interleaved": the lengths of the
         compact files -- one vbq_rans_il_sizes_u16 launch per lambda (a part never holds symbols of two lambdas)."""
-        from . import bitstream
         self._check_coder_bits()
         keys = self._rate_keys(lambs)
-        C = self.num_channels
-        shape = self._file_shape(posterior_means, posterior_logvars, segment, layout, part)
-        if layout == "interleaved":
-            idx = self._file_indices(posterior_means, posterior_logvars, keys)                 # [L, C, B]
-            totals = [self._coder_tables(k, 1024)[0].sizes_interleaved(idx[l], int(part)).view(torch.int32).sum(dtype=torch.int64)
-                      for l, k in enumerate(keys)]
-            words = torch.stack(totals).cpu().numpy()
-            return {k: bitstream.compact_nbytes(shape, C, int(part), int(w)) for k, w in zip(keys, words)}
-        codec = self._coder_stack(keys, int(segment))
+        shape, lay, unit = self._file_layout(posterior_means, posterior_logvars, layout, segment, part)
         idx = self._file_indices(posterior_means, posterior_logvars, keys)                     # [L, C, B]
-        sizes = codec.sizes(idx)                                                               # u32 [L * C, nseg]
-        words = sizes.view(torch.int32).view(len(keys), -1).sum(dim=1, dtype=torch.int64).cpu().numpy()
-        return {k: bitstream.latent_nbytes(shape, C, int(segment), int(w)) for k, w in zip(keys, words)}
+        words = lay.words(self, keys, idx, unit).cpu().numpy()
+        return {k: lay.nbytes(shape, self.num_channels, unit, int(w)) for k, w in zip(keys, words)}
 
     def compress_latents_to_budget(self, posterior_means, posterior_logvars, max_bytes, lambs=None, segment=1024,
                                    layout="segments", part=1 << 17) -> bytes:
@@ -807,7 +798,6 @@ class ChannelwisePriorCDFQuantizer:
         (an integer >= 1), byte for byte compress_latents_to_bytes at that lambda; the header says which lambda it is.  A larger
         lambda usually, but not always, gives a smaller file: the rule takes no monotonicity for granted.  ValueError naming
         the smallest achievable length and its lambda when nothing fits."""
-        from . import bitstream
         bitstream.check_budget(max_bytes)
         nbytes = self.coded_nbytes(posterior_means, posterior_logvars, lambs, segment=segment, layout=layout, part=part)
         lamb = bitstream.smallest_rate_within(nbytes, max_bytes, "lambda")
