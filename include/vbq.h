@@ -724,6 +724,62 @@ int vbq_budget_dp_f64(const double *d_fhat, int64_t n_rows, int32_t K, int32_t N
 int vbq_budget_patience_f64(const double *d_fhat, int64_t E, int32_t N, double lamb, int32_t patience, int32_t *d_out_bits,
                             double *d_out_g, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Fixed-size records: the stored form of rows quantized to one bit budget (vbq_budget_dp_f64 spends exactly total_bits
+ * raw bits on every row), vbq_amd/bitstream.py magic "VBQr".  Every row of a file costs the same number of words, so row r
+ * is found by one multiplication and decoded without an entropy coder.
+ *
+ * One record (one row of K coordinates).  A code point of bit length n has rank index q; with k = q + 1: n = N - ctz(k),
+ * its code is j = k >> (N - n + 1), an n-bit number, and q = ((2 j + 1) << (N - n)) - 1.  The raw bits do not delimit
+ * themselves, so a record stores the lengths at a fixed width W = bit_length(N) (1 for N = 1, 2 for N = 3, 4 for N = 10).
+ * Bit i of a record is bit i % 32 of little-endian u32 word i / 32.
+ *   length block  coordinate k's length n_k in bits [k W, (k+1) W), least significant bit first
+ *   code block    from bit K W: j_k takes n_k bits at K W + sum_{i<k} n_i, least significant bit first; a zero-bit
+ *                 coordinate takes nothing
+ *   padding       zero bits up to record_words = ceil((K W + total_bits) / 32) words
+ * Example: N = 3, K = 3, lengths (2, 0, 1), codes (2, -, 1), total_bits = 3: bytes 92 01 00 00, rank indices 9, 7, 11.
+ * A record costs K W + total_bits bits and up to 31 bits of padding: at N = 10 the length fields are 4 bits per coordinate.
+ *
+ * The file, every field little-endian (version 1):
+ *     offset  size      field
+ *     0       4         magic b"VBQr"
+ *     4       1         version = 1
+ *     5       1         N (1..10)
+ *     6       1         ndim (>= 1)
+ *     7       1         reserved = 0
+ *     8       4         C: 1 (one code book) or K (one per column)
+ *     12      4         total_bits (0 .. K N)
+ *     16      4         record_words (must equal the formula above; at most 8192, so that a record fits in LDS)
+ *     20      4         reserved = 0
+ *     24      8 * ndim  shape (u64 each, every entry >= 1); rows are the slices along axis 0, K = prod(shape[1:])
+ *     ...     4 * C T   the code points, f32 [C][T] in rank order, T = 2^(N+1) - 1, every value finite; then 4 zero bytes
+ *                       when C T is odd, so that the records start 8-byte aligned
+ *     ...     4 * R * record_words   the records of rows 0 .. R - 1 (u32 words).  Nothing follows them.
+ *
+ * vbq_records_words       record_words of (K, N, total_bits); 0 for K < 1, N outside 1..10 or total_bits outside [0, K N].
+ * vbq_records_pack_u16    d_idx u16 [n_rows][K] rank indices -> d_words u32 [n_rows][record_words].  One wave per row: n and
+ *                         j from the index alone, a wave prefix sum of the lengths carried over chunks of 64 coordinates, the
+ *                         fields OR-ed into an LDS image, the image written with coalesced stores.  d_status (u32, may be
+ *                         NULL, OR-ed into; zero it first): bit 0 an index >= T, bit 1 a row whose lengths do not add up to
+ *                         total_bits; such a row gets an all-zero record.
+ * vbq_records_unpack_f32  decodes every row (d_row_ids NULL; n_sel ignored) or the n_sel rows d_row_ids lists (int64, any
+ *                         order, repeats allowed, each in [0, n_rows): the caller checks the range) to any of d_out_values
+ *                         f32 [rows][K] = d_table_sorted[c][q] and d_out_idx u16 [rows][K] = q (either may be NULL; with both
+ *                         NULL the call only validates).  d_table_sorted f32 [n_tables][T] in rank order, n_tables = 1 or K
+ *                         (column k reads row k).  The records are UNTRUSTED: no read leaves a record, whatever its bits.
+ *                         d_status: bit 0 a length field > N, bit 1 lengths that do not add up to total_bits, bit 2 non-zero
+ *                         padding, bit 3 a row id outside [0, n_rows).  A row with any bit decodes to zeros.
+ * All three check their arguments before any device work (VBQ_ERR_INVALID_ARGUMENT for sizes outside the ranges above or
+ * null pointers, VBQ_ERR_UNSUPPORTED for a record above 8192 words); n_rows == 0 or no row to decode returns 0.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+size_t vbq_records_words(int32_t K, int32_t N, int32_t total_bits);
+int vbq_records_pack_u16(const uint16_t *d_idx, int64_t n_rows, int32_t K, int32_t N, int32_t total_bits, uint32_t *d_words,
+                         uint32_t *d_status, void *stream);
+int vbq_records_unpack_f32(const uint32_t *d_words, int64_t n_rows, int32_t K, int32_t N, int32_t total_bits,
+                           const float *d_table_sorted, int32_t n_tables, const int64_t *d_row_ids, int64_t n_sel,
+                           float *d_out_values, uint16_t *d_out_idx, uint32_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

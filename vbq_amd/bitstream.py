@@ -12,7 +12,8 @@ Host-only: writing and strictly validating the headers.  Two formats hold one la
 
 ChannelwisePriorCDFQuantizer.compress_latents_to_bytes (layout="segments" / "interleaved") writes them and decompress_latents
 reads either through `parse_latent`.  A third format (magic b"VBQe", further down) holds one compressed word-embedding matrix:
-vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings.  latent_nbytes / compact_nbytes / embeddings_nbytes give the
+vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings, and a fourth (magic b"VBQr", at the end) a matrix whose rows were
+quantized to one exact bit budget, as fixed-size records: compress_to_records / RecordEmbeddings.  latent_nbytes / compact_nbytes / embeddings_nbytes give the
 exact length of a file without building it, and smallest_rate_within is the byte-budget rule of the rate-control calls
 (coded_nbytes / *_to_budget on the quantizer and in vbq_amd.embeddings).
 
@@ -506,3 +507,191 @@ def parse_embeddings(data) -> Tuple[EmbeddingHeader, np.ndarray, np.ndarray, int
     sizes = np.frombuffer(mv, dtype="<u2", count=h.nseg, offset=h.nbytes)
     _check_sizes(sizes, "segment", 2, segment + 2, n_words)
     return h, table, sizes, h.nbytes + 2 * h.nseg
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Fourth format: ONE matrix whose rows were quantized to ONE exact bit budget (vbq_amd.quantize_rows_to_budget), stored as
+# fixed-size records (vbq_amd.embeddings.compress_to_records / RecordEmbeddings).  Every row costs the same number of words, so
+# row r sits at word r * record_words and decodes without an entropy coder; the price is the lengths stored at fixed width.
+#
+# One record.  A code point of bit length n has rank index q; with k = q + 1: n = N - ctz(k), its code is
+# j = k >> (N - n + 1), an n-bit number, and q = ((2 j + 1) << (N - n)) - 1 (vbq_amd/tables.py).  W = N.bit_length().  Bit i of
+# a record is bit i % 32 of little-endian u32 word i / 32.
+#     length block  coordinate k's length n_k in bits [k W, (k+1) W), least significant bit first
+#     code block    from bit K W: j_k takes n_k bits at K W + sum_{i<k} n_i, least significant bit first
+#     padding       zero bits up to record_words = ceil((K W + total_bits) / 32) words
+#
+# Layout of the file, every field little-endian (version 1):
+#
+#     offset  size      field
+#     0       4         magic b"VBQr"
+#     4       1         version = 1
+#     5       1         N (1..10)
+#     6       1         ndim (>= 1)
+#     7       1         reserved = 0
+#     8       4         C: 1 (one code book) or K (one per column)
+#     12      4         total_bits (0 .. K * N)
+#     16      4         record_words (must equal the formula above; at most 8192: a record fits in LDS)
+#     20      4         reserved = 0
+#     24      8 * ndim  shape (u64 each, every entry >= 1); rows are the slices along axis 0, K = prod(shape[1:])
+#     ...     4 * C*T   code points, f32 [C, T] in rank order, T = 2^(N+1) - 1, every value finite; then 4 zero bytes when
+#                       C * T is odd, so that the records start 8-byte aligned
+#     ...     4 * R * record_words   the records (u32 words) of rows 0 .. R - 1; nothing follows them
+#
+# `parse_records` raises ValueError with a specific message on anything malformed, never struct.error or IndexError.  What a
+# record holds is checked on the device (vbq_records_unpack_f32), once, when RecordEmbeddings loads the file.
+# ---------------------------------------------------------------------------------------------------------------------------
+RECORDS_MAGIC = b"VBQr"
+RECORDS_VERSION = 1
+MAX_RECORD_WORDS = 8192                      # the kernels' limit (vbq_records_pack_u16): the LDS image of one record
+_REC_FIXED = struct.Struct("<4sBBBBIIII")    # the 24 bytes before the shape
+assert _REC_FIXED.size == 24
+_REC_FOREIGN = {MAGIC: "a latent bitstream in segments (magic b'VBQb'), not a record file",
+                COMPACT_MAGIC: "a compact latent bitstream (magic b'VBQc'), not a record file",
+                EMB_MAGIC: "a compressed embedding matrix (magic b'VBQe'), not a record file"}
+
+
+@dataclass(frozen=True)
+class RecordsHeader:
+    N: int
+    shape: Tuple[int, ...]
+    C: int
+    total_bits: int
+
+    @property
+    def n(self) -> int:
+        """Coordinates in the matrix."""
+        return math.prod(self.shape)
+
+    @property
+    def n_rows(self) -> int:
+        return self.shape[0]
+
+    @property
+    def row_length(self) -> int:
+        """K: the coordinates of one row."""
+        return math.prod(self.shape[1:])
+
+    @property
+    def length_bits(self) -> int:
+        """W: the width of a length field."""
+        return self.N.bit_length()
+
+    @property
+    def record_words(self) -> int:
+        return (self.row_length * self.length_bits + self.total_bits + 31) // 32
+
+    @property
+    def T(self) -> int:
+        return 2 ** (self.N + 1) - 1
+
+    @property
+    def nbytes(self) -> int:
+        """Length of the header itself (where the code points start)."""
+        return _REC_FIXED.size + 8 * len(self.shape)
+
+    @property
+    def table_nbytes(self) -> int:
+        """Length of the code-point block, padding included."""
+        return 4 * self.C * self.T + 4 * (self.C * self.T & 1)
+
+    @property
+    def records_offset(self) -> int:
+        return self.nbytes + self.table_nbytes
+
+    @property
+    def total_nbytes(self) -> int:
+        return self.records_offset + 4 * self.n_rows * self.record_words
+
+    def check(self):
+        N, shape = self.N, tuple(self.shape)
+        if not 1 <= N <= MAX_N:
+            raise ValueError(f"N = {N} outside [1, {MAX_N}]")
+        if not 1 <= len(shape) <= 255:
+            raise ValueError(f"matrix shape with {len(shape)} dimensions")
+        if any(d < 1 for d in shape):
+            raise ValueError(f"empty matrix shape {shape}")
+        if math.prod(shape) >= 2 ** 62:
+            raise ValueError(f"matrix shape {shape} is too large")
+        K = self.row_length
+        if self.C not in (1, K):
+            raise ValueError(f"C = {self.C} is neither 1 (one code book) nor K = {K} (one per column)")
+        if not 0 <= self.total_bits <= K * N:
+            raise ValueError(f"total_bits {self.total_bits} outside [0, K*N = {K * N}]")
+        if self.record_words > MAX_RECORD_WORDS:
+            raise ValueError(f"a record of {self.record_words} words exceeds the limit of {MAX_RECORD_WORDS}")
+
+
+def _records_header(shape, N, total_bits, C) -> RecordsHeader:
+    h = RecordsHeader(N=int(N), shape=tuple(int(d) for d in shape), C=int(C), total_bits=int(total_bits))
+    h.check()
+    return h
+
+
+def _check_codepoints(table: np.ndarray):
+    if not np.all(np.isfinite(table)):
+        raise ValueError("non-finite code point in the table")
+
+
+def write_records(header: RecordsHeader, table, words) -> bytes:
+    """header + table (f32 [C, T], rank order) + words (u32, R * record_words of them: the records of vbq_records_pack_u16)
+    -> bytes.  Validates as `parse_records` does."""
+    h = _records_header(header.shape, header.N, header.total_bits, header.C)
+    table = np.ascontiguousarray(table, dtype="<f4")
+    if table.size != h.C * h.T:
+        raise ValueError(f"table of {table.size} code points, C * T = {h.C} * {h.T} needed")
+    _check_codepoints(table)
+    words = np.ascontiguousarray(words, dtype="<u4").reshape(-1)
+    if words.size != h.n_rows * h.record_words:
+        raise ValueError(f"{words.size} record words, {h.n_rows} rows of {h.record_words} words needed")
+    head = _REC_FIXED.pack(RECORDS_MAGIC, RECORDS_VERSION, h.N, len(h.shape), 0, h.C, h.total_bits, h.record_words, 0)
+    return b"".join([head, np.asarray(h.shape, dtype="<u8").tobytes(), table.tobytes(), bytes(h.table_nbytes - table.nbytes),
+                     words.tobytes()])
+
+
+def records_nbytes(shape, N, total_bits, C) -> int:
+    """len(write_records(...)) of a matrix of `shape` at N, total_bits and C code books, without building the file.  ValueError
+    for fields `write_records` rejects."""
+    return _records_header(shape, N, total_bits, C).total_nbytes
+
+
+def records_total_bits_within(shape, N, C, max_bytes) -> int:
+    """The largest total_bits whose record file of a matrix of `shape` is <= max_bytes long (an integer >= 1).  The length is a
+    closed form -- header, code points, R records of ceil((K W + total_bits) / 32) words -- so nothing is searched.  ValueError
+    naming the smallest possible file when even total_bits = 0 does not fit."""
+    budget = check_budget(max_bytes)
+    h = _records_header(shape, N, 0, C)
+    K, KW = h.row_length, h.row_length * h.length_bits
+    words = min((budget - h.records_offset) // (4 * h.n_rows), MAX_RECORD_WORDS)      # per record
+    if 32 * words < KW:
+        raise ValueError(f"no total_bits fits in {budget} bytes: the smallest file (total_bits = 0) is {h.total_nbytes} bytes")
+    return min(K * h.N, 32 * words - KW)
+
+
+def parse_records(data) -> Tuple[RecordsHeader, np.ndarray, int]:
+    """bytes -> (header, code points f32 [C, T] (a read-only view into `data`), byte offset of the records).  ValueError on
+    anything malformed."""
+    mv = memoryview(data).cast("B")
+    magic, version, N, ndim, reserved, C, total_bits, record_words, reserved2 = _unpack_fixed(mv, _REC_FIXED)
+    if magic != RECORDS_MAGIC:
+        raise ValueError(_REC_FOREIGN.get(magic) or f"not a VBQ record file (magic {magic!r})")
+    if version != RECORDS_VERSION:
+        raise ValueError(f"unknown record file version {version}")
+    if reserved != 0:
+        raise ValueError(f"reserved header byte is {reserved}, not 0")
+    if reserved2 != 0:
+        raise ValueError(f"reserved header word is {reserved2}, not 0")
+    shape = _read_shape(mv, _REC_FIXED, ndim, "matrix")
+    h = RecordsHeader(N=N, shape=shape, C=C, total_bits=total_bits)
+    h.check()
+    if record_words != h.record_words:
+        raise ValueError(f"record_words is {record_words}, K*W + total_bits = {h.row_length * h.length_bits + total_bits} "
+                         f"bits need {h.record_words}")
+    if len(mv) < h.records_offset:
+        raise ValueError(f"truncated in the code-point table: {len(mv)} bytes, header and table need {h.records_offset}")
+    table = np.frombuffer(mv, dtype="<f4", count=C * h.T, offset=h.nbytes).reshape(C, h.T)
+    _check_codepoints(table)
+    if any(mv[h.nbytes + table.nbytes: h.records_offset]):
+        raise ValueError("padding after the code-point table is not zero")
+    _check_length(len(mv), h.total_nbytes, f"header, table and {h.n_rows} records of {h.record_words} words")
+    return h, table, h.records_offset

@@ -10,6 +10,9 @@
     compress_to_bytes / decompress / CompressedEmbeddings    (ours) the quantized matrix as a real byte string (rANS,
                                                              vbq_amd.bitstream "VBQe") and row-wise lookups from it
     coded_nbytes / compress_to_budget                        (ours) the exact file length at every beta; the file of a byte budget
+    compress_to_records / compress_to_records_budget / RecordEmbeddings    (ours) rows quantized to one exact bit budget as
+                                                             fixed-size records (vbq_amd.bitstream "VBQr"): a row lookup is one
+                                                             address computation and one short unpack
 """
 from __future__ import annotations
 
@@ -304,6 +307,20 @@ def compress_to_budget(means, stds, codepoints, max_bytes, *, betas=None, segmen
     return compress_to_bytes(means, stds, beta, codepoints, segment=segment)
 
 
+def _row_ids(ids, V: int) -> np.ndarray:
+    """The ids of a `rows` call as int64 [n] on the host: ValueError unless one-dimensional, IndexError for ids that are not
+    integers or lie outside [0, V)."""
+    ids = np.asarray(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids)
+    if ids.ndim != 1:
+        raise ValueError(f"ids must be one-dimensional, got shape {ids.shape}")
+    if ids.size and ids.dtype.kind not in "iu":
+        raise IndexError(f"row ids must be integers, got {ids.dtype}")
+    ids = ids.astype(np.int64)
+    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= V):
+        raise IndexError(f"row {int(ids[(ids < 0) | (ids >= V)][0])} outside [0, {V})")
+    return ids
+
+
 class CompressedEmbeddings:
     """A compressed embedding matrix ("VBQe" bytes) on the device.  The header and table are validated on the host; the
     payload, sizes and segment offsets are uploaded and checked ONCE here, so a damaged size raises at load time.  Then
@@ -369,14 +386,7 @@ class CompressedEmbeddings:
         """Rows `ids` (any order, repeats allowed) -> f32 device tensor [len(ids), *shape[1:]].  IndexError outside [0, V)."""
         h = self.header
         V, D, seg = h.shape[0], h.row_length, h.segment
-        ids = np.asarray(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids)
-        if ids.ndim != 1:
-            raise ValueError(f"ids must be one-dimensional, got shape {ids.shape}")
-        if ids.size and ids.dtype.kind not in "iu":
-            raise IndexError(f"row ids must be integers, got {ids.dtype}")
-        ids = ids.astype(np.int64)
-        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= V):
-            raise IndexError(f"row {int(ids[(ids < 0) | (ids >= V)][0])} outside [0, {V})")
+        ids = _row_ids(ids, V)
         out_shape = (ids.size,) + tuple(h.shape[1:])
         if ids.size == 0:
             return torch.empty(out_shape, dtype=torch.float32, device=self.device)
@@ -402,8 +412,110 @@ class CompressedEmbeddings:
 
 
 def decompress(data, return_np: bool = True):
-    """`compress_to_bytes` inverted: the quantized matrix (f32, bit for bit what compress_coordinates returns), as a NumPy
-    array or (return_np=False) a device tensor.  A damaged byte string raises ValueError (header, table, sizes) or
-    VBQError (payload)."""
-    t = CompressedEmbeddings(data).tensor()
+    """`compress_to_bytes` or `compress_to_records` inverted, by the magic of `data`: the quantized matrix (f32, bit for bit what
+    compress_coordinates returns / the code points quantize_rows_to_budget chose), as a NumPy array or (return_np=False) a
+    device tensor.  A damaged byte string raises ValueError (header, table, sizes) or VBQError (payload, records)."""
+    from .bitstream import RECORDS_MAGIC
+    records = bytes(memoryview(data).cast("B")[:4]) == RECORDS_MAGIC
+    t = (RecordEmbeddings if records else CompressedEmbeddings)(data).tensor()
     return t.cpu().numpy() if return_np else t
+
+
+# ------------------------------------------------------------------------ fixed-size records (vbq_amd.bitstream, "VBQr")
+def _records_args(means, codepoints, N):
+    """(code book f32 level-major [T] or [K, T], matrix shape, C) of a record file."""
+    from .tables import table_size
+    shape = tuple(int(d) for d in np.shape(means)) or (1,)
+    if int(np.prod(shape)) == 0:
+        raise ValueError("an empty matrix has no compressed form")
+    cp = np.asarray(codepoints.cpu().numpy() if isinstance(codepoints, torch.Tensor) else codepoints, dtype=np.float32)
+    K = int(np.prod(shape[1:]))
+    C = K if cp.shape == (K, table_size(N)) else 1
+    return cp, shape, C
+
+
+def compress_to_records(means, stds, total_bits, codepoints, N: int = 10) -> bytes:
+    """The matrix quantized row by row to EXACTLY total_bits raw bits (vbq_amd.quantize_rows_to_budget; rows are the slices
+    along axis 0) as a self-describing byte string of fixed-size records: the budget DP's rank indices, one pack launch
+    (vbq_records_pack_u16), ONE device-to-host copy.  `codepoints`: level-major, one code book [T] or one per column [K, T],
+    T = 2^(N+1) - 1.  `decompress` / `RecordEmbeddings` read it; bitstream.records_nbytes gives its length in advance.  A row
+    costs K * W + total_bits bits whatever it holds (W = 4 at N = 10): what the format buys is a row lookup by address, not
+    size -- `compress_to_bytes` stays the small file."""
+    import operator
+    from . import bitstream as bs, tables
+    from .rows_budget import quantize_rows_to_budget
+    cp, shape, C = _records_args(means, codepoints, N)
+    h = bs.RecordsHeader(N=int(N), shape=shape, C=C, total_bits=operator.index(total_bits))
+    h.check()
+    R, K, RW = h.n_rows, h.row_length, h.record_words
+    idx, _, _ = quantize_rows_to_budget(_dev(means).reshape(R, K), _dev(stds).reshape(R, K), h.total_bits, table=cp, N=h.N)
+    buf = torch.zeros(R * RW + 1, dtype=torch.int32, device=idx.device).view(torch.uint32)       # the records, then the status
+    ops.records_pack(idx, h.total_bits, h.N, status=buf[-1:], out=buf[:-1].view(R, RW))
+    host = buf.cpu().numpy()
+    if host[-1]:
+        raise _lib.VBQError("compress_to_records: the rank indices of a row do not spell the bit lengths it was given (a code "
+                            "book with equal neighbouring code points has no unique rank index)")
+    return bs.write_records(h, tables.level_major_to_sorted(cp.reshape(C, h.T)), host[:-1])
+
+
+def compress_to_records_budget(means, stds, codepoints, max_bytes, N: int = 10) -> bytes:
+    """`compress_to_records` at the largest total_bits whose file is <= max_bytes long (bitstream.records_total_bits_within:
+    a closed form, nothing is searched).  ValueError naming the smallest possible file when even total_bits = 0 does not fit."""
+    from . import bitstream as bs
+    _, shape, C = _records_args(means, codepoints, N)
+    return compress_to_records(means, stds, bs.records_total_bits_within(shape, N, C, max_bytes), codepoints, N)
+
+
+class RecordEmbeddings:
+    """A matrix of fixed-size records ("VBQr" bytes) on the device.  The header and the code points are validated on the host;
+    code points and records are uploaded ONCE and every record is checked in one validating pass here, so a damaged record
+    raises VBQError at load time.  Then `rows(ids)` is one launch that reads only the records asked for -- a row's address
+    is its number times the record length -- and `tensor()` decodes the whole matrix."""
+
+    def __init__(self, data, device=None):
+        from . import bitstream as bs
+        h, _, _ = bs.parse_records(data)
+        raw = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
+        self.header = h
+        self.nbytes = int(raw.size)
+        self.device = torch.device(device) if device is not None else ops.current_device("vbq_amd.embeddings")
+        dev = torch.from_numpy(raw[h.nbytes:].copy()).to(self.device)       # ONE upload: code points, padding, records
+        self._table = dev[:4 * h.C * h.T].view(torch.float32).view(h.C, h.T)
+        self._words = dev[h.table_nbytes:].view(torch.uint32).view(h.n_rows, h.record_words)
+        status = torch.zeros(1, dtype=torch.uint32, device=self.device)
+        ops.records_unpack(self._words, h.row_length, h.N, h.total_bits, None, want_values=False, status=status)
+        bits = int(status.cpu().item())
+        if bits:
+            what = [name for b, name in ((1, "a length field above N"), (2, "lengths that do not add up to total_bits"),
+                                         (4, "non-zero padding")) if bits & b]
+            raise _lib.VBQError("damaged record file: a record holds " + ", ".join(what))
+
+    @property
+    def shape(self):
+        return self.header.shape
+
+    @property
+    def total_bits(self) -> int:
+        return self.header.total_bits
+
+    @property
+    def bits_per_coordinate(self) -> float:
+        """The whole byte string (header and code points included) in bits per coordinate."""
+        return 8.0 * self.nbytes / self.header.n
+
+    def _decode(self, row_ids: Optional[torch.Tensor]) -> torch.Tensor:
+        h = self.header
+        return ops.records_unpack(self._words, h.row_length, h.N, h.total_bits, self._table, row_ids)[0]
+
+    def tensor(self) -> torch.Tensor:
+        """The whole matrix, f32 on the device, shaped like the compressed array."""
+        return self._decode(None).view(self.header.shape)
+
+    def rows(self, ids) -> torch.Tensor:
+        """Rows `ids` (any order, repeats allowed) -> f32 device tensor [len(ids), *shape[1:]].  IndexError outside [0, V)."""
+        h = self.header
+        ids = _row_ids(ids, h.n_rows)
+        out_shape = (ids.size,) + tuple(h.shape[1:])
+        if ids.size == 0:
+            return torch.empty(out_shape, dtype=torch.float32, device=self.device)
+        return self._decode(torch.from_numpy(ids).to(self.device)).view(out_shape)

@@ -650,3 +650,66 @@ def budget_patience(fhat: torch.Tensor, lamb: float, patience: int = 3):
     check(_lib.lib().vbq_budget_patience_f64(_ptr(fhat), E, N, float(lamb), int(patience), _ptr(bits), _ptr(g), _stream(fhat)),
           "vbq_budget_patience_f64")
     return bits, g
+
+
+def records_words(K: int, N: int, total_bits: int) -> int:
+    """vbq_records_words: 32-bit words of one record of K coordinates at exactly total_bits raw bits; ValueError for sizes
+    outside K >= 1, 1 <= N <= 10, 0 <= total_bits <= K * N."""
+    n = int(_lib.lib().vbq_records_words(int(K), int(N), int(total_bits)))
+    if n == 0:
+        raise ValueError(f"no record for K={K} N={N} total_bits={total_bits} (need K >= 1, 1 <= N <= 10, 0 <= total_bits <= K*N)")
+    return n
+
+
+def records_pack(idx: torch.Tensor, total_bits: int, N: int, *, status: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vbq_records_pack_u16: rank indices u16 [R, K] -> the rows' fixed-size records, uint32 [R, record_words] (the "VBQr"
+    record of include/vbq.h).  `status` (uint32 [1], zeroed by the caller) gets bit 0 set for an index >= T and bit 1 for a row
+    whose bit lengths do not add up to total_bits; such a row's record is all zeros."""
+    idx = _dev(idx, torch.uint16, "idx")
+    if idx.dim() != 2:
+        raise ValueError(f"idx must be [R, K], got shape {tuple(idx.shape)}")
+    R, K = idx.shape
+    words = _out(out, (R, records_words(K, N, total_bits)), torch.uint32, idx.device, "out")
+    if status is not None:
+        status = _dev(status, torch.uint32, "status")
+    check(_lib.lib().vbq_records_pack_u16(_ptr(idx), R, K, int(N), int(total_bits), _ptr(words), _ptr(status), _stream(idx)),
+          "vbq_records_pack_u16")
+    return words
+
+
+def records_unpack(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: Optional[torch.Tensor],
+                   row_ids: Optional[torch.Tensor] = None, want_values: bool = True, want_idx: bool = False, *,
+                   status: Optional[torch.Tensor] = None):
+    """vbq_records_unpack_f32: records uint32 [R, record_words] -> (values f32 [rows, K] or None, idx u16 [rows, K] or None) of
+    every row, or of the rows `row_ids` lists (int64 device tensor, any order, repeats allowed; IndexError outside [0, R) is the
+    caller's check -- the kernel only refuses such a row).  table_sorted: f32 [T] / [1, T] (one code book) or [K, T] (one per
+    column) in rank order; not needed without values.  The records are untrusted: `status` (uint32 [1], zeroed by the caller)
+    gets bit 0 for a length field > N, bit 1 for lengths that do not add up to total_bits, bit 2 for non-zero padding, bit 3
+    for a row id out of range, and such a row decodes to zeros.  With neither output wanted the call only validates."""
+    words = _dev(words, torch.uint32, "words")
+    K, N, total_bits = int(K), int(N), int(total_bits)
+    RW = records_words(K, N, total_bits)
+    if words.dim() != 2 or words.shape[1] != RW:
+        raise ValueError(f"words must be [R, {RW}] for K={K} N={N} total_bits={total_bits}, got shape {tuple(words.shape)}")
+    R = words.shape[0]
+    n_tables = 1
+    if want_values:
+        T = table_size(N)
+        if table_sorted is None or table_sorted.numel() not in (T, K * T):
+            raise ValueError(f"table_sorted must hold T = {T} or K*T = {K}*{T} code points")
+        n_tables = table_sorted.numel() // T
+        table_sorted = _table(table_sorted, n_tables, T, "table_sorted")
+    if row_ids is not None:
+        row_ids = _dev(row_ids, torch.int64, "row_ids")
+        if row_ids.dim() != 1:
+            raise ValueError(f"row_ids must be one-dimensional, got shape {tuple(row_ids.shape)}")
+    rows = R if row_ids is None else row_ids.numel()
+    values = _out(None, (rows, K), torch.float32, words.device, "values", want_values)
+    idx = _out(None, (rows, K), torch.uint16, words.device, "idx", want_idx)
+    if status is not None:
+        status = _dev(status, torch.uint32, "status")
+    check(_lib.lib().vbq_records_unpack_f32(_ptr(words), R, K, N, total_bits, _ptr(table_sorted) if want_values else None,
+                                            n_tables, _ptr(row_ids), rows if row_ids is not None else 0, _ptr(values),
+                                            _ptr(idx), _ptr(status), _stream(words)), "vbq_records_unpack_f32")
+    return values, idx

@@ -4,6 +4,7 @@ Where quantize() picks a lambda and takes whatever rate falls out, and compress_
 most" a budget of the whole tensor, this solves the constrained problem per row: the allocation of total_bits over the K
 coordinates, at most N each, with the largest Gaussian score (the budget DP of img-compression/utils.py:106-160, batched:
 vbq_budget_dp_f64).  Rows of equal cost are fixed-size records, addressable without an entropy coder.
+vbq_amd.embeddings.compress_to_records stores them as such (vbq_amd.bitstream, magic b"VBQr"); RecordEmbeddings looks rows up.
 """
 from __future__ import annotations
 
