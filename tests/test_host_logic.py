@@ -572,3 +572,38 @@ def test_evaluation_reads_on_plain_numpy_results():
     assert np.array_equal(u8[1], np.clip(np.round(xh[1.0][0] * 255), 0, 255).astype(np.uint8))
     sums2, sums_cl2, _ = utils.evaluation_reads({"num_bits": nb, "X_hat": xh}, settings)        # no 'num_bits_cl': falls back to num_bits
     assert np.array_equal(sums2, sums) and np.array_equal(sums_cl2, sums)
+
+
+def _loop_sums(tmp, settings):
+    """What the reference's loop body reads of the bit counts (img-compression/utils.py:547-553), restated:
+    np.sum(tmp['num_bits'][s][0]) and np.sum(tmp.get('num_bits_cl', tmp['num_bits'])[s][0]) per setting."""
+    num_bits_cl = tmp.get("num_bits_cl", tmp["num_bits"])
+    return [np.sum(tmp["num_bits"][s][0]) for s in settings], [np.sum(num_bits_cl[s][0]) for s in settings]
+
+
+@pytest.mark.parametrize("kind", ["list", "ndarray", "tuple", "float32", "int_and_float"])
+def test_evaluation_reads_num_bits_cl_absent_present_empty(kind):
+    """utils.evaluation_reads on the host path (dicts of NumPy arrays, no device) with 'num_bits_cl' absent, present, and present
+    but EMPTY -- what compress_latents leaves before the raw-length models exist (quantizer.py:231-232 fills it only then).  The
+    device path (evaluation_device_reads) reads 'num_bits' in the empty case; the host path must give the same sums, not a
+    KeyError.  Settings as the reference's driver passes them (post_process.py:113,115): an ndarray of float64, and other
+    sequences; a batch of two images, of which the loop reads the first."""
+    base = 2 ** np.linspace(-8, 7, 16)
+    settings = {"list": [float(l) for l in base], "ndarray": base, "tuple": tuple(base), "float32": [np.float32(l) for l in base],
+                "int_and_float": [100, 30, 10, 3, 1, 0.3, 0.1, 0.03, 0.01]}[kind]
+    rng = np.random.default_rng(len(settings))
+    nb = {l: rng.gamma(2.0, 2.0, (2, 12, 16, 4)).astype(np.float32) for l in settings}
+    cl = {l: rng.gamma(2.0, 1.0, (2, 12, 16, 4)).astype(np.float32) for l in settings}
+    xh = {l: rng.uniform(-0.1, 1.1, (2, 48, 64, 3)).astype(np.float32) for l in settings}
+    for l in settings:                                                       # exact halves, the ends and beyond: round half to even, the clip
+        xh[l][0, 0, :8, 0] = np.float32([0.5 / 255, 1.5 / 255, 2.5 / 255, 254.5 / 255, 0.0, 1.0, -3.0, 7.0])
+    u8_want = np.stack([np.clip(np.round(xh[l][0] * 255), 0, 255).astype(np.uint8) for l in settings])
+    for name, tmp in (("absent", {"num_bits": nb, "X_hat": xh}), ("present", {"num_bits": nb, "num_bits_cl": cl, "X_hat": xh}),
+                      ("empty", {"num_bits": nb, "num_bits_cl": {}, "X_hat": xh})):
+        sums, sums_cl, u8 = utils.evaluation_reads(tmp, settings)
+        want, want_cl = _loop_sums(tmp, settings) if name != "empty" else _loop_sums({"num_bits": nb}, settings)
+        assert np.array_equal(sums, np.array(want)) and sums.dtype == np.float32, name
+        assert np.array_equal(sums_cl, np.array(want_cl)) and sums_cl.dtype == np.float32, name
+        assert (name == "present") == (not np.array_equal(sums_cl, sums))
+        assert u8.dtype == np.uint8 and np.array_equal(u8, u8_want), name
+        assert utils.evaluation_device_reads(tmp, settings) is None          # nothing here lives on a device

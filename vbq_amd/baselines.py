@@ -23,6 +23,17 @@ def _dev_f32(a):
     return ops.upload(a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float32), dev, torch.float32).reshape(-1)
 
 
+def _host(a):
+    """What a VAE handed back (NumPy, a torch tensor on any device, anything with `.numpy()`) as a NumPy array."""
+    from .quantizer import _to_numpy
+    return _to_numpy(a)
+
+
+def _decode(vae, Z, like):
+    """`vae.decode` of NumPy latents -> NumPy; a VAE whose encoder returned torch tensors gets them back on that device."""
+    return _host(vae.decode(torch.from_numpy(np.ascontiguousarray(Z)).to(like.device) if isinstance(like, torch.Tensor) else Z))
+
+
 def _require_finite(samples, allow_inf):
     """The reference raises on samples it cannot bin: scipy's vq.vq refuses NaN and +-inf ("array must not contain infs
     or NaNs"); UniformQuantizer casts floor(NaN) to INT_MIN, which np.bincount / np.take refuse (+-inf clip to an edge
@@ -127,7 +138,7 @@ class ChannelwiseSimpleQuantizer:
     def fit_latents(self, posterior_means, add_n_smoothing):
         C_ = np.shape(posterior_means)[-1]
         assert C_ == self.num_channels
-        means = np.reshape(np.asarray(posterior_means), (-1, C_))
+        means = np.reshape(_host(posterior_means), (-1, C_))
         for c, q in enumerate(self._quantizers):
             q.fit(means[:, c], add_n_smoothing)
         self.code_points = np.array([q.code_points for q in self._quantizers])
@@ -138,7 +149,7 @@ class ChannelwiseSimpleQuantizer:
         self.fit_latents(posterior_means, add_n_smoothing)
 
     def compress_latents(self, posterior_means):
-        pm = np.asarray(posterior_means)
+        pm = _host(posterior_means)
         C_ = pm.shape[-1]
         assert C_ == self.num_channels
         means = np.reshape(pm, (-1, C_))
@@ -154,7 +165,7 @@ class ChannelwiseSimpleQuantizer:
     def compress(self, X, vae, clip=True):
         posterior_means, _ = vae.encode(X)
         output = self.compress_latents(posterior_means)
-        X_hat = np.asarray(vae.decode(output["Z_hat"]))
+        X_hat = _decode(vae, output["Z_hat"], posterior_means)
         output["X_hat"] = np.clip(X_hat, 0, 1) if clip else X_hat
         return output
 
@@ -176,14 +187,14 @@ class ChannelwiseSimpleQuantizerWrapper:
     def compress(self, X, vae, quantization_levels, clip=True):
         assert quantization_levels == self.quantization_levels
         posterior_means, _ = vae.encode(X)
-        pm = np.asarray(posterior_means)
+        pm = _host(posterior_means)
         output = {"Z_hat": {}, "num_bits": {}}
         for l, q in zip(self.quantization_levels, self._quantizers):
             tmp = q.compress_latents(pm)
             for field in output:
                 output[field][l] = tmp[field]
         Z = np.stack([output["Z_hat"][l] for l in self.quantization_levels])
-        X_hat = np.reshape(np.asarray(vae.decode(np.reshape(Z, (-1,) + pm.shape[1:]))),
+        X_hat = np.reshape(_decode(vae, np.reshape(Z, (-1,) + pm.shape[1:]), posterior_means),
                            (len(self.quantization_levels),) + tuple(np.shape(X)))
         if clip:
             X_hat = np.clip(X_hat, 0, 1)

@@ -582,6 +582,7 @@ class ChannelwisePriorCDFQuantizer:
         `compress` + `utils.evaluation_reads` when the VAE cannot be captured (NumPy VAEs, decoders that synchronise)."""
         from .replay import CompressReplay
         X = np.asarray(X) if not isinstance(X, np.ndarray) else X
+        lambs = list(lambs)                                       # an ndarray, a tuple, ...: `list == ndarray` below would be an array
         cache = self._dev_cache.setdefault("_replays", {})
         last = self._dev_cache.get("_replay_last")                # the loop's common case: the same shape, settings and VAE as last time
         if last is not None and last[0] == X.shape and last[1] is vae and last[2] == lambs and last[3] == bool(clip) and last[4] == X.dtype:
@@ -596,7 +597,7 @@ class ChannelwisePriorCDFQuantizer:
             rp = CompressReplay(self, vae, X, lambs, clip)
             rp.fingerprint = self._replay_fingerprint(lambs)      # (after the capture: its warm-up may have grown the workspace)
             cache[key] = rp
-        self._dev_cache["_replay_last"] = (X.shape, vae, list(lambs), bool(clip), X.dtype, key, rp)
+        self._dev_cache["_replay_last"] = (X.shape, vae, lambs, bool(clip), X.dtype, key, rp)
         return rp.run(X)
 
     def _replay_fingerprint(self, lambs):

@@ -324,6 +324,8 @@ def evaluation_reads(tmp, settings, staging=None):
     device-resident results: three small device tensors, ONE synchronisation (asynchronous copies into pinned memory kept in
     `staging`, a dict the caller holds between images); no latent-shaped array crosses PCIe."""
     num_bits_cl = tmp.get("num_bits_cl", tmp["num_bits"])
+    if not num_bits_cl:                                          # as evaluation_device_reads: no raw-length models, num_bits alone
+        num_bits_cl = tmp["num_bits"]
     dev = evaluation_device_reads(tmp, settings)
     if dev is None:
         return _sums_per_setting(tmp["num_bits"], settings), _sums_per_setting(num_bits_cl, settings), _reconstructions_u8(tmp["X_hat"], settings)
