@@ -780,6 +780,51 @@ int vbq_records_unpack_f32(const uint32_t *d_words, int64_t n_rows, int32_t K, i
                            const float *d_table_sorted, int32_t n_tables, const int64_t *d_row_ids, int64_t n_sel,
                            float *d_out_values, uint16_t *d_out_idx, uint32_t *d_status, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Nearest rows (fused top-k): the k rows of a matrix that score highest against each of Q queries, without a decoded copy of
+ * the matrix.  This is the one definition every layer shares.
+ *   rows      v, V of them (1 <= V < 2^31), K f32 each: the decoded records of a "VBQr" file (vbq_records_topk_f32) or a dense
+ *             [V][K] f32 matrix (vbq_topk_f32; the same kernel with a dense row loader).
+ *   queries   d_queries f32 [Q][K], taken as given.
+ *   raw score s(q, v): the f32 chain acc = fmaf(q_k, v_k, acc) over ascending k from acc = 0 -- what v_mfma_f32_32x32x2_f32
+ *             computes, bit for bit.
+ *   metric    0 (dot): the score is s.  1 (cosine): the score is __fdiv_rn(s, den_v), den_v = __fadd_rn(1e-8f, sqrtf(sum)), sum
+ *             the __fadd_rn / __fmul_rn chain of v_k^2 over ascending k from 0 (the notebook's 1e-8 + norm, as in
+ *             vbq_analogy_ranks_f32).  The caller divides the QUERIES by their norms if it wants the cosine proper (the Python
+ *             layer does, by 1e-8 + |q| in f32).
+ *   order     score descending, then row id ascending; scores compare as IEEE values, so -0.0 == 0.0 and the ids break the
+ *             tie.  The result is the first k rows of that total order among the rows not excluded: unique, whatever the grid
+ *             or the order of the tiles.
+ *   exclusion d_exclude int64 [Q][E], 0 <= E <= 8 (may be NULL when E == 0): a listed row is never returned for that query; a
+ *             negative entry (or one >= V) means "none".
+ *   outputs   d_out_ids int64 [Q][k], d_out_scores f32 [Q][k], 1 <= k <= 64; with fewer than k eligible rows the tail is id -1
+ *             and score -inf.
+ *   records   d_words / K / N / total_bits / d_table_sorted / n_tables as in vbq_records_unpack_f32.  The words are UNTRUSTED:
+ *             no read leaves the staged records; a record that fails the unpack's checks takes part as a row of zeros (score
+ *             +-0) and sets the same bits of d_status (u32, may be NULL, OR-ed into; zero it first): bit 0 a length field > N,
+ *             bit 1 lengths that do not add up to total_bits, bit 2 non-zero padding.
+ *   non-finite queries or rows: memory-safe, nothing more is promised (a NaN score is never returned).
+ *   max_workgroups  launch policy, a per-call argument as above: 0 sizes the row split to the device, n > 0 caps it at n
+ *             workgroups per block of 32 queries.  The result does not depend on it.
+ *   workspace vbq_topk_workspace_bytes(V, K, Q, k, max_workgroups) bytes of device memory for either call (0 for sizes outside
+ *             the ranges above or Q < 1): 12 bytes per (workgroup of the row split, query, result).  No V x K buffer exists at
+ *             any point of vbq_records_topk_f32.
+ * One workgroup holds 32 queries in LDS and walks tiles of rows; the records are re-decoded once per block of 32 queries, so
+ * these calls are for a few queries -- many-query workloads decode once and use vbq_analogy_ranks_f32 or a GEMM.  The tiles
+ * must fit 160 KiB of LDS: every K <= 512 does (n_tables 1 or K, any N and total_bits); above the limit the calls return
+ * VBQ_ERR_UNSUPPORTED and name it.  Sizes and pointers are checked before any device work (VBQ_ERR_INVALID_ARGUMENT); Q == 0
+ * returns 0; VBQ_ERR_WORKSPACE for a workspace that is too small.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+size_t vbq_topk_workspace_bytes(int64_t V, int32_t K, int64_t Q, int32_t k, int32_t max_workgroups);
+int vbq_records_topk_f32(const uint32_t *d_words, int64_t n_rows, int32_t K, int32_t N, int32_t total_bits,
+                         const float *d_table_sorted, int32_t n_tables, const float *d_queries, int64_t Q, int32_t k,
+                         int32_t metric, const int64_t *d_exclude, int32_t E, int64_t *d_out_ids, float *d_out_scores,
+                         uint32_t *d_status, int32_t max_workgroups, void *d_workspace, size_t workspace_bytes, void *stream);
+int vbq_topk_f32(const float *d_emb, int64_t V, int32_t K, const float *d_queries, int64_t Q, int32_t k, int32_t metric,
+                 const int64_t *d_exclude, int32_t E, int64_t *d_out_ids, float *d_out_scores, int32_t max_workgroups,
+                 void *d_workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

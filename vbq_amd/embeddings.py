@@ -13,6 +13,8 @@
     compress_to_records / compress_to_records_budget / RecordEmbeddings    (ours) rows quantized to one exact bit budget as
                                                              fixed-size records (vbq_amd.bitstream "VBQr"): a row lookup is one
                                                              address computation and one short unpack
+    most_similar / RecordEmbeddings.most_similar             (ours) the k nearest rows to a few queries (fused unpack + f32 MFMA +
+                                                             top-k, vbq_topk.hip): the records are searched as they are stored
 """
 from __future__ import annotations
 
@@ -421,6 +423,49 @@ def decompress(data, return_np: bool = True):
     return t.cpu().numpy() if return_np else t
 
 
+# ------------------------------------------------------------------------ nearest rows (vbq_topk.hip)
+def _search_args(queries, K: int, k, metric, exclude, device):
+    """(queries f32 [Q, K] on the device -- for the cosine divided by 1e-8 + |q| in f32 --, exclude int64 [Q, E] or None) of a
+    most_similar call; ValueError for k outside 1..64, an unknown metric, a query of the wrong width or with a non-finite
+    coordinate, and an exclude list that is not [Q, E <= 8]."""
+    import operator
+    k = operator.index(k)
+    if not 1 <= k <= 64:
+        raise ValueError(f"k = {k} outside 1..64")
+    if metric not in ("dot", "cosine"):
+        raise ValueError(f"metric {metric!r} is neither 'dot' nor 'cosine'")
+    q = ops.upload(queries, device, torch.float32)
+    if q.dim() == 1:
+        q = q[None, :]
+    if q.dim() != 2 or q.shape[1] != K:
+        raise ValueError(f"queries must be [Q, {K}] or [{K}], got shape {tuple(q.shape)}")
+    if not bool(torch.isfinite(q).all()):
+        raise ValueError("queries hold a NaN or an infinity")
+    if metric == "cosine":
+        q = q / (1e-8 + torch.sqrt(torch.sum(q * q, dim=1, keepdim=True)))
+    if exclude is not None:
+        exclude = ops.upload(exclude, device, torch.int64)
+        if exclude.dim() == 1 and q.shape[0] == 1:
+            exclude = exclude[None, :]
+        if exclude.dim() != 2 or exclude.shape[0] != q.shape[0] or exclude.shape[1] > 8:
+            raise ValueError(f"exclude must be [{q.shape[0]}, E] with E <= 8, got shape {tuple(exclude.shape)}")
+    return q.contiguous(), k, exclude
+
+
+def most_similar(emb, queries, k: int = 10, metric: str = "cosine", exclude=None):
+    """The k rows of the dense matrix `emb` ([V, K], tensor or ndarray) nearest to each query ([Q, K] or [K]) -> (ids int64
+    [Q, k], scores f32 [Q, k]) device tensors, ordered by score descending, then id ascending, padded with -1 / -inf when fewer
+    than k rows are eligible.  metric "cosine": q . v / ((1e-8 + |q|)(1e-8 + |v|)); "dot": q . v; `exclude` ([Q, E <= 8] row
+    ids, negative = none) names rows never returned for that query.  The semantics are those of include/vbq.h ("Nearest
+    rows"); a "VBQe" file is served as most_similar(CompressedEmbeddings(data).tensor(), ...), a "VBQr" file without decoding it
+    by RecordEmbeddings.most_similar."""
+    e = _dev(emb)
+    if e.dim() != 2:
+        raise ValueError("emb must be [V, K]")
+    q, k, exclude = _search_args(queries, e.shape[1], k, metric, exclude, e.device)
+    return ops.topk(e, q, k, metric, exclude)
+
+
 # ------------------------------------------------------------------------ fixed-size records (vbq_amd.bitstream, "VBQr")
 def _records_args(means, codepoints, N):
     """(code book f32 level-major [T] or [K, T], matrix shape, C) of a record file."""
@@ -519,3 +564,30 @@ class RecordEmbeddings:
         if ids.size == 0:
             return torch.empty(out_shape, dtype=torch.float32, device=self.device)
         return self._decode(torch.from_numpy(ids).to(self.device)).view(out_shape)
+
+    def most_similar(self, queries=None, *, ids=None, k: int = 10, metric: str = "cosine", exclude=None):
+        """The k rows nearest to each query -> (ids int64 [Q, k], scores f32 [Q, k]) device tensors, as the module's
+        `most_similar` on tensor() bit for bit, but straight from the records: no V x K float32 matrix is written or read,
+        only a workspace of 12 bytes per (workgroup, query, result).  Exactly one of `queries` ([Q, K] or [K], tensor or
+        ndarray) and `ids` (row ids: the queries are rows(ids), and each query's own row is excluded in addition to `exclude`,
+        which then holds at most 7 columns) is given.  IndexError for ids outside [0, V).  The records are decoded once per
+        block of 32 queries: this is for a few queries; many (the analogy set) decode once -- tensor() -- and use
+        prediction_ranks or a matrix product.  Records too long for the kernel's tiles (K above 512 can be) raise VBQError
+        naming the limit; tensor() still serves them."""
+        h = self.header
+        if (queries is None) == (ids is None):
+            raise ValueError("give exactly one of queries and ids")
+        K = h.row_length
+        if ids is not None:
+            own = _row_ids(ids, h.n_rows)
+            queries = self.rows(own).reshape(own.size, K)
+        q, k, exclude = _search_args(queries, K, k, metric, exclude, self.device)
+        if ids is not None:
+            own = torch.from_numpy(own).to(self.device)[:, None]
+            exclude = own if exclude is None else torch.cat([own, exclude], dim=1)
+            if exclude.shape[1] > 8:
+                raise ValueError("with ids, exclude holds at most 7 columns (the query's own row is the eighth)")
+        status = torch.zeros(1, dtype=torch.uint32, device=self.device)
+        out = ops.records_topk(self._words, K, h.N, h.total_bits, self._table, q, k, metric, exclude, status=status)
+        assert int(status.cpu().item()) == 0, "a record validated at load failed the unpack's checks"
+        return out

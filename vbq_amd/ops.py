@@ -713,3 +713,79 @@ def records_unpack(words: torch.Tensor, K: int, N: int, total_bits: int, table_s
                                             n_tables, _ptr(row_ids), rows if row_ids is not None else 0, _ptr(values),
                                             _ptr(idx), _ptr(status), _stream(words)), "vbq_records_unpack_f32")
     return values, idx
+
+
+_METRICS = {"dot": 0, "cosine": 1, 0: 0, 1: 1}
+
+
+def _topk_args(queries, K, k, metric, exclude):
+    """What records_topk and topk take alike -> (queries [Q, K], k, metric code, exclude [Q, E] or None, E)."""
+    queries = _dev(queries, torch.float32, "queries")
+    if queries.dim() != 2 or queries.shape[1] != K:
+        raise ValueError(f"queries must be [Q, {K}], got shape {tuple(queries.shape)}")
+    k = int(k)
+    if not 1 <= k <= 64:
+        raise ValueError(f"k = {k} outside 1..64")
+    if metric not in _METRICS:
+        raise ValueError(f"metric {metric!r} is neither 'dot' nor 'cosine'")
+    E = 0
+    if exclude is not None:
+        exclude = _dev(exclude, torch.int64, "exclude")
+        if exclude.dim() != 2 or exclude.shape[0] != queries.shape[0] or exclude.shape[1] > 8:
+            raise ValueError(f"exclude must be [{queries.shape[0]}, E] with E <= 8, got shape {tuple(exclude.shape)}")
+        E = exclude.shape[1]
+    return queries, k, _METRICS[metric], (exclude if E else None), E
+
+
+def _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, device):
+    ids = torch.empty((Q, k), dtype=torch.int64, device=device)
+    scores = torch.empty((Q, k), dtype=torch.float32, device=device)
+    nbytes = int(h.vbq_topk_workspace_bytes(V, K, Q, k, int(max_workgroups))) if Q else 0
+    return ids, scores, _workspace(workspace, nbytes, device, floor=1)
+
+
+def records_topk(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: torch.Tensor, queries: torch.Tensor,
+                 k: int = 10, metric="cosine", exclude: Optional[torch.Tensor] = None, *, status: Optional[torch.Tensor] = None,
+                 max_workgroups: int = 0, workspace: Optional[torch.Tensor] = None):
+    """vbq_records_topk_f32: the k rows of the records uint32 [V, record_words] that score highest against each query, without
+    decoding the matrix (semantics: include/vbq.h, "Nearest rows").  queries f32 [Q, K], taken as given; metric "dot" or
+    "cosine" (the score divided by 1e-8 + |row|); exclude int64 [Q, E <= 8], negative = none.  Returns (ids int64 [Q, k],
+    scores f32 [Q, k]), ordered by score descending then id ascending, padded with -1 / -inf.  The records are untrusted:
+    `status` (uint32 [1], zeroed by the caller) gets the unpack's bits and such a record counts as a row of zeros."""
+    words = _dev(words, torch.uint32, "words")
+    K, N, total_bits = int(K), int(N), int(total_bits)
+    RW = records_words(K, N, total_bits)
+    if words.dim() != 2 or words.shape[1] != RW:
+        raise ValueError(f"words must be [V, {RW}] for K={K} N={N} total_bits={total_bits}, got shape {tuple(words.shape)}")
+    T = table_size(N)
+    if table_sorted is None or table_sorted.numel() not in (T, K * T):
+        raise ValueError(f"table_sorted must hold T = {T} or K*T = {K}*{T} code points")
+    n_tables = table_sorted.numel() // T
+    table_sorted = _table(table_sorted, n_tables, T, "table_sorted")
+    queries, k, metric, exclude, E = _topk_args(queries, K, k, metric, exclude)
+    if status is not None:
+        status = _dev(status, torch.uint32, "status")
+    V, Q = words.shape[0], queries.shape[0]
+    h = _lib.lib()
+    ids, scores, ws = _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, words.device)
+    check(h.vbq_records_topk_f32(_ptr(words), V, K, N, total_bits, _ptr(table_sorted), n_tables, _ptr(queries), Q, k, metric,
+                                 _ptr(exclude), E, _ptr(ids), _ptr(scores), _ptr(status), int(max_workgroups), _ptr(ws),
+                                 ws.numel() * ws.element_size(), _stream(words)), "vbq_records_topk_f32")
+    return ids, scores
+
+
+def topk(emb: torch.Tensor, queries: torch.Tensor, k: int = 10, metric="cosine", exclude: Optional[torch.Tensor] = None, *,
+         max_workgroups: int = 0, workspace: Optional[torch.Tensor] = None):
+    """vbq_topk_f32: records_topk on a dense f32 [V, K] matrix -- the same kernel with a dense row loader, the same scores
+    bit for bit."""
+    emb = _dev(emb, torch.float32, "emb")
+    if emb.dim() != 2:
+        raise ValueError(f"emb must be [V, K], got shape {tuple(emb.shape)}")
+    V, K = emb.shape
+    queries, k, metric, exclude, E = _topk_args(queries, K, k, metric, exclude)
+    Q = queries.shape[0]
+    h = _lib.lib()
+    ids, scores, ws = _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, emb.device)
+    check(h.vbq_topk_f32(_ptr(emb), V, K, _ptr(queries), Q, k, metric, _ptr(exclude), E, _ptr(ids), _ptr(scores),
+                         int(max_workgroups), _ptr(ws), ws.numel() * ws.element_size(), _stream(emb)), "vbq_topk_f32")
+    return ids, scores
