@@ -77,9 +77,25 @@ def test_dense_source_is_accepted_by_the_float64_reference(K, V, Q, k, metric):
 def test_record_source_equals_dense_source_bit_for_bit(K, total, per_column, metric):
     """The same chain and the same order: identical ids and identical score bits.  V = 200 is a whole tile of 128 rows and a
     partial one; Q = 33 a second block of queries."""
+    _record_source_equals_dense_source(K, 10, total, per_column, metric)
+
+
+@gpu
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("per_column", [False, True])
+@pytest.mark.parametrize("N", [1, 3])
+def test_record_source_equals_dense_source_at_short_length_fields(N, per_column, metric):
+    """Length fields of W = 1 and W = 2 bits (the test above has W = 4 only) at K = 65: one whole chunk of 64 coordinates and a
+    carry into the second.  At N = 1 the code book has three entries; the order (score descending, id ascending) is total, so
+    the comparison stays exact, and the float64 reference accepts its own result on this data (no two of the 200 rows are
+    equal, no row is all zeros)."""
+    _record_source_equals_dense_source(65, N, None, per_column, metric)
+
+
+def _record_source_equals_dense_source(K, N, total, per_column, metric):
     _need_gpu()
     from vbq_amd import embeddings as E
-    N, V, Q, k = 10, 200, 33, 64
+    V, Q, k = 200, 33, 64
     total = _mid_word(K, N) if total is None else total
     rng = np.random.default_rng(K + total)
     table = _table(rng, K if per_column else 1, N)
@@ -169,7 +185,9 @@ def test_ties_lead_in_ascending_id_and_exclusions_remove_them(metric):
 def test_a_damaged_record_scores_as_the_zero_row(metric):
     """Through the C call.  The table holds 0.0 at the rank of code 0 of every length, so a record whose codes are all 0 really
     decodes to zeros: the file with that row and the file whose row 17 has a length field above N give the same result, and only
-    the second sets the status bit."""
+    the second sets the status bit.  Then each of the three damages (a length field above N, lengths that do not add up,
+    non-zero padding) on a file of K = 12, V = 40: the status word is the unpack's, the result that of the dense matrix with the
+    row zeroed."""
     _need_gpu()
     from vbq_amd import ops
     N, K, V, Q, k = 10, 65, 150, 3, 64
@@ -207,6 +225,35 @@ def test_a_damaged_record_scores_as_the_zero_row(metric):
     # every bit set: every record fails, every row scores +-0, the ids lead in ascending order
     ids3, scores3, st3 = run(_cuda(np.full_like(w, 0xFFFFFFFF).view(np.int32)).view(torch.uint32))
     assert st3 & 1 and np.array_equal(ids3, np.tile(np.arange(k), (Q, 1))) and not scores3.any()
+    # each damage on a small file of its own: the unpack's status word, and the result of the dense matrix with that row zeroed
+    K, V, k, row = 12, 40, 40, 23
+    total = _mid_word(K, N)
+    tab = _cuda(_table(rng, 1, N))
+    words = _pack(RR.random_indices(rng, V, K, N, total), N, total)
+    q = _cuda(rng.standard_normal((Q, K)).astype(np.float32))
+    dense = ops.records_unpack(words, K, N, total, tab)[0]
+    dense[row] = 0.0
+    want_ids, want_scores = ops.topk(dense, q, k, metric)
+    clean = words.cpu().numpy()
+    end = K * N.bit_length() + total
+    assert end % 32 and clean.shape[1] == RR.record_words(K, N, total)
+    for bit in (1, 2, 4):
+        w = clean.copy()
+        n0 = int(w[row, 0] & 0xF)
+        if bit == 1:                                            # a length field > N
+            w[row, 0] = (w[row, 0] & ~np.uint32(0xF)) | np.uint32(0xD)
+        elif bit == 2:                                          # a valid length, but the lengths no longer add up
+            w[row, 0] = (w[row, 0] & ~np.uint32(0xF)) | np.uint32(n0 + 1 if n0 < N else n0 - 1)
+        else:                                                   # the last padding bit
+            w[row, -1] |= np.uint32(1 << 31)
+        damaged = _cuda(w.view(np.int32)).view(torch.uint32)
+        st_topk = torch.zeros(1, dtype=torch.uint32, device="cuda")
+        got_ids, got_scores = ops.records_topk(damaged, K, N, total, tab, q, k, metric, status=st_topk)
+        st_unpack = torch.zeros(1, dtype=torch.uint32, device="cuda")
+        ops.records_unpack(damaged, K, N, total, None, want_values=False, status=st_unpack)
+        st_topk, st_unpack = int(st_topk.cpu().item()), int(st_unpack.cpu().item())
+        assert st_topk == st_unpack and st_unpack & bit, (bit, st_topk, st_unpack)
+        assert torch.equal(got_ids, want_ids) and torch.equal(got_scores.view(torch.int32), want_scores.view(torch.int32))
 
 
 @gpu

@@ -607,3 +607,14 @@ def test_evaluation_reads_num_bits_cl_absent_present_empty(kind):
         assert (name == "present") == (not np.array_equal(sums_cl, sums))
         assert u8.dtype == np.uint8 and np.array_equal(u8, u8_want), name
         assert utils.evaluation_device_reads(tmp, settings) is None          # nothing here lives on a device
+
+
+def test_build_watches_every_header_of_the_kernels():
+    """A header that build_hip does not compare time stamps against leaves stale objects behind when it changes."""
+    import glob
+    from vbq_amd import build
+    watched = {os.path.realpath(h) for h in build.hip_headers()}
+    in_tree = {os.path.realpath(h) for h in glob.glob(os.path.join(build.CSRC, "*.h"))}
+    assert in_tree and in_tree <= watched, sorted(in_tree - watched)
+    assert os.path.realpath(os.path.join(build.INCLUDE, "vbq.h")) in watched
+    assert all(os.path.isfile(h) for h in watched)

@@ -42,6 +42,12 @@ def hip_sources():
     return [os.path.join(CSRC, s) for s in HIP_SOURCES if os.path.exists(os.path.join(CSRC, s))]
 
 
+def hip_headers():
+    """Every header an object depends on: a change to any of them rebuilds every object."""
+    import glob
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "vbq.h")]
+
+
 def _tmp(path):
     # several ranks (or threads) may find a stale library at the same time: every builder writes its own temporary
     # file and installs it with an atomic rename, so a reader never sees a half-written object or library
@@ -70,7 +76,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     """One object per .hip source (rebuilt only when it or a header changed, in parallel), one link."""
     from concurrent.futures import ThreadPoolExecutor
     srcs = hip_sources()
-    headers = [os.path.join(CSRC, "vbq_common.h"), os.path.join(CSRC, "vbq_rans_common.h"), os.path.join(INCLUDE, "vbq.h")]
+    headers = hip_headers()
     extra = extra_flags()
     objdir = os.path.join(LIBDIR, "obj")
     flags_tag = os.path.join(objdir, "flags.txt")

@@ -7,17 +7,15 @@
 //                     coalesced 4-byte stores.  A row whose lengths do not add up to total_bits, or with an index >= T, gets an
 //                     all-zero record and a status bit.
 //   k_records_unpack  one wave per requested row: the record staged in LDS, the same scan, every field read through a two-word
-//                     window, (n, j) -> rank -> value.  The record bytes are untrusted: no read leaves the LDS image, a row
+//                     window, (n, j) -> rank -> value (decode_record of vbq_records_common.h, which the search shares).  The record bytes are untrusted: no read leaves the LDS image, a row
 //                     that fails a check decodes to zeros and sets a status bit.
 // Workgroups are single waves, so the barriers between the phases of a row are wave-local and the row loop needs no
 // agreement between waves.  gfx950 / ROCm only.
-#include "vbq_common.h"
+#include "vbq_records_common.h"
 
 namespace vbq {
 namespace {
 
-constexpr int kRecordsMaxN = 10;
-constexpr int64_t kRecordsMaxWords = 8192;       // 32 KiB: the LDS image of one record
 constexpr int kRecordsWgPerCu = 16;              // single-wave workgroups the row loop's grid is sized for
 // The one code book in LDS pays once a workgroup decodes this many coordinates per table entry it loads; below that (short
 // lookups) the table is read through L2, where every workgroup shares it.
@@ -25,24 +23,8 @@ constexpr int64_t kRecordsLdsTableReuse = 4;
 
 enum : unsigned int {
     kPackBadIndex = 1u,        // an index >= T
-    kPackBadSum = 2u,          // the lengths of a row do not add up to total_bits
-    kUnpackBadLength = 1u,     // a length field > N
-    kUnpackBadSum = 2u,        // the lengths of a record do not add up to total_bits
-    kUnpackBadPadding = 4u,    // non-zero padding
-    kUnpackBadRow = 8u         // a row id outside [0, n_rows)
+    kPackBadSum = 2u           // the lengths of a row do not add up to total_bits
 };
-
-__host__ __device__ constexpr int length_field_bits(int N) { return N >= 8 ? 4 : (N >= 4 ? 3 : (N >= 2 ? 2 : 1)); }
-
-// Inclusive prefix sum over the 64 lanes of the wave.
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int u = __shfl_up(v, d, kWave);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
 
 // OR the low `nbits` (0..32 - 1) bits of `val` into the image at bit `pos`; the caller keeps pos + nbits inside the image.
 __device__ __forceinline__ void put_bits(unsigned int *img, int pos, int nbits, unsigned int val) {
@@ -50,14 +32,6 @@ __device__ __forceinline__ void put_bits(unsigned int *img, int pos, int nbits, 
     const int w = pos >> 5, sh = pos & 31;
     atomicOr(img + w, val << sh);
     if (sh + nbits > 32) atomicOr(img + w + 1, val >> (32 - sh));
-}
-
-// `nbits` (0..31) bits of the image at bit `pos`, through a window of two words; words outside [0, n_words) read as zero.
-__device__ __forceinline__ unsigned int get_bits(const unsigned int *img, int n_words, int pos, int nbits) {
-    const int w = pos >> 5, sh = pos & 31;
-    const unsigned long long lo = w < n_words ? img[w] : 0u;
-    const unsigned long long hi = w + 1 < n_words ? img[w + 1] : 0u;
-    return (unsigned int)(((hi << 32) | lo) >> sh) & ((1u << nbits) - 1u);
 }
 
 __global__ void __launch_bounds__(kWave)
@@ -113,8 +87,7 @@ k_records_unpack(const unsigned int *__restrict__ words, long n_rows, int K, int
                  float *__restrict__ out_val, uint16_t *__restrict__ out_idx, unsigned int *__restrict__ status) {
     extern __shared__ unsigned int img[];
     const int lane = threadIdx.x;
-    const int W = length_field_bits(N), T = table_size(N);
-    const int code0 = K * W, end = code0 + total_bits;
+    const int T = table_size(N);
     const float *tab = table;
     if (kTableInLds) {
         float *lt = reinterpret_cast<float *>(img + n_words);
@@ -130,35 +103,18 @@ k_records_unpack(const unsigned int *__restrict__ words, long n_rows, int K, int
             for (int i = lane; i < n_words; i += kWave) img[i] = rec[i];
         }
         __syncthreads();
-        unsigned int bad = in_range ? 0u : kUnpackBadRow;
-        int carry = 0;
-        for (int base = 0; in_range && base < K; base += kWave) {
-            const int k = base + lane;
-            int n = 0;
-            if (k < K) {
-                n = (int)get_bits(img, n_words, k * W, W);
-                if (n > N) { bad |= kUnpackBadLength; n = 0; }
-            }
-            const int incl = wave_inclusive_sum(n, lane);
-            const int off = carry + incl - n;
-            carry += __shfl(incl, kWave - 1, kWave);
-            if (k < K) {
-                if (off + n > total_bits) n = 0;                     // over the budget: rejected below; read no code
-                const unsigned int j = get_bits(img, n_words, code0 + off, n);
-                const unsigned int q = ((2u * j + 1u) << (N - n)) - 1u;              // < T for every n <= N and j < 2^n
-                if (out_idx) out_idx[o * K + k] = (uint16_t)q;
-                if (out_val) out_val[o * K + k] = tab[(per_column ? (long)k * T : 0L) + q];
-            }
-        }
-        if (in_range) {
-            if (carry != total_bits) bad |= kUnpackBadSum;
-            if ((end & 31) && (img[n_words - 1] >> (end & 31))) bad |= kUnpackBadPadding;
-        }
-        bad |= __any(bad & kUnpackBadLength) ? kUnpackBadLength : 0u;
+        uint16_t *row_idx = out_idx + o * K;                         // used only where the output was asked for
+        float *row_val = out_val + o * K;
+        unsigned int bad = kUnpackBadRow;
+        if (in_range)
+            bad = decode_record(img, n_words, K, N, total_bits, lane, [&](int k, unsigned int q) {
+                if (out_idx) row_idx[k] = (uint16_t)q;
+                if (out_val) row_val[k] = tab[(per_column ? (long)k * T : 0L) + q];
+            });
         if (bad) {                                                   // wave-uniform: a rejected row decodes to zeros
             for (int k = lane; k < K; k += kWave) {
-                if (out_idx) out_idx[o * K + k] = 0;
-                if (out_val) out_val[o * K + k] = 0.0f;
+                if (out_idx) row_idx[k] = 0;
+                if (out_val) row_val[k] = 0.0f;
             }
             if (lane == 0 && status) atomicOr(status, bad);
         }
@@ -169,12 +125,8 @@ k_records_unpack(const unsigned int *__restrict__ words, long n_rows, int K, int
 int records_check(const char *who, int64_t n_rows, int32_t K, int32_t N, int32_t total_bits, int64_t *n_words) {
     VBQ_REQUIRE(n_rows >= 0 && K >= 1 && N >= 1 && N <= kRecordsMaxN, VBQ_ERR_INVALID_ARGUMENT,
                 "%s: bad sizes n_rows=%lld K=%d N=%d (need K >= 1, 1 <= N <= 10)", who, (long long)n_rows, K, N);
-    VBQ_REQUIRE(total_bits >= 0 && (int64_t)total_bits <= (int64_t)K * N, VBQ_ERR_INVALID_ARGUMENT,
-                "%s: total_bits %d outside [0, K*N = %lld]", who, total_bits, (long long)K * N);
-    *n_words = ((int64_t)K * length_field_bits(N) + total_bits + 31) / 32;
-    VBQ_REQUIRE(*n_words <= kRecordsMaxWords, VBQ_ERR_UNSUPPORTED, "%s: a record of %lld words exceeds the limit of %lld", who,
-                (long long)*n_words, (long long)kRecordsMaxWords);
-    return VBQ_OK;
+    if (int rc = record_check_total_bits(who, K, N, total_bits)) return rc;
+    return record_check_words(who, K, N, total_bits, n_words);
 }
 
 unsigned records_grid(int64_t rows) {
@@ -187,8 +139,8 @@ unsigned records_grid(int64_t rows) {
 
 extern "C" size_t vbq_records_words(int32_t K, int32_t N, int32_t total_bits) {
     using namespace vbq;
-    if (K < 1 || N < 1 || N > kRecordsMaxN || total_bits < 0 || (int64_t)total_bits > (int64_t)K * N) return 0;
-    return (size_t)(((int64_t)K * length_field_bits(N) + total_bits + 31) / 32);
+    if (K < 1 || N < 1 || N > kRecordsMaxN || !record_total_bits_ok(K, N, total_bits)) return 0;
+    return (size_t)record_words(K, N, total_bits);
 }
 
 extern "C" int vbq_records_pack_u16(const uint16_t *d_idx, int64_t n_rows, int32_t K, int32_t N, int32_t total_bits,

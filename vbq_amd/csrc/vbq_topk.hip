@@ -4,8 +4,8 @@
 // (score chain, cosine denominator, total order, exclusion, padding, damaged records) are stated in include/vbq.h.
 //   k_topk<records>  4 waves; blockIdx.y = a block of 32 queries kept in LDS as [k][32] for the whole workgroup, blockIdx.x
 //                    strides over tiles of R = 128, 64 or 32 rows (the largest that fits the LDS).  Per tile: the records of the
-//                    tile are staged with one coalesced copy; each wave decodes every fourth row with the unpack's scan (a wave
-//                    prefix sum of the lengths, the two-word window, rank -> value) into the B tile [k][R + 1] -- the odd row
+//                    tile are staged with one coalesced copy; each wave decodes every fourth row with the unpack's scan
+//                    (decode_record of vbq_records_common.h, rank -> value) into the B tile [k][R + 1] -- the odd row
 //                    stride keeps both the decode's stores (lane -> k) and the operand fetch (lane & 31 -> row, lane >> 5 -> k)
 //                    free of bank conflicts; after a barrier wave w runs the 32x32x2 chain over k for rows 32 w .. 32 w + 31 and
 //                    adds up the rows' squared norms from the operands it fetches anyway.  A score enters a query's list only
@@ -19,7 +19,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "vbq_common.h"
+#include "vbq_records_common.h"
 
 namespace vbq {
 namespace {
@@ -36,34 +36,6 @@ constexpr size_t kTopkLdsLimit = 160 * 1024;         // per CU
 constexpr size_t kTopkLdsTwoPerCu = 80 * 1024;
 constexpr int kTopkAlwaysK = 512;                    // every K up to here fits at the smallest tile, whatever N and total_bits
 constexpr long long kNoId = LLONG_MAX;               // the id of an empty list entry: after every row
-
-constexpr int kRecordsMaxN = 10;                     // as in vbq_records.hip
-constexpr int64_t kRecordsMaxWords = 8192;
-
-enum : unsigned int {
-    kUnpackBadLength = 1u,     // a length field > N
-    kUnpackBadSum = 2u,        // the lengths of a record do not add up to total_bits
-    kUnpackBadPadding = 4u     // non-zero padding
-};
-
-__host__ __device__ constexpr int length_field_bits(int N) { return N >= 8 ? 4 : (N >= 4 ? 3 : (N >= 2 ? 2 : 1)); }
-
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int u = __shfl_up(v, d, kWave);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// `nbits` (0..31) bits of the image at bit `pos`, through a window of two words; words outside [0, n_words) read as zero.
-__device__ __forceinline__ unsigned int get_bits(const unsigned int *img, int n_words, int pos, int nbits) {
-    const int w = pos >> 5, sh = pos & 31;
-    const unsigned long long lo = w < n_words ? img[w] : 0u;
-    const unsigned long long hi = w + 1 < n_words ? img[w + 1] : 0u;
-    return (unsigned int)(((hi << 32) | lo) >> sh) & ((1u << nbits) - 1u);
-}
 
 // (score, id) a comes before b: score descending as IEEE values (-0 == 0), then id ascending.
 __device__ __forceinline__ bool comes_before(float as, long long ai, float bs, long long bi) {
@@ -117,8 +89,7 @@ k_topk(const TopkArgs a) {
     int *flag = excl + kTopkQ * kTopkMaxE;
     unsigned int *stage = reinterpret_cast<unsigned int *>(flag + 4);
     const int n_words = a.n_words;
-    const int W = length_field_bits(a.N), T = table_size(a.N);
-    const int code0 = K * W, end = code0 + a.total_bits;
+    const int T = table_size(a.N);
     const float *tab = a.table;
     if (kRecords && a.table_in_lds) {
         float *lt = reinterpret_cast<float *>(stage + R * n_words);
@@ -162,29 +133,10 @@ k_topk(const TopkArgs a) {
             if (r >= valid) {
                 for (int kk = lane; kk < K2; kk += kWave) col[kk * RS] = 0.0f;
             } else if (kRecords) {
-                const unsigned int *img = stage + r * n_words;
-                unsigned int bad = 0u;
-                int carry = 0;
-                for (int base = 0; base < K; base += kWave) {
-                    const int kk = base + lane;
-                    int n = 0;
-                    if (kk < K) {
-                        n = (int)get_bits(img, n_words, kk * W, W);
-                        if (n > a.N) { bad |= kUnpackBadLength; n = 0; }
-                    }
-                    const int incl = wave_inclusive_sum(n, lane);
-                    const int off = carry + incl - n;
-                    carry += __shfl(incl, kWave - 1, kWave);
-                    if (kk < K) {
-                        if (off + n > a.total_bits) n = 0;                   // over the budget: rejected below; read no code
-                        const unsigned int j = get_bits(img, n_words, code0 + off, n);
-                        const unsigned int q = ((2u * j + 1u) << (a.N - n)) - 1u;        // < T for every n <= N and j < 2^n
-                        col[kk * RS] = tab[(a.per_column ? (long)kk * T : 0L) + q];
-                    }
-                }
-                if (carry != a.total_bits) bad |= kUnpackBadSum;
-                if ((end & 31) && (img[n_words - 1] >> (end & 31))) bad |= kUnpackBadPadding;
-                bad |= __any(bad & kUnpackBadLength) ? kUnpackBadLength : 0u;
+                const unsigned int bad = decode_record(stage + r * n_words, n_words, K, a.N, a.total_bits, lane,
+                                                       [&](int kk, unsigned int q) {
+                    col[kk * RS] = tab[(a.per_column ? (long)kk * T : 0L) + q];
+                });
                 if (bad) {                                                   // wave-uniform: a rejected row counts as zeros
                     for (int kk = lane; kk < K; kk += kWave) col[kk * RS] = 0.0f;
                     if (lane == 0 && a.status) atomicOr(a.status, bad);
@@ -206,7 +158,6 @@ k_topk(const TopkArgs a) {
             const float *qa = Qs + lh * kTopkQ + lr;
             const float *bb = Bs + lh * RS + kTopkQ * wave + lr;
             float sum = 0.0f;                                                // of row lr's squares, the same in every lane
-#pragma unroll 4
             for (int kk = 0; kk < K2; kk += 2) {
                 const float av = qa[kk * kTopkQ], bv = bb[kk * RS];
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
@@ -395,15 +346,13 @@ extern "C" int vbq_records_topk_f32(const uint32_t *d_words, int64_t n_rows, int
     const char *who = "vbq_records_topk_f32";
     VBQ_REQUIRE(K >= 1 && N >= 1 && N <= kRecordsMaxN, VBQ_ERR_INVALID_ARGUMENT, "%s: bad sizes K=%d N=%d (need K >= 1, 1 <= N <= 10)",
                 who, K, N);
-    VBQ_REQUIRE(total_bits >= 0 && (int64_t)total_bits <= (int64_t)K * N, VBQ_ERR_INVALID_ARGUMENT,
-                "%s: total_bits %d outside [0, K*N = %lld]", who, total_bits, (long long)K * N);
+    if (int rc = record_check_total_bits(who, K, N, total_bits)) return rc;
     VBQ_REQUIRE(n_tables == 1 || n_tables == K, VBQ_ERR_INVALID_ARGUMENT, "%s: n_tables = %d is neither 1 nor K = %d", who,
                 n_tables, K);
     if (int rc = topk_check(who, n_rows, K, Q, k, metric, E)) return rc;
     VBQ_REQUIRE(max_workgroups >= 0, VBQ_ERR_INVALID_ARGUMENT, "%s: negative max_workgroups %d", who, max_workgroups);
-    const int64_t n_words = ((int64_t)K * length_field_bits(N) + total_bits + 31) / 32;
-    VBQ_REQUIRE(n_words <= kRecordsMaxWords, VBQ_ERR_UNSUPPORTED, "%s: a record of %lld words exceeds the limit of %lld", who,
-                (long long)n_words, (long long)kRecordsMaxWords);
+    int64_t n_words = 0;
+    if (int rc = record_check_words(who, K, N, total_bits, &n_words)) return rc;
     TopkArgs a = {};
     a.K = K;
     size_t lds = 0;

@@ -531,8 +531,7 @@ class RecordEmbeddings:
         ops.records_unpack(self._words, h.row_length, h.N, h.total_bits, None, want_values=False, status=status)
         bits = int(status.cpu().item())
         if bits:
-            what = [name for b, name in ((1, "a length field above N"), (2, "lengths that do not add up to total_bits"),
-                                         (4, "non-zero padding")) if bits & b]
+            what = [name for b, name in ops.RECORDS_UNPACK_STATUS if bits & b]
             raise _lib.VBQError("damaged record file: a record holds " + ", ".join(what))
 
     @property

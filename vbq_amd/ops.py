@@ -678,6 +678,26 @@ def records_pack(idx: torch.Tensor, total_bits: int, N: int, *, status: Optional
     return words
 
 
+# The status bits of vbq_records_unpack_f32 and vbq_records_topk_f32 that say what is wrong with a record (bit 3, a row id out of
+# range, is about the call, not about a record).
+RECORDS_UNPACK_STATUS = ((1, "a length field above N"), (2, "lengths that do not add up to total_bits"), (4, "non-zero padding"))
+
+
+def _records_inputs(words, rows, K, N, total_bits, table_sorted, want_table=True):
+    """What records_unpack and records_topk check alike: words [`rows`, record_words] and, where the code book is wanted,
+    table_sorted holding T or K*T code points -> (n_tables, table f32 [n_tables, T])."""
+    RW = records_words(K, N, total_bits)
+    if words.dim() != 2 or words.shape[1] != RW:
+        raise ValueError(f"words must be [{rows}, {RW}] for K={K} N={N} total_bits={total_bits}, got shape {tuple(words.shape)}")
+    if not want_table:
+        return 1, table_sorted
+    T = table_size(N)
+    if table_sorted is None or table_sorted.numel() not in (T, K * T):
+        raise ValueError(f"table_sorted must hold T = {T} or K*T = {K}*{T} code points")
+    n_tables = table_sorted.numel() // T
+    return n_tables, _table(table_sorted, n_tables, T, "table_sorted")
+
+
 def records_unpack(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: Optional[torch.Tensor],
                    row_ids: Optional[torch.Tensor] = None, want_values: bool = True, want_idx: bool = False, *,
                    status: Optional[torch.Tensor] = None):
@@ -689,17 +709,8 @@ def records_unpack(words: torch.Tensor, K: int, N: int, total_bits: int, table_s
     for a row id out of range, and such a row decodes to zeros.  With neither output wanted the call only validates."""
     words = _dev(words, torch.uint32, "words")
     K, N, total_bits = int(K), int(N), int(total_bits)
-    RW = records_words(K, N, total_bits)
-    if words.dim() != 2 or words.shape[1] != RW:
-        raise ValueError(f"words must be [R, {RW}] for K={K} N={N} total_bits={total_bits}, got shape {tuple(words.shape)}")
+    n_tables, table_sorted = _records_inputs(words, "R", K, N, total_bits, table_sorted, want_values)
     R = words.shape[0]
-    n_tables = 1
-    if want_values:
-        T = table_size(N)
-        if table_sorted is None or table_sorted.numel() not in (T, K * T):
-            raise ValueError(f"table_sorted must hold T = {T} or K*T = {K}*{T} code points")
-        n_tables = table_sorted.numel() // T
-        table_sorted = _table(table_sorted, n_tables, T, "table_sorted")
     if row_ids is not None:
         row_ids = _dev(row_ids, torch.int64, "row_ids")
         if row_ids.dim() != 1:
@@ -754,14 +765,7 @@ def records_topk(words: torch.Tensor, K: int, N: int, total_bits: int, table_sor
     `status` (uint32 [1], zeroed by the caller) gets the unpack's bits and such a record counts as a row of zeros."""
     words = _dev(words, torch.uint32, "words")
     K, N, total_bits = int(K), int(N), int(total_bits)
-    RW = records_words(K, N, total_bits)
-    if words.dim() != 2 or words.shape[1] != RW:
-        raise ValueError(f"words must be [V, {RW}] for K={K} N={N} total_bits={total_bits}, got shape {tuple(words.shape)}")
-    T = table_size(N)
-    if table_sorted is None or table_sorted.numel() not in (T, K * T):
-        raise ValueError(f"table_sorted must hold T = {T} or K*T = {K}*{T} code points")
-    n_tables = table_sorted.numel() // T
-    table_sorted = _table(table_sorted, n_tables, T, "table_sorted")
+    n_tables, table_sorted = _records_inputs(words, "V", K, N, total_bits, table_sorted)
     queries, k, metric, exclude, E = _topk_args(queries, K, k, metric, exclude)
     if status is not None:
         status = _dev(status, torch.uint32, "status")
