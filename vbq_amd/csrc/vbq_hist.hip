@@ -78,6 +78,67 @@ __device__ __forceinline__ void hist_add8(unsigned int *h, const uint4 v) {
         if (!eq[k]) atomicAdd(&hc[kHistCopies * s[k]], 1u);
 }
 
+// One 16-byte load of eight indices, non-temporal: every index is read exactly once.  Without the hint the loads alone take
+// 128 instead of 110-114 us on the Kodak-24 planes, and in the build step, right behind K1's index writes, the whole kernel
+// 165 instead of 144 us (EXPERIMENTS.md, "K2 through an LDS ring").
+__device__ __forceinline__ uint4 load_octet(const uint16_t *p) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+    return make_uint4(t.x, t.y, t.z, t.w);
+}
+
+// The flush of a histogram workgroup: its bins out of LDS into row (l, c) of counts, added (assign == 0) or stored with the
+// code-length model lut[count] next to them (see k_hist_flat).
+template <int N, typename CountT, int kThreads>
+__device__ __forceinline__ void hist_flush(const unsigned int *h, int l, int c, int C, CountT *__restrict__ counts, int assign,
+                                           const float *__restrict__ assign_lut, long lut_n, float *__restrict__ models) {
+    constexpr int T = table_size(N);
+    constexpr int kHistCopies = hist_copies(T);
+    CountT *dst = counts + ((long)l * C + c) * T;
+    // Flush, the bins of a thread first read and summed, then written (and looked up) together: the LDS reads, the table
+    // gathers and the stores of its FI bins overlap instead of following each other through per-bin branches.
+    constexpr int FI = (T + kThreads - 1) / kThreads;
+    unsigned int v[FI];
+#pragma unroll
+    for (int r = 0; r < FI; ++r) {
+        const int i = (int)threadIdx.x + r * kThreads;
+        const int ii = i < T ? i : T - 1;
+        if constexpr (kHistCopies == 4) {
+            const uint4 q4 = reinterpret_cast<const uint4 *>(h)[bin_slot<N>(ii)];
+            v[r] = (q4.x + q4.y) + (q4.z + q4.w);
+        } else if constexpr (kHistCopies == 2) {
+            const uint2 q2 = reinterpret_cast<const uint2 *>(h)[bin_slot<N>(ii)];
+            v[r] = q2.x + q2.y;
+        } else {
+            v[r] = h[bin_slot<N>(ii)];
+        }
+    }
+    if (assign) {
+#pragma unroll
+        for (int r = 0; r < FI; ++r) {
+            const int i = (int)threadIdx.x + r * kThreads;
+            if (i < T) dst[i] = (CountT)v[r];
+        }
+        if (models) {
+            float m[FI];
+#pragma unroll
+            for (int r = 0; r < FI; ++r) m[r] = assign_lut[(long)v[r] < lut_n ? (long)v[r] : lut_n - 1];
+            float *mdst = models + ((long)l * C + c) * T;
+#pragma unroll
+            for (int r = 0; r < FI; ++r) {
+                const int i = (int)threadIdx.x + r * kThreads;
+                if (i < T) mdst[i] = m[r];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < FI; ++r) {
+            const int i = (int)threadIdx.x + r * kThreads;
+            if (i < T && v[r]) atomicAdd(&dst[i], (CountT)v[r]);
+        }
+    }
+}
+
 // All indices of the workgroup belong to one channel: [l][c][n_per_ch] contiguous.
 // assign_lut != nullptr (only with ONE workgroup per (lambda, channel), gridDim.x == 1): the workgroup owns its whole row of
 // bins, so it STORES them (zeros included: no memset of the 67 MB array beforehand, no atomics) and writes the code-length
@@ -122,7 +183,7 @@ k_hist_flat(const uint16_t *__restrict__ idx, long n_per_ch, long ch_stride, int
     uint4 A[U], B[U];
     auto load_stage = [&](uint4 (&R)[U]) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) R[u] = *reinterpret_cast<const uint4 *>(src + (q + u * stride) * 8);
+        for (int u = 0; u < U; ++u) R[u] = load_octet(src + (q + u * stride) * 8);
         q += U * stride;
     };
     if (stages > 0) load_stage(A);
@@ -151,9 +212,9 @@ k_hist_flat(const uint16_t *__restrict__ idx, long n_per_ch, long ch_stride, int
             for (int u = 0; u < U; ++u) hist_add8<N, kHistCopies>(h, A[u]);
         }
     }
-    for (; full(q, 1); q += stride) hist_add8<N, kHistCopies>(h, *reinterpret_cast<const uint4 *>(src + q * 8));
+    for (; full(q, 1); q += stride) hist_add8<N, kHistCopies>(h, load_octet(src + q * 8));
     for (; q < noct; q += stride) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(src + q * 8);
+        const uint4 v = load_octet(src + q * 8);
         const unsigned int w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -165,49 +226,7 @@ k_hist_flat(const uint16_t *__restrict__ idx, long n_per_ch, long ch_stride, int
         atomicAdd(&h[kHistCopies * bin_slot<N>(src[i])], 1u);
     if (blockIdx.x == 0 && (long)threadIdx.x < head) atomicAdd(&h[kHistCopies * bin_slot<N>(src0[threadIdx.x])], 1u);
     __syncthreads();
-    CountT *dst = counts + ((long)l * C + c) * T;
-    // Flush, the bins of a thread first read and summed, then written (and looked up) together: the LDS reads, the table
-    // gathers and the stores of its FI bins overlap instead of following each other through per-bin branches.
-    constexpr int FI = (T + kHistThreads - 1) / kHistThreads;
-    unsigned int v[FI];
-#pragma unroll
-    for (int r = 0; r < FI; ++r) {
-        const int i = (int)threadIdx.x + r * kHistThreads;
-        const int ii = i < T ? i : T - 1;
-        if constexpr (kHistCopies == 4) {
-            const uint4 q4 = reinterpret_cast<const uint4 *>(h)[bin_slot<N>(ii)];
-            v[r] = (q4.x + q4.y) + (q4.z + q4.w);
-        } else if constexpr (kHistCopies == 2) {
-            const uint2 q2 = reinterpret_cast<const uint2 *>(h)[bin_slot<N>(ii)];
-            v[r] = q2.x + q2.y;
-        } else {
-            v[r] = h[bin_slot<N>(ii)];
-        }
-    }
-    if (assign) {
-#pragma unroll
-        for (int r = 0; r < FI; ++r) {
-            const int i = (int)threadIdx.x + r * kHistThreads;
-            if (i < T) dst[i] = (CountT)v[r];
-        }
-        if (models) {
-            float m[FI];
-#pragma unroll
-            for (int r = 0; r < FI; ++r) m[r] = assign_lut[(long)v[r] < lut_n ? (long)v[r] : lut_n - 1];
-            float *mdst = models + ((long)l * C + c) * T;
-#pragma unroll
-            for (int r = 0; r < FI; ++r) {
-                const int i = (int)threadIdx.x + r * kHistThreads;
-                if (i < T) mdst[i] = m[r];
-            }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < FI; ++r) {
-            const int i = (int)threadIdx.x + r * kHistThreads;
-            if (i < T && v[r]) atomicAdd(&dst[i], (CountT)v[r]);
-        }
-    }
+    hist_flush<N, CountT, kHistThreads>(h, l, c, C, counts, assign, assign_lut, lut_n, models);
 }
 
 // Channel-last [rows][C], C > 1: a workgroup owns 16 consecutive channels of one lambda.
