@@ -825,6 +825,48 @@ int vbq_topk_f32(const float *d_emb, int64_t V, int32_t K, const float *d_querie
                  const int64_t *d_exclude, int32_t E, int64_t *d_out_ids, float *d_out_scores, int32_t max_workgroups,
                  void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Pooled rows (embedding bags): per output row the sum, mean or max of a short list of rows, without the [n_ids][K] matrix
+ * of the listed rows in between.  This is the one definition every layer shares.
+ *   rows      v, V of them (V >= 1), K f32 each: the decoded records of a "VBQr" file (vbq_records_bag_f32) or a dense [V][K]
+ *             f32 matrix (vbq_bag_f32; the same kernel with a dense row loader, so the two agree bit for bit).
+ *   d_ids     int64 [n_ids] (may be NULL when n_ids == 0).
+ *   d_offsets int64 [n_bags + 1]: bag b is the entries i in [offsets[b], offsets[b+1]), IN THAT ORDER.
+ *   d_weights f32 [n_ids], or NULL.
+ *   entries   a negative id is padding: skipped silently, not counted.  An id >= V is skipped, not counted, and sets status
+ *             bit 3 (the unpack's "row id outside [0, n_rows)").
+ *   mode      0 sum   per coordinate k: acc = +0.0f, then for each counted entry in order acc = __fadd_rn(acc, v_k), or with
+ *                     weights acc = __fadd_rn(acc, __fmul_rn(w_i, v_k)): two separately rounded f32 operations, never
+ *                     contracted, so NumPy float32 arithmetic reproduces the result bit for bit.
+ *             1 mean  the unweighted sum, then __fdiv_rn(acc, (float)count), count the number of counted entries; count == 0
+ *                     gives +0.0f.  Weights with mean are an argument error.
+ *             2 max   acc is the first counted entry's v_k; a later entry replaces it only where v_k > acc as IEEE values: the
+ *                     value met first stays on a tie, -0.0 does not displace +0.0 (nor +0.0 a -0.0 met first).  A bag with no
+ *                     counted entry gives +0.0f.  Weights with max are an argument error.
+ *   records   d_words / K / N / total_bits / d_table_sorted / n_tables as in vbq_records_unpack_f32.  The words are UNTRUSTED:
+ *             no read leaves the staged record; a record that fails the unpack's checks takes part as a row of zeros (it is
+ *             counted) and sets the same bits 0-2 of d_status: a length field > N, lengths that do not add up to total_bits,
+ *             non-zero padding.
+ *   offsets   UNTRUSTED too: each bag's range is clamped into [0, n_ids] and begin > end is an empty bag; either sets status
+ *             bit 4.  No read leaves d_ids or d_weights, whatever the offsets hold.
+ *   d_out     f32 [n_bags][K]; every row is written, an empty bag gives zeros.  The result does not depend on the grid.
+ *   d_status  u32, may be NULL, OR-ed into; zero it first.
+ * One wave pools one bag, entry by entry (a fixed order of additions is the definition, so a bag is never split): the calls
+ * are for many short bags; a few very long bags run serially.  Per bag the kernel keeps the staged record and two sets of K
+ * accumulators in LDS, 4 (record_words + 2 K) bytes, and the one code book beside them where it fits and is re-used enough.
+ * That must fit 160 KiB: every K <= 16804 does for any (N, total_bits, n_tables) (ceil(14 K / 32) + 2 K <= 40960 words at
+ * N = 10, total_bits = 10 K), the dense source up to K = 20480; above, the calls return VBQ_ERR_UNSUPPORTED and name the limit.
+ * Sizes, the mode and null pointers are checked before any device work (VBQ_ERR_INVALID_ARGUMENT, also for weights with mode
+ * 1 or 2); n_bags == 0 returns 0; n_ids == 0 with n_bags > 0 writes zeros.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_records_bag_f32(const uint32_t *d_words, int64_t n_rows, int32_t K, int32_t N, int32_t total_bits,
+                        const float *d_table_sorted, int32_t n_tables, const int64_t *d_ids, int64_t n_ids,
+                        const int64_t *d_offsets, int64_t n_bags, const float *d_weights, int32_t mode, float *d_out,
+                        uint32_t *d_status, void *stream);
+int vbq_bag_f32(const float *d_emb, int64_t V, int32_t K, const int64_t *d_ids, int64_t n_ids, const int64_t *d_offsets,
+                int64_t n_bags, const float *d_weights, int32_t mode, float *d_out, uint32_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@
                                                              address computation and one short unpack
     most_similar / RecordEmbeddings.most_similar             (ours) the k nearest rows to a few queries (fused unpack + f32 MFMA +
                                                              top-k, vbq_topk.hip): the records are searched as they are stored
+    bag / RecordEmbeddings.bag                               (ours) pooled rows -- the sum, mean or max of a list of rows per
+                                                             output, torch.nn.EmbeddingBag on the compressed table (vbq_bag.hip)
 """
 from __future__ import annotations
 
@@ -466,6 +468,81 @@ def most_similar(emb, queries, k: int = 10, metric: str = "cosine", exclude=None
     return ops.topk(e, q, k, metric, exclude)
 
 
+# ------------------------------------------------------------------------ pooled rows (vbq_bag.hip)
+_BAG_MODES = ("sum", "mean", "max")
+
+
+def _bag_args(ids, offsets, weights, mode, V: int):
+    """The host checks of a `bag` call -> (ids int64 [n], offsets int64 [B + 1], weights f32 [n] or None), NumPy arrays for
+    the C call of include/vbq.h ("Pooled rows").  ids: 1-D with `offsets` [B] (bag starts, torch.nn.EmbeddingBag's convention:
+    the last bag runs to the end), or 2-D [B, L] without (row b is bag b); negative ids are padding in both forms.  ValueError
+    for an unknown mode, weights with a mode other than "sum", weights that are not finite or not shaped like ids, and offsets
+    that do not start at 0, decrease or exceed len(ids); IndexError for ids that are not integers or reach V."""
+    def host(a):
+        return np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+    if mode not in _BAG_MODES:
+        raise ValueError(f"mode {mode!r} is none of 'sum', 'mean', 'max'")
+    if weights is not None and mode != "sum":
+        raise ValueError(f"weights go with mode 'sum' only, not {mode!r}")
+    ids = host(ids)
+    if ids.ndim not in (1, 2):
+        raise ValueError(f"ids must be [n] (with offsets) or [B, L], got shape {ids.shape}")
+    if ids.size and ids.dtype.kind not in "iu":
+        raise IndexError(f"row ids must be integers, got {ids.dtype}")
+    if weights is not None:
+        weights = host(weights)
+        if weights.shape != ids.shape:
+            raise ValueError(f"weights {weights.shape} and ids {ids.shape} differ in shape")
+        weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if not np.isfinite(weights).all():
+            raise ValueError("weights hold a NaN or an infinity")
+    if ids.ndim == 2:
+        if offsets is not None:
+            raise ValueError("two-dimensional ids are one bag per row: offsets must be None")
+        offsets = np.arange(ids.shape[0] + 1, dtype=np.int64) * ids.shape[1]
+    else:
+        if offsets is None:
+            raise ValueError("one-dimensional ids need offsets (the bag starts)")
+        offsets = host(offsets)
+        if offsets.ndim != 1 or (offsets.size and offsets.dtype.kind not in "iu"):
+            raise ValueError(f"offsets must be one-dimensional integers, got shape {offsets.shape} of {offsets.dtype}")
+        offsets = np.concatenate([offsets.astype(np.int64), np.array([ids.size], np.int64)])
+        if offsets[0] != 0 or (np.diff(offsets) < 0).any():
+            raise ValueError(f"offsets must start at 0, never decrease and stay within len(ids) = {ids.size}")
+    ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    if ids.size and int(ids.max()) >= V:
+        raise IndexError(f"row {int(ids[ids >= V][0])} outside [0, {V}) (negative ids are padding)")
+    return ids, offsets, weights
+
+
+def _bag_call(call, device, args, mode, tail):
+    """Uploads of `args` (what _bag_args returned), the one launch `call(ids, offsets, weights=, mode=, status=)` and the look
+    at the status word -> f32 [B, *tail]."""
+    ids, offsets, weights = (None if a is None else torch.from_numpy(a).to(device) for a in args)
+    status = torch.zeros(1, dtype=torch.uint32, device=device)
+    out = call(ids, offsets, weights=weights, mode=mode, status=status)
+    assert int(status.cpu().item()) == 0, "ids and offsets checked on the host, records validated at load: no status bit is due"
+    return out.view((out.shape[0],) + tuple(tail))
+
+
+def bag(emb, ids, offsets=None, *, mode: str = "sum", weights=None):
+    """Pooled rows of the dense matrix `emb` ([V, K], tensor or ndarray): per bag the sum, mean or max of the rows its ids list
+    -> f32 device tensor [B, K], in one launch and without a [len(ids), K] matrix of the listed rows (vbq_bag_f32; the semantics
+    are those of include/vbq.h, "Pooled rows": additions in the order of the list, each rounded to f32).  `ids` is 1-D with
+    `offsets` [B] (bag starts as in torch.nn.EmbeddingBag: the last bag runs to the end) or 2-D [B, L] without; negative ids are
+    padding; `weights` (shaped like ids, finite) go with mode "sum" only.  IndexError for an id that is not an integer or
+    reaches V; ValueError for offsets that do not start at 0, decrease or exceed len(ids), for weights of another shape or with
+    another mode, and for an unknown mode.  A "VBQe" file is served as bag(CompressedEmbeddings(data).tensor(), ...), a "VBQr"
+    file without decoding it by RecordEmbeddings.bag, bit for bit the same.  One wave pools one bag: this is for many short
+    bags; a few very long bags run serially ("Pooled rows")."""
+    shape = tuple(int(d) for d in np.shape(emb))
+    if len(shape) != 2:
+        raise ValueError("emb must be [V, K]")
+    args = _bag_args(ids, offsets, weights, mode, shape[0])                         # the host checks need no device
+    e = _dev(emb)
+    return _bag_call(lambda *a, **kw: ops.bag(e, *a, **kw), e.device, args, mode, shape[1:])
+
+
 # ------------------------------------------------------------------------ fixed-size records (vbq_amd.bitstream, "VBQr")
 def _records_args(means, codepoints, N):
     """(code book f32 level-major [T] or [K, T], matrix shape, C) of a record file."""
@@ -590,3 +667,16 @@ class RecordEmbeddings:
         out = ops.records_topk(self._words, K, h.N, h.total_bits, self._table, q, k, metric, exclude, status=status)
         assert int(status.cpu().item()) == 0, "a record validated at load failed the unpack's checks"
         return out
+
+    def bag(self, ids, offsets=None, *, mode: str = "sum", weights=None):
+        """Pooled rows -> f32 device tensor [B, *shape[1:]]: per bag the sum, mean or max of the rows its ids list, as the
+        module's `bag` on tensor() bit for bit, but straight from the records in one launch: no [len(ids), K] float32 matrix is
+        written or read.  `ids` is 1-D with `offsets` [B] (bag starts as in torch.nn.EmbeddingBag: the last bag runs to the
+        end) or 2-D [B, L] without; negative ids are padding; `weights` (shaped like ids, finite) go with mode "sum" only.
+        IndexError for an id that is not an integer or reaches V; ValueError for bad offsets, weights or mode (the module's
+        `bag` lists them).  One wave pools one bag, entry by entry in the order given: this is for many short bags; a few very
+        long bags run serially.  Rows too long for the kernel's LDS (K above 16804 can be) raise VBQError naming the limit."""
+        h = self.header
+        args = _bag_args(ids, offsets, weights, mode, h.n_rows)
+        return _bag_call(lambda *a, **kw: ops.records_bag(self._words, h.row_length, h.N, h.total_bits, self._table, *a, **kw),
+                         self.device, args, mode, h.shape[1:])

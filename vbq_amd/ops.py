@@ -793,3 +793,63 @@ def topk(emb: torch.Tensor, queries: torch.Tensor, k: int = 10, metric="cosine",
     check(h.vbq_topk_f32(_ptr(emb), V, K, _ptr(queries), Q, k, metric, _ptr(exclude), E, _ptr(ids), _ptr(scores),
                          int(max_workgroups), _ptr(ws), ws.numel() * ws.element_size(), _stream(emb)), "vbq_topk_f32")
     return ids, scores
+
+
+_BAG_MODES = {"sum": 0, "mean": 1, "max": 2, 0: 0, 1: 1, 2: 2}
+BAG_BAD_ROW, BAG_BAD_OFFSETS = 8, 16             # status bits 3 and 4 of the bag calls (bits 0..2: RECORDS_UNPACK_STATUS)
+
+
+def _bag_args(ids, offsets, weights, mode, status, out, K, device):
+    """What records_bag and bag take alike -> (ids [n], offsets [B + 1], weights [n] or None, mode code, status, out [B, K])."""
+    ids = _dev(ids, torch.int64, "ids")
+    offsets = _dev(offsets, torch.int64, "offsets")
+    if ids.dim() != 1:
+        raise ValueError(f"ids must be one-dimensional, got shape {tuple(ids.shape)}")
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError(f"offsets must be [B + 1] (bag b is ids[offsets[b]:offsets[b + 1]]), got shape {tuple(offsets.shape)}")
+    if mode not in _BAG_MODES:
+        raise ValueError(f"mode {mode!r} is none of 'sum', 'mean', 'max'")
+    mode = _BAG_MODES[mode]
+    if weights is not None:
+        if mode != 0:
+            raise ValueError("weights go with mode 'sum' only")
+        weights = _dev(weights, torch.float32, "weights")
+        if weights.shape != ids.shape:
+            raise ValueError(f"weights {tuple(weights.shape)} and ids {tuple(ids.shape)} differ in shape")
+    if status is not None:
+        status = _dev(status, torch.uint32, "status")
+    return ids, offsets, weights, mode, status, _out(out, (offsets.numel() - 1, K), torch.float32, device, "out")
+
+
+def records_bag(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: torch.Tensor, ids: torch.Tensor,
+                offsets: torch.Tensor, *, weights: Optional[torch.Tensor] = None, mode="sum",
+                status: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vbq_records_bag_f32: per bag the sum, mean or max of the rows its ids list, straight from the records uint32
+    [V, record_words]: no [len(ids), K] matrix exists (semantics: include/vbq.h, "Pooled rows").  ids int64 [n]; offsets int64
+    [B + 1], bag b is ids[offsets[b]:offsets[b + 1]] in that order; weights f32 [n] with mode "sum" only.  Returns f32 [B, K].
+    A negative id is padding.  `status` (uint32 [1], zeroed by the caller) gets the unpack's bits 0..2 for a damaged record
+    (which counts as a row of zeros), bit 3 for an id >= V (skipped) and bit 4 for a bag whose offsets left [0, n] or ran
+    backwards (clamped).  One wave pools one bag: many short bags are the case this is for, a few very long ones run
+    serially."""
+    words = _dev(words, torch.uint32, "words")
+    K, N, total_bits = int(K), int(N), int(total_bits)
+    n_tables, table_sorted = _records_inputs(words, "V", K, N, total_bits, table_sorted)
+    ids, offsets, weights, mode, status, out = _bag_args(ids, offsets, weights, mode, status, out, K, words.device)
+    check(_lib.lib().vbq_records_bag_f32(_ptr(words), words.shape[0], K, N, total_bits, _ptr(table_sorted), n_tables, _ptr(ids),
+                                         ids.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(weights), mode, _ptr(out),
+                                         _ptr(status), _stream(words)), "vbq_records_bag_f32")
+    return out
+
+
+def bag(emb: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, *, weights: Optional[torch.Tensor] = None, mode="sum",
+        status: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vbq_bag_f32: records_bag on a dense f32 [V, K] matrix -- the same kernel with a dense row loader, the same result bit
+    for bit."""
+    emb = _dev(emb, torch.float32, "emb")
+    if emb.dim() != 2:
+        raise ValueError(f"emb must be [V, K], got shape {tuple(emb.shape)}")
+    V, K = emb.shape
+    ids, offsets, weights, mode, status, out = _bag_args(ids, offsets, weights, mode, status, out, K, emb.device)
+    check(_lib.lib().vbq_bag_f32(_ptr(emb), V, K, _ptr(ids), ids.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(weights), mode,
+                                 _ptr(out), _ptr(status), _stream(emb)), "vbq_bag_f32")
+    return out

@@ -22,6 +22,7 @@ before.  The choice is made once per (shape, settings, vae) and reported by `mod
 """
 from __future__ import annotations
 
+import gc
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -141,17 +142,28 @@ class CompressReplay:
             for _ in range(2):
                 _, reads = self._step()
         torch.cuda.current_stream(dev).wait_stream(side)
+        # A cyclic collection that starts while the stream is capturing runs the finalizers of whatever dead device objects it
+        # finds -- an earlier quantizer and its replays (they refer to each other), their graphs, page-locked buffers and
+        # streams -- and the runtime aborts the process on the calls those make in capture mode.  torch.cuda.graph no longer
+        # collects on entry: collect here, and keep the collector off until the capture has ended.
+        gc.collect()
         torch.cuda.synchronize(dev)
         # page-locked memory cannot be allocated while a stream is capturing: the landing buffers of the reads come first
         host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in reads]
         del reads
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            if mode == "full":
-                self._x_dev.copy_(self._x_host, non_blocking=True)               # the image's way to the device: a node as well
-            out, reads = self._step()
-            for h, t in zip(host, reads):                                        # the copies to the host are nodes of the graph too
-                h.copy_(t, non_blocking=True)
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                if mode == "full":
+                    self._x_dev.copy_(self._x_host, non_blocking=True)           # the image's way to the device: a node as well
+                out, reads = self._step()
+                for h, t in zip(host, reads):                                    # the copies to the host are nodes of the graph too
+                    h.copy_(t, non_blocking=True)
+        finally:
+            if collecting:
+                gc.enable()
         self.graph, self._out, self._dev_reads, self._host_reads = g, out, reads, host
         from .lazy import LazyArray
         stacks = {}
