@@ -605,6 +605,55 @@ int vbq_rans_il_decode_u16(const uint16_t *d_payload, int64_t n_words, const uin
                            uint32_t *d_status, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Class-mapped rANS: the segment coder above with a frequency table that may change from symbol to symbol -- the coder of
+ * the lambda-map latent file (vbq_amd/bitstream.py, magic "VBQm").  These three entry points were added without an ABI
+ * version bump: nothing that existed before changed.
+ *
+ * Format, constants and state updates are those of vbq_rans_encode_u16: every stream of n symbols is cut into segments of
+ * `seg` symbols, each an independent rANS stream (32-bit state, start state 2^16, 16-bit words, 15 probability bits) coded
+ * last symbol to first: a symbol of frequency f and exclusive cumulative frequency c first emits x & 0xffff and shifts
+ * x >>= 16 when x >= f << 17, then x = (x / f << 15) + x % f + c; after the first symbol the state goes out low half, then
+ * high half.  The decoder starts from those two words and reads backwards: slot = x & 32767, the symbol is the one with
+ * c <= slot < c + f, x = f (x >> 15) + slot - c, and x = x << 16 | word while x < 2^16.  What is new:
+ *   d_cls    u8 [n]                       one class per symbol POSITION, in [0, n_classes), shared by all streams
+ *   d_freq   u16 [n_classes][n_streams][T] the table of symbol i of stream s is row d_freq[d_cls[i]][s] (f and c above)
+ *   d_idx    u16 [n_planes][n_streams][n]  n_planes == n_classes: symbol i of stream s is d_idx[d_cls[i]][s][i] -- the
+ *            encoder reads straight from the [L][C][B] planes of a solve at n_classes lambdas, no select pass;
+ *            n_planes == 1: it is d_idx[0][s][i]
+ *   1 <= n_classes <= 4
+ * d_words u16 [n_streams][nseg][seg + 2] and d_sizes u32 [n_streams][nseg] have exactly the layout of vbq_rans_encode_u16
+ * (sizes in [2, seg + 2]), so vbq_rans_pack_u16 / vbq_rans_unpack_u16 serve unchanged; a segment whose symbols all have
+ * class p is word for word what vbq_rans_encode_u16 writes with row d_freq[p][s].  An index outside the table or a class
+ * outside [0, n_classes) is read safely by the encoder (as symbol 0 / class 0); the caller checks its map.
+ * vbq_rans_map_sizes_u16: the d_sizes of vbq_rans_map_encode_u16 for the same arguments, without the words.
+ * vbq_rans_map_decode_u16: words, sizes AND classes are UNTRUSTED.  d_status (u32, device, may be NULL; OR-ed into, zero it
+ *   first): bits 0 - 3 as vbq_rans_decode_u16 (bit 3: any of the n_classes rows of the stream), bit 6 (64) a class
+ *   >= n_classes in the segment -- it is compared before it selects any table.  Segments with bits 0 / 3 / 6 decode to
+ *   zeros; every index written to d_idx u16 [n_streams][n] is below T.
+ * Sizes, n_classes, n_planes and null pointers are checked before any device work (VBQ_ERR_INVALID_ARGUMENT); n == 0 or
+ * n_streams == 0 returns VBQ_OK and does nothing.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_map_encode_u16(const uint16_t *d_idx, int32_t n_planes, const uint8_t *d_cls, int32_t n_classes, int64_t n_streams,
+                            int64_t n, int32_t N, int32_t seg, const uint16_t *d_freq, uint16_t *d_words, uint32_t *d_sizes,
+                            void *stream);
+int vbq_rans_map_sizes_u16(const uint16_t *d_idx, int32_t n_planes, const uint8_t *d_cls, int32_t n_classes, int64_t n_streams,
+                           int64_t n, int32_t N, int32_t seg, const uint16_t *d_freq, uint32_t *d_sizes, void *stream);
+int vbq_rans_map_decode_u16(const uint16_t *d_words, const uint32_t *d_sizes, const uint8_t *d_cls, int32_t n_classes,
+                            int64_t n_streams, int64_t n, int32_t N, int32_t seg, const uint16_t *d_freq, uint16_t *d_idx,
+                            uint32_t *d_status, void *stream);
+/* The lambda-map latent file (magic "VBQm", version 1, every field little-endian): one latent tensor coded at up to four
+ * lambdas, a class per latent position saying which.
+ *   0   4      magic "VBQm"        4  1  version = 1     5  1  N (1..10)     6  1  ndim (>= 1)     7  1  P (1..4)
+ *   8   4      C (u32)             12 4  segment (u32, 1..65533)             16 8  n_words (u64)
+ *   24  8 P    the lambdas (f64, finite, distinct), class 0 first
+ *   ..  16 P   digests (blake2b-128 of the code points and frequencies of each lambda, as VBQb), same order
+ *   ..  8 ndim latent shape (u64 each, channel last: shape[-1] == C); B = prod(shape) / C positions
+ *   ..         class block: 2 bits per position, position b in byte b / 4 at bits 2 (b % 4) and 2 (b % 4) + 1; ceil(B / 4)
+ *              bytes, zero-padded to a multiple of 8 bytes; padding bits are zero and every class is < P
+ *   ..  2 C nseg  segment sizes (u16, each in [2, segment + 2]), stream-major (channel), as VBQb
+ *   ..  2 n_words payload, as VBQb: channel c is stream c, its symbol b coded with the table of (lambda[class[b]], c). */
+
+/* ----------------------------------------------------------------------------------
  * Packed counters for the histogram all-reduce: three 21-bit fields per int64 word.
  * An integer SUM all-reduce of the words adds the fields independently while every GLOBAL count is
  * below 2^21, at 2.67 instead of 4 bytes per bin on the wire.  n bins <-> (n + 2) / 3 words.

@@ -43,6 +43,10 @@ The header is a multiple of 8 bytes long, so the sizes and the payload can be vi
 with a specific message on anything malformed -- never struct.error or IndexError -- and check every size with vectorised
 NumPy before anything reaches the device (the kernels' own checks are the second line of defence).  `parse` rejects a compact
 file by its magic and `parse_compact` rejects a file in segments.
+
+A fifth format (magic b"VBQm", after the two latent files below) holds one latent tensor coded at SEVERAL lambdas: a palette
+of up to four and a class per latent position saying which one applies there (a lambda map: compress_latents_to_bytes_mapped;
+decompress_latents reads it by its magic).  write_mapped / parse_mapped / mapped_nbytes; `parse_latent` rejects it.
 """
 from __future__ import annotations
 
@@ -61,6 +65,7 @@ COMPACT_VERSION = 1
 MAX_N = 10                                   # the coder's limit (vbq_rans_encode_u16)
 MAX_SEGMENT = 65533                          # seg + 2 must fit in a u16 size
 MAX_PART = 1 << 24                           # the coder's limit (vbq_rans_il_encode_u16)
+MAX_CLASSES = 4                              # the coder's limit (vbq_rans_map_encode_u16); a class takes 2 bits in a VBQm file
 PART_STATE_WORDS = 128                       # the 64 lane states every part begins with
 _FIXED = struct.Struct("<4sBBBBIIdQ16s")     # the 48 bytes before the shape
 assert _FIXED.size == 48
@@ -315,6 +320,202 @@ def parse_latent(data):
     """What `parse_compact` returns for a compact file, and what `parse` returns -- or raises -- for everything else."""
     compact = bytes(memoryview(data).cast("B")[:4]) == COMPACT_MAGIC
     return _parse_latent(data, CompactHeader if compact else Header)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The lambda-map latent file: ONE latent tensor coded at up to four lambdas (ChannelwisePriorCDFQuantizer.
+# compress_latents_to_bytes_mapped).  A palette of P lambdas and a class per latent POSITION (the latent shape without its
+# channel axis, B = prod(shape) / C positions in row order, shared by the C channels): channel c is stream c in segments as in
+# a VBQb file, and its symbol b is coded with the frequency table of (lambda[class[b]], c) -- the class-mapped coder of
+# include/vbq.h (vbq_rans_map_encode_u16).  The decoder needs no lambda, only the tables; the digests say which.
+# Layout, every field little-endian (version 1):
+#
+#     offset  size      field
+#     0       4         magic b"VBQm"
+#     4       1         version = 1
+#     5       1         N = max_bits_per_coord (1..10)
+#     6       1         ndim of the latent shape (>= 1)
+#     7       1         P, the number of classes (1..4)
+#     8       4         C, the number of channels (u32)
+#     12      4         segment, symbols per rANS segment (u32, 1..65533)
+#     16      8         n_words, payload length in 16-bit words (u64)
+#     24      8 * P     the lambdas (f64, finite, distinct), class 0 first
+#     ...     16 * P    digests: `digest` of each lambda's tables, in the same order
+#     ...     8 * ndim  latent shape (u64 each, channel last: shape[-1] == C, every entry >= 1)
+#     ...               class block: 2 bits per position, position b in byte b // 4 at bits 2 (b % 4) and 2 (b % 4) + 1;
+#                       ceil(B / 4) bytes, zero-padded to a multiple of 8 bytes; padding bits are zero, every class < P
+#     ...     2*C*nseg  segment sizes (u16, each in [2, segment + 2]), nseg = ceil(B / segment), stream-major, as VBQb
+#     ...     2*n_words payload (u16), as VBQb; sum(sizes) == n_words
+#
+# `parse_mapped` raises ValueError with a specific message on anything malformed, never struct.error or IndexError, and checks
+# every class and size with vectorised NumPy before anything reaches the device.
+# ---------------------------------------------------------------------------------------------------------------------------
+MAPPED_MAGIC = b"VBQm"
+MAPPED_VERSION = 1
+_MAP_FIXED = struct.Struct("<4sBBBBIIQ")     # the 24 bytes before the lambdas
+assert _MAP_FIXED.size == 24
+_MAP_FOREIGN = {MAGIC: "a latent bitstream at one lambda (magic b'VBQb'), not a lambda-map file",
+                COMPACT_MAGIC: "a compact latent bitstream (magic b'VBQc'), not a lambda-map file"}
+
+
+def pack_classes(classes) -> bytes:
+    """Classes (integers in [0, 4), any shape, row order) -> the class block of a VBQm file, padding included."""
+    c = np.ascontiguousarray(classes).reshape(-1).astype(np.uint8)
+    B = c.size
+    q = np.zeros(4 * ((B + 3) // 4), dtype=np.uint8)
+    q[:B] = c
+    q = q.reshape(-1, 4)
+    block = (q[:, 0] | (q[:, 1] << 2) | (q[:, 2] << 4) | (q[:, 3] << 6)).astype(np.uint8).tobytes()
+    return block + bytes(-len(block) % 8)
+
+
+def unpack_classes(block, B: int) -> np.ndarray:
+    """The first B classes of a class block (bytes or a u8 array) -> u8 [B]."""
+    b = np.frombuffer(block, dtype=np.uint8, count=(B + 3) // 4)
+    return ((b[:, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(-1)[:B]
+
+
+@dataclass(frozen=True)
+class MappedHeader:
+    N: int
+    C: int
+    shape: Tuple[int, ...]
+    segment: int
+    lambs: Tuple[float, ...]
+    digests: Tuple[bytes, ...]
+    n_words: int
+
+    @property
+    def P(self) -> int:
+        return len(self.lambs)
+
+    @property
+    def n_rows(self) -> int:
+        """B: latent positions = symbols per stream."""
+        return math.prod(self.shape) // self.C
+
+    @property
+    def nseg(self) -> int:
+        return (self.n_rows + self.segment - 1) // self.segment
+
+    @property
+    def n_sizes(self) -> int:
+        return self.C * self.nseg
+
+    @property
+    def nbytes(self) -> int:
+        """Length of the header itself (where the class block starts)."""
+        return _MAP_FIXED.size + 24 * self.P + 8 * len(self.shape)
+
+    @property
+    def classes_nbytes(self) -> int:
+        """Length of the class block, padding included."""
+        return 8 * ((self.n_rows + 31) // 32)
+
+    @property
+    def sizes_offset(self) -> int:
+        return self.nbytes + self.classes_nbytes
+
+    @property
+    def sizes_nbytes(self) -> int:
+        return 2 * self.n_sizes
+
+    @property
+    def total_nbytes(self) -> int:
+        return self.sizes_offset + self.sizes_nbytes + 2 * self.n_words
+
+    def check(self):
+        if not 1 <= self.P <= MAX_CLASSES:
+            raise ValueError(f"P = {self.P} classes outside [1, {MAX_CLASSES}]")
+        if len(self.digests) != self.P:
+            raise ValueError(f"{len(self.digests)} digests for {self.P} lambdas")
+        # what a latent file at one lambda checks: N, C, the shape, the segment, a 16-byte digest, n_words -- per lambda
+        for lamb, dig in zip(self.lambs, self.digests):
+            Header(N=self.N, C=self.C, shape=self.shape, lamb=lamb, digest=dig, n_words=self.n_words, segment=self.segment).check()
+        if len(set(float(l) for l in self.lambs)) != self.P:
+            raise ValueError(f"repeated lambda in the palette {tuple(float(l) for l in self.lambs)}")
+
+
+def _mapped_header(h: MappedHeader) -> MappedHeader:
+    h = MappedHeader(N=int(h.N), C=int(h.C), shape=tuple(int(d) for d in h.shape), segment=int(h.segment),
+                     lambs=tuple(float(l) for l in h.lambs), digests=tuple(bytes(d) for d in h.digests), n_words=int(h.n_words))
+    h.check()
+    return h
+
+
+def _check_classes(classes: np.ndarray, P: int):
+    """classes: u8, any shape.  ValueError naming the first position whose class is >= P."""
+    wrong = classes >= P
+    if wrong.any():
+        bad = int(np.flatnonzero(wrong)[0])
+        raise ValueError(f"class {int(classes.reshape(-1)[bad])} at position {bad} is not below P = {P}")
+
+
+def write_mapped(header: MappedHeader, classes, sizes, payload) -> bytes:
+    """header + classes (integers in [0, P), B of them in any shape) + sizes (any integer array of C * nseg entries) + payload
+    (u16 [n_words]) -> bytes.  Validates as `parse_mapped` does."""
+    h = _mapped_header(header)
+    classes = np.asarray(classes)
+    if classes.dtype.kind not in "iu":
+        raise ValueError(f"classes must be integers, got {classes.dtype}")
+    classes = classes.reshape(-1)
+    if classes.size != h.n_rows:
+        raise ValueError(f"{classes.size} classes, the shape has {h.n_rows} positions")
+    if classes.size and int(classes.min()) < 0:
+        raise ValueError(f"negative class {int(classes.min())}")
+    _check_classes(np.minimum(classes, 255).astype(np.uint8), h.P)
+    sizes = _flat_sizes(sizes, h.n_sizes, "segment")
+    _check_sizes(sizes, "segment", 2, h.segment + 2, h.n_words)
+    payload = _checked_payload(payload, h.n_words)
+    head = _MAP_FIXED.pack(MAPPED_MAGIC, MAPPED_VERSION, h.N, len(h.shape), h.P, h.C, h.segment, h.n_words)
+    return b"".join([head, np.asarray(h.lambs, dtype="<f8").tobytes(), b"".join(h.digests), np.asarray(h.shape, dtype="<u8").tobytes(),
+                     pack_classes(classes), sizes.astype("<u2").tobytes(), payload.tobytes()])
+
+
+def mapped_nbytes(shape, C, segment, n_words, P) -> int:
+    """len(write_mapped(...)) of a latent tensor of `shape` (channel-last, C channels) with a palette of P lambdas, in segments
+    of `segment` symbols and a payload of n_words 16-bit words, without building the file.  ValueError for fields
+    `write_mapped` rejects."""
+    P = int(P)
+    if not 1 <= P <= MAX_CLASSES:
+        raise ValueError(f"P = {P} classes outside [1, {MAX_CLASSES}]")
+    return _mapped_header(MappedHeader(N=MAX_N, C=C, shape=shape, segment=segment, lambs=tuple(float(p) for p in range(P)),
+                                       digests=(bytes(16),) * P, n_words=n_words)).total_nbytes
+
+
+def parse_mapped(data) -> Tuple[MappedHeader, np.ndarray, np.ndarray, int]:
+    """bytes -> (header, classes u8 [B], sizes u16 [C * nseg] (a read-only view into `data`), byte offset of the payload).
+    ValueError on anything malformed."""
+    mv = memoryview(data).cast("B")
+    magic, version, N, ndim, P, C, segment, n_words = _unpack_fixed(mv, _MAP_FIXED)
+    if magic != MAPPED_MAGIC:
+        raise ValueError(_MAP_FOREIGN.get(magic) or f"not a VBQ lambda-map bitstream (magic {magic!r})")
+    if version != MAPPED_VERSION:
+        raise ValueError(f"unknown lambda-map bitstream version {version}")
+    if not 1 <= P <= MAX_CLASSES:
+        raise ValueError(f"P = {P} classes outside [1, {MAX_CLASSES}]")
+    if ndim < 1:
+        raise ValueError("latent shape with 0 dimensions")
+    hlen = _MAP_FIXED.size + 24 * P + 8 * ndim
+    if len(mv) < hlen:
+        raise ValueError(f"truncated in the palette or the latent shape: {len(mv)} bytes, the header is {hlen}")
+    lambs = tuple(float(l) for l in np.frombuffer(mv, dtype="<f8", count=P, offset=_MAP_FIXED.size))
+    d0 = _MAP_FIXED.size + 8 * P
+    digests = tuple(bytes(mv[d0 + 16 * p: d0 + 16 * p + 16]) for p in range(P))
+    shape = tuple(int(d) for d in np.frombuffer(mv, dtype="<u8", count=ndim, offset=d0 + 16 * P))
+    h = MappedHeader(N=N, C=C, shape=shape, segment=segment, lambs=lambs, digests=digests, n_words=n_words)
+    h.check()
+    _check_length(len(mv), h.total_nbytes, f"header, {h.n_rows} classes, {h.n_sizes} segment sizes and {n_words} payload words")
+    B = h.n_rows
+    block = np.frombuffer(mv, dtype=np.uint8, count=h.classes_nbytes, offset=h.nbytes)
+    quads = (block[:, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3          # every 2-bit field, padding included
+    if quads.reshape(-1)[B:].any():
+        raise ValueError("padding bits after the classes are not zero")
+    classes = quads.reshape(-1)[:B]
+    _check_classes(classes, P)
+    sizes = np.frombuffer(mv, dtype="<u2", count=h.n_sizes, offset=h.sizes_offset)
+    _check_sizes(sizes, "segment", 2, segment + 2, n_words)
+    return h, classes, sizes, h.sizes_offset + h.sizes_nbytes
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

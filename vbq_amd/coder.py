@@ -6,6 +6,8 @@ histograms into integer frequency tables and the indices into a bitstream, and d
 Format: include/vbq.h (vbq_rans_encode_u16).  Nothing here changes the quantization path.
 pack_device / unpack_device / encode_packed / decode_packed turn the padded per-segment layout into the contiguous payload of
 a compressed file (vbq_amd.bitstream) and back on the device (vbq_rans_pack_u16 / vbq_rans_unpack_u16).
+MappedRansCodec is the same segment coder with a table per symbol: a class map picks one of up to four tables at every
+position (vbq_rans_map_*_u16; the lambda map of a VBQm file).
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .bitstream import MAX_PART, check_part  # the format's limits live with the format
+from .bitstream import MAX_CLASSES, MAX_PART, check_part  # the format's limits live with the format
 
 PROB_BITS = 15
 DEFAULT_SEGMENT = 1024
@@ -109,12 +111,13 @@ def ideal_bits(counts, freq, prob_bits: int = PROB_BITS) -> float:
 
 
 def _raise_status(st: int):
-    """The OR-ed status word of vbq_rans_decode_u16 / vbq_rans_unpack_u16 -> VBQError (nothing when 0)."""
+    """The OR-ed status word of vbq_rans_decode_u16 / vbq_rans_unpack_u16 / vbq_rans_map_decode_u16 -> VBQError (nothing
+    when 0)."""
     if st:
         what = [m for b, m in ((1, "segment size out of range"), (2, "segment ran out of words"),
                                (4, "left-over words / wrong final state"), (8, "invalid frequency table"),
                                (16, "segment sizes do not add up to the payload length"),
-                               (32, "segment id out of range")) if st & b]
+                               (32, "segment id out of range"), (64, "class outside the palette")) if st & b]
         raise _lib.VBQError("rANS bitstream rejected: " + ", ".join(what))
 
 
@@ -136,6 +139,11 @@ class RansCodec:
             raise ValueError("every frequency row must be >= 1 and sum to 2**15")
         self.N, self.segment, self.T = N, None if segment is None else int(segment), T
         self._freq_dev: Optional[torch.Tensor] = None
+
+    @property
+    def n_streams(self) -> int:
+        """Streams of one encode / decode call: one per frequency row."""
+        return self.freq_host.shape[0]
 
     def _freq(self, device):
         if self._freq_dev is None or self._freq_dev.device != device:
@@ -160,7 +168,7 @@ class RansCodec:
     def _decoded(self, device, n: int, launch) -> torch.Tensor:
         """The tail of every decode: idx u16 [S, n] and a zeroed status word, launch(idx, status) -- one or more launches
         that OR their flags into the word --, then ONE synchronisation to read it; VBQError when a flag is set."""
-        idx = torch.empty((self.freq_host.shape[0], n), dtype=torch.uint16, device=device)
+        idx = torch.empty((self.n_streams, n), dtype=torch.uint16, device=device)
         status = torch.zeros(1, dtype=torch.uint32, device=device)
         launch(idx, status)
         _raise_status(int(status.cpu().item()))
@@ -232,7 +240,7 @@ class RansCodec:
         sizes u32 [S, nseg], status u32 [1]) in the layout `decode` reads.  Nothing is checked on the host here."""
         payload = ops._dev(payload, torch.uint16, "payload")
         sizes = ops._dev(sizes, torch.uint16, "sizes")
-        S = self.freq_host.shape[0]
+        S = self.n_streams
         nseg = self._nseg(n)
         if sizes.numel() != S * nseg:
             raise ValueError(f"expected {S * nseg} segment sizes for {S} streams of {n} symbols, got {sizes.numel()}")
@@ -335,3 +343,126 @@ class RansCodec:
         sz = sizes.cpu().numpy().astype(np.int64)
         keep = np.arange(w.shape[-1])[None, None, :] < sz[..., None]
         return w[keep].tobytes()
+
+
+
+class MappedRansCodec(RansCodec):
+    """The segment coder with a table per symbol (vbq_rans_map_*_u16, include/vbq.h "Class-mapped rANS"): freq u16 [P, S, T],
+    1 <= P <= 4, and a class map cls [n] with values in [0, P), shared by the S streams -- symbol i of stream s is coded with
+    freq[cls[i], s].  Words and sizes have the layout of RansCodec, so its pack / unpack calls serve unchanged."""
+
+    def __init__(self, freq, N: int = 10, segment: int = DEFAULT_SEGMENT):
+        f = freq if isinstance(freq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(freq, dtype=np.uint16)))
+        if f.dim() != 3 or not 1 <= f.shape[0] <= MAX_CLASSES or f.shape[2] != ops.table_size(N):
+            raise ValueError(f"freq must be [P, S, {ops.table_size(N)}] with 1 <= P <= {MAX_CLASSES}, got {tuple(f.shape)}")
+        super().__init__(f, N=N, segment=int(segment))                   # (rows checked there; freq_host is [P * S, T])
+        self.P, self.S = int(f.shape[0]), int(f.shape[1])
+
+    @property
+    def n_streams(self) -> int:
+        return self.S
+
+    def _parts(self, n_symbols, part):
+        raise ValueError("the class-mapped coder has no interleaved layout")
+
+    def _classes(self, cls, n: int, device, check: bool) -> torch.Tensor:
+        """cls as u8 [n] on the device.  check: ValueError for a class outside [0, P) (the encoder's side; the decoder's
+        classes are untrusted and checked in the kernel)."""
+        if not isinstance(cls, torch.Tensor):
+            cls = torch.from_numpy(np.array(cls))                        # (a copy: the array may be read-only)
+        if cls.dtype.is_floating_point or cls.dtype == torch.bool:
+            raise ValueError(f"classes must be integers, got {cls.dtype}")
+        cls = cls.reshape(-1)
+        if cls.numel() != n:
+            raise ValueError(f"{cls.numel()} classes for {n} symbols per stream")
+        if check and n:                                                  # where the classes are: a host array costs no sync
+            lo, hi = torch.aminmax(cls.to(torch.int64))
+            if int(lo) < 0 or int(hi) >= self.P:
+                raise ValueError(f"class outside [0, {self.P})")
+        cls = cls.to(device)
+        if cls.dtype != torch.uint8:                                     # (no wrap-around into the palette: the kernel rejects 255)
+            cls = cls.to(torch.int64)
+            cls = torch.where((cls < 0) | (cls > 255), 255, cls)
+        return cls.to(torch.uint8).contiguous()
+
+    def _planes(self, idx):
+        """The checked index tensor [P, S, n] or [S, n] -> (idx, n_planes, n, nseg)."""
+        idx = ops._dev(idx, torch.uint16, "idx")
+        n = idx.shape[-1]
+        if tuple(idx.shape) == (self.P, self.S, n) and idx.dim() == 3:
+            planes = self.P
+        elif tuple(idx.shape) == (self.S, n):
+            planes = 1
+        else:
+            raise ValueError(f"idx must be [{self.P}, {self.S}, n] or [{self.S}, n], got {tuple(idx.shape)}")
+        return idx, planes, n, self._nseg(n)
+
+    def _map_encode(self, idx, planes, cls, n, words, sizes):
+        check(_lib.lib().vbq_rans_map_encode_u16(ops._ptr(idx), planes, ops._ptr(cls), self.P, self.S, n, self.N, self.segment,
+                                                 ops._ptr(self._freq(idx.device)), ops._ptr(words), ops._ptr(sizes),
+                                                 ops._stream(idx)), "vbq_rans_map_encode_u16")
+
+    def _map_decode(self, words, sizes, cls, n, idx, status):
+        check(_lib.lib().vbq_rans_map_decode_u16(ops._ptr(words), ops._ptr(sizes), ops._ptr(cls), self.P, self.S, n, self.N,
+                                                 self.segment, ops._ptr(self._freq(idx.device)), ops._ptr(idx), ops._ptr(status),
+                                                 ops._stream(idx)), "vbq_rans_map_decode_u16")
+
+    def encode(self, idx, cls) -> Tuple[torch.Tensor, torch.Tensor]:
+        """idx u16 [P, S, n] (plane p holds the symbols of class p: the encoder picks idx[cls[i], s, i]) or [S, n] (already
+        selected); cls [n] integers in [0, P).  -> (words u16 [S, nseg, segment+2], sizes u32 [S, nseg])."""
+        idx, planes, n, nseg = self._planes(idx)
+        cls = self._classes(cls, n, idx.device, check=True)
+        words = torch.zeros((self.S, nseg, self.segment + 2), dtype=torch.uint16, device=idx.device)
+        sizes = torch.zeros((self.S, nseg), dtype=torch.uint32, device=idx.device)
+        self._map_encode(idx, planes, cls, n, words, sizes)
+        return words, sizes
+
+    def sizes(self, idx, cls) -> torch.Tensor:
+        """The sizes `encode` returns, without the words (vbq_rans_map_sizes_u16)."""
+        idx, planes, n, nseg = self._planes(idx)
+        cls = self._classes(cls, n, idx.device, check=True)
+        sizes = torch.zeros((self.S, nseg), dtype=torch.uint32, device=idx.device)
+        check(_lib.lib().vbq_rans_map_sizes_u16(ops._ptr(idx), planes, ops._ptr(cls), self.P, self.S, n, self.N, self.segment,
+                                                ops._ptr(self._freq(idx.device)), ops._ptr(sizes), ops._stream(idx)),
+              "vbq_rans_map_sizes_u16")
+        return sizes
+
+    def decode(self, words, sizes, cls, n: int) -> torch.Tensor:
+        """words, sizes and cls are untrusted: shapes are checked here, everything else in the kernel (a class >= P included);
+        a damaged stream raises VBQError.  -> u16 indices [S, n]."""
+        words = ops._dev(words, torch.uint16, "words")
+        sizes = ops._dev(sizes, torch.uint32, "sizes")
+        n = int(n)
+        nseg = self._nseg(n)
+        if words.numel() != self.S * nseg * (self.segment + 2) or sizes.numel() != self.S * nseg:
+            raise ValueError(f"expected words [{self.S}, {nseg}, {self.segment + 2}] and sizes [{self.S}, {nseg}] for {n} symbols "
+                             f"per stream, got {tuple(words.shape)} and {tuple(sizes.shape)}")
+        cls = self._classes(cls, n, words.device, check=False)
+        return self._decoded(words.device, n, lambda idx, status: self._map_decode(words, sizes, cls, n, idx, status))
+
+    def encode_packed(self, idx, cls) -> Tuple[np.ndarray, np.ndarray]:
+        """encode + vbq_rans_pack_u16 on the device -> (sizes u32 [S, nseg], payload u16 [total]) on the host, in two
+        device-to-host copies, as RansCodec.encode_packed."""
+        idx, planes, n, nseg = self._planes(idx)
+        cls = self._classes(cls, n, idx.device, check=True)
+        dev, S = idx.device, self.S
+        words = torch.empty((S, nseg, self.segment + 2), dtype=torch.uint16, device=dev)    # pack reads valid words only
+        aux = torch.empty(8 + 4 * S * nseg, dtype=torch.uint8, device=dev)                  # total u64, then sizes u32
+        total, sizes = aux[:8].view(torch.uint64), aux[8:].view(torch.uint32).view(S, nseg)
+        payload = torch.empty(S * nseg * (self.segment + 2), dtype=torch.uint16, device=dev)
+        offsets = torch.empty((S, nseg), dtype=torch.int64, device=dev)
+        self._map_encode(idx, planes, cls, n, words, sizes)
+        self._pack(words, sizes, payload, offsets, total)
+        h = aux.cpu().numpy()
+        n_words = int(h[:8].view(np.uint64)[0])
+        return h[8:].view(np.uint32).reshape(S, nseg), payload[:n_words].cpu().numpy()
+
+    def decode_packed(self, payload, sizes, cls, n: int) -> torch.Tensor:
+        """vbq_rans_unpack_u16 + the mapped decoder, one status word for both: u16 indices [S, n]."""
+        n = int(n)
+        cls = self._classes(cls, n, payload.device, check=False)
+
+        def launch(idx, status):
+            words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
+            self._map_decode(words, out_sizes, cls, n, idx, status)
+        return self._decoded(payload.device, n, launch)

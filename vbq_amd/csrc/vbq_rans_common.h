@@ -1,7 +1,8 @@
-// What the two rANS coders share -- vbq_rans.hip (segments, one lane per segment) and vbq_rans_il.hip (parts, the 64 lanes of a
-// wave together): the coder's constants and the per-symbol state updates of the encoder and of the decoder.  32-bit state,
-// start state 2^16, 16-bit renormalisation words, 15 probability bits; format: include/vbq.h.  How the tables reach LDS is
-// each kernel's own business (the three staging routines map lanes to symbols differently).
+// What the rANS coders share -- vbq_rans.hip (segments, one lane per segment), vbq_rans_map.hip (the same with a table per
+// symbol) and vbq_rans_il.hip (parts, the 64 lanes of a wave together): the coder's constants and the per-symbol state updates
+// of the encoder and of the decoder.  32-bit state, start state 2^16, 16-bit renormalisation words, 15 probability bits;
+// format: include/vbq.h.  How the tables reach LDS is each kernel's own business (the staging routines map lanes to symbols
+// differently).
 #pragma once
 #include "vbq_common.h"
 
@@ -37,6 +38,18 @@ __device__ __forceinline__ unsigned rans_pop(unsigned &x, const uint16_t *start,
     while (c_l[sym + 1] <= slot) ++sym;                          // c_l[T] = 2^15 > slot ends the walk below T
     const unsigned fc = fc_l[sym];
     x = (fc & 0xffffu) * (x >> kPB) + slot - (fc >> 16);
+    return sym;
+}
+
+// The same step without the fc table: f = c[sym + 1] - c[sym], for a decoder that keeps several tables in LDS at once
+// (vbq_rans_map.hip) and has no room for a third array per table.
+__device__ __forceinline__ unsigned rans_pop(unsigned &x, const uint16_t *start, const uint16_t *c_l) {
+    const unsigned slot = x & ((1u << kPB) - 1u);
+    unsigned sym = start[slot >> 4];
+    unsigned c1 = c_l[sym + 1];
+    while (c1 <= slot) c1 = c_l[++sym + 1];
+    const unsigned c0 = c_l[sym];
+    x = (c1 - c0) * (x >> kPB) + slot - c0;
     return sym;
 }
 

@@ -731,8 +731,11 @@ class ChannelwisePriorCDFQuantizer:
         """Inverse of compress_latents_to_bytes: Z_hat shaped like the latents (NumPy, or a device tensor with
         return_np=False), bit-identical to compress_latents(...)["Z_hat"][lamb].  ValueError for a malformed header or
         a stream made with another quantizer / entropy model (digest), KeyError for a lambda this quantizer has no
-        model for, VBQError for a damaged payload."""
+        model for, VBQError for a damaged payload.  A lambda-map file (magic b"VBQm", compress_latents_to_bytes_mapped) is
+        read by its magic: bit-identical to compress_latents_mapped(...)["Z_hat"]."""
         self._check_coder_bits()
+        if bytes(memoryview(data).cast("B")[:4]) == bitstream.MAPPED_MAGIC:
+            return self._decompress_latents_mapped(data, return_np)
         h, _, _ = bitstream.parse_latent(data)
         lay = next(l for l in _LAYOUTS.values() if l.header is type(h))
         if h.N != self.max_bits_per_coord or h.C != self.num_channels:
@@ -753,6 +756,109 @@ class ChannelwisePriorCDFQuantizer:
         """`vae.encode(X)`, then compress_latents_to_bytes."""
         posterior_means, posterior_logvars = vae.encode(X)
         return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment, layout=layout, part=part)
+
+    # ------------------------------------------------------------------ lambda maps (vbq_amd.bitstream, magic b"VBQm")
+    # A palette `lambs` of 1..4 distinct built lambdas and `classes`, integers in [0, P) shaped like the latents without the
+    # channel axis: position b of every channel is quantized and coded at lambs[classes[b]].  The solve is independent per
+    # latent and the decoder never needs lambda, so the result at (b, c) is exactly what compress_latents gives there for that
+    # lambda; the coder switches the frequency table from symbol to symbol (coder.MappedRansCodec).
+    def _map_inputs(self, posterior_means, lambs, classes):
+        """(palette keys, classes as a NumPy u8 array [B]); ValueError for P outside 1..4, a repeated lambda, classes of the
+        wrong shape or dtype or outside [0, P); KeyError for a lambda without a model."""
+        lambs = list(lambs)
+        if not 1 <= len(lambs) <= bitstream.MAX_CLASSES:
+            raise ValueError(f"a palette of {len(lambs)} lambdas: need 1..{bitstream.MAX_CLASSES}")
+        keys = [self._lambda_key(l) for l in lambs]
+        if len(set(float(k) for k in keys)) != len(keys):
+            raise ValueError(f"repeated lambda in the palette {lambs}")
+        shape = tuple(int(d) for d in np.shape(posterior_means))
+        cls = _to_numpy(classes)
+        if cls.dtype.kind not in "iu":
+            raise ValueError(f"classes must be integers, got {cls.dtype}")
+        if tuple(cls.shape) != shape[:-1]:
+            raise ValueError(f"classes of shape {tuple(cls.shape)}: the latents {shape} need {shape[:-1]}")
+        if cls.size and (int(cls.min()) < 0 or int(cls.max()) >= len(keys)):
+            raise ValueError(f"class outside [0, {len(keys)}): the palette has {len(keys)} lambdas")
+        return keys, np.ascontiguousarray(cls.reshape(-1).astype(np.uint8))
+
+    def _mapped_codec(self, keys, segment):
+        """(MappedRansCodec over the tables of `keys`, their digests), cached as _coder_stack caches its codecs."""
+        from .coder import MappedRansCodec
+        digests = tuple(self._coder_tables(k, segment)[1] for k in keys)                       # refreshes the per-lambda cache
+        per = self._dev_cache["_coder_tables"][2]
+        hit = self._dev_cache.get("_coder_maps")
+        if hit is None or hit[0] is not self._code_counts or hit[1] != self._add_n_smoothing:
+            hit = self._dev_cache["_coder_maps"] = (self._code_counts, self._add_n_smoothing, {})
+        codecs = hit[2]
+        tag = (tuple(float(k) for k in keys), segment)
+        codec = codecs.get(tag)
+        if codec is None:
+            if len(codecs) >= 8:
+                codecs.clear()
+            codec = codecs[tag] = MappedRansCodec(np.stack([per[k]["freq"] for k in keys]), N=self.max_bits_per_coord,
+                                                  segment=segment)
+        return codec, digests
+
+    def compress_latents_mapped(self, posterior_means, posterior_logvars, lambs, classes, return_np=True):
+        """{"Z_hat", "num_bits"} shaped like the latents: at position b, channel c exactly compress_latents(posterior_means,
+        posterior_logvars, lambs)[...][lambs[classes[b]]] there -- one solve of the palette, then a per-position selection."""
+        keys, cls = self._map_inputs(posterior_means, lambs, classes)
+        shape = tuple(int(d) for d in np.shape(posterior_means))
+        out = self.compress_latents(posterior_means, posterior_logvars, keys, return_np=False)
+        pick = torch.from_numpy(cls).to(self.device, torch.int64).reshape((1,) + shape[:-1] + (1,)).expand((1,) + shape)
+        res = {name: torch.gather(torch.stack([out[name][k] for k in keys]), 0, pick)[0] for name in ("Z_hat", "num_bits")}
+        return {name: t.cpu().numpy() for name, t in res.items()} if return_np else res
+
+    def _mapped_file_inputs(self, posterior_means, posterior_logvars, lambs, classes, segment):
+        self._check_coder_bits()
+        keys, cls = self._map_inputs(posterior_means, lambs, classes)
+        shape, _, segment = self._file_layout(posterior_means, posterior_logvars, "segments", segment, None)
+        codec, digests = self._mapped_codec(keys, segment)
+        idx = self._file_indices(posterior_means, posterior_logvars, keys)                     # [P, C, B]
+        return keys, cls, shape, segment, codec, digests, idx
+
+    def compress_latents_to_bytes_mapped(self, posterior_means, posterior_logvars, lambs, classes, segment=1024) -> bytes:
+        """compress_latents_mapped, entropy-coded into a self-describing byte string (vbq_amd.bitstream, magic b"VBQm").  One
+        solve of the palette (the indices of compress_latents_to_bytes at each lambda); the mapped encoder reads symbol b of
+        channel c straight out of plane classes[b] of that result with the table of (lambs[classes[b]], c); pack; two
+        device-to-host copies.  decompress_latents reads the file.  ValueError for a palette outside 1..4 lambdas or with a
+        repeat and for classes of the wrong shape or outside [0, P); KeyError for a lambda without a model."""
+        keys, cls, shape, segment, codec, digests, idx = self._mapped_file_inputs(posterior_means, posterior_logvars, lambs,
+                                                                                  classes, segment)
+        sizes, payload = codec.encode_packed(idx, cls)
+        h = bitstream.MappedHeader(N=self.max_bits_per_coord, C=self.num_channels, shape=shape, segment=segment,
+                                   lambs=tuple(float(k) for k in keys), digests=digests, n_words=int(payload.size))
+        return bitstream.write_mapped(h, cls, sizes, payload)
+
+    def coded_nbytes_mapped(self, posterior_means, posterior_logvars, lambs, classes, segment=1024) -> int:
+        """len(compress_latents_to_bytes_mapped(...)) for the same arguments, exact, without building the file: the solve,
+        one vbq_rans_map_sizes_u16 launch (segment sizes only, no words), one copy of their total."""
+        keys, cls, shape, segment, codec, _, idx = self._mapped_file_inputs(posterior_means, posterior_logvars, lambs, classes,
+                                                                            segment)
+        n_words = int(codec.sizes(idx, cls).view(torch.int32).sum(dtype=torch.int64).item())
+        return bitstream.mapped_nbytes(shape, self.num_channels, segment, n_words, len(keys))
+
+    def compress_to_bytes_mapped(self, X, vae, lambs, classes, segment=1024) -> bytes:
+        """`vae.encode(X)`, then compress_latents_to_bytes_mapped; `classes` is at latent resolution."""
+        posterior_means, posterior_logvars = vae.encode(X)
+        return self.compress_latents_to_bytes_mapped(posterior_means, posterior_logvars, lambs, classes, segment=segment)
+
+    def _decompress_latents_mapped(self, data, return_np):
+        """decompress_latents of a lambda-map file: the digest of every class, the mapped decoder, the gather."""
+        h, classes, _, _ = bitstream.parse_mapped(data)
+        if h.N != self.max_bits_per_coord or h.C != self.num_channels:
+            raise ValueError(f"stream is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
+                             f"C = {self.num_channels}")
+        keys = [self._lambda_key(l) for l in h.lambs]
+        codec, digests = self._mapped_codec(keys, h.segment)
+        if digests != h.digests:
+            raise ValueError("stream was compressed with a different quantizer or entropy model (digest mismatch)")
+        tail = np.frombuffer(memoryview(data).cast("B"), dtype="<u2", count=h.n_sizes + h.n_words, offset=h.sizes_offset)
+        buf = torch.from_numpy(tail.copy()).to(self.device)                                 # sizes, then payload: one upload
+        idx = codec.decode_packed(buf[h.n_sizes:], buf[: h.n_sizes], classes, h.n_rows)
+        zhat = ops.gather(idx[None], self._sorted_dev(), self.num_channels, N=self.max_bits_per_coord, layout="cb",
+                          out_layout="bc").reshape(h.shape)
+        return zhat.cpu().numpy() if return_np else zhat
 
     # ------------------------------------------------------------------ rate control: exact lengths, byte budgets
     def _rate_keys(self, lambs):
