@@ -1,0 +1,177 @@
+"""The launch rules of the older kernels stated a second time, as pure functions of the shape and the CU count: which kernel a
+call takes, how many workgroups it gets and how each workgroup walks its share.  tests/test_gpu_large_paths.py picks its shapes
+with them and asserts, before every launch, that the shape reaches the path the test is named after;
+tests/test_launch_plans_host.py reads the constants below out of the .hip sources, so that retuning one of them says which
+shapes have to move.
+
+    lookup_plan     lookup_lds_passes / k_lookup_lds                    vbq_amd/csrc/vbq_latents.hip
+    rank_plan       vbq_analogy_ranks_f32 / k_rank_gemm                 vbq_amd/csrc/vbq_ranks.hip
+    *_grid          vbq_moments_f32, vbq_rd_sums_u16, vbq_index_max_u16, vbq_check_inputs_f32, launch_hist (k_hist_tiled)
+                                                                        vbq_amd/csrc/vbq_hist.hip
+"""
+from collections import namedtuple
+
+# ---- vbq_latents.hip
+LDS_MIN_LOOKUPS_Z = 9 << 14      # kLdsMinLookupsZ: lambdas x rows from which Z_hat comes out of the LDS
+LDS_MIN_LOOKUPS_NB = 3 << 10     # kLdsMinLookupsNb: rows from which num_bits comes out of the LDS
+LDS_ROWS = 256                   # kLdsRows: rows per block
+LDS_AHEAD = 2                    # VBQ_LDS_AHEAD: blocks per iteration of the pipelined loop
+LDS_CH = 16                      # kLdsCh: channel tables per workgroup
+LDS_MAX_N = 10                   # `if constexpr (N > 10)`: larger tables do not fit
+LDS_RENUMBER = 16                # `(gridDim.x & 15) == 0`: channel groups are renumbered in blocks of 16
+# ---- vbq_ranks.hip
+RANK_BM = 128                    # kBM: questions per tile
+RANK_BN = 128                    # kBN: words per tile
+RANK_BK = 32                     # VBQ_RANK_BK: k per LDS stage
+RANK_WGS = 2                     # VBQ_RANK_WGS: workgroups per CU
+RANK_MAX_SPLITS = 256            # `s <= 256` of the best_s loop
+# ---- vbq_hist.hip
+MOMENTS_FLAT_WGS = 2048          # cap = 2048 / n_ch + 1 workgroups per channel
+MOMENTS_FLAT_LOADS = 4           # 16-byte loads in flight per lane in the main loop
+MOMENTS_BC_WGS = 2048            # `if (gx > 2048) gx = 2048`
+MOMENTS_BC_PER_THREAD = 16       # gx = ceil(E / (256 * 16))
+MOMENTS_MAX_CH = 4096            # n_ch <= 4096
+SCAN_WGS = 4096                  # `if (gx > 4096) gx = 4096` of index_max and check_inputs
+RD_WGS_PER_CU = 8                # cap = num_cus() * 8 / chunks + 1
+RD_CHUNK = 8                     # kRdChunk: lambdas per workgroup
+HIST_TILED_WGS = 512             # gx = 512 / (groups * L) + 1
+HIST_TILED_ROWS = 64             # rows per pass of a k_hist_tiled workgroup (1024 threads / 16 channels)
+HIST_TILE_CH = 16                # kTileChannels
+THREADS = 256                    # workgroup size of the reductions and scans
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+# ---------------------------------------------------------------------------------------------------------------- lookups
+Walk = namedtuple("Walk", "pipelined rest last_rows")
+"""How one workgroup walks `rows` rows of one lambda: iterations of the pipelined loop (LDS_AHEAD whole blocks each, FULL),
+blocks of the ragged-rest loop, rows of the last of them (LDS_ROWS when it is whole)."""
+
+LookupPlan = namedtuple("LookupPlan", "eligible z_lds nb_lds groups renumbered last_group_channels splits per last_split_rows")
+
+
+def walk(rows, whole_group=True):
+    it = rows // (LDS_AHEAD * LDS_ROWS) if whole_group else 0
+    left = rows - it * LDS_AHEAD * LDS_ROWS
+    rest = cdiv(left, LDS_ROWS)
+    last = left - (rest - 1) * LDS_ROWS if rest else 0
+    return Walk(it, rest, last)
+
+
+def lookup_plan(L, C, B, N, cus, want_zhat=True, want_num_bits=True):
+    """lookup_lds_passes: which of Z_hat / num_bits leave the generic kernel, and the grid of the sorted-table pass (channel
+    groups x row splits of `per` rows, the last one shorter).  The num_bits pass is groups x L workgroups of all B rows."""
+    groups = cdiv(C, LDS_CH)
+    eligible = N <= LDS_MAX_N and B % 4 == 0 and C % 4 == 0
+    z = eligible and want_zhat and L * B >= LDS_MIN_LOOKUPS_Z
+    nb = eligible and want_num_bits and B >= LDS_MIN_LOOKUPS_NB
+    blocks = cdiv(B, LDS_ROWS)
+    splits = max(1, min(cdiv(2 * cus, groups), blocks))
+    per = cdiv(blocks, splits) * LDS_ROWS
+    splits = cdiv(B, per)
+    return LookupPlan(eligible, z, nb, groups, groups % LDS_RENUMBER == 0, C - (groups - 1) * LDS_CH, splits, per,
+                      B - (splits - 1) * per)
+
+
+def renumbered(grp, groups):
+    """The channel group workgroup `grp` of `groups` serves (k_lookup_lds, the XCD renumbering)."""
+    if groups % LDS_RENUMBER:
+        return grp
+    return (grp & ~15) + ((grp & 7) << 1) + ((grp >> 3) & 1)
+
+
+def find_lookup_shape(cus, C, N, blocks_per_split, last_rows, prefer=None, max_elements=44_000_000):
+    """(L, B) at which the sorted-table pass gives every split `blocks_per_split` blocks and the last split `last_rows` rows
+    (None: any), with Z_hat out of the LDS: B = `prefer` when it qualifies, else the smallest such multiple of 4, and L the
+    fewest lambdas (two at least: the tables stay for the second) that take Z_hat to the LDS.  None if there is none."""
+    def lambdas(B):
+        return max(2, cdiv(LDS_MIN_LOOKUPS_Z, B))
+
+    def ok(B):
+        p = lookup_plan(lambdas(B), C, B, N, cus)
+        return (p.z_lds and p.per == blocks_per_split * LDS_ROWS and last_rows in (None, p.last_split_rows) and p.splits >= 2
+                and lambdas(B) * B * C <= max_elements)
+    if prefer is not None and ok(prefer):
+        return lambdas(prefer), prefer
+    per = blocks_per_split * LDS_ROWS
+    for k in range(1, 4 * cus * blocks_per_split + 2):
+        B = k * LDS_ROWS + 4 if last_rows is None else k * per + last_rows
+        if B % 4 == 0 and ok(B):
+            return lambdas(B), B
+    return None
+
+
+# ---------------------------------------------------------------------------------------------------------------- rank GEMM
+RankPlan = namedtuple("RankPlan", "qb nt best_s tiles_per_wg splits last_wg_tiles nk k2 kend_last")
+
+
+def rank_plan(V, K, Q, cus):
+    """vbq_analogy_ranks_f32: question blocks x word-tile ranges, and the k-chunks of a tile (nk stages, the last one multiplied
+    up to kend_last)."""
+    qb, nt = cdiv(Q, RANK_BM), cdiv(V, RANK_BN)
+    slots = cus * RANK_WGS
+    best_s, best_cost = 1, -1
+    for s in range(1, min(nt, RANK_MAX_SPLITS) + 1):
+        tpw = cdiv(nt, s)
+        cost = cdiv(qb * s, slots) * tpw
+        if best_cost < 0 or cost < best_cost or (cost == best_cost and tpw >= 8 and s > best_s):
+            best_cost, best_s = cost, s
+    tpw = cdiv(nt, best_s)
+    splits = cdiv(nt, tpw)
+    nk = cdiv(K, RANK_BK)
+    k2 = (K + 1) & ~1
+    return RankPlan(qb, nt, best_s, tpw, splits, nt - (splits - 1) * tpw, nk, k2, k2 - (nk - 1) * RANK_BK)
+
+
+def find_rank_words(cus, Q, K, min_tiles_per_wg, shorter_last, prefer=None, max_work=1_000_000_000, partial=37):
+    """V (its last tile holding `partial` words) at which a workgroup gets at least `min_tiles_per_wg` tiles, the last workgroup
+    fewer when `shorter_last`; `prefer` when it qualifies, else the smallest such V with V * Q * K <= max_work.  None if none."""
+    def ok(V):
+        p = rank_plan(V, K, Q, cus)
+        return (p.tiles_per_wg >= min_tiles_per_wg and p.splits >= 2 and V % RANK_BN != 0 and V * Q * K <= max_work
+                and (not shorter_last or p.last_wg_tiles < p.tiles_per_wg))
+    if prefer is not None and ok(prefer):
+        return prefer
+    for nt in range(2, max_work // (Q * K * RANK_BN) + 2):
+        V = (nt - 1) * RANK_BN + partial
+        if ok(V):
+            return V
+    return None
+
+
+# ---------------------------------------------------------------------------------------------------------------- grid caps
+def moments_flat_grid(n_per_ch, n_ch):
+    """vbq_moments_f32, C = 1 or channel-major -> (workgroups per channel, float4 per channel that the main loop needs
+    more than: with fewer no lane enters it)."""
+    gx = max(1, min(cdiv(n_per_ch // 4, THREADS), MOMENTS_FLAT_WGS // n_ch + 1))
+    return gx, (MOMENTS_FLAT_LOADS - 1) * gx * THREADS
+
+
+def moments_bc_grid(rows, n_ch):
+    """vbq_moments_f32, channel-last -> (workgroups, the element stride of a lane)."""
+    gx = max(min(cdiv(rows * n_ch, THREADS * MOMENTS_BC_PER_THREAD), MOMENTS_BC_WGS), cdiv(n_ch, THREADS))
+    return gx, (gx * THREADS // n_ch) * n_ch
+
+
+def rd_sums_grid(E, L, cus):
+    """vbq_rd_sums_u16 -> (workgroups per chunk of lambdas, chunks, grid passes over the E elements)."""
+    chunks = cdiv(L, RD_CHUNK)
+    gx = min(cdiv(E, THREADS), cus * RD_WGS_PER_CU // chunks + 1)
+    return gx, chunks, cdiv(E, gx * THREADS)
+
+
+def scan_grid(n):
+    """vbq_index_max_u16 / vbq_check_inputs_f32 -> (workgroups, grid passes)."""
+    gx = min(cdiv(n, THREADS), SCAN_WGS)
+    return gx, cdiv(n, gx * THREADS)
+
+
+def hist_tiled_grid(rows, n_ch, L):
+    """launch_hist, channel-last with C > 1 -> (workgroups per channel group and lambda, channel groups, row passes of the
+    busiest workgroup)."""
+    groups = cdiv(n_ch, HIST_TILE_CH)
+    iters = cdiv(rows, HIST_TILED_ROWS)
+    gx = max(1, min(HIST_TILED_WGS // (groups * L) + 1, iters))
+    return gx, groups, cdiv(iters, gx)

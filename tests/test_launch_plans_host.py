@@ -1,0 +1,185 @@
+"""tests/launch_plans.py against the sources it restates, without a GPU: every constant a plan depends on is read out of the
+.hip files with a regular expression and compared with the Python copy, and the plan functions are checked on numbers worked
+out by hand for 256 CUs -- the shapes tests/test_gpu_large_paths.py derives on an MI355X.  A failure here after a retuning
+means: move the shapes of that module so that they still reach the paths they are named after."""
+import os
+import re
+
+import pytest
+
+import launch_plans as LP
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vbq_amd", "csrc")
+CUS = 256
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _one(pattern, text, what):
+    found = re.findall(pattern, text)
+    assert len(found) == 1, f"{what}: expected one match of {pattern!r}, found {len(found)} -- the source moved, restate it"
+    return found[0]
+
+
+def _int(expr):
+    """'9 << 14' or '256' -> int."""
+    m = re.fullmatch(r"\s*(\d+)\s*(?:<<\s*(\d+))?\s*", expr)
+    assert m, expr
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+def test_lookup_constants_match_the_source():
+    s = _src("vbq_latents.hip")
+    assert _int(_one(r"constexpr int64_t kLdsMinLookupsZ = ([^;]+);", s, "kLdsMinLookupsZ")) == LP.LDS_MIN_LOOKUPS_Z
+    assert _int(_one(r"constexpr int64_t kLdsMinLookupsNb = ([^;]+);", s, "kLdsMinLookupsNb")) == LP.LDS_MIN_LOOKUPS_NB
+    assert int(_one(r"#define VBQ_LDS_AHEAD (\d+)", s, "VBQ_LDS_AHEAD")) == LP.LDS_AHEAD
+    ch, rows = _one(r"constexpr int kLdsCh = (\d+), kLdsRows = (\d+), kLdsPitch = kLdsRows, kLdsAhead = VBQ_LDS_AHEAD;", s, "kLdsCh")
+    assert (int(ch), int(rows)) == (LP.LDS_CH, LP.LDS_ROWS)
+    # the rule itself: the lines the plan restates are still there
+    _one(r"if \(\(gridDim\.x & 15\) == 0\) grp = \(grp & ~15\) \+ \(\(grp & 7\) << 1\) \+ \(\(grp >> 3\) & 1\);", s, "renumbering")
+    assert _one(r"if constexpr \(N > (\d+)\) \{\s*return VBQ_OK;", s, "largest N") == str(LP.LDS_MAX_N)
+    _one(r"if \(B % 4 != 0 \|\| C % 4 != 0 \|\|", s, "preconditions")
+    _one(r"\(int64_t\)L \* B >= kLdsMinLookupsZ;", s, "want_z")
+    _one(r"&& B >= kLdsMinLookupsNb;", s, "want_nb")
+    _one(r"int64_t splits = \(2 \* \(int64_t\)num_cus\(\) \+ groups - 1\) / groups;", s, "splits")
+    _one(r"const int64_t per = \(\(blocks \+ splits - 1\) / splits\) \* kLdsRows;\s*splits = \(B \+ per - 1\) / per;", s, "per")
+    _one(r"for \(; r0 \+ \(long\)kLdsAhead \* kLdsRows <= r_end; r0 \+= \(long\)kLdsAhead \* kLdsRows\)", s, "pipelined loop")
+
+
+def test_rank_constants_match_the_source():
+    s = _src("vbq_ranks.hip")
+    assert int(_one(r"constexpr int kBM = (\d+);", s, "kBM")) == LP.RANK_BM
+    assert int(_one(r"constexpr int kBN = (\d+);", s, "kBN")) == LP.RANK_BN
+    assert int(_one(r"#define VBQ_RANK_BK (\d+)", s, "VBQ_RANK_BK")) == LP.RANK_BK
+    assert int(_one(r"#define VBQ_RANK_WGS (\d+)", s, "VBQ_RANK_WGS")) == LP.RANK_WGS
+    assert int(_one(r"for \(long s = 1; s <= nt && s <= (\d+); \+\+s\)", s, "best_s loop")) == LP.RANK_MAX_SPLITS
+    _one(r"const long slots = \(long\)num_cus\(\) \* VBQ_RANK_WGS;", s, "slots")
+    _one(r"const long cost = \(\(qb \* s \+ slots - 1\) / slots\) \* tpw;", s, "cost")
+    _one(r"\(cost == best_cost && tpw >= 8 && s > best_s\)", s, "tie rule")
+    _one(r"const int kend = last_k \? K2 - kc \* kBK : kBK;", s, "kend")
+    _one(r"\(int\)\(\(K \+ 1\) & ~1\), tiles_per_wg, below\);", s, "K2")
+
+
+def test_reduction_caps_match_the_source():
+    s = _src("vbq_hist.hip")
+    assert int(_one(r"const int64_t cap = (\d+) / n_ch \+ 1;", s, "moments cap")) == LP.MOMENTS_FLAT_WGS
+    assert int(_one(r"for \(; q \+ (\d+) \* stride < nq; q \+= \d+ \* stride\)", s, "moments main loop")) == LP.MOMENTS_FLAT_LOADS - 1
+    per, cap = _one(r"int64_t gx = \(E \+ 256 \* (\d+) - 1\) / \(256 \* \d+\);\s*if \(gx > (\d+)\) gx = \d+;", s, "moments_bc grid")
+    assert (int(per), int(cap)) == (LP.MOMENTS_BC_PER_THREAD, LP.MOMENTS_BC_WGS)
+    assert int(_one(r"n_ch >= 1 && n_ch <= (\d+), VBQ_ERR_INVALID_ARGUMENT,\s*\"vbq_moments_f32", s, "moments limit")) == LP.MOMENTS_MAX_CH
+    for who in ("check_inputs", "index_max"):
+        body = s[s.index(f'extern "C" int vbq_{who}_'):]
+        body = body[:body.index("\n}\n")]                                      # that entry point alone
+        assert int(_one(r"int64_t gx = \(n \+ 255\) / 256;\s*if \(gx > (\d+)\) gx = \d+;", body, who)) == LP.SCAN_WGS
+    assert int(_one(r"const int64_t cap = \(int64_t\)num_cus\(\) \* (\d+) / chunks \+ 1;", s, "rd_sums cap")) == LP.RD_WGS_PER_CU
+    assert int(_one(r"constexpr int kRdChunk = (\d+);", s, "kRdChunk")) == LP.RD_CHUNK
+    assert int(_one(r"int64_t gx = (\d+) / \(\(int64_t\)groups \* L\) \+ 1;", s, "hist_tiled grid")) == LP.HIST_TILED_WGS
+    rows, stride = _one(r"for \(long r = \(long\)blockIdx\.x \* (\d+) \+ slot; r < n_rows; r \+= \(long\)gridDim\.x \* (\d+)\)", s, "hist_tiled rows")
+    assert int(rows) == int(stride) == LP.HIST_TILED_ROWS
+    assert int(_one(r"constexpr int kHistTiledThreads = (\d+);", s, "kHistTiledThreads")) == LP.HIST_TILED_ROWS * LP.HIST_TILE_CH
+    assert int(_one(r"constexpr int kTileChannels = (\d+);", _src("vbq_common.h") + s, "kTileChannels")) == LP.HIST_TILE_CH
+
+
+# ------------------------------------------------------------------------------------------------ worked numbers, 256 CUs
+def test_lookup_plan_worked_numbers():
+    p = LP.lookup_plan(8, 256, 20740, 10, CUS)
+    assert p.z_lds and p.nb_lds and p.groups == 16 and p.renumbered
+    assert (p.splits, p.per, p.last_split_rows) == (28, 768, 4)
+    assert LP.walk(p.per) == LP.Walk(1, 1, 256) and LP.walk(p.last_split_rows) == LP.Walk(0, 1, 4)
+    assert LP.walk(20740) == LP.Walk(40, 2, 4)                     # the num_bits pass: 81 whole blocks and four rows
+    p = LP.lookup_plan(5, 256, 33028, 10, CUS)
+    assert p.z_lds and (p.splits, p.per) == (26, 1280) and LP.walk(p.per) == LP.Walk(2, 1, 256)
+    assert LP.walk(p.last_split_rows) == LP.Walk(2, 1, 4)
+    p = LP.lookup_plan(8, 260, 20740, 10, CUS)
+    assert p.z_lds and p.groups == 17 and not p.renumbered and p.last_group_channels == 4
+    assert (p.splits, p.per, p.last_split_rows) == (28, 768, 4) and LP.walk(p.per, whole_group=False) == LP.Walk(0, 3, 256)
+    p = LP.lookup_plan(3, 64, 65540, 10, CUS)
+    assert p.z_lds and p.groups == 4 and (p.splits, p.per, p.last_split_rows) == (86, 768, 260)
+    assert LP.walk(260) == LP.Walk(0, 2, 4)
+    p = LP.lookup_plan(64, 16, 2308, 10, CUS)
+    assert p.z_lds and not p.nb_lds and (p.groups, p.splits, p.per, p.last_split_rows) == (1, 10, 256, 4)
+    p = LP.lookup_plan(2, 256, 3076, 10, CUS)
+    assert not p.z_lds and p.nb_lds and LP.walk(3076) == LP.Walk(6, 1, 4)
+    # the existing shapes of test_gather_latents_one_pass_against_numpy: one block per split, the pipelined loop never runs
+    for L, C, B in ((16, 64, 4096), (3, 20, 16388), (2, 36, 3076)):
+        p = LP.lookup_plan(L, C, B, 10, CUS)
+        assert not p.renumbered and (not p.z_lds or p.per == LP.LDS_ROWS)
+    # refusals of the LDS form
+    assert not LP.lookup_plan(8, 256, 20742, 10, CUS).eligible and not LP.lookup_plan(8, 254, 20740, 10, CUS).eligible
+    assert not LP.lookup_plan(8, 256, 20740, 11, CUS).eligible
+    assert not LP.lookup_plan(8, 256, 18428, 10, CUS).z_lds and LP.lookup_plan(8, 256, 18432, 10, CUS).z_lds
+    assert not LP.lookup_plan(1, 256, 3068, 10, CUS).nb_lds and LP.lookup_plan(1, 256, 3072, 10, CUS).nb_lds
+
+
+def test_renumbering_is_a_permutation_inside_every_sixteen():
+    for groups in (16, 32, 48):
+        got = [LP.renumbered(g, groups) for g in range(groups)]
+        assert sorted(got) == list(range(groups))
+        assert all(a // 16 == g // 16 for g, a in enumerate(got))
+        assert all(abs(got.index(2 * k) - got.index(2 * k + 1)) == 8 for k in range(groups // 2))   # one XCD of eight
+    assert [LP.renumbered(g, 17) for g in range(17)] == list(range(17))
+
+
+def test_find_lookup_shape_takes_the_worked_shape_or_an_equivalent_one():
+    assert LP.find_lookup_shape(CUS, 256, 10, 3, 4, prefer=20740) == (8, 20740)
+    assert LP.find_lookup_shape(CUS, 256, 10, 5, None, prefer=33028) == (5, 33028)
+    assert LP.find_lookup_shape(CUS, 260, 10, 3, 4, prefer=20740) == (8, 20740)
+    assert LP.find_lookup_shape(CUS, 64, 10, 3, 260, prefer=65540) == (3, 65540)
+    for cus in (32, 64, 80, 104, 128, 228, 256, 304):              # other devices: the worked rows do not fit, others do
+        for C, bps, last in ((256, 3, 4), (256, 5, None), (260, 3, 4), (64, 3, 260)):
+            found = LP.find_lookup_shape(cus, C, 10, bps, last, prefer=20740)
+            assert found is not None, (cus, C)
+            L, B = found
+            p = LP.lookup_plan(L, C, B, 10, cus)
+            assert p.z_lds and p.per == bps * 256 and last in (None, p.last_split_rows) and L * B * C <= 44_000_000
+
+
+def test_rank_plan_worked_numbers():
+    p = LP.rank_plan(10277, 100, 1000, CUS)
+    assert (p.qb, p.nt, p.tiles_per_wg, p.splits, p.last_wg_tiles) == (8, 81, 2, 41, 1)
+    p = LP.rank_plan(33000, 1, 520, CUS)
+    assert (p.qb, p.nt, p.tiles_per_wg, p.splits, p.last_wg_tiles) == (5, 258, 3, 86, 3)
+    for K, nk, k2, kend in ((1, 1, 2, 2), (31, 1, 32, 32), (32, 1, 32, 32), (33, 2, 34, 2), (64, 2, 64, 32), (65, 3, 66, 2)):
+        p = LP.rank_plan(10277, K, 1000, CUS)
+        assert (p.nk, p.k2, p.kend_last) == (nk, k2, kend)
+    # every shape the suite compared with a reference before: one tile per workgroup
+    for V, K, Q in ((1, 3, 2), (127, 16, 1), (129, 17, 130), (1000, 300, 257), (5000, 33, 64)):
+        assert LP.rank_plan(V, K, Q, CUS).tiles_per_wg == 1
+    p = LP.rank_plan(100_000, 100, 19_544, CUS)                    # the notebook's size: several tiles, a clamped last range
+    assert p.tiles_per_wg >= 2 and p.last_wg_tiles < p.tiles_per_wg
+
+
+def test_find_rank_words_takes_the_worked_shape_or_an_equivalent_one():
+    assert LP.find_rank_words(CUS, 1000, 65, 2, True, prefer=10277) == 10277
+    assert LP.find_rank_words(CUS, 520, 1, 3, False, prefer=33000) == 33000
+    for cus in (64, 80, 104, 128, 228, 256, 304):
+        V = LP.find_rank_words(cus, 1000, 65, 2, True)
+        p = LP.rank_plan(V, 65, 1000, cus)
+        assert p.tiles_per_wg >= 2 and p.last_wg_tiles < p.tiles_per_wg and V * 1000 * 65 <= 1e9
+        V = LP.find_rank_words(cus, 520, 1, 3, False)
+        assert LP.rank_plan(V, 1, 520, cus).tiles_per_wg >= 3
+
+
+def test_grid_caps_worked_numbers():
+    assert LP.moments_flat_grid(6_300_000, 1) == (2049, 3 * 2049 * 256)        # "more than 6.29 M floats at C = 1"
+    assert 4 * LP.moments_flat_grid(6_300_000, 1)[1] == 6_294_528
+    assert LP.moments_flat_grid(101_380, 64) == (33, 25_344)                   # "more than 101 376 rows at C = 64"
+    assert LP.moments_flat_grid(39_960, 1)[0] * 3 * 256 > 39_960 // 4          # the largest shape tested before: no main loop
+    assert LP.moments_bc_grid(33, 4096) == (33, 8192)
+    assert LP.rd_sums_grid(4995, 8, CUS) == (20, 1, 1)                         # the one shape tested before: one pass
+    assert LP.rd_sums_grid(640_000, 9, CUS) == (1025, 2, 3)
+    assert LP.rd_sums_grid(524_544, 8, CUS)[2] == 1 and LP.rd_sums_grid(524_545, 8, CUS)[2] == 2      # "needs E > 524 k"
+    assert LP.scan_grid(1 << 20) == (4096, 1) and LP.scan_grid((1 << 20) + 1) == (4096, 2)
+    assert LP.scan_grid((1 << 21) + 3) == (4096, 3) and LP.scan_grid(24_576) == (96, 1)
+    assert LP.hist_tiled_grid(20_000, 40, 32) == (6, 3, 53)
+
+
+@pytest.mark.parametrize("rows,want", [(0, (0, 0, 0)), (4, (0, 1, 4)), (256, (0, 1, 256)), (260, (0, 2, 4)), (512, (1, 0, 0)),
+                                       (768, (1, 1, 256)), (1028, (2, 1, 4)), (1280, (2, 1, 256))])
+def test_walk(rows, want):
+    assert tuple(LP.walk(rows)) == want
+    assert LP.walk(rows, whole_group=False).pipelined == 0
+    assert LP.walk(rows, whole_group=False).rest == LP.cdiv(rows, 256)
