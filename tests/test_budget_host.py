@@ -1,5 +1,6 @@
 """Rate control on the host: the exact file lengths of bitstream.latent_nbytes / embeddings_nbytes against len(write(...)) /
-len(write_embeddings(...)), the byte-budget rule and its max_bytes checks, and the argument checks of vbq_rans_sizes_u16 (callable without a device)."""
+len(write_embeddings(...)), the byte-budget rule and its max_bytes checks, and the argument checks of vbq_rans_sizes_u16 and of
+the other five entry points over (n_streams, n, N, seg) (callable without a device)."""
 import math
 
 import numpy as np
@@ -105,3 +106,28 @@ def test_sizes_entry_point_checks_its_arguments_before_the_device():
     assert h.vbq_rans_sizes_u16(None, 2, 10, 10, 8, None, None, None) == -1 and b"null pointer" in h.vbq_last_error()
     assert h.vbq_rans_sizes_u16(None, 0, 10, 10, 8, None, None, None) == 0                 # nothing to do
     assert h.vbq_rans_sizes_u16(None, 3, 0, 10, 8, None, None, None) == 0
+
+
+def test_segment_entry_points_share_their_size_checks():
+    """The six entry points over (n_streams, n, N, seg) refuse alike, each under its own name, before any pointer is followed:
+    bad sizes, and more segments per stream than the kernels' int holds -- the encoder and the decoder too, which once cast that
+    count unchecked."""
+    from vbq_amd import _lib, build
+    build.build_hip()
+    h = _lib.lib()
+    p = 4096                                                     # a non-null pointer that is never followed
+    calls = {
+        "vbq_rans_encode_u16": lambda n, N, q=p: h.vbq_rans_encode_u16(p, 1, n, N, 1, p, p, q, None),
+        "vbq_rans_sizes_u16": lambda n, N, q=p: h.vbq_rans_sizes_u16(p, 1, n, N, 1, p, q, None),
+        "vbq_rans_decode_u16": lambda n, N, q=p: h.vbq_rans_decode_u16(p, p, 1, n, N, 1, p, q, None, None),
+        "vbq_rans_map_encode_u16": lambda n, N, q=p: h.vbq_rans_map_encode_u16(p, 1, p, 1, 1, n, N, 1, p, p, q, None),
+        "vbq_rans_map_sizes_u16": lambda n, N, q=p: h.vbq_rans_map_sizes_u16(p, 1, p, 1, 1, n, N, 1, p, q, None),
+        "vbq_rans_map_decode_u16": lambda n, N, q=p: h.vbq_rans_map_decode_u16(p, p, p, 1, 1, n, N, 1, p, q, None, None),
+    }
+    for name, call in calls.items():
+        assert call(10, 11) == -1
+        assert h.vbq_last_error().startswith(name.encode() + b": bad sizes n_streams=1 n=10 N=11 seg=1"), name
+        assert call(2 ** 31 + 1, 10) == -1
+        assert h.vbq_last_error() == name.encode() + b": 2147483649 segments per stream are too many", name
+        assert call(2 ** 31 - 1, 10, None) == -1                 # 2^31 - 1 segments pass the checks: on to the pointers
+        assert h.vbq_last_error() == name.encode() + b": null pointer argument", name

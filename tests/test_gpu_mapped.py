@@ -84,6 +84,29 @@ def test_codec_rejects_bad_calls_on_the_host():
     words, sizes = codec.encode(d_planes, cls)
     with pytest.raises(ValueError, match="expected words"):
         codec.decode(words[:, :-1], sizes, cls, 1003)
+    # the refusals both codecs word alike, in full
+    import re
+    from vbq_amd.coder import RansCodec
+    plain = RansCodec(freq[0].copy(), N=N, segment=SEG)
+    shape = "expected words [3, 16, 66] and sizes [3, 16] for 1003 symbols per stream, got (3, 15, 66) and (3, 16)"
+    for call in (lambda: codec.decode(words[:, :-1], sizes, cls, 1003), lambda: plain.decode(words[:, :-1], sizes, 1003)):
+        with pytest.raises(ValueError, match="^" + re.escape(shape) + "$"):
+            call()
+    with pytest.raises(ValueError, match="^" + re.escape(shape.replace("(3, 16)", "(3, 15)")) + "$"):
+        plain.decode(words[:, :-1], sizes[:, :-1], 1003)
+    for call in (plain.encode, plain.sizes, plain.encode_packed):
+        with pytest.raises(ValueError, match="^2 index streams but 3 frequency rows$"):
+            call(d_planes[0, :2])
+    no_seg = RansCodec(freq[0].copy(), N=N, segment=None)
+    text = "^this codec was made without a segment: it serves the interleaved layout only$"
+    for call in (lambda: no_seg.encode(d_planes[0]), lambda: no_seg.sizes(d_planes[0]), lambda: no_seg.encode_packed(d_planes[0]),
+                 lambda: no_seg.decode(words, sizes, 1003)):
+        with pytest.raises(ValueError, match=text):
+            call()
+    for call in (lambda: codec.sizes_interleaved(d_planes, 4096), lambda: codec.encode_interleaved(d_planes, 4096),
+                 lambda: codec.decode_interleaved(words.reshape(-1), sizes.reshape(-1), 1003, 4096)):
+        with pytest.raises(ValueError, match="^the class-mapped coder has no interleaved layout$"):
+            call()
 
 
 def _raw_decode(codec, words, sizes, cls, n):

@@ -174,45 +174,62 @@ class RansCodec:
         _raise_status(int(status.cpu().item()))
         return idx
 
-    def _encode(self, idx, S, n, words, sizes):
-        check(_lib.lib().vbq_rans_encode_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(idx.device)),
-                                             ops._ptr(words), ops._ptr(sizes), ops._stream(idx)), "vbq_rans_encode_u16")
+    # What MappedRansCodec overrides: how the inputs are prepared (`sel` = what its launches take besides: nothing here) and
+    # the three launches.
+    def _inputs(self, idx, cls):
+        """The encoder's side -> (idx, n, nseg, sel)."""
+        idx, _, n, nseg = self._streams(idx)
+        return idx, n, nseg, None
 
-    def _decode(self, words, sizes, n, idx, status):
+    def _decode_sel(self, cls, n, device):
+        """The decoder's side -> sel."""
+        return None
+
+    def _encode(self, idx, sel, n, words, sizes):
+        check(_lib.lib().vbq_rans_encode_u16(ops._ptr(idx), self.n_streams, n, self.N, self.segment,
+                                             ops._ptr(self._freq(idx.device)), ops._ptr(words), ops._ptr(sizes),
+                                             ops._stream(idx)), "vbq_rans_encode_u16")
+
+    def _sizes(self, idx, sel, n, sizes):
+        check(_lib.lib().vbq_rans_sizes_u16(ops._ptr(idx), self.n_streams, n, self.N, self.segment,
+                                            ops._ptr(self._freq(idx.device)), ops._ptr(sizes), ops._stream(idx)),
+              "vbq_rans_sizes_u16")
+
+    def _decode(self, words, sizes, sel, n, idx, status):
         """status: u32 [1] the decoder ORs its flags into (read it with _raise_status)."""
         check(_lib.lib().vbq_rans_decode_u16(ops._ptr(words), ops._ptr(sizes), idx.shape[0], n, self.N, self.segment,
                                              ops._ptr(self._freq(idx.device)), ops._ptr(idx), ops._ptr(status),
                                              ops._stream(idx)), "vbq_rans_decode_u16")
 
-    def encode(self, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def encode(self, idx: torch.Tensor, *, _cls=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """idx: u16 device tensor [..., n] with prod(leading dims) == number of frequency rows.
         Returns (words u16 [S, nseg, segment+2], sizes u32 [S, nseg])."""
-        idx, S, n, nseg = self._streams(idx)
-        words = torch.zeros((S, nseg, self.segment + 2), dtype=torch.uint16, device=idx.device)
-        sizes = torch.zeros((S, nseg), dtype=torch.uint32, device=idx.device)
-        self._encode(idx, S, n, words, sizes)
+        idx, n, nseg, sel = self._inputs(idx, _cls)
+        words = torch.zeros((self.n_streams, nseg, self.segment + 2), dtype=torch.uint16, device=idx.device)
+        sizes = torch.zeros((self.n_streams, nseg), dtype=torch.uint32, device=idx.device)
+        self._encode(idx, sel, n, words, sizes)
         return words, sizes
 
-    def sizes(self, idx: torch.Tensor) -> torch.Tensor:
+    def sizes(self, idx: torch.Tensor, *, _cls=None) -> torch.Tensor:
         """The sizes `encode` returns -- u32 [S, nseg], 16-bit words per segment -- without the words (vbq_rans_sizes_u16): the
         exact coded length of every segment at 4 bytes of output per segment instead of a padded word buffer."""
-        idx, S, n, nseg = self._streams(idx)
-        sizes = torch.zeros((S, nseg), dtype=torch.uint32, device=idx.device)
-        check(_lib.lib().vbq_rans_sizes_u16(ops._ptr(idx), S, n, self.N, self.segment, ops._ptr(self._freq(idx.device)),
-                                            ops._ptr(sizes), ops._stream(idx)), "vbq_rans_sizes_u16")
+        idx, n, nseg, sel = self._inputs(idx, _cls)
+        sizes = torch.zeros((self.n_streams, nseg), dtype=torch.uint32, device=idx.device)
+        self._sizes(idx, sel, n, sizes)
         return sizes
 
-    def decode(self, words: torch.Tensor, sizes: torch.Tensor, n: int) -> torch.Tensor:
+    def decode(self, words: torch.Tensor, sizes: torch.Tensor, n: int, *, _cls=None) -> torch.Tensor:
         """words / sizes are untrusted (they may come from a file): shapes are checked here, segment sizes and
         word counts in the kernel; a damaged stream raises VBQError instead of returning garbage."""
         words = ops._dev(words, torch.uint16, "words")
         sizes = ops._dev(sizes, torch.uint32, "sizes")
-        S = self.freq_host.shape[0]
+        S = self.n_streams
         nseg = self._nseg(n)
         if words.numel() != S * nseg * (self.segment + 2) or sizes.numel() != S * nseg:
             raise ValueError(f"expected words [{S}, {nseg}, {self.segment + 2}] and sizes [{S}, {nseg}] for {n} symbols per "
                              f"stream, got {tuple(words.shape)} and {tuple(sizes.shape)}")
-        return self._decoded(words.device, n, lambda idx, status: self._decode(words, sizes, n, idx, status))
+        sel = self._decode_sel(_cls, n, words.device)
+        return self._decoded(words.device, n, lambda idx, status: self._decode(words, sizes, sel, n, idx, status))
 
     # ------------------------------------------------------------ packed payload (vbq_amd.bitstream, vbq_rans_pack_u16)
     def pack_device(self, words: torch.Tensor, sizes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -255,28 +272,30 @@ class RansCodec:
                                              ops._stream(payload)), "vbq_rans_unpack_u16")
         return words, out_sizes, status
 
-    def encode_packed(self, idx: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+    def encode_packed(self, idx: torch.Tensor, *, _cls=None) -> Tuple[np.ndarray, np.ndarray]:
         """encode + pack on the device -> (sizes u32 [S, nseg], payload u16 [total]) on the host, in TWO device-to-host
         copies: the total together with the sizes, then the payload."""
-        idx, S, n, nseg = self._streams(idx)
-        dev = idx.device
+        idx, n, nseg, sel = self._inputs(idx, _cls)
+        dev, S = idx.device, self.n_streams
         words = torch.empty((S, nseg, self.segment + 2), dtype=torch.uint16, device=dev)    # pack reads valid words only
         aux = torch.empty(8 + 4 * S * nseg, dtype=torch.uint8, device=dev)                  # total u64, then sizes u32
         total, sizes = aux[:8].view(torch.uint64), aux[8:].view(torch.uint32).view(S, nseg)
         payload = torch.empty(S * nseg * (self.segment + 2), dtype=torch.uint16, device=dev)
         offsets = torch.empty((S, nseg), dtype=torch.int64, device=dev)
-        self._encode(idx, S, n, words, sizes)
+        self._encode(idx, sel, n, words, sizes)
         self._pack(words, sizes, payload, offsets, total)
         h = aux.cpu().numpy()
         n_words = int(h[:8].view(np.uint64)[0])
         return h[8:].view(np.uint32).reshape(S, nseg), payload[:n_words].cpu().numpy()
 
-    def decode_packed(self, payload: torch.Tensor, sizes: torch.Tensor, n: int) -> torch.Tensor:
+    def decode_packed(self, payload: torch.Tensor, sizes: torch.Tensor, n: int, *, _cls=None) -> torch.Tensor:
         """unpack + the existing decoder, one status word for both (one synchronisation): u16 indices [S, n].
         A damaged payload raises VBQError."""
+        sel = self._decode_sel(_cls, n, payload.device)
+
         def launch(idx, status):
             words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
-            self._decode(words, out_sizes, n, idx, status)
+            self._decode(words, out_sizes, sel, n, idx, status)
         return self._decoded(payload.device, n, launch)
 
     # ------------------------------------------------------------ wave-interleaved layout (bitstream VBQc, vbq_rans_il_*_u16)
@@ -345,7 +364,6 @@ class RansCodec:
         return w[keep].tobytes()
 
 
-
 class MappedRansCodec(RansCodec):
     """The segment coder with a table per symbol (vbq_rans_map_*_u16, include/vbq.h "Class-mapped rANS"): freq u16 [P, S, T],
     1 <= P <= 4, and a class map cls [n] with values in [0, P), shared by the S streams -- symbol i of stream s is coded with
@@ -385,8 +403,8 @@ class MappedRansCodec(RansCodec):
             cls = torch.where((cls < 0) | (cls > 255), 255, cls)
         return cls.to(torch.uint8).contiguous()
 
-    def _planes(self, idx):
-        """The checked index tensor [P, S, n] or [S, n] -> (idx, n_planes, n, nseg)."""
+    def _inputs(self, idx, cls):
+        """The checked index tensor [P, S, n] or [S, n] and its class map -> (idx, n, nseg, (n_planes, cls))."""
         idx = ops._dev(idx, torch.uint16, "idx")
         n = idx.shape[-1]
         if tuple(idx.shape) == (self.P, self.S, n) and idx.dim() == 3:
@@ -395,74 +413,48 @@ class MappedRansCodec(RansCodec):
             planes = 1
         else:
             raise ValueError(f"idx must be [{self.P}, {self.S}, n] or [{self.S}, n], got {tuple(idx.shape)}")
-        return idx, planes, n, self._nseg(n)
+        nseg = self._nseg(n)
+        return idx, n, nseg, (planes, self._classes(cls, n, idx.device, check=True))
 
-    def _map_encode(self, idx, planes, cls, n, words, sizes):
-        check(_lib.lib().vbq_rans_map_encode_u16(ops._ptr(idx), planes, ops._ptr(cls), self.P, self.S, n, self.N, self.segment,
+    def _decode_sel(self, cls, n, device):
+        return self._classes(cls, n, device, check=False)
+
+    def _encode(self, idx, sel, n, words, sizes):
+        check(_lib.lib().vbq_rans_map_encode_u16(ops._ptr(idx), sel[0], ops._ptr(sel[1]), self.P, self.S, n, self.N, self.segment,
                                                  ops._ptr(self._freq(idx.device)), ops._ptr(words), ops._ptr(sizes),
                                                  ops._stream(idx)), "vbq_rans_map_encode_u16")
 
-    def _map_decode(self, words, sizes, cls, n, idx, status):
+    def _sizes(self, idx, sel, n, sizes):
+        check(_lib.lib().vbq_rans_map_sizes_u16(ops._ptr(idx), sel[0], ops._ptr(sel[1]), self.P, self.S, n, self.N, self.segment,
+                                                ops._ptr(self._freq(idx.device)), ops._ptr(sizes), ops._stream(idx)),
+              "vbq_rans_map_sizes_u16")
+
+    def _decode(self, words, sizes, cls, n, idx, status):
         check(_lib.lib().vbq_rans_map_decode_u16(ops._ptr(words), ops._ptr(sizes), ops._ptr(cls), self.P, self.S, n, self.N,
                                                  self.segment, ops._ptr(self._freq(idx.device)), ops._ptr(idx), ops._ptr(status),
                                                  ops._stream(idx)), "vbq_rans_map_decode_u16")
 
+    _map_decode = _decode                                                # (the name the tests launch it by)
+
     def encode(self, idx, cls) -> Tuple[torch.Tensor, torch.Tensor]:
         """idx u16 [P, S, n] (plane p holds the symbols of class p: the encoder picks idx[cls[i], s, i]) or [S, n] (already
         selected); cls [n] integers in [0, P).  -> (words u16 [S, nseg, segment+2], sizes u32 [S, nseg])."""
-        idx, planes, n, nseg = self._planes(idx)
-        cls = self._classes(cls, n, idx.device, check=True)
-        words = torch.zeros((self.S, nseg, self.segment + 2), dtype=torch.uint16, device=idx.device)
-        sizes = torch.zeros((self.S, nseg), dtype=torch.uint32, device=idx.device)
-        self._map_encode(idx, planes, cls, n, words, sizes)
-        return words, sizes
+        return super().encode(idx, _cls=cls)
 
     def sizes(self, idx, cls) -> torch.Tensor:
         """The sizes `encode` returns, without the words (vbq_rans_map_sizes_u16)."""
-        idx, planes, n, nseg = self._planes(idx)
-        cls = self._classes(cls, n, idx.device, check=True)
-        sizes = torch.zeros((self.S, nseg), dtype=torch.uint32, device=idx.device)
-        check(_lib.lib().vbq_rans_map_sizes_u16(ops._ptr(idx), planes, ops._ptr(cls), self.P, self.S, n, self.N, self.segment,
-                                                ops._ptr(self._freq(idx.device)), ops._ptr(sizes), ops._stream(idx)),
-              "vbq_rans_map_sizes_u16")
-        return sizes
+        return super().sizes(idx, _cls=cls)
 
     def decode(self, words, sizes, cls, n: int) -> torch.Tensor:
         """words, sizes and cls are untrusted: shapes are checked here, everything else in the kernel (a class >= P included);
         a damaged stream raises VBQError.  -> u16 indices [S, n]."""
-        words = ops._dev(words, torch.uint16, "words")
-        sizes = ops._dev(sizes, torch.uint32, "sizes")
-        n = int(n)
-        nseg = self._nseg(n)
-        if words.numel() != self.S * nseg * (self.segment + 2) or sizes.numel() != self.S * nseg:
-            raise ValueError(f"expected words [{self.S}, {nseg}, {self.segment + 2}] and sizes [{self.S}, {nseg}] for {n} symbols "
-                             f"per stream, got {tuple(words.shape)} and {tuple(sizes.shape)}")
-        cls = self._classes(cls, n, words.device, check=False)
-        return self._decoded(words.device, n, lambda idx, status: self._map_decode(words, sizes, cls, n, idx, status))
+        return super().decode(words, sizes, int(n), _cls=cls)
 
     def encode_packed(self, idx, cls) -> Tuple[np.ndarray, np.ndarray]:
         """encode + vbq_rans_pack_u16 on the device -> (sizes u32 [S, nseg], payload u16 [total]) on the host, in two
-        device-to-host copies, as RansCodec.encode_packed."""
-        idx, planes, n, nseg = self._planes(idx)
-        cls = self._classes(cls, n, idx.device, check=True)
-        dev, S = idx.device, self.S
-        words = torch.empty((S, nseg, self.segment + 2), dtype=torch.uint16, device=dev)    # pack reads valid words only
-        aux = torch.empty(8 + 4 * S * nseg, dtype=torch.uint8, device=dev)                  # total u64, then sizes u32
-        total, sizes = aux[:8].view(torch.uint64), aux[8:].view(torch.uint32).view(S, nseg)
-        payload = torch.empty(S * nseg * (self.segment + 2), dtype=torch.uint16, device=dev)
-        offsets = torch.empty((S, nseg), dtype=torch.int64, device=dev)
-        self._map_encode(idx, planes, cls, n, words, sizes)
-        self._pack(words, sizes, payload, offsets, total)
-        h = aux.cpu().numpy()
-        n_words = int(h[:8].view(np.uint64)[0])
-        return h[8:].view(np.uint32).reshape(S, nseg), payload[:n_words].cpu().numpy()
+        device-to-host copies."""
+        return super().encode_packed(idx, _cls=cls)
 
     def decode_packed(self, payload, sizes, cls, n: int) -> torch.Tensor:
         """vbq_rans_unpack_u16 + the mapped decoder, one status word for both: u16 indices [S, n]."""
-        n = int(n)
-        cls = self._classes(cls, n, payload.device, check=False)
-
-        def launch(idx, status):
-            words, out_sizes, _ = self.unpack_device(payload, sizes, n, status)
-            self._map_decode(words, out_sizes, cls, n, idx, status)
-        return self._decoded(payload.device, n, launch)
+        return super().decode_packed(payload, sizes, int(n), _cls=cls)

@@ -10,37 +10,14 @@
 // segment and consuming words backwards -- reproduces them first-to-last.  One thread per
 // segment; the 64 segments of a workgroup belong to one stream and share its frequency /
 // cumulative tables in LDS.  oracle/vbq_oracle.c (rans_* functions) is the bit-exact checker.
+// Table staging, the bucket table, the segment reader (the rules for untrusted words) and the
+// argument check of the entry points are vbq_rans_common.h's, shared with vbq_rans_map.hip.
 #include "vbq_rans_common.h"
 
 namespace vbq {
 namespace {
 
 constexpr int kRansThreads = 64;
-
-// Frequencies and exclusive cumulative frequencies of one stream into LDS, as ONE u32 table fc[sym] = f | c << 16 (f >= 1,
-// c < 2^15: one LDS read per symbol in the encoder) and -- for the decoder's slot search -- c alone with c[T] = 2^15.
-__device__ __forceinline__ void stage_tables(const uint16_t *__restrict__ freq, int T, uint32_t *fc_l, uint16_t *c_l) {
-    // exclusive prefix sum of <= 2048 frequencies by one wave: each lane owns a contiguous chunk
-    const int lane = threadIdx.x;
-    const int per = (T + kRansThreads - 1) / kRansThreads;
-    unsigned sum = 0;
-    for (int i = lane * per; i < min(T, (lane + 1) * per); ++i) sum += freq[i];
-    unsigned incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    unsigned run = incl - sum;
-    for (int i = lane * per; i < min(T, (lane + 1) * per); ++i) {
-        const unsigned f = freq[i];
-        fc_l[i] = f | (run << 16);                               // (an invalid table may overflow the 16 bits: the decoder rejects
-        if (c_l) c_l[i] = (uint16_t)run;                         //  it through c_l[T] below before using any entry)
-        run += f;
-    }
-    if (lane == 63 && c_l) c_l[T] = (uint16_t)(incl == (1u << kPB) ? incl : 0u);   // 2^15 for a valid table, 0 marks an invalid one
-    __syncthreads();
-}
 
 // One thread per segment; a lane walks its segment from the last symbol to the first.  Symbols come in 16-byte groups of eight
 // where the layout allows it (segment length and stream length multiples of eight: one load per eight symbols instead of eight
@@ -50,7 +27,8 @@ k_rans_encode(const uint16_t *__restrict__ idx, long n, int T, int seg, int nseg
               uint16_t *__restrict__ words, uint32_t *__restrict__ sizes) {
     __shared__ uint32_t fc_l[2048];
     const long s = blockIdx.y;                                   // stream
-    stage_tables(freq + s * T, T, fc_l, nullptr);
+    stage_segment_table<true>(freq + s * T, T, fc_l, nullptr);
+    __syncthreads();
     const int g = blockIdx.x * kRansThreads + threadIdx.x;       // segment within the stream
     if (g >= nseg) return;
     const long a = (long)g * seg;
@@ -91,7 +69,8 @@ k_rans_sizes(const uint16_t *__restrict__ idx, long n, int T, int seg, int nseg,
              uint32_t *__restrict__ sizes) {
     __shared__ uint32_t fc_l[2048];
     const long s = blockIdx.y;                                   // stream
-    stage_tables(freq + s * T, T, fc_l, nullptr);
+    stage_segment_table<true>(freq + s * T, T, fc_l, nullptr);
+    __syncthreads();
     const int g = blockIdx.x * kRansThreads + threadIdx.x;       // segment within the stream
     if (g >= nseg) return;
     const long a = (long)g * seg;
@@ -121,7 +100,8 @@ k_rans_sizes(const uint16_t *__restrict__ idx, long n, int T, int seg, int nseg,
 // Untrusted input: the segment sizes and words may come from a damaged or foreign file.  Every read is kept
 // inside the segment's (seg + 2)-word buffer and every decoded symbol below T; what is wrong is reported in
 // *status (bit 0: a segment size outside [2, seg + 2]; bit 1: a segment ran out of words; bit 2: words left
-// over or a final state other than the encoder's start state; bit 3: a frequency row that does not sum to 2^15).
+// over or a final state other than the encoder's start state -- SegmentReader; bit 3: a frequency row that does
+// not sum to 2^15 -- stage_segment_table).
 __global__ void __launch_bounds__(kRansThreads)
 k_rans_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict__ sizes, long n, int T, int seg, int nseg,
               const uint16_t *__restrict__ freq, uint16_t *__restrict__ idx, uint32_t *__restrict__ status) {
@@ -131,17 +111,12 @@ k_rans_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict__ s
     // up (a bucket of 16 slots holds 1 symbol on average), instead of 11 dependent LDS reads of a bisection
     __shared__ uint16_t start[(1 << kPB) / 16];
     const long s = blockIdx.y;
-    stage_tables(freq + s * T, T, fc_l, c_l);
+    stage_segment_table<true>(freq + s * T, T, fc_l, c_l);
+    __syncthreads();
     const bool table_ok = c_l[T] == (uint16_t)(1u << kPB);
     if (table_ok) {
         for (int bkt = threadIdx.x; bkt < (1 << kPB) / 16; bkt += kRansThreads) {
-            const unsigned slot = 16u * bkt;
-            int lo = 0, hi = T;                                  // last symbol with cum <= slot
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (c_l[mid] <= slot) lo = mid; else hi = mid;
-            }
-            start[bkt] = (uint16_t)lo;
+            start[bkt] = bucket_start(c_l, T, 16u * bkt);
         }
     }
     __syncthreads();
@@ -159,17 +134,13 @@ k_rans_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict__ s
         if (status) atomicOr(status, bad);
         return;
     }
-    int k = (int)k0;
-    unsigned x = ((unsigned)in[k - 1] << 16) | in[k - 2];
-    k -= 2;
+    SegmentReader rd;
+    rd.open(in, k0);
     bool starved = false;
     auto get = [&]() -> unsigned {                               // one symbol; after a starved stream: zeros
         if (starved) return 0u;
-        const unsigned lo = rans_pop(x, start, c_l, fc_l);
-        if (x < kRansL) {
-            if (k == 0) { bad |= 2u; starved = true; }           // a valid stream never renormalises past its first word
-            else x = (x << 16) | in[--k];
-        }
+        const unsigned lo = rans_pop(rd.x, start, c_l, fc_l);
+        if (!rd.refill()) { bad |= 2u; starved = true; }
         return lo;
     };
     long i = a;
@@ -185,7 +156,7 @@ k_rans_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict__ s
         }
     }
     for (; i < b; ++i) dst[i] = (uint16_t)get();
-    if (!bad && (k != 0 || x != kRansL)) bad |= 4u;              // the encoder started from kRansL with no words written
+    if (!bad && !rd.clean()) bad |= 4u;
     if (bad && status) atomicOr(status, bad);
 }
 
@@ -293,28 +264,18 @@ k_copy_segments(const uint16_t *__restrict__ src, const SizeT *__restrict__ size
     for (; j < (int)k; j += 64) d[j] = s[j];
 }
 
-// The sizes every entry point over (n_streams, n, N, seg) accepts (pack / unpack / the value decoder take other arguments and
-// word their own messages).
-int check_seg(const char *who, int64_t n_streams, int64_t n, int32_t N, int32_t seg) {
-    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && N >= 1 && N <= 10 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
-                VBQ_ERR_INVALID_ARGUMENT, "%s: bad sizes n_streams=%lld n=%lld N=%d seg=%d", who, (long long)n_streams,
-                (long long)n, N, seg);
-    return VBQ_OK;
-}
-
 }  // namespace
 }  // namespace vbq
 
 extern "C" int vbq_rans_encode_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t seg,
                                    const uint16_t *d_freq, uint16_t *d_words, uint32_t *d_sizes, void *stream) {
     using namespace vbq;
-    if (int r = check_seg("vbq_rans_encode_u16", n_streams, n, N, seg)) return r;
+    int64_t nseg;
+    if (int r = check_segments("vbq_rans_encode_u16", n_streams, n, N, seg, nseg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_idx && d_freq && d_words && d_sizes, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_encode_u16: null pointer argument");
-    const int64_t nseg = (n + seg - 1) / seg;
-    hipLaunchKernelGGL(k_rans_encode, dim3((unsigned)((nseg + kRansThreads - 1) / kRansThreads), (unsigned)n_streams),
-                       dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream), d_idx, (long)n, table_size(N), (int)seg,
-                       (int)nseg, d_freq, d_words, d_sizes);
+    hipLaunchKernelGGL(k_rans_encode, segment_grid(nseg, n_streams), dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream),
+                       d_idx, (long)n, table_size(N), (int)seg, (int)nseg, d_freq, d_words, d_sizes);
     VBQ_CHECK_LAUNCH("rans_encode");
     return VBQ_OK;
 }
@@ -322,15 +283,12 @@ extern "C" int vbq_rans_encode_u16(const uint16_t *d_idx, int64_t n_streams, int
 extern "C" int vbq_rans_sizes_u16(const uint16_t *d_idx, int64_t n_streams, int64_t n, int32_t N, int32_t seg,
                                   const uint16_t *d_freq, uint32_t *d_sizes, void *stream) {
     using namespace vbq;
-    if (int r = check_seg("vbq_rans_sizes_u16", n_streams, n, N, seg)) return r;
+    int64_t nseg;
+    if (int r = check_segments("vbq_rans_sizes_u16", n_streams, n, N, seg, nseg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_idx && d_freq && d_sizes, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_sizes_u16: null pointer argument");
-    const int64_t nseg = (n + seg - 1) / seg;
-    VBQ_REQUIRE(nseg <= INT32_MAX, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_sizes_u16: %lld segments per stream are too many",
-                (long long)nseg);
-    hipLaunchKernelGGL(k_rans_sizes, dim3((unsigned)((nseg + kRansThreads - 1) / kRansThreads), (unsigned)n_streams),
-                       dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream), d_idx, (long)n, table_size(N), (int)seg,
-                       (int)nseg, d_freq, d_sizes);
+    hipLaunchKernelGGL(k_rans_sizes, segment_grid(nseg, n_streams), dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream),
+                       d_idx, (long)n, table_size(N), (int)seg, (int)nseg, d_freq, d_sizes);
     VBQ_CHECK_LAUNCH("rans_sizes");
     return VBQ_OK;
 }
@@ -339,13 +297,12 @@ extern "C" int vbq_rans_decode_u16(const uint16_t *d_words, const uint32_t *d_si
                                    int32_t N, int32_t seg, const uint16_t *d_freq, uint16_t *d_idx, uint32_t *d_status,
                                    void *stream) {
     using namespace vbq;
-    if (int r = check_seg("vbq_rans_decode_u16", n_streams, n, N, seg)) return r;
+    int64_t nseg;
+    if (int r = check_segments("vbq_rans_decode_u16", n_streams, n, N, seg, nseg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_idx && d_freq && d_words && d_sizes, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_decode_u16: null pointer argument");
-    const int64_t nseg = (n + seg - 1) / seg;
-    hipLaunchKernelGGL(k_rans_decode, dim3((unsigned)((nseg + kRansThreads - 1) / kRansThreads), (unsigned)n_streams),
-                       dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream), d_words, d_sizes, (long)n, table_size(N),
-                       (int)seg, (int)nseg, d_freq, d_idx, d_status);
+    hipLaunchKernelGGL(k_rans_decode, segment_grid(nseg, n_streams), dim3(kRansThreads), 0, reinterpret_cast<hipStream_t>(stream),
+                       d_words, d_sizes, (long)n, table_size(N), (int)seg, (int)nseg, d_freq, d_idx, d_status);
     VBQ_CHECK_LAUNCH("rans_decode");
     return VBQ_OK;
 }
@@ -410,6 +367,8 @@ namespace {
 //   k_rans_decode_values  one lane per segment as k_rans_decode; the decoded rank indexes a value table in LDS.  The frequency
 //                         table may hold zeros (a model fitted to the data it codes: coder.exact_frequencies); the slot search
 //                         then still ends on the one symbol whose slot range holds the slot, as every empty range is skipped.
+//                         (Its staging stays its own: one pass also loads the values, rejects entries >= 2^15 before a
+//                         cumulative sum could overflow, and fills start[] from the ranges without a bisection.)
 constexpr int kFillThreads = 256;
 constexpr int kValThreads = 64;                                  // one wave: the table staging scans with wave shuffles alone
 
@@ -488,18 +447,13 @@ k_rans_decode_values(const uint16_t *__restrict__ payload, long n_words, const u
         if (status) atomicOr(status, bad);
         return;
     }
-    const uint16_t *in = payload + off;                          // reads stay in [off, off + k0) within [0, n_words)
-    int k = (int)k0;
-    unsigned x = ((unsigned)in[k - 1] << 16) | in[k - 2];
-    k -= 2;
+    SegmentReader rd;
+    rd.open(payload + off, k0);                                  // reads stay in [off, off + k0) within [0, n_words)
     bool starved = false;
     auto get = [&]() -> float {                                  // one value; after a starved stream: the value of symbol 0
         if (starved) return val_l[0];
-        const unsigned sym = rans_pop(x, start, c_l, fc_l);
-        if (x < kRansL) {
-            if (k == 0) { bad |= 2u; starved = true; }
-            else x = (x << 16) | in[--k];
-        }
+        const unsigned sym = rans_pop(rd.x, start, c_l, fc_l);
+        if (!rd.refill()) { bad |= 2u; starved = true; }
         return val_l[sym];
     };
     int j = 0;
@@ -512,7 +466,7 @@ k_rans_decode_values(const uint16_t *__restrict__ payload, long n_words, const u
         }
     }
     for (; j < len; ++j) dst[j] = get();
-    if (!bad && (k != 0 || x != kRansL)) bad |= 4u;
+    if (!bad && !rd.clean()) bad |= 4u;
     if (bad && status) atomicOr(status, bad);
 }
 

@@ -1,9 +1,9 @@
 // Class-mapped rANS: the segment coder of vbq_rans.hip with a frequency table that may change from symbol to symbol.  A class
 // map cls[i] in [0, P), P <= 4, shared by every stream, picks for symbol i of stream s the table d_freq[cls[i]][s] -- one latent
-// tensor coded at several lambdas (the lambda map of a VBQm file, vbq_amd/bitstream.py).  Format, constants and the per-symbol
-// state updates are the segment coder's (include/vbq.h; vbq_rans_common.h): one lane per segment, the 64 segments of a
-// workgroup belong to one stream, symbols are coded last to first.  A segment whose symbols all have class p comes out word for
-// word what vbq_rans_encode_u16 writes with row d_freq[p][s].
+// tensor coded at several lambdas (the lambda map of a VBQm file, vbq_amd/bitstream.py).  Format, constants, the per-symbol
+// state updates, table staging, the bucket table, the segment reader and the size check are the segment coder's (include/vbq.h;
+// vbq_rans_common.h): one lane per segment, the 64 segments of a workgroup belong to one stream, symbols are coded last to
+// first.  A segment whose symbols all have class p comes out word for word what vbq_rans_encode_u16 writes with row d_freq[p][s].
 //
 // Tables in LDS, per class, only the n_classes in use (dynamic LDS, sized by the launch):
 //   encoder / sizes   fc[sym] = f | c << 16                                    8 KB per class
@@ -19,30 +19,6 @@ constexpr int kMapMaxClasses = 4;
 constexpr int kMapT = 2048;                                      // table stride in LDS (T <= 2047)
 constexpr int kMapCStride = kMapT + 2;                           // c[0..T], an even count of u16
 constexpr int kMapBuckets = (1 << kPB) / 16;
-
-// Exclusive cumulative frequencies of one table by one wave, each lane a contiguous chunk: fc[i] = f | c << 16 when fc_l is
-// given, c alone with c_l[T] = 2^15 (0 for a row that does not sum to 2^15) when c_l is.
-__device__ __forceinline__ void map_stage_table(const uint16_t *__restrict__ freq, int T, uint32_t *fc_l, uint16_t *c_l) {
-    const int lane = threadIdx.x;
-    const int per = (T + kMapThreads - 1) / kMapThreads;
-    const int i0 = min(T, lane * per), i1 = min(T, (lane + 1) * per);
-    unsigned sum = 0;
-    for (int i = i0; i < i1; ++i) sum += freq[i];
-    unsigned incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    unsigned run = incl - sum;
-    for (int i = i0; i < i1; ++i) {
-        const unsigned f = freq[i];
-        if (fc_l) fc_l[i] = f | (run << 16);
-        if (c_l) c_l[i] = (uint16_t)run;                         // (an invalid row may overflow 16 bits: rejected through c_l[T])
-        run += f;
-    }
-    if (lane == 63 && c_l) c_l[T] = (uint16_t)(incl == (1u << kPB) ? incl : 0u);
-}
 
 struct MapEncodeArgs {
     const uint16_t *idx;                                         // [n_planes][S][n]
@@ -62,7 +38,7 @@ __global__ void __launch_bounds__(kMapThreads) k_rans_map_encode(const MapEncode
     extern __shared__ uint32_t map_fc_l[];                       // [P][kMapT]
     const long s = blockIdx.y;
     const int T = a.T, P = a.P;
-    for (int p = 0; p < P; ++p) map_stage_table(a.freq + ((long)p * a.S + s) * T, T, map_fc_l + p * kMapT, nullptr);
+    for (int p = 0; p < P; ++p) stage_segment_table<true>(a.freq + ((long)p * a.S + s) * T, T, map_fc_l + p * kMapT, nullptr);
     __syncthreads();
     const int g = blockIdx.x * kMapThreads + threadIdx.x;
     if (g >= a.nseg) return;
@@ -127,20 +103,14 @@ k_rans_map_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict
     uint16_t *c_all = map_dec_l;
     uint16_t *start_all = map_dec_l + P * kMapCStride;
     const long s = blockIdx.y;
-    for (int p = 0; p < P; ++p) map_stage_table(freq + ((long)p * S + s) * T, T, nullptr, c_all + p * kMapCStride);
+    for (int p = 0; p < P; ++p) stage_segment_table<false>(freq + ((long)p * S + s) * T, T, nullptr, c_all + p * kMapCStride);
     __syncthreads();
     bool table_ok = true;
     for (int p = 0; p < P; ++p) table_ok &= c_all[p * kMapCStride + T] == (uint16_t)(1u << kPB);
     if (table_ok) {
         for (int t = threadIdx.x; t < P * kMapBuckets; t += kMapThreads) {
             const uint16_t *c_l = c_all + (t / kMapBuckets) * kMapCStride;
-            const unsigned slot = 16u * (t % kMapBuckets);
-            int lo = 0, hi = T;                                  // last symbol with c <= slot
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (c_l[mid] <= slot) lo = mid; else hi = mid;
-            }
-            start_all[t] = (uint16_t)lo;
+            start_all[t] = bucket_start(c_l, T, 16u * (t % kMapBuckets));
         }
     }
     __syncthreads();
@@ -158,18 +128,14 @@ k_rans_map_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict
         if (status) atomicOr(status, bad);
         return;
     }
-    int k = (int)k0;
-    unsigned x = ((unsigned)in[k - 1] << 16) | in[k - 2];
-    k -= 2;
+    SegmentReader rd;
+    rd.open(in, k0);
     bool dead = false;                                           // starved, or a class outside the palette: zeros from here on
     auto get = [&](unsigned c) -> unsigned {                     // one symbol of class c
         if (dead) return 0u;
         if (c >= (unsigned)P) { bad |= 64u; dead = true; return 0u; }
-        const unsigned sym = rans_pop(x, start_all + c * kMapBuckets, c_all + c * kMapCStride);
-        if (x < kRansL) {
-            if (k == 0) { bad |= 2u; dead = true; }              // a valid stream never renormalises past its first word
-            else x = (x << 16) | in[--k];
-        }
+        const unsigned sym = rans_pop(rd.x, start_all + c * kMapBuckets, c_all + c * kMapCStride);
+        if (!rd.refill()) { bad |= 2u; dead = true; }
         return sym;
     };
     long i = a;
@@ -188,31 +154,27 @@ k_rans_map_decode(const uint16_t *__restrict__ words, const uint32_t *__restrict
     for (; i < b; ++i) dst[i] = (uint16_t)get(cls[i]);
     if (bad & 64u)
         for (long j = a; j < b; ++j) dst[j] = 0;                 // the whole segment, what came before the bad class too
-    if (!bad && (k != 0 || x != kRansL)) bad |= 4u;              // the encoder started from kRansL with no words written
+    if (!bad && !rd.clean()) bad |= 4u;
     if (bad && status) atomicOr(status, bad);
 }
 
-// What the three entry points take alike, before any device work.
-int map_check(const char *who, int32_t n_planes, int32_t n_classes, int64_t n_streams, int64_t n, int32_t N, int32_t seg) {
+// What the three entry points take alike, before any device work: the palette, then the segment coder's sizes.
+int map_check(const char *who, int32_t n_planes, int32_t n_classes, int64_t n_streams, int64_t n, int32_t N, int32_t seg,
+              int64_t &nseg) {
     VBQ_REQUIRE(n_classes >= 1 && n_classes <= kMapMaxClasses, VBQ_ERR_INVALID_ARGUMENT, "%s: n_classes = %d outside [1, %d]", who,
                 n_classes, kMapMaxClasses);
     VBQ_REQUIRE(n_planes == 1 || n_planes == n_classes, VBQ_ERR_INVALID_ARGUMENT, "%s: n_planes = %d is neither 1 nor n_classes = %d",
                 who, n_planes, n_classes);
-    VBQ_REQUIRE(n_streams >= 0 && n >= 0 && N >= 1 && N <= 10 && seg >= 1 && seg <= 65533 && n_streams <= 65535,
-                VBQ_ERR_INVALID_ARGUMENT, "%s: bad sizes n_streams=%lld n=%lld N=%d seg=%d", who, (long long)n_streams, (long long)n, N,
-                seg);
-    VBQ_REQUIRE((n + seg - 1) / seg <= INT32_MAX, VBQ_ERR_INVALID_ARGUMENT, "%s: %lld segments per stream are too many", who,
-                (long long)((n + seg - 1) / seg));
-    return VBQ_OK;
+    return check_segments(who, n_streams, n, N, seg, nseg);
 }
 
 template <bool kWords>
 int map_encode(const char *who, const uint16_t *d_idx, int32_t n_planes, const uint8_t *d_cls, int32_t n_classes, int64_t n_streams,
                int64_t n, int32_t N, int32_t seg, const uint16_t *d_freq, uint16_t *d_words, uint32_t *d_sizes, void *stream) {
-    if (int r = map_check(who, n_planes, n_classes, n_streams, n, N, seg)) return r;
+    int64_t nseg;
+    if (int r = map_check(who, n_planes, n_classes, n_streams, n, N, seg, nseg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_idx && d_cls && d_freq && d_sizes && (d_words || !kWords), VBQ_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
-    const int64_t nseg = (n + seg - 1) / seg;
     MapEncodeArgs a = {};
     a.idx = d_idx;
     a.cls = d_cls;
@@ -226,8 +188,8 @@ int map_encode(const char *who, const uint16_t *d_idx, int32_t n_planes, const u
     a.T = table_size(N);
     a.seg = seg;
     a.nseg = (int)nseg;
-    hipLaunchKernelGGL(k_rans_map_encode<kWords>, dim3((unsigned)((nseg + kMapThreads - 1) / kMapThreads), (unsigned)n_streams),
-                       dim3(kMapThreads), (size_t)n_classes * kMapT * sizeof(uint32_t), reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(k_rans_map_encode<kWords>, segment_grid(nseg, n_streams), dim3(kMapThreads),
+                       (size_t)n_classes * kMapT * sizeof(uint32_t), reinterpret_cast<hipStream_t>(stream), a);
     VBQ_CHECK_LAUNCH(who);
     return VBQ_OK;
 }
@@ -254,12 +216,12 @@ extern "C" int vbq_rans_map_decode_u16(const uint16_t *d_words, const uint32_t *
                                        uint16_t *d_idx, uint32_t *d_status, void *stream) {
     using namespace vbq;
     const char *who = "vbq_rans_map_decode_u16";
-    if (int r = map_check(who, 1, n_classes, n_streams, n, N, seg)) return r;
+    int64_t nseg;
+    if (int r = map_check(who, 1, n_classes, n_streams, n, N, seg, nseg)) return r;
     if (n_streams == 0 || n == 0) return VBQ_OK;
     VBQ_REQUIRE(d_words && d_sizes && d_cls && d_freq && d_idx, VBQ_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
-    const int64_t nseg = (n + seg - 1) / seg;
-    hipLaunchKernelGGL(k_rans_map_decode, dim3((unsigned)((nseg + kMapThreads - 1) / kMapThreads), (unsigned)n_streams),
-                       dim3(kMapThreads), (size_t)n_classes * (kMapCStride + kMapBuckets) * sizeof(uint16_t),
+    hipLaunchKernelGGL(k_rans_map_decode, segment_grid(nseg, n_streams), dim3(kMapThreads),
+                       (size_t)n_classes * (kMapCStride + kMapBuckets) * sizeof(uint16_t),
                        reinterpret_cast<hipStream_t>(stream), d_words, d_sizes, d_cls, (int)n_classes, (int)n_streams, (long)n,
                        table_size(N), (int)seg, (int)nseg, d_freq, d_idx, d_status);
     VBQ_CHECK_LAUNCH(who);
