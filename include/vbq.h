@@ -916,6 +916,48 @@ int vbq_records_bag_f32(const uint32_t *d_words, int64_t n_rows, int32_t K, int3
 int vbq_bag_f32(const float *d_emb, int64_t V, int32_t K, const int64_t *d_ids, int64_t n_ids, const int64_t *d_offsets,
                 int64_t n_bags, const float *d_weights, int32_t mode, float *d_out, uint32_t *d_status, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Window decode: a box of one latent file in segments (vbq_amd/bitstream.py, magic "VBQb"), or the same-sized boxes of
+ * many files, in ONE launch, straight from the packed payloads into channel-last f32 values -- the latent-side counterpart
+ * of vbq_rans_decode_values_f32 with a table per (file, channel) and several files per launch.
+ *   d_payload  u16 [n_words]: the payloads of all files, concatenated in file order.
+ *   d_sizes    u16 [M]: all files' segment sizes, concatenated in the same order; d_offsets int64 [M] their exclusive prefix
+ *              sum (vbq_rans_segment_offsets_u16 over the concatenation), so that an offset addresses d_payload directly.
+ *   d_files    int64 [n_files][8], per file: seg_base, n, D1, D2, a0, a1, a2, table.  A file's stream is n symbols per
+ *              channel, n = D0 D1 D2; row b = (i0 D1 + i1) D2 + i2.  Segment g of channel c is entry seg_base + c nseg_f + g
+ *              of d_sizes / d_offsets, nseg_f = ceil(n / seg).  The box of the file is [a0, a0 + w0) x [a1, a1 + w1) x
+ *              [a2, a2 + w2); its extents w0, w1, w2 are the same for every file.  `table` picks the block of d_freq (the
+ *              file's lambda).
+ *   d_segs     int32 [n_files][n_sel]: per file the segment ids within a stream to decode (the same for every channel), any
+ *              order; -1 is padding and skipped silently.
+ *   d_channels int32 [n_ch_sel]: the channels to decode, any order, repeats allowed; NULL = all n_ch in order (n_ch_sel must
+ *              then be n_ch).
+ *   d_freq     u16 [n_tables][n_ch][T], T = 2^(N+1) - 1, every row summing to 2^15; d_values f32 [n_ch][T], the sorted code
+ *              points.
+ *   d_out      f32 [n_files][w0][w1][w2][n_ch_sel].  One lane decodes one listed segment in full, first symbol to last (so
+ *              the end-state check holds as in vbq_rans_decode_u16), and for every symbol inside the box stores
+ *              d_values[c][symbol] at d_out[f][i0 - a0][i1 - a1][i2 - a2][j], j the channel's place in d_channels.
+ *              Positions of the box that no listed segment covers are left untouched.
+ *   d_status   u32 [n_files], may be NULL, OR-ed into; zero it first.  Per file: bits 0 - 3 as vbq_rans_decode_u16 (a segment
+ *              whose words do not lie in [0, n_words) counts as bit 0); bit 5 (32) a listed id outside [0, nseg_f), or
+ *              seg_base + c nseg_f + g outside [0, M); bit 7 (128) an inconsistent descriptor -- n not a multiple of D1 D2,
+ *              a box outside the dimensions, `table` outside [0, n_tables) -- or a channel outside [0, n_ch): nothing of that
+ *              file is written.  Segments with bits 0 / 3 write zeros at their positions inside the box; with bits 1 / 2
+ *              what the segment wrote is meaningless.
+ * Payload, sizes and offsets are UNTRUSTED, with the rules of vbq_rans_decode_values_f32: no read leaves [off, off + size)
+ * within [0, n_words), no write leaves d_out, every decoded symbol is below T.
+ * Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): n_files <= 65535, n_ch_sel <= 65535, seg in 1..65533, N in
+ * 1..10, n_ch >= 1, n_tables >= 1, every other size >= 0, an output whose byte count fits in 63 bits, no null pointer
+ * (d_channels, d_status and, with n_words == 0, d_payload excepted).  n_files == 0, n_sel == 0, n_ch_sel == 0 or an empty
+ * box return VBQ_OK with no launch.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_decode_window_f32(const uint16_t *d_payload, int64_t n_words, const uint16_t *d_sizes, const int64_t *d_offsets,
+                               int64_t M, const int64_t *d_files, int32_t n_files, const int32_t *d_segs, int32_t n_sel,
+                               const int32_t *d_channels, int32_t n_ch_sel, int32_t n_ch, int32_t seg, int32_t N,
+                               const uint16_t *d_freq, int32_t n_tables, const float *d_values, int64_t w0, int64_t w1,
+                               int64_t w2, float *d_out, uint32_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,10 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p]),
     "vbq_bag_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vbq_rans_decode_window_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
 }
 
 

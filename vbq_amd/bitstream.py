@@ -322,6 +322,101 @@ def parse_latent(data):
     return _parse_latent(data, CompactHeader if compact else Header)
 
 
+# ---- windows of a file in segments (ChannelwisePriorCDFQuantizer.decompress_latents_window / _batch; include/vbq.h, "Window
+# decode").  The leading axes of a latent tensor (its shape without the channel axis) number the rows of every stream in row
+# order; a region is one slice per leading axis, and the kernel follows a row's position in at most three nested levels.
+def _region_axes(leading_shape, region):
+    """The region normalised -> [(d, start, stop)] per leading axis, stop >= start."""
+    shape = tuple(int(d) for d in leading_shape)
+    if any(d < 1 for d in shape):
+        raise ValueError(f"empty leading shape {shape}")
+    region = () if region is None else (region,) if isinstance(region, slice) else tuple(region)
+    if len(region) > len(shape):
+        raise ValueError(f"a region of {len(region)} slices for {len(shape)} leading axes")
+    axes = []
+    for axis, d in enumerate(shape):
+        sl = region[axis] if axis < len(region) else slice(None)
+        if not isinstance(sl, slice):
+            raise ValueError(f"region entry {axis} is {type(sl).__name__}, not a slice (an index would drop the axis)")
+        if sl.step not in (None, 1):
+            raise ValueError(f"region entry {axis} has step {sl.step}: only step 1 is a box")
+        try:
+            s, e, _ = sl.indices(d)
+        except TypeError as err:
+            raise ValueError(f"region entry {axis}: {err}") from None
+        axes.append((d, s, max(e, s)))
+    return axes
+
+
+def _collapse(axes, full=None):
+    """Nested levels [(D, lo, hi)] of a normalised region, greedily: an axis merges into the level before it when it is taken in
+    full (full[axis] where given: several files that must share one collapse) or when that level has extent 1."""
+    levels = []
+    for axis, (d, s, e) in enumerate(axes):
+        whole = (s == 0 and e == d) if full is None else full[axis]
+        if levels and (whole or levels[-1][2] - levels[-1][1] == 1):
+            D, lo, hi = levels[-1]
+            levels[-1] = (D * d, lo * d + s, (hi - 1) * d + e)
+        else:
+            levels.append((d, s, e))
+    return levels
+
+
+def _three_levels(levels):
+    if len(levels) > 3:
+        raise ValueError(f"the region needs {len(levels)} nested levels, the window decode has three: take more axes in full "
+                         "or at extent 1")
+    levels = [(1, 0, 1)] * (3 - len(levels)) + levels
+    return tuple(tuple(int(l[k]) for l in levels) for k in range(3))
+
+
+def region_box(leading_shape, region):
+    """A region of the leading axes -> (dims, lo, hi, extents): the box [lo[k], hi[k]) in a geometry of three nested levels
+    dims = (D0, D1, D2) with prod(dims) == prod(leading_shape) and row b = (i0 D1 + i1) D2 + i2, and the extent of every
+    ORIGINAL axis (the shape of the result).  `region` is a tuple of slices of step 1 or None, one per leading axis, normalised
+    as slice.indices does; fewer than the axes leaves the trailing axes full.  ValueError for an int, another step, too many
+    entries, and for a region that does not collapse to three levels."""
+    axes = _region_axes(leading_shape, region)
+    dims, lo, hi = _three_levels(_collapse(axes))
+    return dims, lo, hi, tuple(e - s for _, s, e in axes)
+
+
+def region_boxes(leading_shapes, regions):
+    """region_box for several files whose boxes must have the same extents at every LEVEL (one launch decodes them all):
+    -> ([(dims, lo, hi)] per file, extents).  The files share one collapse -- an axis merges when EVERY file takes it in full,
+    or into a level of extent 1 -- so files of different shapes still agree on the box.  ValueError when the extents differ."""
+    axes = [_region_axes(shape, region) for shape, region in zip(leading_shapes, regions)]
+    if not axes:
+        return [], ()
+    extents = [tuple(e - s for _, s, e in a) for a in axes]
+    for i, ext in enumerate(extents):
+        if ext != extents[0]:
+            raise ValueError(f"file {i}: a region of extents {ext}, file 0 has {extents[0]}: one call decodes boxes of one shape")
+    full = [all(a[k][1] == 0 and a[k][2] == a[k][0] for a in axes) for k in range(len(axes[0]))]
+    return [_three_levels(_collapse(a, full)) for a in axes], extents[0]
+
+
+def box_segments(dims, lo, hi, segment) -> np.ndarray:
+    """The segments of `segment` symbols that hold at least one row of the box (region_box) -> int32, ascending."""
+    check_segment(segment)
+    dims, lo, hi = (tuple(int(v) for v in t) for t in (dims, lo, hi))
+    if not (len(dims) == len(lo) == len(hi) == 3) or any(not 0 <= l <= h <= d for d, l, h in zip(dims, lo, hi)):
+        raise ValueError(f"box [{lo}, {hi}) does not lie in {dims}")
+    if any(h == l for l, h in zip(lo, hi)):
+        return np.zeros(0, np.int32)
+    nseg = (math.prod(dims) + segment - 1) // segment
+    if nseg > np.iinfo(np.int32).max:
+        raise ValueError(f"{nseg} segments per stream are too many")
+    # one run of consecutive rows per (i0, i1) of the box; the union of their segment ranges through a difference array
+    i0 = np.arange(lo[0], hi[0], dtype=np.int64)[:, None]
+    i1 = np.arange(lo[1], hi[1], dtype=np.int64)[None, :]
+    first = ((i0 * dims[1] + i1) * dims[2]).reshape(-1)
+    mark = np.zeros(nseg + 1, np.int64)
+    np.add.at(mark, (first + lo[2]) // segment, 1)
+    np.add.at(mark, (first + hi[2] - 1) // segment + 1, -1)
+    return np.flatnonzero(np.cumsum(mark[:-1]) > 0).astype(np.int32)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # The lambda-map latent file: ONE latent tensor coded at up to four lambdas (ChannelwisePriorCDFQuantizer.
 # compress_latents_to_bytes_mapped).  A palette of P lambdas and a class per latent POSITION (the latent shape without its

@@ -111,13 +111,14 @@ def ideal_bits(counts, freq, prob_bits: int = PROB_BITS) -> float:
 
 
 def _raise_status(st: int):
-    """The OR-ed status word of vbq_rans_decode_u16 / vbq_rans_unpack_u16 / vbq_rans_map_decode_u16 -> VBQError (nothing
-    when 0)."""
+    """The OR-ed status word of vbq_rans_decode_u16 / vbq_rans_unpack_u16 / vbq_rans_map_decode_u16 /
+    vbq_rans_decode_window_f32 -> VBQError (nothing when 0)."""
     if st:
         what = [m for b, m in ((1, "segment size out of range"), (2, "segment ran out of words"),
                                (4, "left-over words / wrong final state"), (8, "invalid frequency table"),
                                (16, "segment sizes do not add up to the payload length"),
-                               (32, "segment id out of range"), (64, "class outside the palette")) if st & b]
+                               (32, "segment id out of range"), (64, "class outside the palette"),
+                               (128, "inconsistent window descriptor")) if st & b]
         raise _lib.VBQError("rANS bitstream rejected: " + ", ".join(what))
 
 

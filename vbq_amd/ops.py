@@ -853,3 +853,58 @@ def bag(emb: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, *, weights:
     check(_lib.lib().vbq_bag_f32(_ptr(emb), V, K, _ptr(ids), ids.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(weights), mode,
                                  _ptr(out), _ptr(status), _stream(emb)), "vbq_bag_f32")
     return out
+
+
+WINDOW_BAD_SEGMENT, WINDOW_BAD_FILE = 32, 128    # status bits 5 and 7 of the window decode (bits 0..3: the segment decoder's)
+
+
+def rans_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: torch.Tensor, files: torch.Tensor,
+                       segs: torch.Tensor, freq: torch.Tensor, values: torch.Tensor, box: Sequence[int], *, seg: int, N: int = 10,
+                       channels: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None):
+    """vbq_rans_decode_window_f32 (include/vbq.h, "Window decode"): the box of extents box = (w0, w1, w2) of every listed file,
+    straight from the concatenated payloads.  payload u16 [n_words]; sizes u16 [M] and offsets int64 [M] (their exclusive prefix
+    sum) over all files; files int64 [F, 8] (seg_base, n, D1, D2, a0, a1, a2, table); segs int32 [F, n_sel], -1 = skip; freq
+    u16 [n_tables, C, T]; values f32 [C, T]; channels int32 [C_sel] or None for all C in order.  Returns (out f32
+    [F, w0, w1, w2, C_sel], status u32 [F]); positions no listed segment covers keep what `out` held.  `status` is OR-ed into:
+    zeroed here unless given."""
+    payload = _dev(payload, torch.uint16, "payload")
+    sizes = _dev(sizes, torch.uint16, "sizes")
+    offsets = _dev(offsets, torch.int64, "offsets")
+    files = _dev(files, torch.int64, "files")
+    segs = _dev(segs, torch.int32, "segs")
+    freq = _dev(freq, torch.uint16, "freq")
+    values = _dev(values, torch.float32, "values")
+    seg, N = int(seg), int(N)
+    T = table_size(N)
+    if payload.dim() != 1 or sizes.dim() != 1 or offsets.shape != sizes.shape:
+        raise ValueError(f"expected payload [n_words], sizes [M] and offsets [M], got {tuple(payload.shape)}, {tuple(sizes.shape)} "
+                         f"and {tuple(offsets.shape)}")
+    if files.dim() != 2 or files.shape[1] != 8:
+        raise ValueError(f"files must be [F, 8] (seg_base, n, D1, D2, a0, a1, a2, table), got {tuple(files.shape)}")
+    F = files.shape[0]
+    if segs.dim() != 2 or segs.shape[0] != F:
+        raise ValueError(f"segs must be [F = {F}, n_sel], got {tuple(segs.shape)}")
+    if freq.dim() != 3 or freq.shape[2] != T or values.dim() != 2 or tuple(values.shape) != tuple(freq.shape[1:]):
+        raise ValueError(f"expected freq [n_tables, C, {T}] and values [C, {T}], got {tuple(freq.shape)} and {tuple(values.shape)}")
+    n_tables, n_ch = freq.shape[0], freq.shape[1]
+    if channels is not None:
+        channels = _dev(channels, torch.int32, "channels")
+        if channels.dim() != 1:
+            raise ValueError(f"channels must be one-dimensional, got shape {tuple(channels.shape)}")
+    n_ch_sel = n_ch if channels is None else channels.numel()
+    box = tuple(int(w) for w in box)
+    if len(box) != 3 or min(box) < 0:
+        raise ValueError(f"box must be three extents >= 0, got {box}")
+    if status is None:
+        status = torch.zeros(F, dtype=torch.uint32, device=payload.device)
+    else:
+        status = _dev(status, torch.uint32, "status")
+        if status.numel() != F:
+            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+    out = _out(out, (F,) + box + (n_ch_sel,), torch.float32, payload.device, "out")
+    check(_lib.lib().vbq_rans_decode_window_f32(_ptr(payload), payload.numel(), _ptr(sizes), _ptr(offsets), sizes.numel(),
+                                                _ptr(files), F, _ptr(segs), segs.shape[1], _ptr(channels), n_ch_sel, n_ch, seg,
+                                                N, _ptr(freq), n_tables, _ptr(values), box[0], box[1], box[2], _ptr(out),
+                                                _ptr(status), _stream(payload)), "vbq_rans_decode_window_f32")
+    return out, status

@@ -752,6 +752,133 @@ class ChannelwisePriorCDFQuantizer:
         zhat = zhat.reshape(h.shape)
         return zhat.cpu().numpy() if return_np else zhat
 
+    # ------------------------------------------------------------------ windows and batches (include/vbq.h, "Window decode")
+    def _window_headers(self, files):
+        """The parsed headers of `files` with the checks of decompress_latents on each, (headers, sizes, payload offsets, keys);
+        ValueError naming the index of a file that is no b"VBQb" file of this quantizer or has another segment."""
+        heads, sizes, starts, keys = [], [], [], []
+        for i, data in enumerate(files):
+            magic = bytes(memoryview(data).cast("B")[:4])
+            foreign = {bitstream.COMPACT_MAGIC: "a compact file (magic b'VBQc'): its parts are not addressable",
+                       bitstream.MAPPED_MAGIC: "a lambda-map file (magic b'VBQm'): it has a table per symbol"}.get(magic)
+            if foreign:
+                raise ValueError(f"file {i} is {foreign}; windows and batches read files in segments (magic b'VBQb')")
+            try:
+                h, sz, start = bitstream.parse(data)
+            except ValueError as e:
+                raise ValueError(f"file {i}: {e}") from None
+            if h.N != self.max_bits_per_coord or h.C != self.num_channels:
+                raise ValueError(f"file {i} is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
+                                 f"C = {self.num_channels}")
+            if heads and h.segment != heads[0].segment:
+                raise ValueError(f"file {i} is in segments of {h.segment} symbols, file 0 in segments of {heads[0].segment}: "
+                                 "one call decodes files of one segment length")
+            key = self._lambda_key(h.lamb)
+            if self._coder_tables(key, h.segment)[1] != h.digest:
+                raise ValueError(f"file {i} was compressed with a different quantizer or entropy model (digest mismatch)")
+            heads.append(h), sizes.append(sz), starts.append(start), keys.append(key)
+        return heads, sizes, starts, keys
+
+    def decompress_latents_batch(self, files, regions=None, channels=None, return_np=False):
+        """The same-sized boxes of many latent files in ONE launch: f32 [F, *extents, C_sel], every value bit-identical to
+        decompress_latents(files[f])[regions[f]][..., channels].  `files`: b"VBQb" byte strings of this quantizer -- any built
+        lambdas and any latent shapes, one `segment`; each gets the checks of decompress_latents (ValueError naming the
+        file's index, KeyError for a lambda without a model).  `regions`: None (whole files, whose shapes must then agree), ONE
+        region for all files -- a tuple of slices of step 1, one per leading axis (bitstream.region_box) -- or a list with one
+        such tuple (or None) per file; the extents must agree.  `channels`: None or channel numbers, any order, repeats
+        allowed.  Work: one staging buffer and one upload, one vbq_rans_segment_offsets_u16 over all sizes, one
+        vbq_rans_decode_window_f32 over the segments that hold a row of a box, one read of the status words.  A damaged
+        file raises VBQError naming the index of the first one; damage in segments no box touches is not seen."""
+        from . import _lib, coder
+        plan = self._window_plan(files, regions, channels)
+        if plan.host is None:                                      # no file, no channel or an empty extent: nothing to launch
+            out = torch.empty(plan.shape, dtype=torch.float32, device=self.device)
+            return out.cpu().numpy() if return_np else out
+        out, status = self._window_run(plan, torch.from_numpy(plan.host).to(self.device))
+        st = status.cpu().numpy()
+        for f in np.flatnonzero(st[:-1]):
+            try:
+                coder._raise_status(int(st[f]))
+            except _lib.VBQError as e:
+                raise _lib.VBQError(f"file {int(f)}: {e}") from None
+        coder._raise_status(int(st[-1]))
+        return out.cpu().numpy() if return_np else out
+
+    _WindowPlan = namedtuple("_WindowPlan", "shape host cut F n_sel C_sel M n_words segment tables box")
+
+    def _window_plan(self, files, regions, channels):
+        """The host side of decompress_latents_batch: every check, the boxes, the segment lists and the ONE staging buffer
+        (plan.host, u8; None when there is nothing to decode): descriptors int64 [F, 8], segment lists int32 [F, n_sel] and
+        channels int32 [C_sel] (each padded to 8 bytes), then all sizes u16 [M], then all payloads u16 -- the last two straight
+        from the files.  plan.cut: where each part starts."""
+        self._check_coder_bits()
+        files = list(files)
+        F, C = len(files), self.num_channels
+        one = regions is None or isinstance(regions, slice) or (isinstance(regions, (tuple, list)) and
+                                                                 all(isinstance(r, slice) for r in regions))
+        regions = [regions] * F if one else list(regions)
+        if len(regions) != F:
+            raise ValueError(f"{len(regions)} regions for {F} files")
+        ch = None
+        if channels is not None:
+            ch = np.asarray(channels).reshape(-1)
+            if ch.size and (ch.dtype.kind not in "iu" or int(ch.min()) < 0 or int(ch.max()) >= C):
+                raise ValueError(f"channels must be integers in [0, {C})")
+            ch = ch.astype(np.int32)
+        C_sel = C if ch is None else int(ch.size)
+        heads, sizes, starts, keys = self._window_headers(files)
+        boxes, extents = bitstream.region_boxes([h.shape[:-1] for h in heads], regions)
+        shape = (F,) + tuple(extents) + (C_sel,)
+        if F == 0 or C_sel == 0 or 0 in extents:
+            return self._WindowPlan(shape, None, None, F, 0, C_sel, 0, 0, None, [], None)
+        segment = heads[0].segment
+        tables = sorted(set(keys), key=float)                      # (a stable tag for the codec cache of _coder_stack)
+        lists = [bitstream.box_segments(dims, lo, hi, segment) for dims, lo, hi in boxes]
+        n_sel = max(l.size for l in lists)
+        M, n_words = sum(h.n_sizes for h in heads), sum(h.n_words for h in heads)
+        desc = np.empty((F, 8), np.int64)
+        base = 0
+        for f, (h, (dims, lo, hi)) in enumerate(zip(heads, boxes)):
+            desc[f] = (base, h.n_rows, dims[1], dims[2], lo[0], lo[1], lo[2], tables.index(keys[f]))
+            base += h.n_sizes
+        seg_ids = np.full(F * n_sel + (F * n_sel & 1), -1, np.int32)
+        for f, l in enumerate(lists):
+            seg_ids[f * n_sel: f * n_sel + l.size] = l
+        chans = np.zeros(0, np.int32) if ch is None else np.concatenate([ch, np.zeros(C_sel & 1, np.int32)])
+        head = [desc.view(np.uint8).reshape(-1), seg_ids.view(np.uint8), chans.view(np.uint8)]
+        raws = [np.frombuffer(memoryview(d).cast("B"), dtype=np.uint8) for d in files]
+        host = np.concatenate(head + [r[h.nbytes: h.nbytes + 2 * h.n_sizes] for r, h in zip(raws, heads)]
+                              + [r[s: s + 2 * h.n_words] for r, h, s in zip(raws, heads, starts)])
+        cut = [int(c) for c in np.cumsum([0, head[0].size, head[1].size, head[2].size, 2 * M, 2 * n_words])]
+        box = tuple(h - l for l, h in zip(boxes[0][1], boxes[0][2]))
+        return self._WindowPlan(shape, host, cut, F, n_sel, C_sel, M, n_words, segment, tables, box)
+
+    def _window_run(self, plan, dev):
+        """The device side: `dev` is plan.host on the device.  One vbq_rans_segment_offsets_u16 over all sizes and one
+        vbq_rans_decode_window_f32 -> (out f32 plan.shape, status u32 [F + 1]: per file, then the scan's); nothing is read
+        back."""
+        from . import _lib
+        F, C, cut = plan.F, self.num_channels, plan.cut
+        d_files = dev[cut[0]:cut[1]].view(torch.int64).view(F, 8)
+        d_segs = dev[cut[1]:cut[1] + 4 * F * plan.n_sel].view(torch.int32).view(F, plan.n_sel)
+        d_ch = dev[cut[2]:cut[2] + 4 * plan.C_sel].view(torch.int32) if cut[3] > cut[2] else None
+        d_sizes, d_payload = dev[cut[3]:cut[4]].view(torch.uint16), dev[cut[4]:cut[5]].view(torch.uint16)
+        offsets = torch.empty(plan.M, dtype=torch.int64, device=dev.device)
+        status = torch.zeros(F + 1, dtype=torch.uint32, device=dev.device)
+        _lib.check(_lib.lib().vbq_rans_segment_offsets_u16(ops._ptr(d_sizes), plan.M, plan.segment, plan.n_words,
+                                                            ops._ptr(offsets), ops._ptr(status[F:]), ops._stream(dev)),
+                   "vbq_rans_segment_offsets_u16")
+        freq = self._coder_stack(plan.tables, plan.segment)._freq(dev.device).view(len(plan.tables), C, -1)
+        out, _ = ops.rans_decode_window(d_payload, d_sizes, offsets, d_files, d_segs, freq, self._sorted_dev(), plan.box,
+                                        seg=plan.segment, N=self.max_bits_per_coord, channels=d_ch, status=status[:F])
+        return out.view(plan.shape), status
+
+    def decompress_latents_window(self, data, region, channels=None, return_np=True):
+        """decompress_latents(data)[region][..., channels] without decoding the rest: the batch of one file
+        (decompress_latents_batch) with the file axis dropped.  Only the segments that hold a row of the region are decoded --
+        and checked: damage elsewhere in the file goes unseen."""
+        return self.decompress_latents_batch([data], regions=[region], channels=channels, return_np=return_np)[0]
+
     def compress_to_bytes(self, X, vae, lamb, segment=1024, layout="segments", part=1 << 17) -> bytes:
         """`vae.encode(X)`, then compress_latents_to_bytes."""
         posterior_means, posterior_logvars = vae.encode(X)
