@@ -19,6 +19,11 @@ constexpr int kHistThreads = VBQ_HIST_THREADS;
 #ifndef VBQ_HIST_U
 #define VBQ_HIST_U 3
 #endif
+// Cut-off level of the lane-private hot counters (hist_add8_hot): 0 = none (hist_add8 at every depth), else 64 << (Lh + 1) more
+// LDS words.  3 and 4 measured alike (both at the kernel's load-only time), 3 takes 4 KB instead of 8.
+#ifndef VBQ_HIST_HOT
+#define VBQ_HIST_HOT 3
+#endif
 
 // LDS slot of rank index q.  In rank order every code point of bit levels 0..5 sits at
 // q = 31 (mod 32) -- one LDS bank -- and those are exactly the bins that fill up at large
@@ -29,7 +34,8 @@ constexpr int kHistThreads = VBQ_HIST_THREADS;
 template <int N>
 __device__ __forceinline__ unsigned int bin_slot(unsigned int q) { return (q ^ (q >> 6)) & ((2u << N) - 1u); }
 
-// Eight indices of one thread (one 16-B load) into the LDS histogram.
+// Eight indices of one thread (one 16-B load) into the LDS histogram: the form of N = 11 and 12, whose bins leave no room
+// for hot words (N <= 10: hist_add8_hot below).
 // An LDS atomic wave-instruction costs ~3 cycles per lane that shares a bank with another
 // lane (same address included, unless ALL lanes agree), and at large lambda 50-90 % of the
 // indices are one and the same bin.  So: (1) the thread counts how many of its eight indices
@@ -76,6 +82,60 @@ __device__ __forceinline__ void hist_add8(unsigned int *h, const uint4 v) {
 #pragma unroll
     for (int k = 1; k < 8; ++k)
         if (!eq[k]) atomicAdd(&hc[kHistCopies * s[k]], 1u);
+}
+
+// ---- lane-private counters for the shallow levels (N <= 10, where the bins have four copies)
+// In rank order the code points of bit levels 0 .. Lh are the ranks q with m = q + 1 a multiple of 2^(N - Lh): k = m >> (N - Lh)
+// in [1, 2^(Lh+1) - 1].  Those few ranks hold most of a row from lambda ~ 0.02 up (on the Kodak-24 sweep, Lh = 3: 21 % at
+// 2^-8, 43 % at 0.022, 92 % at 1) and no single one of them dominates, so hist_add8's merging of ONE bin per wave-instruction
+// leaves every ds_add with most of its 64 lanes on a handful of words.  Here a hot rank's counter is the word
+// hot[k * 64 + lane]: its bank is the lane number, and however many lanes of a wave-instruction hold hot ranks they never
+// meet on a bank.  The waves of the workgroup share the words through the same ds_add_u32; hist_fold_hot adds them into the
+// bins before the flush.  Any index that is not hot -- foreign values up to 65535 included: m = 65536 has its low bits clear,
+// hence the range test on k, folded into hot_bits -- takes hist_add8's word, so the counts of every u16 input are what they
+// were.  Eight unpredicated ds_add_u32 per octet, ~11 VALU operations per index, no ballots and no branches: K2 on the
+// Kodak-24 planes 147 -> 117 us, 3 us above the same kernel with the counting taken out (EXPERIMENTS.md).
+__host__ __device__ constexpr int hist_hot_level(int N, int T) {
+    return hist_copies(T) == 4 && VBQ_HIST_HOT > 0 ? (VBQ_HIST_HOT < N ? VBQ_HIST_HOT : N) : 0;
+}
+__host__ __device__ constexpr int hist_hot_words(int Lh) { return Lh == 0 ? 0 : 128 << Lh; }
+
+template <int N, int Lh>
+__device__ __forceinline__ void hist_add8_hot(unsigned int *h, const uint4 v) {
+    constexpr int sh = N - Lh;
+    constexpr unsigned int hot_bits = ((2u << Lh) - 1u) << sh;          // the bits of m that a hot rank may have set
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int hot0 = 4u * (8192u + lane), bin0 = 4u * (lane & 3u);     // byte offsets into h
+    const unsigned int w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const unsigned int q = (j & 1) ? w[j >> 1] >> 16 : w[j >> 1] & 0xffffu;
+        const unsigned int m = q + 1u;                                  // 1 .. 65536
+        const bool is_hot = (m & ~hot_bits) == 0u;
+        // both offsets computed outside the ?: -- one v_cndmask; written inside it, each side lands behind an exec-masked branch
+        const unsigned int cold = (bin_slot<N>(q) << 4) | bin0;
+        const unsigned int hot = ((m >> sh) << 8) | hot0;
+        atomicAdd(reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(h) + (is_hot ? hot : cold)), 1u);
+    }
+    // one octet at a time: scheduled across the octets of a stage, the offsets of all its indices are live at once and the
+    // kernel no longer fits the 64 registers of eight waves per SIMD
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// Behind the counting barrier: the 64 lane words of every hot rank summed and ADDED to copy 0 of the rank's bin (the scalar
+// paths of k_hist_flat count hot ranks in the bins).  One 16-byte LDS read per thread, 16 threads per rank.
+template <int N, int Lh, int kThreads>
+__device__ __forceinline__ void hist_fold_hot(unsigned int *h) {
+    constexpr int n4 = hist_hot_words(Lh) / 4;
+    static_assert(n4 % 64 == 0, "whole waves take part in the shuffles");
+    for (int i = (int)threadIdx.x; i < n4; i += kThreads) {
+        const uint4 w = reinterpret_cast<const uint4 *>(h + 8192)[i];
+        unsigned int sum = (w.x + w.y) + (w.z + w.w);
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        const unsigned int k = (unsigned int)i >> 4;                    // k = 0 is no rank: its words stay zero
+        if ((i & 15) == 0 && k && sum) h[4u * bin_slot<N>((k << (N - Lh)) - 1u)] += sum;
+    }
 }
 
 // One 16-byte load of eight indices, non-temporal: every index is read exactly once.  Without the hint the loads alone take
@@ -143,15 +203,23 @@ __device__ __forceinline__ void hist_flush(const unsigned int *h, int l, int c, 
 // assign_lut != nullptr (only with ONE workgroup per (lambda, channel), gridDim.x == 1): the workgroup owns its whole row of
 // bins, so it STORES them (zeros included: no memset of the 67 MB array beforehand, no atomics) and writes the code-length
 // model lut[count] next to them (quantizer.py:141-146 fused into the flush; models may be nullptr).
-template <int N, typename CountT>
-__global__ void __launch_bounds__(kHistThreads)
+// Lh: cut-off level of the lane-private hot counters behind the bins (0: none, the bins alone with hist_add8).
+// The LDS (32 KB + 4 KB of hot words) admits four workgroups per CU, that is kHistThreads / 64 waves per SIMD: the registers
+// must allow as many.
+template <int N, typename CountT, int Lh = hist_hot_level(N, table_size(N))>
+__global__ void __launch_bounds__(kHistThreads) __attribute__((amdgpu_waves_per_eu(kHistThreads / 64)))
 k_hist_flat(const uint16_t *__restrict__ idx, long n_per_ch, long ch_stride, int C, long E,
             CountT *__restrict__ counts, int vec_ok, int assign = 0, const float *__restrict__ assign_lut = nullptr,
             long lut_n = 0, float *__restrict__ models = nullptr) {
     constexpr int T = table_size(N);
     constexpr int kHistCopies = hist_copies(T);
     static_assert(T + 1 <= 8192, "bins are laid out for at most 8192 slots");
-    __shared__ __align__(16) unsigned int h[8192];
+    constexpr int kWords = 8192 + hist_hot_words(Lh);               // 32 KB of bins, then the hot words
+    __shared__ __align__(16) unsigned int h[kWords];
+    auto add8 = [&](const uint4 v) {
+        if constexpr (Lh > 0) hist_add8_hot<N, Lh>(h, v);
+        else hist_add8<N, kHistCopies>(h, v);
+    };
     // assign == 2: the grid is (1, L, C) and walks the channels from the LAST one down, all lambdas of a channel together --
     // the order in which the solve kernel's output is most recent (and still in the memory-side cache) comes first
     const int c = assign == 2 ? C - 1 - (int)blockIdx.z : (int)blockIdx.y;
@@ -188,31 +256,34 @@ k_hist_flat(const uint16_t *__restrict__ idx, long n_per_ch, long ch_stride, int
     };
     if (stages > 0) load_stage(A);
 #pragma unroll
-    for (int r = 0; r < 2048 / kHistThreads; ++r)                                                  // 32 KB
-        reinterpret_cast<uint4 *>(h)[(int)threadIdx.x + r * kHistThreads] = make_uint4(0, 0, 0, 0);
+    for (int r = 0; r < (kWords / 4 + kHistThreads - 1) / kHistThreads; ++r) {                      // 32 KB + the hot words
+        const int i = (int)threadIdx.x + r * kHistThreads;
+        if ((r + 1) * kHistThreads <= kWords / 4 || i < kWords / 4) reinterpret_cast<uint4 *>(h)[i] = make_uint4(0, 0, 0, 0);
+    }
     __syncthreads();
     if (stages > 0) {
         const long pairs = (stages - 1) / 2;                    // iterations in which BOTH refills exist
         for (long p = 0; p < pairs; ++p) {
             load_stage(B);
 #pragma unroll
-            for (int u = 0; u < U; ++u) hist_add8<N, kHistCopies>(h, A[u]);
+            for (int u = 0; u < U; ++u) add8(A[u]);
             load_stage(A);
 #pragma unroll
-            for (int u = 0; u < U; ++u) hist_add8<N, kHistCopies>(h, B[u]);
+            for (int u = 0; u < U; ++u) add8(B[u]);
         }
-        if (stages - (2 * pairs + 1) > 0) {                     // one more stage after the one A holds
+        // one more stage after the one A holds: counted by the code below, through A (with the counting of the last stage
+        // written out on both sides of this branch the compiler computes its common part ahead of it and spills)
+        if (stages - (2 * pairs + 1) > 0) {
             load_stage(B);
 #pragma unroll
-            for (int u = 0; u < U; ++u) hist_add8<N, kHistCopies>(h, A[u]);
+            for (int u = 0; u < U; ++u) add8(A[u]);
 #pragma unroll
-            for (int u = 0; u < U; ++u) hist_add8<N, kHistCopies>(h, B[u]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) hist_add8<N, kHistCopies>(h, A[u]);
+            for (int u = 0; u < U; ++u) A[u] = B[u];
         }
+#pragma unroll
+        for (int u = 0; u < U; ++u) add8(A[u]);
     }
-    for (; full(q, 1); q += stride) hist_add8<N, kHistCopies>(h, load_octet(src + q * 8));
+    for (; full(q, 1); q += stride) add8(load_octet(src + q * 8));
     for (; q < noct; q += stride) {
         const uint4 v = load_octet(src + q * 8);
         const unsigned int w[4] = {v.x, v.y, v.z, v.w};
@@ -226,6 +297,10 @@ k_hist_flat(const uint16_t *__restrict__ idx, long n_per_ch, long ch_stride, int
         atomicAdd(&h[kHistCopies * bin_slot<N>(src[i])], 1u);
     if (blockIdx.x == 0 && (long)threadIdx.x < head) atomicAdd(&h[kHistCopies * bin_slot<N>(src0[threadIdx.x])], 1u);
     __syncthreads();
+    if constexpr (Lh > 0) {
+        hist_fold_hot<N, Lh, kHistThreads>(h);
+        __syncthreads();
+    }
     hist_flush<N, CountT, kHistThreads>(h, l, c, C, counts, assign, assign_lut, lut_n, models);
 }
 
