@@ -109,14 +109,15 @@ template <int N>
 int launch_quant_pruned(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch, const float *table,
                         const Lambdas32 &lam, const float *len, int32_t L, uint16_t *out_idx, int64_t E, int vec_ok, hipStream_t st);
 
-// K1t (vbq_quantize_fast.hip): first entropy-model pass without a per-lambda loop; N = 10, raw lengths.  Returns 1 when the
-// lambda sweep is not eligible (caller falls back to the dense counting kernel).
+// K1t (vbq_quantize_fast.hip; the threshold-sweep routines it shares with K1e and K1nt: vbq_sweep.h): first entropy-model pass
+// without a per-lambda loop; N = 10, raw lengths.  Returns 1 when the lambda sweep is not eligible (build_sweep_table,
+// vbq_sweep_host.h; the caller falls back to the dense counting kernel).
 int launch_level_counts_hull10(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch,
                                const float *table, const double *lam, int32_t L, int vec_ok,
                                unsigned long long *level_counts, int reserved, hipStream_t st);
 
-// K1e (vbq_quantize_fast.hip): rank indices of a raw-length lambda sweep from K1t's thresholds; N = 10.  Returns 1 when the
-// sweep is not eligible (caller falls back to launch_quant_fast).
+// K1e (vbq_quantize_fast.hip, vbq_sweep.h): rank indices of a raw-length lambda sweep from K1t's thresholds; N = 10.  Returns 1
+// when the sweep is not eligible (K1t's rule, and fewer than 16 lambdas; the caller falls back to launch_quant_fast).
 int launch_quant_hull_idx10(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch,
                             const float *table, const double *lam, int32_t L, int vec_ok, uint16_t *out_idx, int64_t E,
                             hipStream_t st);

@@ -6,10 +6,13 @@
 // The notebook scores all 2047 points; only the two neighbours of mu on each bit level can
 // win (rounding is monotone, so a farther point of the same level never scores lower), so
 // the same 21-candidate descent as K1 is used, scanned in level-major order.
-#include <string.h>
+// K1nt, further down, solves a whole beta sweep from ten thresholds per element: its f32 threshold, position and guard-band
+// routines are those of K1t and K1e (vbq_sweep.h), the sorted sweep and its bucket table come from vbq_sweep_host.h.
+#include <stddef.h>
 #include <math.h>
 
 #include "vbq_common.h"
+#include "vbq_sweep.h"
 
 namespace vbq {
 namespace {
@@ -489,7 +492,7 @@ k_quant_notebook_pruned(const float *__restrict__ means, const float *__restrict
 // K1nt: the beta sweep without a per-beta argmin (N = 10).
 //
 // The notebook's cost of bit level n is a LINE in the penalty weight, err_n + w * n with w = fl32(fl32(2 beta) * fl32(sigma^2))
-// (ipynb:438-440), and the same eleven lines serve every beta of the sweep.  As in K1t (vbq_quantize_fast.hip) the winner is the
+// (ipynb:438-440), and the same eleven lines serve every beta of the sweep.  As in K1t (vbq_quantize_fast.hip; shared code: vbq_sweep.h) the winner is the
 // lower envelope of the lines, described by ten thresholds per element,
 //       T_n = max_{j > n} min_{i <= n} (err_i - err_j) / (j - i),          T_0 >= T_1 >= ... >= T_9,
 // and the level at w is #{ n : w < T_n }.  Here the kernel must produce an INDEX per (element, beta), so the thresholds are
@@ -513,55 +516,17 @@ k_quant_notebook_pruned(const float *__restrict__ means, const float *__restrict
 // ------------------------------------------------------------------------------------------
 constexpr int kNbKeys = 1536;            // 24 octaves of 64 buckets (the notebook's sweep spans 23.3)
 constexpr int kNbKeyShift = 17;          // key = float bits >> 17: sign, exponent, 6 mantissa bits
-struct NbSweep {
-    float b[kMaxBetaChunk];              // fl32(2 beta), ascending; +big beyond L
-    unsigned char perm[kMaxBetaChunk];   // position of b[l] in the caller's order
+struct NbSweep {                          // SweepTable<kMaxBetaChunk, kNbKeys> (vbq_sweep_host.h) with the sigma^2 range in front of the table
+    float val[kMaxBetaChunk];            // fl32(2 beta), ascending; +big beyond L
+    unsigned char perm[kMaxBetaChunk];   // position of val[l] in the caller's order
     int L, key0, nkeys;                  // keys = float bits >> kNbKeyShift; bucket k <-> key0 + k
     float var_lo, var_hi;                // sigma^2 range in which every fl32(b var) is a normal number
-    unsigned char lut[kNbKeys];          // lut[k] = #{ l : b[l] below the lower edge of bucket k }
+    unsigned char lut[kNbKeys];          // lut[k] = #{ l : val[l] below the lower edge of bucket k }
 };
-constexpr float kNbBig = 3.0e38f;
-
-__device__ __forceinline__ float nb_min(float a, float b) {
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float nb_max(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float nb_max3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float nb_min3abs(float a, float b, float c) {
-    float r;
-    asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// The ten thresholds T_n = max_{j > n} min_{i <= n} (dv_i - dv_j) / (j - i) of an element (see the kernel's header).
-__device__ __forceinline__ void nb_thresholds(const float (&dv)[11], float (&Tn)[10]) {
-    constexpr int N = 10, N1 = 11;
-    float Pm[N1];
-#pragma unroll
-    for (int nn = 0; nn < N; ++nn) {
-#pragma unroll
-        for (int j = nn + 1; j < N1; ++j) {
-            const float r = __fmul_rn(__fsub_rn(dv[nn], dv[j]), 1.0f / (float)(j - nn));
-            Pm[j] = nn == 0 ? r : nb_min(Pm[j], r);
-        }
-        float t = Pm[nn + 1];
-        int j = nn + 2;
-#pragma unroll
-        for (; j + 1 < N1; j += 2) t = nb_max3(t, Pm[j], Pm[j + 1]);
-        if (j < N1) t = nb_max(t, Pm[j]);
-        Tn[nn] = nb_min(t, 1.0e38f);
-    }
-}
+static_assert(sizeof(NbSweep) == 1876 && offsetof(NbSweep, val) == 0 && offsetof(NbSweep, perm) == 256 && offsetof(NbSweep, L) == 320 &&
+              offsetof(NbSweep, key0) == 324 && offsetof(NbSweep, nkeys) == 328 && offsetof(NbSweep, var_lo) == 332 &&
+              offsetof(NbSweep, var_hi) == 336 && offsetof(NbSweep, lut) == 340,
+              "NbSweep travels in the kernel arguments: its layout is fixed");
 
 // CW: words of eight 4-bit fields per column (positions 0 .. L: 5 for L <= 32, 9 for L <= 64).  NF > 0: the sweep has exactly NF full
 // words (L >> 3 == NF) and they are emitted as ONE straight block -- all 16 NF rank reads of a lane pair in flight together --
@@ -597,12 +562,10 @@ k_quant_notebook_hull(const float *__restrict__ means, const float *__restrict__
     const int L = sw.L;
     const unsigned int tid = threadIdx.x;
     for (int i = tid; i < T; i += blockDim.x) tb[i] = codebook[i];
-    for (int k = tid; k < kNbKeys / 4; k += blockDim.x)       // the bucket table travels in the kernel arguments
-        reinterpret_cast<uint32_t *>(lut)[k] = reinterpret_cast<const uint32_t *>(sw.lut)[k];
+    stage_sweep_lut(lut, sw.lut);                             // the bucket table travels in the kernel arguments
     if (tid < kMaxBetaChunk + 2) {
         const int i = (int)tid;
-        auto at = [&](int l) { return l < 0 ? -kNbBig : (l < L ? sw.b[l < kMaxBetaChunk ? l : kMaxBetaChunk - 1] : kNbBig); };
-        rec[i] = make_float4(at(i - 1), at(i), at(i + 1), 0.0f);
+        rec[i] = sweep_rec(sw.val, L, i);
     }
     for (int i = tid; i < CW * NE * 256; i += blockDim.x) cnt[i] = 0;
     if (tid < kMaxBetaChunk) perm_s[tid] = sw.perm[tid];
@@ -690,21 +653,19 @@ k_quant_notebook_hull(const float *__restrict__ means, const float *__restrict__
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
             float Tn[N];
-            nb_thresholds(dv[k], Tn);
-            float big = dv[k][0];
+            sweep_thresholds<N>(dv[k], Tn);
+            float big = dv[k][0];                              // sweep_max_du (vbq_sweep.h) restated: calling it reschedules the block
 #pragma unroll
-            for (int j = 1; j + 1 < N1; j += 2) big = nb_max3(big, dv[k][j], dv[k][j + 1]);
-            fix[k] = __builtin_amdgcn_ballot_w64(!(big < kNbBig) || slow[k]);
-            // positions: bucket -> count of sweep points below the bucket -> the one sweep point that may share it
+            for (int j = 1; j + 1 < N1; j += 2) big = vmax3(big, dv[k][j], dv[k][j + 1]);
+            fix[k] = __builtin_amdgcn_ballot_w64(!(big < kSweepBig) || slow[k]);
+            // positions: bucket -> count of sweep points below the bucket -> the one sweep point that may share it (vbq_sweep.h)
 #pragma unroll
             for (int nn = 0; nn < N; ++nn) {
-                const int key = min(max(((int)__float_as_uint(Tn[nn]) >> kNbKeyShift) - key0, 0), nkeys - 1);
-                const uint32_t c0 = lut[key];
-                const float4 nb = rec[c0];
+                float4 nb;
                 const float t = Tn[nn];
-                const uint32_t a = c0 + (nb.y < t ? 1u : 0u);                     // b_(a-1) < T <= b_(a)
-                const float G = __fmul_rn(fmaf(fabsf(t), (float)(nn + 1), dv[k][nn]), 9.5367431640625e-07f);
-                const float dist = nb_min3abs(__fsub_rn(t, nb.x), __fsub_rn(t, nb.y), __fsub_rn(t, nb.z));
+                const uint32_t a = sweep_position<kNbKeyShift>(t, key0, nkeys, lut, rec, nb);      // b_(a-1) < T <= b_(a)
+                const float G = sweep_band(t, nn, dv[k][nn]);
+                const float dist = sweep_distance(t, nb);
                 fix[k] |= __builtin_amdgcn_ballot_w64(dist <= G);
                 atomicAdd(&cnt[((a >> 3) * NE + k) * 256 + tid], 1u << (4u * (a & 7u)));
             }
@@ -724,19 +685,17 @@ k_quant_notebook_hull(const float *__restrict__ means, const float *__restrict__
                     asm volatile("" : "+v"(d));
                     d2[j] = d;
                 }
-                nb_thresholds(d2, Tn);
-                float big = d2[0];
+                sweep_thresholds<N>(d2, Tn);
+                float big = d2[0];                             // sweep_max_du restated, as above
 #pragma unroll
-                for (int j = 1; j + 1 < N1; j += 2) big = nb_max3(big, d2[j], d2[j + 1]);
-                uint64_t fl = (!(big < kNbBig) || slow[k]) ? all_l : 0ull;
+                for (int j = 1; j + 1 < N1; j += 2) big = vmax3(big, d2[j], d2[j + 1]);
+                uint64_t fl = (!(big < kSweepBig) || slow[k]) ? all_l : 0ull;
 #pragma unroll
                 for (int nn = 0; nn < N; ++nn) {
-                    const int key = min(max(((int)__float_as_uint(Tn[nn]) >> kNbKeyShift) - key0, 0), nkeys - 1);
-                    const uint32_t c0 = lut[key];
-                    const float4 nb = rec[c0];
-                    const uint32_t a = c0 + (nb.y < Tn[nn] ? 1u : 0u);
-                    const float G = __fmul_rn(fmaf(fabsf(Tn[nn]), (float)(nn + 1), d2[nn]), 9.5367431640625e-07f);
-                    const float dist = nb_min3abs(__fsub_rn(Tn[nn], nb.x), __fsub_rn(Tn[nn], nb.y), __fsub_rn(Tn[nn], nb.z));
+                    float4 nb;
+                    const uint32_t a = sweep_position<kNbKeyShift>(Tn[nn], key0, nkeys, lut, rec, nb);
+                    const float G = sweep_band(Tn[nn], nn, d2[nn]);
+                    const float dist = sweep_distance(Tn[nn], nb);
                     if (mine && dist <= G) {
                         // the sweep points inside a band are consecutive and next to T: walk outwards from its position
                         // (b_(a-1) < T <= b_(a); rec[l + 1].x = b_(l))
@@ -796,6 +755,7 @@ k_quant_notebook_hull(const float *__restrict__ means, const float *__restrict__
                             uint32_t r2[NE];
 #pragma unroll
                             for (int k = 0; k < NE; ++k) {
+                                // sweep_rank_offset (vbq_sweep.h) restated: calling it here reorders the six-word block
                                 const uint32_t sh = j < 3 ? (P[wd][k] << (10 - 4 * j)) : (P[wd][k] >> (4 * j - 10));
                                 r2[k] = *reinterpret_cast<const unsigned short *>(rkb + ((sh & 0x3c00u) | base[k]));
                             }
@@ -819,10 +779,7 @@ k_quant_notebook_hull(const float *__restrict__ means, const float *__restrict__
                     P[k] = (cw[wd][k] + run[k]) * 0x11111111u;
                     run[k] = P[k] >> 28;
                 }
-                auto addr = [&](int j, int k) {
-                    const uint32_t sh = j < 3 ? (P[k] << (10 - 4 * j)) : (P[k] >> (4 * j - 10));
-                    return (sh & 0x3c00u) | base[k];
-                };
+                auto addr = [&](int j, int k) { return sweep_rank_offset(P[k], j, base[k]); };
                 auto row = [&](int j) { return ((j < 4 ? pw.x : pw.y) >> (8 * (j & 3))) & 0xffu; };
                 if (wd < nfull) {                                                     // a whole word: eight sweep points, no tests
                     uint32_t rank[8][NE];
@@ -897,48 +854,17 @@ k_quant_notebook_hull(const float *__restrict__ means, const float *__restrict__
 }
 
 // Host side of K1nt: sort the sweep by fl32(2 beta), check that the bucket table applies (distinct values at least one
-// bucket apart, within 24 octaves).  Returns 1 when the sweep is not eligible (the caller takes the per-beta kernel).
+// bucket apart, within 24 octaves: build_sweep_table, vbq_sweep_host.h).  Returns 1 when the sweep is not eligible (the caller
+// takes the per-beta kernel).
 int launch_notebook_hull10(const float *means, const float *stds, int64_t n, const double *codebook, const double *betas,
                            int Lc, uint16_t *oi, float *ov, int vec_ok, int dbg, hipStream_t st) {
     if (Lc < 1 || Lc > kMaxBetaChunk) return 1;
     NbSweep sw;
-    int order[kMaxBetaChunk];
     float b[kMaxBetaChunk];
-    for (int i = 0; i < Lc; ++i) { order[i] = i; b[i] = (float)(2.0 * betas[i]); }
-    for (int i = 1; i < Lc; ++i)
-        for (int j = i; j > 0 && b[order[j]] < b[order[j - 1]]; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
-    int prev_key = -1;
-    for (int i = 0; i < kMaxBetaChunk; ++i) { sw.b[i] = kNbBig; sw.perm[i] = 0; }
-    for (int i = 0; i < Lc; ++i) {
-        const float v = b[order[i]];
-        if (!(v >= 2e-12f && v <= 2e18f)) return 1;
-        uint32_t bits;
-        memcpy(&bits, &v, 4);
-        const int key = (int)(bits >> kNbKeyShift);
-        if (key <= prev_key) return 1;
-        prev_key = key;
-        sw.b[i] = v;
-        sw.perm[i] = (unsigned char)order[i];
-    }
-    uint32_t b0;
-    memcpy(&b0, &sw.b[0], 4);
-    sw.key0 = (int)(b0 >> kNbKeyShift);
-    sw.nkeys = prev_key - sw.key0 + 2;
-    sw.L = Lc;
-    if (sw.nkeys > kNbKeys) return 1;
-    {
-        int l = 0;
-        for (int k = 0; k < kNbKeys; ++k) {
-            while (l < Lc) {
-                uint32_t bits;
-                memcpy(&bits, &sw.b[l], 4);
-                if ((int)(bits >> kNbKeyShift) < sw.key0 + k) ++l; else break;
-            }
-            sw.lut[k] = (unsigned char)l;
-        }
-    }
-    sw.var_lo = fmaxf(4e-38f / sw.b[0], 1e-30f);
-    sw.var_hi = fminf(1e38f / sw.b[Lc - 1], 1e30f);
+    for (int i = 0; i < Lc; ++i) b[i] = (float)(2.0 * betas[i]);
+    if (!build_sweep_table<kNbKeyShift>(b, Lc, 2e-12f, 2e18f, sw)) return 1;
+    sw.var_lo = fmaxf(4e-38f / sw.val[0], 1e-30f);
+    sw.var_hi = fminf(1e38f / sw.val[Lc - 1], 1e30f);
     int64_t gx = ((n + 1) / 2 + 255) / 256;
     constexpr int rounds = 2;                               // grid = this many times the resident workgroups (measured)
     const int64_t cap = (int64_t)num_cus() * (ov ? 2 : (Lc <= 32 ? 4 : 3)) * rounds;              // persistent grid: every CU's resident workgroups, two rounds

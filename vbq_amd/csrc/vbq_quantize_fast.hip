@@ -29,9 +29,14 @@
 //          the flag is raised when it is below 2^-20 * S (tested as packed word <= bits(2^-19 * S)).
 //    A wave with any flagged lane re-solves those lanes for that lambda with the literal
 //    21-candidate scan (exact_rank_scan).  Both events have probability ~1e-6 per solve.
-#include <string.h>
+//
+// Also here: K1t and K1e, which solve a whole raw-length lambda sweep from ten thresholds per element (further down).  Their
+// threshold, position and guard-band routines, shared with K1nt (vbq_notebook.hip), are in vbq_sweep.h; the host routine that
+// sorts the sweep and builds its bucket table is in vbq_sweep_host.h.
+#include <stddef.h>
 
 #include "vbq_common.h"
+#include "vbq_sweep.h"
 
 namespace vbq {
 namespace {
@@ -73,30 +78,6 @@ __device__ __forceinline__ void store_idx2(uint32_t *p, uint32_t v) {
     if constexpr (NT) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
-
-// v_min_f32 / v_max_f32 as they are (IEEE mode: a NaN operand loses).  fminf / fmaxf make the compiler canonicalise
-// operands it cannot prove quiet (a v_max x, x in front of every second min of the threshold recurrences).
-__device__ __forceinline__ float vmin(float a, float b) {
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float vmax(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float vmin3abs(float a, float b, float c) {       // min(|a|, |b|, |c|)
-    float r;
-    asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
 
 // Minimum of M values as a tree of v_min3_f32 (ceil((M-1)/2) instructions).
 template <int M>
@@ -508,13 +489,10 @@ constexpr int kHullThreads = VBQ_HULL_THREADS;
 #endif
 constexpr int kHullKeys = 2048;         // 16 octaves of 128 buckets
 constexpr int kFixQueue = 192;          // K1t: deferred fix-ups per workgroup (about ten are expected per 2 300 elements)
-struct HullSweep {
-    float lam[32];          // the sweep rounded to f32, ascending
-    unsigned char perm[32]; // position of lam[l] in the caller's order
-    int L, key0, nkeys;     // keys = float bits >> 16 (sign, exponent, 7 mantissa bits); bucket b <-> key0 + b
-    unsigned char lut[kHullKeys];   // lut[b] = #{ l : lam[l] below the lower edge of bucket b }
-};
-constexpr float kHullBig = 3.0e38f;
+struct HullSweep : SweepTable<32, kHullKeys> {};     // keys = float bits >> 16: sign, exponent, 7 mantissa bits
+static_assert(sizeof(HullSweep) == 2220 && offsetof(HullSweep, val) == 0 && offsetof(HullSweep, perm) == 128 && offsetof(HullSweep, L) == 160 &&
+              offsetof(HullSweep, key0) == 164 && offsetof(HullSweep, nkeys) == 168 && offsetof(HullSweep, lut) == 172,
+              "HullSweep travels in the kernel arguments: its layout is fixed");
 
 // Distortion of the NEARER neighbour of z on every bit level (du is monotone in |P - z|, so one exact quotient per level).
 // The visited point is one neighbour of z on its level; the other one sits on z's side of it (the same point again at the
@@ -543,55 +521,6 @@ __device__ __forceinline__ void hull_du_nearest(const char *tbb, float z, float 
         du[n] = __fmul_rn(0.5f, __fmul_rn(t, t));
         g = 2 * g + (below ? 4u : 0u);
     }
-}
-
-// The ten thresholds T_n = max_{j > n} min_{i <= n} (du_i - du_j) / (j - i) of an element, clamped into the tables' range
-// (inf / NaN only come from non-finite costs, which are flagged separately).
-template <int N>
-__device__ __forceinline__ void hull_thresholds(const float (&du)[N + 1], float (&Tn)[N]) {
-    constexpr int N1 = N + 1;
-    float Pm[N1];                                              // Pm[j] = min_{i <= n} (du_i - du_j) / (j - i)
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-#pragma unroll
-        for (int j = n + 1; j < N1; ++j) {
-            const float r = __fmul_rn(__fsub_rn(du[n], du[j]), 1.0f / (float)(j - n));
-            Pm[j] = n == 0 ? r : vmin(Pm[j], r);
-        }
-        float t = Pm[n + 1];
-        int j = n + 2;
-#pragma unroll
-        for (; j + 1 < N1; j += 2) t = vmax3(t, Pm[j], Pm[j + 1]);
-        if (j < N1) t = vmax(t, Pm[j]);
-        Tn[n] = vmin(t, 1.0e38f);
-    }
-}
-
-template <int N>
-__device__ __forceinline__ float hull_max_du(const float (&du)[N + 1]) {
-    constexpr int N1 = N + 1;
-    float big = du[0];
-#pragma unroll
-    for (int j = 1; j + 1 < N1; j += 2) big = vmax3(big, du[j], du[j + 1]);
-    if ((N1 & 1) == 0) big = vmax(big, du[N1 - 1]);
-    return big;
-}
-
-// Position of a threshold in the sorted sweep, a = #{ l : lam_(l) < T }: bucket of the threshold's bit pattern (an
-// arithmetic shift keeps T <= 0 negative, so one median clamps "below the sweep", "above it" and the table range), then the
-// one sweep point that may share the bucket.  nb = { lam_(cnt-1), lam_(cnt), lam_(cnt+1) }: T lies between the outer two,
-// so its distance to the sweep is the smallest of the three distances.
-__device__ __forceinline__ uint32_t hull_position(float t, int key0, int nkeys, const unsigned char *lut, const float4 *rec,
-                                                  float4 &nb) {
-    const int key = min(max(((int)__float_as_uint(t) >> 16) - key0, 0), nkeys - 1);    // v_med3_i32
-    const uint32_t cnt = lut[key];
-    nb = rec[cnt];
-    return cnt + (nb.y < t ? 1u : 0u);                        // lam_(a-1) < T <= lam_(a)
-}
-
-// Guard band |lambda - T_n| <= 2^-20 (du_n + |T_n| (n + 1)): every sweep point outside it is decided by the lines.
-__device__ __forceinline__ float hull_band(float t, int n, float du_n) {
-    return __fmul_rn(fmaf(fabsf(t), (float)(n + 1), du_n), 9.5367431640625e-07f);
 }
 
 // Bit level of the winner at one sweep point from the per-level best distortions (the counting kernels' question: which
@@ -630,16 +559,16 @@ __device__ __forceinline__ void hull_counts_fix(uint64_t lanes, const float (&du
     }
     float Tn[N];
     uint32_t apos[N];
-    hull_thresholds<N>(du, Tn);
-    uint32_t fl = (!(hull_max_du<N>(du) < kHullBig) || all_points) ? 0xffffffffu : 0u;   // non-finite costs: every lambda re-solved
+    sweep_thresholds<N>(du, Tn);
+    uint32_t fl = (!(sweep_max_du<N>(du) < kSweepBig) || all_points) ? 0xffffffffu : 0u;   // non-finite costs: every lambda re-solved
     float G[N];
     uint32_t near = 0;                                         // bit n: a sweep point lies inside the band of threshold n
 #pragma unroll
     for (int n = 0; n < N; ++n) {                              // straight code: the twenty table reads overlap
         float4 nb;
-        apos[n] = hull_position(Tn[n], key0, nkeys, lut, rec, nb);
-        G[n] = hull_band(Tn[n], n, du[n]);
-        const float dist = vmin3abs(__fsub_rn(Tn[n], nb.x), __fsub_rn(Tn[n], nb.y), __fsub_rn(Tn[n], nb.z));
+        apos[n] = sweep_position<16>(Tn[n], key0, nkeys, lut, rec, nb);
+        G[n] = sweep_band(Tn[n], n, du[n]);
+        const float dist = sweep_distance(Tn[n], nb);
         near |= (mine && dist <= G[n]) ? (1u << n) : 0u;
     }
 #pragma unroll
@@ -700,12 +629,12 @@ k_level_counts_hull(const float *__restrict__ mu, const float *__restrict__ sg, 
     if (threadIdx.x < 32) perm_s[threadIdx.x] = sw.perm[threadIdx.x];
     for (int i = threadIdx.x; i < N * LB * KC; i += blockDim.x) H[i] = 0;
     for (int i = threadIdx.x; i < L * N1; i += blockDim.x) corr[i] = 0;
-    for (int b = threadIdx.x; b < kHullKeys / 4; b += blockDim.x)   // the bucket table travels in the kernel arguments
+    // the bucket table travels in the kernel arguments.  stage_sweep_lut (vbq_sweep.h) restated: calling it reorders this prologue
+    for (int b = threadIdx.x; b < kHullKeys / 4; b += blockDim.x)
         reinterpret_cast<uint32_t *>(lut)[b] = reinterpret_cast<const uint32_t *>(sw.lut)[b];
     if (threadIdx.x < 34) {
         const int i = (int)threadIdx.x;
-        auto at = [&](int l) { return l < 0 ? -kHullBig : (l < L ? sw.lam[l < 32 ? l : 31] : kHullBig); };
-        rec[i] = make_float4(at(i - 1), at(i), at(i + 1), 0.0f);
+        rec[i] = sweep_rec(sw.val, L, i);
     }
     if (threadIdx.x == 0) { n_valid = 0; fixn = 0; }
     __syncthreads();
@@ -760,14 +689,14 @@ k_level_counts_hull(const float *__restrict__ mu, const float *__restrict__ sg, 
             my_valid += valid ? 1u : 0u;
             const unsigned int vinc = valid ? inc : 0u;        // padding lanes add 0: no exec juggling
             float Tn[N];
-            hull_thresholds<N>(du[k], Tn);
-            fix[k] = __builtin_amdgcn_ballot_w64(!(hull_max_du<N>(du[k]) < kHullBig)) | (force_slow ? ~0ull : 0ull);
+            sweep_thresholds<N>(du[k], Tn);
+            fix[k] = __builtin_amdgcn_ballot_w64(!(sweep_max_du<N>(du[k]) < kSweepBig)) | (force_slow ? ~0ull : 0ull);
 #pragma unroll
             for (int n = 0; n < N; ++n) {
                 float4 nb;
-                const uint32_t a = hull_position(Tn[n], key0, nkeys, lut, rec, nb);
-                const float G = hull_band(Tn[n], n, du[k][n]);
-                const float dist = vmin3abs(__fsub_rn(Tn[n], nb.x), __fsub_rn(Tn[n], nb.y), __fsub_rn(Tn[n], nb.z));
+                const uint32_t a = sweep_position<16>(Tn[n], key0, nkeys, lut, rec, nb);
+                const float G = sweep_band(Tn[n], n, du[k][n]);
+                const float dist = sweep_distance(Tn[n], nb);
                 fix[k] |= __builtin_amdgcn_ballot_w64(dist <= G);
                 atomicAdd(&H[((uint32_t)n * LB + a) * (unsigned)KC + copy], vinc);
             }
@@ -898,11 +827,10 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
         const int l = i / PS, n = i - l * PS;
         penl[i] = n < N1 ? __fmul_rn(lam.lam[l], (float)n) : 0.0f;
     }
-    for (int b = tid; b < kHullKeys / 4; b += blockDim.x)
-        reinterpret_cast<uint32_t *>(lut)[b] = reinterpret_cast<const uint32_t *>(sw.lut)[b];
-    if (tid < 34) {
+    stage_sweep_lut(lut, sw.lut);
+    if (tid < 34) {                                          // sweep_rec (vbq_sweep.h) restated: with L a constant (LFIX) the call keeps a clamp
         const int i = (int)tid;
-        auto at = [&](int l) { return l < 0 ? -kHullBig : (l < L ? sw.lam[l < 32 ? l : 31] : kHullBig); };
+        auto at = [&](int l) { return l < 0 ? -kSweepBig : (l < L ? sw.val[l < 32 ? l : 31] : kSweepBig); };
         rec[i] = make_float4(at(i - 1), at(i), at(i + 1), 0.0f);
     }
     if (tid < 32) perm_s[tid] = sw.perm[tid];
@@ -996,11 +924,12 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
             const bool valid = i0 + k < n_per_ch;
             float Pm[N1], Tn[N];
             uint64_t near[N];
+            // sweep_max_du and sweep_thresholds (vbq_sweep.h) restated: calling either one here reschedules the whole block
             float big = du[k][0];
 #pragma unroll
             for (int j = 1; j + 1 < N1; j += 2) big = vmax3(big, du[k][j], du[k][j + 1]);
             if ((N1 & 1) == 0) big = vmax(big, du[k][N1 - 1]);
-            uint32_t fl = (!(big < kHullBig) || force_slow) ? 0xffffffffu : 0u;
+            uint32_t fl = (!(big < kSweepBig) || force_slow) ? 0xffffffffu : 0u;
             uint64_t any_near = 0;
 #pragma unroll
             for (int n = 0; n < N; ++n) {
@@ -1021,8 +950,7 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
             uint32_t c0[N];
 #pragma unroll
             for (int n = 0; n < N; ++n) {
-                const int key = min(max(((int)__float_as_uint(Tn[n]) >> 16) - sw.key0, 0), sw.nkeys - 1);
-                c0[n] = lut[key];
+                c0[n] = lut[sweep_bucket<16>(Tn[n], sw.key0, sw.nkeys)];
             }
 #pragma unroll
             for (int h = 0; h < N; h += VBQ_K1E_STAGE) {
@@ -1034,8 +962,8 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
                     const int n = h + i;
                     const float t = Tn[n];
                     const uint32_t a = c0[n] + (nb[i].y < t ? 1u : 0u);          // lam_(a-1) < T <= lam_(a)
-                    const float G = __fmul_rn(fmaf(fabsf(t), (float)(n + 1), du[k][n]), 9.5367431640625e-07f);
-                    const float dist = vmin3abs(__fsub_rn(t, nb[i].x), __fsub_rn(t, nb[i].y), __fsub_rn(t, nb[i].z));
+                    const float G = sweep_band(t, n, du[k][n]);
+                    const float dist = sweep_distance(t, nb[i]);
                     near[n] = __builtin_amdgcn_ballot_w64(dist <= G);
                     any_near |= near[n];
                     atomicAdd(&cnt[((a >> 3) * NE + k) * 256 + tid], 1u << (4u * (a & 7u)));
@@ -1046,17 +974,16 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
                 for (int n = 0; n < N; ++n) {
                     if (near[n] == 0) continue;
                     if ((near[n] >> lane) & 1ull) {
-                        const float G = __fmul_rn(fmaf(fabsf(Tn[n]), (float)(n + 1), du[k][n]), 9.5367431640625e-07f);
+                        const float G = sweep_band(Tn[n], n, du[k][n]);
                         for (int l = 0; l < L; ++l)
-                            fl |= (fabsf(__fsub_rn(sw.lam[l], Tn[n])) <= G) ? (1u << l) : 0u;
+                            fl |= (fabsf(__fsub_rn(sw.val[l], Tn[n])) <= G) ? (1u << l) : 0u;
                     }
                 }
             }
             if (__builtin_amdgcn_ballot_w64(tiny[k] != 0u) != 0ull) {      // rare: a marked level and where it wins
                 auto pos_of = [&](float t) {                   // the position of a threshold again (not kept: registers)
-                    const int key = min(max(((int)__float_as_uint(t) >> 16) - sw.key0, 0), sw.nkeys - 1);
-                    const uint32_t cc = lut[key];
-                    return cc + (rec[cc].y < t ? 1u : 0u);
+                    float4 nb;
+                    return sweep_position<16>(t, sw.key0, sw.nkeys, lut, rec, nb);
                 };
 #pragma unroll
                 for (int n = 1; n <= N; ++n) {
@@ -1115,8 +1042,7 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
                             uint32_t r2[NE];
 #pragma unroll
                             for (int k = 0; k < NE; ++k) {
-                                const uint32_t sh = j < 3 ? (P[wd][k] << (10 - 4 * j)) : (P[wd][k] >> (4 * j - 10));
-                                r2[k] = *reinterpret_cast<const unsigned short *>(rkb + ((sh & 0x3c00u) | lbase[k]));
+                                r2[k] = *reinterpret_cast<const unsigned short *>(rkb + sweep_rank_offset(P[wd][k], j, lbase[k]));
                             }
                             v[8 * w2 + j] = r2[0] | (r2[1] << 16);
                         }
@@ -1152,10 +1078,7 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
                     P[k] = (cw[wd][k] + run[k]) * 0x11111111u;
                     run[k] = P[k] >> 28;
                 }
-                auto addr = [&](int j, int k) {
-                    const uint32_t sh = j < 3 ? (P[k] << (10 - 4 * j)) : (P[k] >> (4 * j - 10));
-                    return (sh & 0x3c00u) | lbase[k];
-                };
+                auto addr = [&](int j, int k) { return sweep_rank_offset(P[k], j, lbase[k]); };
                 auto plane = [&](int j) { return ((j < 4 ? pw.x : pw.y) >> (8 * (j & 3))) & 0xffu; };
                 if (wd < nfull) {                                                     // a whole word: eight sweep points, no tests
                     uint32_t rank[8][NE];
@@ -1496,43 +1419,12 @@ int launch_quant_pruned(const float *mu, const float *sg, int64_t n_per_ch, int6
 }
 
 
-// Sort the sweep by its f32 values and build the bucket table.  false: the sweep is not eligible for the threshold kernels
-// (more than 32 values, a value outside the fast kernels' range, two values in one bucket, more than 16 octaves).
-static bool build_hull_sweep(const double *lam, int L, HullSweep &sw) {
-    if (L < 1 || L > 32) return false;
-    int order[32];
-    for (int i = 0; i < L; ++i) order[i] = i;
-    for (int i = 1; i < L; ++i)                              // insertion sort by the f32 value
-        for (int j = i; j > 0 && (float)lam[order[j]] < (float)lam[order[j - 1]]; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
-    int prev_key = -1;
-    for (int i = 0; i < 32; ++i) { sw.lam[i] = kHullBig; sw.perm[i] = 0; }
-    for (int i = 0; i < L; ++i) {
-        const float v = (float)lam[order[i]];
-        if (!(v >= 1.9e-12f && v <= 1.8e19f)) return false;
-        uint32_t bits;
-        memcpy(&bits, &v, 4);
-        const int key = (int)(bits >> 16);
-        if (key <= prev_key) return false;                    // two sweep points in one bucket (or equal): dense kernel
-        prev_key = key;
-        sw.lam[i] = v;
-        sw.perm[i] = (unsigned char)order[i];
-    }
-    uint32_t b0;
-    memcpy(&b0, &sw.lam[0], 4);
-    sw.key0 = (int)(b0 >> 16);
-    sw.nkeys = prev_key - sw.key0 + 2;
-    sw.L = L;
-    if (sw.nkeys > kHullKeys) return false;
-    int l = 0;
-    for (int b = 0; b < kHullKeys; ++b) {
-        while (l < L) {
-            uint32_t bits;
-            memcpy(&bits, &sw.lam[l], 4);
-            if ((int)(bits >> 16) < sw.key0 + b) ++l; else break;
-        }
-        sw.lut[b] = (unsigned char)l;
-    }
-    return true;
+// The lambda sweep of K1t and K1e as a sorted table (vbq_sweep_host.h): at most 32 values in the fast kernels' range, keys of
+// 7 mantissa bits, 16 octaves.  false: not eligible for the threshold kernels.
+static bool build_lambda_sweep(const double *lam, int L, HullSweep &sw) {
+    float v[32];
+    for (int i = 0; i < L && i < 32; ++i) v[i] = (float)lam[i];
+    return build_sweep_table<16>(v, L, 1.9e-12f, 1.8e19f, sw);
 }
 
 // The grid of K1t (k_level_counts_hull) for one launch: workgroups per channel (all resident).  Pure, as quant_fast_grid.
@@ -1575,7 +1467,7 @@ int launch_level_counts_hull10(const float *mu, const float *sg, int64_t n_per_c
                                unsigned long long *level_counts, int reserved, hipStream_t st) {
     if (L < 1 || L > 32) return 1;
     HullSweep sw;
-    if (!build_hull_sweep(lam, L, sw)) return 1;
+    if (!build_lambda_sweep(lam, L, sw)) return 1;
     const int64_t gx = level_counts_hull_grid(n_per_ch, n_ch, reserved);
     const int dbg = fast_debug();
     Lambdas32 l32;
@@ -1596,7 +1488,7 @@ int launch_quant_hull_idx10(const float *mu, const float *sg, int64_t n_per_ch, 
     // s[plane]): planes of 2^31 elements or more (a 16-lambda sweep of that size is 64 GB of indices: it fits) go to K1.
     if (2 * (uint64_t)E > 0xffffffffull) return 1;
     HullSweep sw;
-    if (!build_hull_sweep(lam, L, sw)) return 1;
+    if (!build_lambda_sweep(lam, L, sw)) return 1;
     const int64_t npairs = (n_per_ch + 1) / 2;
     int64_t gx = (npairs + 255) / 256;
     constexpr int rounds = 2;                               // grid = this many times the resident workgroups (measured)
