@@ -6,8 +6,9 @@ shapes have to move.
 
     lookup_plan     lookup_lds_passes / k_lookup_lds                    vbq_amd/csrc/vbq_latents.hip
     rank_plan       vbq_analogy_ranks_f32 / k_rank_gemm                 vbq_amd/csrc/vbq_ranks.hip
-    *_grid          vbq_moments_f32, vbq_rd_sums_u16, vbq_index_max_u16, vbq_check_inputs_f32, launch_hist (k_hist_tiled)
-                                                                        vbq_amd/csrc/vbq_hist.hip
+    *_grid          vbq_moments_f32, vbq_rd_sums_u16, vbq_index_max_u16, vbq_check_inputs_f32
+                                                                        vbq_amd/csrc/vbq_reduce.hip
+                    launch_hist (k_hist_tiled)                          vbq_amd/csrc/vbq_hist.hip
 """
 from collections import namedtuple
 
@@ -25,7 +26,7 @@ RANK_BN = 128                    # kBN: words per tile
 RANK_BK = 32                     # VBQ_RANK_BK: k per LDS stage
 RANK_WGS = 2                     # VBQ_RANK_WGS: workgroups per CU
 RANK_MAX_SPLITS = 256            # `s <= 256` of the best_s loop
-# ---- vbq_hist.hip
+# ---- vbq_reduce.hip
 MOMENTS_FLAT_WGS = 2048          # cap = 2048 / n_ch + 1 workgroups per channel
 MOMENTS_FLAT_LOADS = 4           # 16-byte loads in flight per lane in the main loop
 MOMENTS_BC_WGS = 2048            # `if (gx > 2048) gx = 2048`
@@ -34,6 +35,7 @@ MOMENTS_MAX_CH = 4096            # n_ch <= 4096
 SCAN_WGS = 4096                  # `if (gx > 4096) gx = 4096` of index_max and check_inputs
 RD_WGS_PER_CU = 8                # cap = num_cus() * 8 / chunks + 1
 RD_CHUNK = 8                     # kRdChunk: lambdas per workgroup
+# ---- vbq_hist.hip
 HIST_TILED_WGS = 512             # gx = 512 / (groups * L) + 1
 HIST_TILED_ROWS = 64             # rows per pass of a k_hist_tiled workgroup (1024 threads / 16 channels)
 HIST_TILE_CH = 16                # kTileChannels

@@ -660,6 +660,88 @@ def test_prep_planes_is_transpose_and_exact_sqrt(rows, cols):
     assert torch.equal(m2, m_p) and torch.equal(s2, var.t().contiguous())
 
 
+def _tile_case(shape, dtype, seed):
+    """Device tensor for the tile-walk tests below: u16 ranks, or f32 with the special values of the test above in front."""
+    rng = np.random.default_rng(seed)
+    if dtype == np.uint16:
+        return torch.from_numpy(rng.integers(0, 65536, shape).astype(np.uint16)).cuda()
+    x = rng.normal(-4, 3, shape).astype(np.float32)
+    x.reshape(-1)[:5] = [-200.0, 88.0, -87.5, 0.0, -103.0]
+    return torch.from_numpy(x).cuda()
+
+
+def _same_bits(a, b):
+    assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
+    bits = torch.int16 if a.element_size() == 2 else torch.int32
+    return torch.equal(a.view(bits), b.view(bits))
+
+
+def _planes_t(x):
+    """torch's own [batch, rows, cols] -> [batch, cols, rows] (through int16 for the u16 stacks: the copy moves bits)."""
+    bits = torch.int16 if x.element_size() == 2 else torch.int32
+    return x.view(bits).permute(0, 2, 1).contiguous().view(x.dtype)
+
+
+def _one_in(x):
+    """The same values as a contiguous view that starts ONE element into a larger buffer: 16-byte accesses are out."""
+    buf = torch.empty(x.numel() + 1, dtype=x.dtype, device=x.device)
+    bits = torch.int16 if x.element_size() == 2 else torch.int32
+    v = buf[1:].view(x.shape)
+    v.view(bits).copy_(x.view(bits))
+    assert v.is_contiguous() and v.data_ptr() % 16 == x.element_size()
+    return v
+
+
+def _prep_wants(mu, lv):
+    """{spread: (spread input, mean plane, sigma plane)} by torch, for log-variances lv."""
+    var = torch.exp(lv)
+    mu_t = mu.t().contiguous()
+    return {"sigma": (var, mu_t, var.t().contiguous()), "variance": (var, mu_t, torch.sqrt(var).t().contiguous()),
+            "logvar": (lv, mu_t, (torch.exp(lv) ** 0.5).t().contiguous())}
+
+
+def test_prep_planes_ragged_tiles_on_the_vector_path():
+    """(132, 68): multiples of 4, not of 64 -- 3 x 2 tiles, one whole, ragged right, ragged bottom and the corner, all with
+    16-byte accesses (aligned tensors); every spread kind."""
+    from vbq_amd import ops
+    mu, lv = _tile_case((132, 68), np.float32, 1), _tile_case((132, 68), np.float32, 2)
+    for spread, (sp, want_m, want_s) in _prep_wants(mu, lv).items():
+        assert (mu.data_ptr() | sp.data_ptr()) % 16 == 0
+        m, s = ops.prep_planes(mu, sp, spread=spread)
+        assert (m.data_ptr() | s.data_ptr()) % 16 == 0
+        assert _same_bits(m, want_m) and _same_bits(s, want_s), spread
+
+
+def test_transpose_planes_ragged_tiles_on_the_vector_path():
+    """(2, 72, 136): multiples of 8 -- 2 x 3 tiles per plane, whole and ragged ones together, on more than one plane."""
+    from vbq_amd import ops
+    for dtype in (np.uint16, np.float32):
+        x = _tile_case((2, 72, 136), dtype, 3)
+        assert x.data_ptr() % 16 == 0
+        assert _same_bits(ops.transpose_planes(x), _planes_t(x))
+
+
+def test_tile_walks_take_misaligned_pointers():
+    """Vector-eligible shapes whose input, then whose output, starts one element off a 16-byte boundary: the pointer test
+    alone sends them to the scalar path."""
+    from vbq_amd import ops
+    x = _tile_case((132, 68), np.float32, 4)
+    want = x.t().contiguous()
+    assert _same_bits(ops.transpose(_one_in(x)), want)
+    assert _same_bits(ops.transpose(x, out=_one_in(torch.empty_like(want))), want)
+    for dtype in (np.uint16, np.float32):
+        p = _tile_case((2, 72, 136), dtype, 5)
+        want_p = _planes_t(p)
+        assert _same_bits(ops.transpose_planes(_one_in(p)), want_p)
+        assert _same_bits(ops.transpose_planes(p, out=_one_in(torch.empty_like(want_p))), want_p)
+    mu, lv = _tile_case((132, 68), np.float32, 6), _tile_case((132, 68), np.float32, 7)
+    for spread, (sp, want_m, want_s) in _prep_wants(mu, lv).items():
+        for m, s in (ops.prep_planes(_one_in(mu), sp, spread=spread), ops.prep_planes(mu, _one_in(sp), spread=spread),
+                     ops.prep_planes(mu, sp, spread=spread, out_mu=_one_in(torch.empty_like(want_m))),
+                     ops.prep_planes(mu, sp, spread=spread, out_sigma=_one_in(torch.empty_like(want_s)))):
+            assert _same_bits(m, want_m) and _same_bits(s, want_s), spread
+
+
 @pytest.mark.timeout(600)
 def test_logvar_to_sigma_is_torchs_for_every_float32():
     """compress_latents hands the encoder's log-variances to the planes kernel, which takes sigma = sqrtf(expf(.)) itself

@@ -2,8 +2,8 @@
 operation: the LDS lookups of the evaluation loop (k_lookup_lds: XCD renumbering, the pipelined loop of whole blocks, ragged
 channel groups, both mixed dispatches), the rank GEMM with several word tiles per workgroup (k_rank_gemm: accumulator reset,
 prefetch across tiles, the clamped last range, the k seam of the last chunk), and the grid-capped reductions and scans of
-vbq_hist.hip (k_moments_flat's main loop, k_moments_bc at its channel limit, k_rd_sums, k_index_max, k_check_inputs, k_hist_tiled
-with several row passes).
+vbq_reduce.hip (k_moments_flat's main loop, k_moments_bc at its channel limit, k_rd_sums, k_index_max, k_check_inputs) and
+vbq_hist.hip (k_hist_tiled with several row passes).
 
 The launchers size their grids from the CU count and from thresholds, so the shapes are derived from the device's CU count with
 the launch rules restated in tests/launch_plans.py (kept equal to the sources by tests/test_launch_plans_host.py), and every test

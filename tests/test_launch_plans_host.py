@@ -64,7 +64,7 @@ def test_rank_constants_match_the_source():
 
 
 def test_reduction_caps_match_the_source():
-    s = _src("vbq_hist.hip")
+    s = _src("vbq_reduce.hip")
     assert int(_one(r"const int64_t cap = (\d+) / n_ch \+ 1;", s, "moments cap")) == LP.MOMENTS_FLAT_WGS
     assert int(_one(r"for \(; q \+ (\d+) \* stride < nq; q \+= \d+ \* stride\)", s, "moments main loop")) == LP.MOMENTS_FLAT_LOADS - 1
     per, cap = _one(r"int64_t gx = \(E \+ 256 \* (\d+) - 1\) / \(256 \* \d+\);\s*if \(gx > (\d+)\) gx = \d+;", s, "moments_bc grid")
@@ -76,6 +76,7 @@ def test_reduction_caps_match_the_source():
         assert int(_one(r"int64_t gx = \(n \+ 255\) / 256;\s*if \(gx > (\d+)\) gx = \d+;", body, who)) == LP.SCAN_WGS
     assert int(_one(r"const int64_t cap = \(int64_t\)num_cus\(\) \* (\d+) / chunks \+ 1;", s, "rd_sums cap")) == LP.RD_WGS_PER_CU
     assert int(_one(r"constexpr int kRdChunk = (\d+);", s, "kRdChunk")) == LP.RD_CHUNK
+    s = _src("vbq_hist.hip")
     assert int(_one(r"int64_t gx = (\d+) / \(\(int64_t\)groups \* L\) \+ 1;", s, "hist_tiled grid")) == LP.HIST_TILED_WGS
     rows, stride = _one(r"for \(long r = \(long\)blockIdx\.x \* (\d+) \+ slot; r < n_rows; r \+= \(long\)gridDim\.x \* (\d+)\)", s, "hist_tiled rows")
     assert int(rows) == int(stride) == LP.HIST_TILED_ROWS

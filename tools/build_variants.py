@@ -3,8 +3,9 @@
 
     python tools/build_variants.py tag1:-DFOO=1,-DBAR tag2:-DFOO=2 ...
 
-Recompiles the sources that read experiment macros (vbq_quantize_fast.hip, vbq_notebook.hip, vbq_hist.hip) with the extra
-flags of each tag, links them with the cached objects of the regular build and writes tools/bin/libvbq_<tag>.so
+Recompiles the sources that read experiment macros (vbq_quantize_fast.hip, vbq_notebook.hip, vbq_hist.hip -- K2 and what its
+flush uses, nothing else --, vbq_latents.hip) with the extra flags of each tag, links them with the cached objects of the regular
+build and writes tools/bin/libvbq_<tag>.so
 (git-ignored; *.so files travel to the GPU box).  Select one with VBQ_HIP_LIBRARY=tools/bin/libvbq_<tag>.so.
 """
 import os

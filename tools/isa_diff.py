@@ -2,6 +2,7 @@
 """Developer tool: do two trees compile the same gfx950 machine code?  The check of a refactor, without a GPU.
 
     python tools/isa_diff.py PARENT_TREE HEAD_TREE vbq_amd/csrc/vbq_notebook.hip [more sources] [-DVBQ_ONLY_N10]
+    python tools/isa_diff.py PARENT_TREE HEAD_TREE --a-sources vbq_amd/csrc/a.hip,... --b-sources vbq_amd/csrc/b.hip,...
 
 PARENT_TREE is a checkout of the parent OUTSIDE the repository (`git worktree add DIR REV`, or `git archive REV | tar -x
 -C DIR`).  Each source (a path relative to a tree's root) is compiled device-only to assembly in both trees with the flags
@@ -11,6 +12,9 @@ of vbq_amd/build.py (HIPCC_FLAGS + extra_flags()) and each tree's own include di
 per kernel (and per out-of-line device function): `identical`, or the number of differing lines and the descriptor
 fields of both sides.  --show SUBSTRING also prints the unified diff of the functions whose name contains it.
 The exit status is 1 when anything differs.  Texts are compared; no instruction is looked for.
+With --a-sources / --b-sources (comma-separated) the functions of each side are pooled over its list before they are paired:
+the form for a refactor that moves functions between files, whose mangled names do not depend on the file that holds them.
+A name defined twice on one side is an error.
 """
 import argparse
 import difflib
@@ -113,7 +117,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("tree_a")
     ap.add_argument("tree_b")
-    ap.add_argument("sources", nargs="+")
+    ap.add_argument("sources", nargs="*")
+    ap.add_argument("--a-sources", default="")
+    ap.add_argument("--b-sources", default="")
     ap.add_argument("--a-flags", default="")
     ap.add_argument("--b-flags", default="")
     ap.add_argument("--show", default=None)
@@ -122,15 +128,27 @@ def main():
         ap.error("unknown arguments: " + " ".join(common))
     trees = [os.path.abspath(args.tree_a), os.path.abspath(args.tree_b)]
     side_flags = [shlex.split(args.a_flags), shlex.split(args.b_flags)]
-    jobs = [(t, s, extra_flags() + common + f) for s in args.sources for t, f in zip(trees, side_flags)]
+    pools = [[s for s in p.split(",") if s] for p in (args.a_sources, args.b_sources)]
+    if bool(pools[0]) != bool(pools[1]) or bool(pools[0]) == bool(args.sources):
+        ap.error("give sources to compare file by file, or --a-sources and --b-sources to compare them pooled")
+    # one comparison per source, or ONE of everything side A defines against everything side B defines
+    groups = [(" + ".join(pools[0]) + " | " + " + ".join(pools[1]), pools)] if pools[0] else [(s, ([s], [s])) for s in args.sources]
+    jobs = [(t, s, extra_flags() + common + f) for _, sides in groups for t, f, srcs in zip(trees, side_flags, sides) for s in srcs]
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1, len(jobs))) as ex:
-        asms = list(ex.map(lambda j: split(compile_asm(*j)), jobs))
+        asms = iter(list(ex.map(lambda j: split(compile_asm(*j)), jobs)))
     differ = 0
-    for i, src in enumerate(args.sources):
-        fa, fb = asms[2 * i], asms[2 * i + 1]
+    for title, sides in groups:
+        fa, fb = {}, {}
+        for pooled, srcs in zip((fa, fb), sides):
+            for src in srcs:
+                funcs = next(asms)
+                twice = sorted(set(funcs) & set(pooled))
+                if twice:
+                    sys.exit(f"{src}: defined in another source of the same side as well: {', '.join(twice)}")
+                pooled.update(funcs)
         names = list(fa) + [n for n in fb if n not in fa]
         dem = demangle(names)
-        print(f"== {src}: {len(names)} functions")
+        print(f"== {title}: {len(names)} functions")
         for n in names:
             if n not in fa or n not in fb:
                 differ += 1

@@ -1,12 +1,8 @@
 // The per-image call of the reference's evaluation loop -- ChannelwisePriorCDFQuantizer.compress_latents,
 // img-compression/quantizer.py:190-240, called once per image by utils.py:542-554 -- as ONE C call and three launches:
 //
-//   k_prep_planes       channel-last means / spreads [B][C] -> channel-major planes [C][B] (quantizer.py:163-164,223),
-//                       with sigma = sqrt(exp(logvar)) folded in when the caller hands the log-variances as they come out of
-//                       the encoder (quantizer.py:197,202: `tf.exp(posterior_logvars) ** 0.5`): sqrtf is the IEEE root
-//                       (__fsqrt_rn is NOT on gfx950) and expf is the device library's exp -- the numbers torch's
-//                       `exp(x) ** 0.5` gives on this device for every one of the 2^32 float32 inputs
-//                       (tests/test_gpu_api.py::test_logvar_to_sigma_is_torchs_for_every_float32)
+//   k_prep_planes       channel-last means / spreads [B][C] -> channel-major planes [C][B], sigma = sqrt(exp(logvar)) folded in
+//                       (vbq_transpose.hip)
 //   K1 / K1e / K1p      the solve on planes (vbq_quantize_f32)
 //   k_gather_latents    ONE pass over the rank indices [L][C][B]: Z_hat = sorted table[c][q]  (quantizer.py:224-225),
 //                       raw_num_bits = level(q) or level_len[l][c][level(q)] (:171-175,186-188), num_bits =
@@ -14,6 +10,7 @@
 //                       optionally the indices themselves channel-last.  From two images up the Z_hat and num_bits lookups
 //                       go to k_lookup_lds (16 channel tables resident in the LDS) and this pass keeps the rest.
 // and, at the end of the file, the whole two-pass build of quantizer.py:82-150 as one C call (vbq_build_entropy_models_f32).
+// The plain lookups of vbq_gather_f32 (k_gather, k_gather_transpose) sit behind the fused ones.
 //
 // The level of rank index q is N - ctz(q + 1) (slot (n, i) <-> rank (2i + 1) 2^(N-n) - 1), so no per-rank length table is
 // built or read.
@@ -25,58 +22,6 @@
 
 namespace vbq {
 namespace {
-
-// ---------------------------------------------------------------------------- planes from channel-last latents
-// in [rows][cols] -> out [cols][rows], 64 x 64 tiles through LDS; blockIdx.y = 0: means, 1: spreads (sqrt when asked).
-__global__ void __launch_bounds__(256)
-k_prep_planes(const float *__restrict__ in0, const float *__restrict__ in1, long rows, long cols, float *__restrict__ out0,
-              float *__restrict__ out1, int sqrt1, int v4) {
-    __shared__ float tile[64][65];
-    const bool second = blockIdx.y == 1;
-    const float *in = second ? in1 : in0;
-    float *out = second ? out1 : out0;
-    const int kind = second ? sqrt1 : 0;                         // 0: copy, 1: sqrt(x), 2: sqrt(exp(x))
-    auto f = [kind](float x) { return kind == 0 ? x : sqrtf(kind == 2 ? expf(x) : x); };
-    const long ctiles = (cols + 63) / 64;
-    const long r0 = ((long)blockIdx.x / ctiles) * 64, c0 = ((long)blockIdx.x % ctiles) * 64;
-    if (v4 && r0 + 64 <= rows && c0 + 64 <= cols) {
-        float4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = threadIdx.x + 256 * k, lr = i >> 4, lc = (i & 15) * 4;
-            v[k] = *reinterpret_cast<const float4 *>(in + (r0 + lr) * cols + c0 + lc);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = threadIdx.x + 256 * k, lr = i >> 4, lc = (i & 15) * 4;
-            if (kind) { v[k].x = f(v[k].x); v[k].y = f(v[k].y); v[k].z = f(v[k].z); v[k].w = f(v[k].w); }
-            tile[lr][lc] = v[k].x; tile[lr][lc + 1] = v[k].y; tile[lr][lc + 2] = v[k].z; tile[lr][lc + 3] = v[k].w;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = threadIdx.x + 256 * k, lc = i >> 4, lr = (i & 15) * 4;
-            *reinterpret_cast<float4 *>(out + (c0 + lc) * rows + r0 + lr) =
-                make_float4(tile[lr][lc], tile[lr + 1][lc], tile[lr + 2][lc], tile[lr + 3][lc]);
-        }
-        return;
-    }
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;          // 64 x 4
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const long r = r0 + ty + 4 * k, c = c0 + tx;
-        if (r < rows && c < cols) {
-            const float x = in[r * cols + c];
-            tile[ty + 4 * k][tx] = f(x);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const long c = c0 + ty + 4 * k, r = r0 + tx;
-        if (r < rows && c < cols) out[c * rows + r] = tile[tx][ty + 4 * k];
-    }
-}
 
 // ---------------------------------------------------------------------------- fused lookups of one solve
 // idx planes [L][C][B] -> up to four channel-last outputs [L][B][C].  Tile = 64 channels x 32 rows: the index reads are
@@ -461,23 +406,85 @@ extern "C" int vbq_gather_latents_u16(const uint16_t *d_idx_planes, int64_t n_ro
                           d_out_num_bits, d_out_idx, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int vbq_prep_planes_f32(const float *d_means_bc, const float *d_spread_bc, int32_t spread_kind, int64_t n_rows,
-                                   int32_t n_ch, float *d_mu_cb, float *d_sigma_cb, void *stream) {
+// ---------------------------------------------------------------------------- plain table lookups (vbq_gather_f32)
+namespace vbq {
+namespace {
+// same layout in and out: one coalesced pass
+__global__ void __launch_bounds__(256)
+k_gather(const uint16_t *__restrict__ idx, long n_rows, int C, int layout, long E, int T,
+         const float *__restrict__ tab, int per_lambda, float *__restrict__ out) {
+    const int l = blockIdx.y;
+    const uint16_t *src = idx + (long)l * E;
+    float *dst = out + (long)l * E;
+    const float *tl = tab + (per_lambda ? (long)l * C * T : 0);
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (long)gridDim.x * blockDim.x) {
+        const int c = (C == 1) ? 0 : (layout == VBQ_LAYOUT_BC ? (int)(e % C) : (int)(e / n_rows));
+        dst[e] = tl[(long)c * T + min((int)src[e], T - 1)];     // foreign indices >= T stay inside the table
+    }
+}
+
+// idx and out in different layouts: 32 x 32 tiles through LDS, both sides coalesced.
+// in_rows x in_cols is the shape of the idx matrix as stored ([C][B] for CB, [B][C] for BC).
+__global__ void __launch_bounds__(256)
+k_gather_transpose(const uint16_t *__restrict__ idx, long in_rows, long in_cols, int in_layout, long E, int C, int T,
+                   const float *__restrict__ tab, int per_lambda, float *__restrict__ out) {
+    __shared__ float tile[32][33];
+    const int l = blockIdx.z;
+    const uint16_t *src = idx + (long)l * E;
+    float *dst = out + (long)l * E;
+    const float *tl = tab + (per_lambda ? (long)l * C * T : 0);
+    const long ctiles = (in_cols + 31) / 32;                         // tiles numbered along blockIdx.x, columns fastest
+    const long r0 = ((long)blockIdx.x / ctiles) * 32, c0 = ((long)blockIdx.x % ctiles) * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long r = r0 + ty + 8 * k, c = c0 + tx;
+        if (r < in_rows && c < in_cols) {
+            const int ch = in_layout == VBQ_LAYOUT_CB ? (int)r : (int)c;
+            tile[ty + 8 * k][tx] = tl[(long)ch * T + min((int)src[r * in_cols + c], T - 1)];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long c = c0 + ty + 8 * k, r = r0 + tx;                 // output row = input column
+        if (r < in_rows && c < in_cols) dst[c * in_rows + r] = tile[tx][ty + 8 * k];
+    }
+}
+}  // namespace
+}  // namespace vbq
+
+extern "C" int vbq_gather_f32(const uint16_t *d_idx, int64_t n_rows, int32_t n_ch, int32_t layout,
+                              int32_t n_lambda, int32_t N, const float *d_tab, int32_t tab_per_lambda,
+                              float *d_out, int32_t out_layout, void *stream) {
     using namespace vbq;
-    VBQ_REQUIRE(n_rows >= 0 && n_ch >= 1, VBQ_ERR_INVALID_ARGUMENT, "vbq_prep_planes_f32: bad sizes");
-    VBQ_REQUIRE(spread_kind >= VBQ_SPREAD_SIGMA && spread_kind <= VBQ_SPREAD_LOGVAR, VBQ_ERR_INVALID_ARGUMENT,
-                "vbq_prep_planes_f32: unknown spread_kind %d", spread_kind);
+    VBQ_REQUIRE(n_rows == 0 || (d_idx && d_tab && d_out), VBQ_ERR_INVALID_ARGUMENT, "vbq_gather_f32: null pointer argument");
+    VBQ_REQUIRE(n_rows >= 0 && n_ch >= 1 && n_lambda >= 1 && n_lambda <= 65535 && N >= 0 && N <= 15,
+                VBQ_ERR_INVALID_ARGUMENT, "vbq_gather_f32: bad sizes");
+    VBQ_REQUIRE((layout == VBQ_LAYOUT_BC || layout == VBQ_LAYOUT_CB) &&
+                    (out_layout == VBQ_LAYOUT_BC || out_layout == VBQ_LAYOUT_CB),
+                VBQ_ERR_INVALID_ARGUMENT, "vbq_gather_f32: unknown layout %d -> %d", layout, out_layout);
     if (n_rows == 0) return VBQ_OK;
-    VBQ_REQUIRE(d_means_bc && d_spread_bc && d_mu_cb && d_sigma_cb && d_means_bc != d_mu_cb && d_spread_bc != d_sigma_cb,
-                VBQ_ERR_INVALID_ARGUMENT, "vbq_prep_planes_f32: null or aliased pointers");
-    const int64_t tiles = ((n_rows + 63) / 64) * (((int64_t)n_ch + 63) / 64);
-    VBQ_REQUIRE(tiles <= 0x7fffffffll, VBQ_ERR_UNSUPPORTED, "vbq_prep_planes_f32: more than 2^31 - 1 tiles of 64 x 64");
-    const uintptr_t all = reinterpret_cast<uintptr_t>(d_means_bc) | reinterpret_cast<uintptr_t>(d_spread_bc) |
-                          reinterpret_cast<uintptr_t>(d_mu_cb) | reinterpret_cast<uintptr_t>(d_sigma_cb);
-    const int v4 = n_rows % 4 == 0 && n_ch % 4 == 0 && (all & 15) == 0;
-    hipLaunchKernelGGL(k_prep_planes, dim3((unsigned)tiles, 2), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), d_means_bc,
-                       d_spread_bc, (long)n_rows, (long)n_ch, d_mu_cb, d_sigma_cb, (int)spread_kind, v4);
-    VBQ_CHECK_LAUNCH("prep_planes");
+    const int64_t E = n_rows * (int64_t)n_ch;
+    if (n_ch > 1 && layout != out_layout) {
+        const int64_t in_rows = layout == VBQ_LAYOUT_CB ? n_ch : n_rows;
+        const int64_t in_cols = layout == VBQ_LAYOUT_CB ? n_rows : n_ch;
+        const int64_t tiles = ((in_cols + 31) / 32) * ((in_rows + 31) / 32);
+        VBQ_REQUIRE(n_lambda <= 65535 && tiles <= 0x7fffffffll, VBQ_ERR_UNSUPPORTED,
+                    "vbq_gather_f32: grid too large for the transposing form");
+        hipLaunchKernelGGL(k_gather_transpose, dim3((unsigned)tiles, 1, (unsigned)n_lambda),
+                           dim3(256), 0, reinterpret_cast<hipStream_t>(stream), d_idx, (long)in_rows, (long)in_cols,
+                           (int)layout, (long)E, (int)n_ch, table_size(N), d_tab, (int)tab_per_lambda, d_out);
+        VBQ_CHECK_LAUNCH("gather_transpose");
+        return VBQ_OK;
+    }
+    int64_t gx = (E + 255) / 256;
+    const int64_t cap = 4096 / n_lambda + 1;
+    if (gx > cap) gx = cap;
+    hipLaunchKernelGGL(k_gather, dim3((unsigned)gx, (unsigned)n_lambda), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), d_idx, (long)n_rows, (int)n_ch, (int)layout, (long)E,
+                       table_size(N), d_tab, (int)tab_per_lambda, d_out);
+    VBQ_CHECK_LAUNCH("gather");
     return VBQ_OK;
 }
 
