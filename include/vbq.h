@@ -958,6 +958,51 @@ int vbq_rans_decode_window_f32(const uint16_t *d_payload, int64_t n_words, const
                                const uint16_t *d_freq, int32_t n_tables, const float *d_values, int64_t w0, int64_t w1,
                                int64_t w2, float *d_out, uint32_t *d_status, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Batch encode: every segment of MANY latent files in segments (vbq_amd/bitstream.py, magic "VBQb") in ONE launch -- the
+ * writer's counterpart of the window decode.  vbq_rans_encode_u16 gives a workgroup 64 consecutive segments of one stream;
+ * a small file has a few segments per channel and leaves most lanes idle.  Here the caller lists the work as items
+ * (file, segment) in blocks of 64 that share a frequency table, and a workgroup codes one block of one channel: its lanes take
+ * segments of different files.
+ *   d_idx      u16 [n_idx]: the rank indices of all files.  Symbol i of channel c of file f is
+ *              d_idx[idx_base_f + c * idx_stride_f + i], 0 <= i < n_f.
+ *   d_files    int64 [n_files][6], per file: idx_base, idx_stride, n, seg_base, table, 0.  The file has n symbols per channel in
+ *              nseg_f = ceil(n / seg) segments; `table` picks the block of d_freq (the file's lambda); the last field is
+ *              reserved.
+ *   d_items    int32 [n_items][2]: (file, segment within a stream), n_items a multiple of 64.  Items 64 b .. 64 b + 63 are block
+ *              b; the files of one block must share one `table` (the block's table is that of its first item whose file names a
+ *              valid one).  An item with file == -1 is padding and skipped silently.  Every (file, segment) to be coded appears
+ *              once; the same item serves every channel.
+ *   d_freq     u16 [n_tables][n_ch][T], T = 2^(N+1) - 1, every entry >= 1, every row summing to 2^15.
+ *   d_canon    u16 [n_ch][T] or NULL.  Given: symbol d_canon[c][idx] is coded instead of idx (the canonical rank of a run of
+ *              equal code points); the map is applied once to the staged table, not per symbol.  An entry outside the table
+ *              counts as 0.
+ *   d_words    u16 [M][seg + 2], d_sizes u32 [M].  Segment g of channel c of file f goes to slot seg_base_f + c * nseg_f + g:
+ *              its words and its size are exactly what vbq_rans_encode_u16 writes for the same symbols with the row
+ *              d_freq[table_f][c] -- same state machine, same emission order, final state low half then high half; an index
+ *              outside the table is coded as symbol 0.  Slots that no item names, and the words of a slot past its size, are
+ *              left untouched.  With seg_base the file-major exclusive sum of n_ch * nseg_f, ONE
+ *              vbq_rans_pack_u16(d_words, d_sizes, n_streams = 1, n = M * seg, seg, ...) packs all files, in file order.
+ *   d_status   u32 [n_files], may be NULL, OR-ed into; zero it first.  Bit 7 (128) for a file:
+ *                of the descriptor -- `table` outside [0, n_tables), n < 1, symbols of some channel outside [0, n_idx), slots
+ *                outside [0, M): every item of the file finds the same, so nothing of that file is written;
+ *                of one item -- a segment id outside [0, nseg_f), or a file whose table is not the block's: that item writes
+ *                nothing.
+ *              An item whose file id lies outside [0, n_files) (other than -1) writes nothing and sets bit 7 of word 0: it has
+ *              no word of its own.
+ * Descriptors and items are range-checked on the device, without overflow, before anything is indexed with them.  Index loads
+ * are 16 bytes wide where a segment's address allows it and 2 bytes wide for an unaligned head or tail: the words do not depend
+ * on the alignment.
+ * Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): n_files <= 65535, n_ch <= 65535, seg in 1..65533, N in 1..10,
+ * n_tables >= 1, every size >= 0, n_items a multiple of 64, M * (seg + 2) words addressable, no null pointer (d_canon and
+ * d_status excepted).  n_files == 0, n_items == 0 or n_ch == 0 return VBQ_OK with no launch.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_encode_files_u16(const uint16_t *d_idx, int64_t n_idx, const int64_t *d_files, int32_t n_files,
+                              const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t seg, int32_t N,
+                              const uint16_t *d_freq, int32_t n_tables, const uint16_t *d_canon, uint16_t *d_words,
+                              uint32_t *d_sizes, int64_t M, uint32_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

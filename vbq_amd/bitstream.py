@@ -53,6 +53,7 @@ from __future__ import annotations
 import hashlib
 import math
 import struct
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import ClassVar, Tuple
 
@@ -415,6 +416,77 @@ def box_segments(dims, lo, hi, segment) -> np.ndarray:
     np.add.at(mark, (first + lo[2]) // segment, 1)
     np.add.at(mark, (first + hi[2] - 1) // segment + 1, -1)
     return np.flatnonzero(np.cumsum(mark[:-1]) > 0).astype(np.int32)
+
+
+# ---- batches of files in segments, written (ChannelwisePriorCDFQuantizer.compress_latents_to_bytes_batch; include/vbq.h, "Batch
+# encode").  One encode launch codes every segment of every file: the plan says where a file's rows sit among the rows solved at
+# its lambda, where its segments go, and which 64 segments share a workgroup.
+ENCODE_BLOCK = 64                            # items per workgroup of vbq_rans_encode_files_u16
+ENCODE_ROW_ALIGN = 8                         # a file's run of rows starts at a multiple of 8 rows: 16 bytes of u16 indices
+MAX_BATCH_FILES = 65535                      # the kernel's limit (vbq_rans_encode_files_u16)
+EncodePlan = namedtuple("EncodePlan", "nseg seg_base M row0 group_rows group_row_base n_rows files items")
+
+
+def encode_plan(rows, tables, segment, C, n_tables=None) -> EncodePlan:
+    """What vbq_rans_encode_files_u16 reads, from the rows per channel n_f >= 1 of F files, their table numbers (the files'
+    lambdas, 0 .. n_tables - 1; default n_tables: the largest + 1), the segment length and the number of channels C:
+
+        nseg            int64 [F]         ceil(n_f / segment)
+        seg_base, M     int64 [F], int    the file-major exclusive sum of C * nseg_f and its total: a file's size block is
+                                          sizes[seg_base_f : seg_base_f + C * nseg_f] of the M slots
+        row0            int64 [F]         the files of a table sit next to each other, in file order, in that table's group
+                                          of rows; file f owns rows [row0_f, row0_f + n_f) of its group, row0_f a multiple of
+                                          ENCODE_ROW_ALIGN (the rows up to the next file's are padding: solved, never coded)
+        group_rows      int64 [n_tables]  B_g, the rows of every group, padding included (the index planes are [C, B_g])
+        group_row_base  int64 [n_tables]  the rows of the groups before it; n_rows their total.  The indices of all groups
+                                          are one array: group g's planes start at element C * group_row_base_g
+        files           int64 [F, 6]      the descriptors: idx_base = C * group_row_base_g + row0_f, idx_stride = B_g, n_f,
+                                          seg_base_f, table, 0
+        items           int32 [n_items, 2]  the work items (file, segment): table by table, within a table file by file and
+                                          segment by segment, every table's list padded with (-1, -1) to a multiple of
+                                          ENCODE_BLOCK -- so every block of ENCODE_BLOCK items holds one table only
+
+    ValueError for a bad segment, C < 1, a row count < 1, a table outside [0, n_tables) or more than MAX_BATCH_FILES files."""
+    check_segment(segment)
+    segment, C = int(segment), int(C)
+    if C < 1:
+        raise ValueError("zero channels")
+    n = np.asarray(rows, dtype=np.int64).reshape(-1)
+    tab = np.asarray(tables, dtype=np.int64).reshape(-1)
+    F = n.size
+    if tab.size != F:
+        raise ValueError(f"{tab.size} tables for {F} files")
+    if F > MAX_BATCH_FILES:
+        raise ValueError(f"{F} files: one call takes at most {MAX_BATCH_FILES}")
+    if F and int(n.min()) < 1:
+        raise ValueError(f"file {int(np.flatnonzero(n < 1)[0])} has no rows")
+    n_tables = (int(tab.max()) + 1 if F else 0) if n_tables is None else int(n_tables)
+    if F and (int(tab.min()) < 0 or int(tab.max()) >= n_tables):
+        raise ValueError(f"table outside [0, {n_tables})")
+    nseg = (n + segment - 1) // segment
+    if F and int(nseg.max()) > np.iinfo(np.int32).max:
+        raise ValueError(f"{int(nseg.max())} segments per stream are too many")
+    per_file = C * nseg
+    seg_base = np.cumsum(per_file) - per_file
+    padded = (n + ENCODE_ROW_ALIGN - 1) // ENCODE_ROW_ALIGN * ENCODE_ROW_ALIGN
+    row0 = np.zeros(F, np.int64)
+    group_rows = np.zeros(n_tables, np.int64)
+    lists = []
+    for t in range(n_tables):
+        fs = np.flatnonzero(tab == t)
+        run = np.cumsum(padded[fs])
+        row0[fs] = run - padded[fs]
+        group_rows[t] = run[-1] if fs.size else 0
+        reps = nseg[fs]
+        first = np.cumsum(reps) - reps
+        item = np.stack([np.repeat(fs, reps), np.arange(int(reps.sum())) - np.repeat(first, reps)], axis=1)
+        lists += [item, np.full((-item.shape[0] % ENCODE_BLOCK, 2), -1, np.int64)]
+    group_row_base = np.cumsum(group_rows) - group_rows
+    items = (np.concatenate(lists) if lists else np.zeros((0, 2), np.int64)).astype(np.int32)
+    files = np.stack([C * group_row_base[tab] + row0, group_rows[tab], n, seg_base, tab, np.zeros(F, np.int64)], axis=1) \
+        if F else np.zeros((0, 6), np.int64)
+    return EncodePlan(nseg, seg_base, int(per_file.sum()), row0, group_rows, group_row_base, int(group_rows.sum()),
+                      np.ascontiguousarray(files, dtype=np.int64), np.ascontiguousarray(items))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -908,3 +908,54 @@ def rans_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: torc
                                                 N, _ptr(freq), n_tables, _ptr(values), box[0], box[1], box[2], _ptr(out),
                                                 _ptr(status), _stream(payload)), "vbq_rans_decode_window_f32")
     return out, status
+
+
+ENCODE_BAD_FILE = 128                            # status bit 7 of the batch encode
+
+
+def rans_encode_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor, freq: torch.Tensor, M: int, *, seg: int,
+                      N: int = 10, canon: Optional[torch.Tensor] = None, words: Optional[torch.Tensor] = None,
+                      sizes: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """vbq_rans_encode_files_u16 (include/vbq.h, "Batch encode"): every listed segment of every file in one launch.  idx u16
+    [n_idx], all files' rank indices; files int64 [F, 6] (idx_base, idx_stride, n, seg_base, table, 0); items int32 [n_items, 2]
+    (file, segment), n_items a multiple of 64, a block of 64 of one table, file -1 = padding (bitstream.encode_plan builds
+    both); freq u16 [n_tables, C, T]; canon u16 [C, T] or None.  Returns (words u16 [M, seg + 2], sizes u32 [M], status u32
+    [F]): slot seg_base_f + c nseg_f + g holds segment g of channel c of file f as RansCodec.encode writes it; slots no item
+    names keep what `words` / `sizes` held (new ones are zeroed).  `status` is OR-ed into: zeroed here unless given."""
+    idx = _dev(idx, torch.uint16, "idx")
+    files = _dev(files, torch.int64, "files")
+    items = _dev(items, torch.int32, "items")
+    freq = _dev(freq, torch.uint16, "freq")
+    seg, N, M = int(seg), int(N), int(M)
+    T = table_size(N)
+    if files.dim() != 2 or files.shape[1] != 6:
+        raise ValueError(f"files must be [F, 6] (idx_base, idx_stride, n, seg_base, table, 0), got {tuple(files.shape)}")
+    if items.dim() != 2 or items.shape[1] != 2:
+        raise ValueError(f"items must be [n_items, 2] (file, segment), got {tuple(items.shape)}")
+    if freq.dim() != 3 or freq.shape[2] != T:
+        raise ValueError(f"expected freq [n_tables, C, {T}], got {tuple(freq.shape)}")
+    F, n_tables, n_ch = files.shape[0], freq.shape[0], freq.shape[1]
+    if canon is not None:
+        canon = _dev(canon, torch.uint16, "canon")
+        if tuple(canon.shape) != (n_ch, T):
+            raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
+    if M < 0:
+        raise ValueError(f"M = {M} slots")
+    given = words is not None
+    words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words")
+    if sizes is None:
+        sizes = torch.zeros(M, dtype=torch.uint32, device=idx.device)
+        if not given:
+            words.zero_()
+    else:
+        sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes")
+    if status is None:
+        status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
+    else:
+        status = _dev(status, torch.uint32, "status")
+        if status.numel() != F:
+            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+    check(_lib.lib().vbq_rans_encode_files_u16(_ptr(idx), idx.numel(), _ptr(files), F, _ptr(items), items.shape[0], n_ch, seg, N,
+                                               _ptr(freq), n_tables, _ptr(canon), _ptr(words), _ptr(sizes), M, _ptr(status),
+                                               _stream(idx)), "vbq_rans_encode_files_u16")
+    return words, sizes, status

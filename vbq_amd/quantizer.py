@@ -366,10 +366,10 @@ class ChannelwisePriorCDFQuantizer:
             rows.append(lv[None, :].astype(model.dtype) + model)
         return torch.from_numpy(np.stack(rows).astype(np.float32))
 
-    def _solve_idx(self, mu_cb, sg_cb, lambs, level_len):
-        """u16 rank indices [L, C, B] on the device."""
+    def _solve_idx(self, mu_cb, sg_cb, lambs, level_len, out_idx=None):
+        """u16 rank indices [L, C, B] on the device (written into out_idx where given)."""
         return ops.quantize(mu_cb, sg_cb, self._table_dev(), [float(l) for l in lambs], N=self.max_bits_per_coord,
-                            level_len=level_len, layout="cb")
+                            level_len=level_len, layout="cb", out_idx=out_idx)
 
     def _workspace(self, name: str, nbytes: int) -> torch.Tensor:
         """A persistent device workspace, grown on demand (planes + index planes of the per-image call)."""
@@ -883,6 +883,167 @@ class ChannelwisePriorCDFQuantizer:
         """`vae.encode(X)`, then compress_latents_to_bytes."""
         posterior_means, posterior_logvars = vae.encode(X)
         return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment, layout=layout, part=part)
+
+    # ------------------------------------------------------------------ batches of files, written (include/vbq.h, "Batch encode")
+    def _batch_file_inputs(self, latents, lambs, segment):
+        """Every check of compress_latents_to_bytes_batch, before any device work -> (pairs, shapes, keys, segment)."""
+        self._check_coder_bits()
+        bitstream.check_segment(segment)
+        pairs = list(latents)
+        F = len(pairs)
+        lambs = [lambs] * F if np.ndim(lambs) == 0 else list(lambs)
+        if len(lambs) != F:
+            raise ValueError(f"{len(lambs)} lambdas for {F} files")
+        if F > bitstream.MAX_BATCH_FILES:
+            raise ValueError(f"{F} files: one call takes at most {bitstream.MAX_BATCH_FILES}")
+        shapes = []
+        for i, pair in enumerate(pairs):
+            try:
+                means, logvars = pair
+            except (TypeError, ValueError):
+                raise ValueError(f"file {i}: expected a pair (posterior_means, posterior_logvars)") from None
+            try:
+                shapes.append(self._file_layout(means, logvars, "segments", segment, None)[0])
+            except ValueError as e:
+                raise ValueError(f"file {i}: {e}") from None
+            if 0 in shapes[-1]:
+                raise ValueError(f"file {i}: empty latent shape {shapes[-1]}")
+        keys = [self._lambda_key(l) for l in lambs] if F else []
+        return pairs, shapes, keys, int(segment)
+
+    def compress_latents_to_bytes_batch(self, latents, lambs, segment=1024):
+        """[compress_latents_to_bytes(means_f, logvars_f, lambs[f], segment=segment) for f], byte for byte, with ONE encode
+        launch for all files.  `latents`: a sequence of F pairs (posterior_means, posterior_logvars), channel-last [..., C],
+        NumPy or tensors, on the host or the device; shapes and numbers of leading axes may differ from file to file.  `lambs`:
+        one built lambda for all files or a sequence of F, repeats and any order allowed.  Files in segments only (magic
+        b"VBQb"); the table may have repeated code points.  F == 0 returns [].  Errors are those of the one-file call, raised
+        before any device work: ValueError naming the file's index for a bad shape pair, ValueError for a bad `segment`, for
+        len(lambs) != F or for more than 65535 files, KeyError for a lambda without a model.
+        Work per call, L the number of DISTINCT lambdas: one staging buffer and one upload (the plan of bitstream.encode_plan,
+        zeroed sizes and status words, and -- for inputs that are not all device tensors -- the latents; all-device inputs are
+        joined by one torch.cat instead); per distinct lambda one vbq_prep_planes_f32 and one solve over the rows of the files
+        that use it (their rows are adjacent, each file's run rounded up to 8 rows of mean 0, logvar 0 that are solved and
+        never coded; no latent is solved at a lambda its file does not use); ONE vbq_rans_encode_files_u16 over every segment
+        of every file; ONE vbq_rans_pack_u16 over all of them (two launches): 2 L + 3 launches.  Two device-to-host copies:
+        the total, all segment sizes and the status words, then the first `total` payload words.  The F files are assembled
+        on the host (bitstream.Header / bitstream.write); a file's n_words and payload slice come from the cumulative sum of
+        the sizes already there."""
+        from . import _lib
+        b = self._encode_batch_plan(latents, lambs, segment)
+        if b is None:
+            return []
+        plan, C, N = b.plan, self.num_channels, self.max_bits_per_coord
+        d_host, lat = self._encode_batch_upload(b)
+        payload = self._encode_batch_run(b, d_host, lat)
+        F, M = len(b.keys), plan.M
+        h = d_host[:b.back].cpu().numpy()
+        total, sizes, status = int(h[:8].view(np.uint64)[0]), h[8:8 + 4 * M].view(np.uint32), h[8 + 4 * M:].view(np.uint32)
+        for f in np.flatnonzero(status):
+            raise _lib.VBQError(f"file {int(f)}: the batch encoder refused its descriptor (status {int(status[f])})")
+        pay = payload[:total].cpu().numpy()
+        ends = np.cumsum(sizes, dtype=np.int64)[plan.seg_base + C * plan.nseg - 1]      # of every file's words in `pay`
+        out = []
+        for f in range(F):
+            n_words = int(ends[f] - (ends[f - 1] if f else 0))
+            hd = bitstream.Header(N=N, C=C, shape=b.shapes[f], lamb=float(b.keys[f]), digest=b.digests[b.keys[f]],
+                                  n_words=n_words, segment=b.segment)
+            sz = sizes[int(plan.seg_base[f]): int(plan.seg_base[f] + C * plan.nseg[f])]
+            out.append(bitstream.write(hd, sz, pay[int(ends[f]) - n_words: int(ends[f])]))
+        return out
+
+    _EncodeBatch = namedtuple("_EncodeBatch", "plan shapes keys tables digests segment rows pairs on_device host cut back")
+
+    def _encode_batch_plan(self, latents, lambs, segment):
+        """The host side of compress_latents_to_bytes_batch: every check, the plan of bitstream.encode_plan and the ONE staging
+        buffer (b.host, a host tensor u8, see _encode_stage): total u64 | sizes u32 [M] | status u32 [F] -- what comes back
+        first (b.back bytes), zeroed by the upload -- | descriptors int64 [F, 6] | items int32 [n_items, 2] | and, unless every
+        input is a device tensor, means f32 [R, C] | logvars f32 [R, C] with every file's rows where the plan puts them.
+        b.cut: where each part after the first starts.  None when there is no file."""
+        pairs, shapes, keys, segment = self._batch_file_inputs(latents, lambs, segment)
+        F, C = len(pairs), self.num_channels
+        if F == 0:
+            return None
+        tables = sorted(set(keys), key=float)                     # (a stable tag for the codec cache of _coder_stack)
+        digests = {k: self._coder_tables(k, segment)[1] for k in tables}
+        rows = [int(np.prod(sh[:-1], dtype=np.int64)) for sh in shapes]
+        plan = bitstream.encode_plan(rows, [tables.index(k) for k in keys], segment, C, len(tables))
+        M, R = plan.M, plan.n_rows
+        back = 8 + 4 * M + 4 * F
+        cut = [int(c) for c in np.cumsum([back + (-back % 8), plan.files.nbytes, plan.items.nbytes])]
+        on_device = all(isinstance(a, torch.Tensor) and a.is_cuda for pair in pairs for a in pair)
+        host_t = self._encode_stage(cut[2] + (0 if on_device else 8 * R * C))
+        host = host_t.numpy()
+        host[:cut[0]] = 0
+        host[cut[0]:cut[1]] = plan.files.view(np.uint8).reshape(-1)
+        host[cut[1]:cut[2]] = plan.items.view(np.uint8).reshape(-1)
+        if not on_device:
+            stage = host[cut[2]:].view(np.float32).reshape(2, R, C)
+            row_base = plan.group_row_base[plan.files[:, 4]] + plan.row0          # of every file among the R staged rows
+            for f, (means, logvars) in enumerate(pairs):
+                r0, r1 = int(row_base[f]), int(row_base[f]) + rows[f]
+                stage[0, r0:r1] = _to_numpy(means).reshape(-1, C)
+                stage[1, r0:r1] = _to_numpy(logvars).reshape(-1, C)
+                stage[:, r1:r1 + (-rows[f] % bitstream.ENCODE_ROW_ALIGN)] = 0     # the padding rows: mean 0, logvar 0
+        return self._EncodeBatch(plan, shapes, keys, tables, digests, segment, rows, pairs, on_device, host_t, cut, back)
+
+    def _encode_stage(self, nbytes: int) -> torch.Tensor:
+        """The staging buffer of _encode_batch_plan, a host tensor u8 [nbytes]: a view of ONE pinned block kept between calls and grown on
+        demand (no page faults of a new allocation per call, and the upload is one DMA transfer), up to 1 GiB; a larger
+        batch stages in pageable memory.  Not cleared: the plan writes every byte it uploads.  A plan's buffer is valid
+        until the next plan of this quantizer."""
+        if nbytes > 1 << 30:
+            return torch.empty(nbytes, dtype=torch.uint8)
+        st = self._dev_cache.get("_encode_stage")
+        if st is None or st.numel() < nbytes:
+            st = self._dev_cache["_encode_stage"] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
+        return st[:nbytes]
+
+    def _encode_batch_upload(self, b):
+        """-> (b.host on the device, the latents f32 [2, R, C] on the device): the one upload; inputs that are all device
+        tensors are joined by one torch.cat, each file's run padded to a multiple of 8 rows with zeros."""
+        dev, C, plan = self.device, self.num_channels, b.plan
+        d_host = b.host.to(dev)
+        if not b.on_device:
+            return d_host, d_host[b.cut[2]:].view(torch.float32).view(2, plan.n_rows, C)
+        row_base = plan.group_row_base[plan.files[:, 4]] + plan.row0
+        zeros = self._dev("_pad_rows", lambda: torch.zeros((bitstream.ENCODE_ROW_ALIGN, C), dtype=torch.float32))
+        pieces = [[], []]
+        for f in np.argsort(row_base, kind="stable"):
+            for which in (0, 1):
+                pieces[which] += [b.pairs[f][which].detach().to(dev, torch.float32).reshape(-1, C),
+                                  zeros[: -b.rows[f] % bitstream.ENCODE_ROW_ALIGN]]
+        return d_host, torch.cat(pieces[0] + pieces[1]).view(2, plan.n_rows, C)
+
+    def _encode_batch_run(self, b, d_host, lat):
+        """The device side: per distinct lambda one vbq_prep_planes_f32 and one solve of its files' rows into its planes of the
+        one index array, ONE vbq_rans_encode_files_u16, ONE vbq_rans_pack_u16 -> the payload u16 (its first `total` words are
+        valid); total, sizes and status land in d_host[:b.back].  Nothing is read back."""
+        from . import _lib
+        plan, C, N, dev, segment = b.plan, self.num_channels, self.max_bits_per_coord, d_host.device, b.segment
+        F, M, R, cut = len(b.keys), plan.M, plan.n_rows, b.cut
+        d_total, d_sizes = d_host[:8].view(torch.uint64), d_host[8:8 + 4 * M].view(torch.uint32)
+        d_status = d_host[8 + 4 * M:b.back].view(torch.uint32)
+        d_files = d_host[cut[0]:cut[1]].view(torch.int64).view(F, 6)
+        d_items = d_host[cut[1]:cut[2]].view(torch.int32).view(-1, 2)
+        idx = torch.empty(C * R, dtype=torch.uint16, device=dev)
+        for t, key in enumerate(b.tables):
+            r0, B = int(plan.group_row_base[t]), int(plan.group_rows[t])
+            mu_cb, sg_cb = self._prep(lat[0, r0:r0 + B], lat[1, r0:r0 + B], spread="logvar")
+            self._solve_idx(mu_cb, sg_cb, [key], self._level_len_dev([key]), out_idx=idx[C * r0:C * (r0 + B)].view(1, C, B))
+        freq = self._coder_stack(b.tables, segment)._freq(dev).view(len(b.tables), C, -1)
+        canon = None if self._strict else self._dev("canon_u16", lambda: torch.from_numpy(self._canon.astype(np.uint16)))
+        words = torch.empty((M, segment + 2), dtype=torch.uint16, device=dev)      # pack reads valid words only
+        payload = torch.empty(M * (segment + 2), dtype=torch.uint16, device=dev)
+        offsets = torch.empty(M, dtype=torch.int64, device=dev)
+        ops.rans_encode_files(idx, d_files, d_items, freq, M, seg=segment, N=N, canon=canon, words=words, sizes=d_sizes,
+                              status=d_status)
+        _lib.check(_lib.lib().vbq_rans_pack_u16(ops._ptr(words), ops._ptr(d_sizes), 1, M * segment, segment, ops._ptr(payload),
+                                                ops._ptr(offsets), ops._ptr(d_total), ops._stream(words)), "vbq_rans_pack_u16")
+        return payload
+
+    def compress_to_bytes_batch(self, Xs, vae, lambs, segment=1024):
+        """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_bytes_batch."""
+        return self.compress_latents_to_bytes_batch([vae.encode(X) for X in Xs], lambs, segment=segment)
 
     # ------------------------------------------------------------------ lambda maps (vbq_amd.bitstream, magic b"VBQm")
     # A palette `lambs` of 1..4 distinct built lambdas and `classes`, integers in [0, P) shaped like the latents without the
