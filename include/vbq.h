@@ -1003,6 +1003,44 @@ int vbq_rans_encode_files_u16(const uint16_t *d_idx, int64_t n_idx, const int64_
                               const uint16_t *d_freq, int32_t n_tables, const uint16_t *d_canon, uint16_t *d_words,
                               uint32_t *d_sizes, int64_t M, uint32_t *d_status, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Batch sizes: the coded length of MANY latent files in segments at SEVERAL lambdas in ONE launch -- the sizes-only counterpart
+ * of the batch encode, for rate control over a batch.  vbq_rans_sizes_u16 gives a workgroup 64 consecutive segments of one
+ * stream; here the caller lists the work as items (file, segment) in blocks of 64 and a workgroup sizes one block of one
+ * channel at one lambda.  Every file is sized at every lambda.
+ *   d_idx      u16 [n_idx]: the rank indices of all files at all lambdas, one plane of lambda_stride indices per lambda.
+ *              Symbol i of channel c of file f at lambda l is d_idx[l * lambda_stride + idx_base_f + c * idx_stride_f + i],
+ *              0 <= i < n_f.
+ *   d_files    int64 [n_files][6], the batch encoder's descriptors: idx_base, idx_stride and n are read; seg_base, table and
+ *              the reserved field are ignored.  The file has nseg_f = ceil(n / seg) segments per channel.
+ *   d_items    int32 [n_items][2]: (file, segment within a stream), n_items a multiple of 64.  Items 64 b .. 64 b + 63 are block
+ *              b; the files of a block need share nothing.  An item with file == -1 is padding and skipped silently.  The same
+ *              item serves every channel and every lambda.
+ *   d_freq     u16 [n_lambda][n_ch][T], T = 2^(N+1) - 1, every entry >= 1, every row summing to 2^15.
+ *   d_canon    u16 [n_ch][T] or NULL, as in the batch encode: symbol d_canon[c][idx] is sized instead of idx; the map is
+ *              applied once to the staged table.  An entry outside the table counts as 0.
+ *   d_totals   u64 [n_lambda][n_files], ADDED to: zero it first.  d_totals[l][f] grows by the size in 16-bit words (the
+ *              renormalisation words + the two words of the final state) of every listed segment of every channel of file f,
+ *              coded with the row d_freq[l][c]: exactly the d_sizes entry vbq_rans_encode_files_u16 and vbq_rans_sizes_u16
+ *              give for the same symbols; an index outside the table is coded as symbol 0.  Integer adds commute: the result
+ *              does not depend on scheduling.
+ *   d_status   u32 [n_files], may be NULL, OR-ed into; zero it first.  Bit 7 (128) for a file:
+ *                of the descriptor -- n < 1, or symbols of some channel outside [0, lambda_stride): nothing of that file is
+ *                added;
+ *                of one item -- a segment id outside [0, nseg_f): that item adds nothing.
+ *              An item whose file id lies outside [0, n_files) (other than -1) adds nothing and sets bit 7 of word 0.
+ * Descriptors and items are range-checked on the device, without overflow, before anything is indexed with them.  Index loads
+ * are 16 bytes wide where a segment's address allows it and 2 bytes wide for an unaligned head or tail.
+ * Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): n_files <= 65535, n_ch <= 65535, seg in 1..65533, N in 1..10,
+ * n_lambda in 1..65535, every size >= 0, n_items a multiple of 64, n_lambda * lambda_stride <= n_idx, no null pointer (d_canon
+ * and d_status excepted).  n_files == 0, n_items == 0 or n_ch == 0 return VBQ_OK with no launch.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, int64_t lambda_stride, const int64_t *d_files,
+                             int32_t n_files, const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t seg, int32_t N,
+                             const uint16_t *d_freq, int32_t n_lambda, const uint16_t *d_canon, uint64_t *d_totals,
+                             uint32_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

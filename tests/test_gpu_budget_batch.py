@@ -1,0 +1,415 @@
+"""Rate control for batches on the GPU: vbq_rans_sizes_files_u16 against the sum of the C checker's segment sizes, per file and
+lambda -- totals that are added to, unlisted segments, status bits --, and the quantizer's coded_nbytes_batch /
+compress_latents_to_budget_batch / compress_latents_to_total_budget / compress_to_budget_batch against the loop of the one-file
+calls: dicts == dicts and bytes == bytes."""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from oracle import c_oracle as CO
+from vbq_amd import bitstream as bs
+
+pytestmark = pytest.mark.gpu
+N = 10
+LAMBS = [2.0 ** -6, 2.0 ** -2, 2.0, 16.0]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.fail("gpu-marked test run without a ROCm device")
+
+
+# ---------------------------------------------------------------------------------------------------------------- kernel level
+class Batch:
+    """Synthetic indices and frequency tables (built as `Batch` of test_gpu_encode_files.py builds them) with L independent
+    tables and index planes: every file in table 0 of bitstream.encode_plan, one plane of lambda_stride indices per lambda;
+    what no file owns holds T - 1, which no check may ever see coded.  tight: the files follow each other without padding
+    rows and every plane starts one element in, so that plane bases are no multiples of 8 symbols (descriptors of the test's
+    own; segments and items stay the plan's)."""
+
+    def __init__(self, rows, L, C_, seg, bits, seed, canon=False, tight=False):
+        from vbq_amd.coder import quantize_frequencies
+        rng = np.random.default_rng(seed)
+        T = 2 ** (bits + 1) - 1
+        self.C, self.seg, self.bits, self.T, self.rows, self.L, self.F = C_, seg, bits, T, rows, L, len(rows)
+        centre = rng.integers(T // 8, T - T // 8, (L, C_))
+        spread = np.array([0.3, 2.0, 25.0, 300.0])[rng.integers(0, 4, (L, C_))] * T / 2047
+        draw = lambda l, n: np.clip(np.rint(rng.normal(centre[l, :, None], spread[l, :, None], (C_, n))), 0, T - 1).astype(np.uint16)
+        self.freq = np.stack([quantize_frequencies(np.stack([np.bincount(r, minlength=T) for r in draw(l, 4000)]))
+                              for l in range(L)])                                      # [L, C, T]
+        self.idx = [[draw(l, n) for n in rows] for l in range(L)]                      # [l][f] -> [C, n]
+        # pairs of ranks mapped to the first of each pair: not the identity
+        self.canon = np.tile((np.arange(T) & ~1).astype(np.uint16), (C_, 1)) if canon else None
+        self.plan = p = bs.encode_plan(rows, [0] * len(rows), seg, C_, 1)
+        self.files = p.files.copy()
+        self.stride_l = C_ * p.n_rows
+        if tight:
+            total = sum(rows)
+            for f in range(len(rows)):
+                self.files[f, :2] = 1 + sum(rows[:f]), total
+            self.stride_l = 1 + C_ * total
+        flat = np.full(L * self.stride_l, T - 1, np.uint16)
+        for l in range(L):
+            for f, idx in enumerate(self.idx[l]):
+                base, stride, n = (int(v) for v in self.files[f, :3])
+                for c in range(C_):
+                    a = l * self.stride_l + base + c * stride
+                    flat[a: a + n] = idx[c]
+        self.d_idx, self.d_freq = torch.from_numpy(flat).cuda(), torch.from_numpy(self.freq).cuda()
+        self.d_canon = None if self.canon is None else torch.from_numpy(self.canon).cuda()
+        # the reference, once: the checker's size of every segment [l][f] -> u32 [C, nseg]
+        coded = lambda i: i if self.canon is None else np.take_along_axis(self.canon, i.astype(np.int64), axis=1)   # noqa: E731
+        self.sizes = [[CO.rans_encode(coded(i), self.freq[l], seg)[1].astype(np.int64) for i in self.idx[l]] for l in range(L)]
+        self.want = np.array([[int(s.sum()) for s in per_l] for per_l in self.sizes], np.uint64)        # [L, F]
+
+    def run(self, files=None, items=None, totals=None):
+        """One launch -> (totals [L, F], status [F]) on the host."""
+        from vbq_amd import ops
+        files = torch.from_numpy(np.ascontiguousarray(self.files if files is None else files, np.int64)).cuda()
+        items = np.ascontiguousarray(self.plan.items if items is None else items, np.int32).reshape(-1, 2)
+        items = np.concatenate([items, np.full((-items.shape[0] % 64, 2), -1, np.int32)])
+        if totals is not None:
+            totals = torch.from_numpy(np.ascontiguousarray(totals, np.uint64).view(np.int64)).cuda().view(torch.uint64)
+        totals, status = ops.rans_sizes_files(self.d_idx, files, torch.from_numpy(items).cuda(), self.d_freq,
+                                              lambda_stride=self.stride_l, seg=self.seg, N=self.bits, canon=self.d_canon,
+                                              totals=totals)
+        torch.cuda.synchronize()
+        return totals.view(torch.int64).cpu().numpy().view(np.uint64), status.cpu().tolist()
+
+
+KERNEL_CASES = {  # rows, L, C, seg, bits, canon
+    # a segment shorter than 8, an exact one, a short last one; laid out tight: unaligned plane bases, the 2-byte paths
+    "rows-and-lambdas": ([1, 7, 64, 65, 200], 3, 3, 64, N, False),
+    # two blocks; lanes of one block belong to different files
+    "several-blocks": ([70 * 7, 7, 5, 1], 2, 2, 7, N, False),
+    "four-bits": ([16, 40, 3, 33], 2, 5, 16, 4, False),
+    # bases that are multiples of 8 and segments of 1024: the 16-byte loads
+    "aligned-vector-path": ([1536, 1536], 2, 32, 1024, N, False),
+    "canonical-map": ([1, 7, 64, 65, 200], 3, 3, 64, N, True),
+}
+_BATCHES = {}
+
+
+def _batch(case):
+    """The batch of a case and its reference: built once, shared, never changed."""
+    if case not in _BATCHES:
+        rows, L, C_, seg, bits, canon = KERNEL_CASES[case]
+        _BATCHES[case] = Batch(rows, L, C_, seg, bits, seed=len(case), canon=canon, tight=case in ("rows-and-lambdas", "canonical-map"))
+    return _BATCHES[case]
+
+
+@pytest.mark.parametrize("case", list(KERNEL_CASES))
+def test_kernel_totals_equal_the_sum_of_the_checkers_sizes(case):
+    k = _batch(case)
+    p = k.plan
+    if case == "several-blocks":
+        assert p.items.shape[0] == 128 and {int(f) for f in p.items[64:128, 0]} == {0, 1, 2, 3, -1}
+    if case == "aligned-vector-path":
+        assert np.all(k.files[:, 0] % 8 == 0) and np.all(k.files[:, 1] % 8 == 0) and k.stride_l % 8 == 0
+        assert k.d_idx.data_ptr() % 16 == 0
+    if case == "rows-and-lambdas":
+        assert np.sum(k.files[:, 0] % 8 != 0) >= 3 and np.any(k.files[:, 1] % 8 != 0) and k.stride_l % 8 != 0
+    if case == "canonical-map":                                   # the map changes what is coded
+        plain = [[int(CO.rans_encode(i, k.freq[l], k.seg)[1].sum()) for i in k.idx[l]] for l in range(k.L)]
+        assert plain != k.want.tolist()
+    totals, st = k.run()
+    assert st == [0] * k.F
+    assert totals.dtype == np.uint64 and totals.shape == (k.L, k.F)
+    assert np.array_equal(totals, k.want), (totals, k.want)
+
+
+def test_totals_are_added_to_not_stored():
+    k = _batch("rows-and-lambdas")
+    before = np.full((k.L, k.F), 1 << 40, np.uint64) + np.arange(k.L * k.F, dtype=np.uint64).reshape(k.L, k.F)
+    totals, st = k.run(totals=before)
+    assert st == [0] * k.F
+    assert np.array_equal(totals, before + k.want)
+
+
+def test_unlisted_segments_add_nothing():
+    k = _batch("rows-and-lambdas")
+    p = k.plan
+    f = 4                                                         # 200 rows: segments 0 .. 3, the last one short
+    assert int(p.nseg[f]) == 4
+    keep = p.items[~((p.items[:, 0] == f) & ((p.items[:, 1] == 1) | (p.items[:, 1] == 3)))]
+    totals, st = k.run(items=keep)
+    assert st == [0] * k.F
+    want = k.want.copy()
+    for l in range(k.L):
+        want[l, f] = int(k.sizes[l][f][:, [0, 2]].sum())
+        assert want[l, f] < k.want[l, f]
+    assert np.array_equal(totals, want)
+    # no item at all of a file: its totals stay zero
+    totals, st = k.run(items=p.items[p.items[:, 0] != 2])
+    want = k.want.copy()
+    want[:, 2] = 0
+    assert st == [0] * k.F and np.array_equal(totals, want)
+
+
+def test_status_bits_of_defective_descriptors_and_items():
+    """One launch over four files of two segments each carries a segment id equal to nseg of file 1 beside file 1's own
+    segments, an item of file id n_files, and a descriptor (file 3) whose last channel ends one past lambda_stride: file 1 and
+    file 3 get status 128, the unknown file id lands in word 0, the refused items add nothing -- file 3 adds nothing at all
+    -- and every other total is exact, file 1's own segments included.  Then every field of a descriptor pushed out of range,
+    one at a time.  Nothing of this faults: every check runs before anything is indexed."""
+    rows, C_, seg, L = [100, 100, 100, 100], 3, 64, 2
+    k = Batch(rows, L, C_, seg, N, seed=9)
+    p = k.plan
+    good = [[int(v) for v in row] for row in p.files]
+    assert all(int(s) == 2 for s in p.nseg)
+    every = [(f, g) for f in range(4) for g in range(2)]
+    totals, st = k.run(files=good, items=every)
+    assert st == [0, 0, 0, 0] and np.array_equal(totals, k.want)
+
+    bad = [list(r) for r in good]
+    bad[3][0] = k.stride_l - (C_ - 1) * bad[3][1] - 100 + 1      # the last channel's symbols end one past lambda_stride
+    totals, st = k.run(files=bad, items=every + [(1, 2), (4, 0)])
+    assert st == [128, 128, 0, 128], st
+    want = k.want.copy()
+    want[:, 3] = 0
+    assert np.array_equal(totals, want), (totals, want)
+
+    for field, value in ((0, -8), (0, 1 << 62), (1, -1), (1, 1 << 62), (2, 0), (2, -5), (2, 1 << 62)):
+        bad = [list(r) for r in good]
+        bad[1][field] = value
+        totals, st = k.run(files=bad, items=every)
+        assert st == [0, 128, 0, 0], (field, value, st)
+        want = k.want.copy()
+        want[:, 1] = 0
+        assert np.array_equal(totals, want), (field, value)
+    # the fields the sizes call ignores may hold anything
+    loose = [list(r) for r in good]
+    loose[1][3], loose[1][4], loose[1][5] = -1, 1 << 40, -7
+    totals, st = k.run(files=loose, items=every)
+    assert st == [0, 0, 0, 0] and np.array_equal(totals, k.want)
+    # stray segment and file ids
+    totals, st = k.run(files=good, items=every + [(1, 2), (1, -1), (1, 1 << 30)])
+    assert st == [0, 128, 0, 0] and np.array_equal(totals, k.want)
+    totals, st = k.run(files=good, items=every + [(4, 0), (-2, 0), (1 << 30, 1)])
+    assert st == [128, 0, 0, 0] and np.array_equal(totals, k.want)
+
+
+# ------------------------------------------------------------------------------------------------------------- quantizer level
+def _gaussian_quantizer(C_, seed):
+    from vbq_amd import ChannelwisePriorCDFQuantizer, priors
+    rng = np.random.default_rng(seed)
+    scale = np.exp(rng.uniform(np.log(0.3), np.log(3.0), C_))
+    q = ChannelwisePriorCDFQuantizer(C_, N)
+    q.build_code_points(priors.FactoredGaussianPrior(np.zeros(C_), scale))
+    return q, scale, rng
+
+
+def _latents(rng, scale, shape):
+    m = (scale * rng.standard_normal(shape)).astype(np.float32)
+    lv = (2 * (-2 + 0.7 * rng.standard_normal(shape))).astype(np.float32)
+    return m, lv
+
+
+def _same_files(got, want):
+    """bytes == bytes, file by file; where they differ, say in which part of the file."""
+    assert isinstance(got, list) and len(got) == len(want)
+    for f, (g, w) in enumerate(zip(got, want)):
+        assert isinstance(g, bytes)
+        if g != w:
+            h, _, start = bs.parse(w)
+            first = next((i for i, (x, y) in enumerate(zip(g, w)) if x != y), min(len(g), len(w)))
+            part = "header" if first < h.nbytes else "size block" if first < start else "payload"
+            pytest.fail(f"file {f}: {len(g)} bytes against {len(w)} (lambda {bs.parse(g)[0].lamb} against {h.lamb}), "
+                        f"first difference at byte {first} ({part})")
+
+
+def _same_tables(got, want):
+    """dict == dict, file by file, the keys in the same order."""
+    assert isinstance(got, list) and len(got) == len(want)
+    for f, (g, w) in enumerate(zip(got, want)):
+        assert isinstance(g, dict) and list(g) == list(w), f
+        assert g == w, (f, g, w)
+        assert all(type(v) is int for v in g.values()), f
+
+
+_BUILT = {}
+
+
+def _built(C_):
+    """A quantizer with C channels, five latents of different shapes and their one-file results: shared, never changed."""
+    if C_ not in _BUILT:
+        q, scale, rng = _gaussian_quantizer(C_, C_)
+        shapes = [(1, 32, 48, C_), (2, 17, 23, C_), (1, 20, 30, C_), (1, 1, 1, C_), (5, C_)]
+        lat = [_latents(rng, scale, s) for s in shapes]
+        q.build_entropy_models_from_latents(lat[0][0].reshape(-1, C_), lat[0][1].reshape(-1, C_), LAMBS, add_n_smoothing=1,
+                                            spread="logvar")
+        _BUILT[C_] = (q, lat, {})
+    return _BUILT[C_]
+
+
+def _lengths(C_, seg):
+    """[coded_nbytes(latent f, LAMBS) for f]: the one-file calls, each made once."""
+    q, lat, cache = _built(C_)
+    if ("nbytes", seg) not in cache:
+        cache[("nbytes", seg)] = [q.coded_nbytes(m, lv, LAMBS, segment=seg) for m, lv in lat]
+    return cache[("nbytes", seg)]
+
+
+def _budget_loop(C_, seg, budgets):
+    """The one-file budget calls of the five latents, each made once per budget."""
+    q, lat, cache = _built(C_)
+    out = []
+    for f, budget in enumerate(budgets):
+        if ("budget", f, budget, seg) not in cache:
+            cache[("budget", f, budget, seg)] = q.compress_latents_to_budget(*lat[f], budget, LAMBS, segment=seg)
+        out.append(cache[("budget", f, budget, seg)])
+    return out
+
+
+def _inputs(lat, kind):
+    if kind == "numpy":
+        return lat
+    on_dev = [(torch.from_numpy(m).cuda(), torch.from_numpy(lv).cuda()) for m, lv in lat]
+    if kind == "device":
+        return on_dev
+    return [on_dev[0], lat[1], (torch.from_numpy(lat[2][0]), lat[2][1]), lat[3], on_dev[4]]               # host and device
+
+
+@pytest.mark.parametrize("C_,seg", [(32, 64), (32, 1024), (256, 1024)])
+def test_lengths_of_a_batch_equal_the_list_of_one_file_lengths(C_, seg):
+    q, lat, _ = _built(C_)
+    want = _lengths(C_, seg)
+    _same_tables(q.coded_nbytes_batch(lat, LAMBS, segment=seg), want)
+    if C_ != 32:
+        return
+    _same_tables(q.coded_nbytes_batch(_inputs(lat, "device"), LAMBS, segment=seg), want)
+    _same_tables(q.coded_nbytes_batch(_inputs(lat, "mixed"), LAMBS, segment=seg), want)
+    _same_tables(q.coded_nbytes_batch(lat, segment=seg), [{k: w[k] for k in q.lambs} for w in want])          # every lambda
+    picked = [LAMBS[2], LAMBS[0], LAMBS[2]]                       # an order of the caller's, a repeat: each key once, in order
+    _same_tables(q.coded_nbytes_batch(lat[1:3], picked, segment=seg), [{k: w[k] for k in (LAMBS[2], LAMBS[0])} for w in want[1:3]])
+    # a length is the length of the file
+    assert want[1][LAMBS[1]] == len(q.compress_latents_to_bytes(*lat[1], LAMBS[1], segment=seg))
+
+
+def _chosen(files):
+    return [bs.parse(data)[0].lamb for data in files]
+
+
+@pytest.mark.parametrize("C_,seg", [(32, 64), (32, 1024)])
+def test_per_file_budgets_equal_the_loop_of_one_file_budget_calls(C_, seg):
+    q, lat, _ = _built(C_)
+    nb = _lengths(C_, seg)
+    # exactly a length; one byte less than a length; room for the smallest lambda; the two small files at their own lengths
+    budgets = [nb[0][LAMBS[1]], nb[1][LAMBS[1]] - 1, 10 * nb[2][LAMBS[0]], nb[3][LAMBS[3]], nb[4][LAMBS[2]]]
+    want = _budget_loop(C_, seg, budgets)
+    assert _chosen(want)[0] <= LAMBS[1] < _chosen(want)[1] and _chosen(want)[2] == LAMBS[0]
+    assert len(set(_chosen(want))) >= 3                           # (not a test that passes by coding everything at one rate)
+    for kind in ("numpy", "device", "mixed") if seg == 64 else ("numpy",):
+        got = q.compress_latents_to_budget_batch(_inputs(lat, kind), budgets, LAMBS, segment=seg)
+        _same_files(got, want)
+        assert all(len(g) <= b for g, b in zip(got, budgets))
+    _same_files(q.compress_latents_to_budget_batch(lat, np.array(budgets), LAMBS, segment=seg), want)
+
+
+def test_one_budget_for_all_files():
+    C_, seg = 32, 64
+    q, lat, _ = _built(C_)
+    nb = _lengths(C_, seg)
+    budget = max(min(t.values()) for t in nb) + 40                # every file has a fit; the large ones only at large lambdas
+    want = _budget_loop(C_, seg, [budget] * 5)
+    assert len(set(_chosen(want))) >= 2
+    _same_files(q.compress_latents_to_budget_batch(lat, budget, LAMBS, segment=seg), want)
+    _same_files(q.compress_latents_to_budget_batch(lat, np.int64(budget), LAMBS, segment=seg), want)
+
+
+def test_a_file_that_nothing_fits_raises_and_returns_nothing():
+    C_, seg = 32, 64
+    q, lat, _ = _built(C_)
+    nb = _lengths(C_, seg)
+    big = 10 * nb[0][LAMBS[0]]
+    least = min(nb[2].values())
+    with pytest.raises(ValueError, match=rf"file 2: no lambda fits in 1 bytes: the smallest file is {least} bytes"):
+        q.compress_latents_to_budget_batch(lat, [big, big, 1, big, 1], LAMBS, segment=seg)
+    with pytest.raises(ValueError, match="file 0: no lambda fits in 1 bytes"):
+        q.compress_latents_to_budget_batch(lat, 1, LAMBS, segment=seg)
+
+
+def test_total_budget_takes_one_lambda_for_all_files():
+    C_, seg = 32, 64
+    q, lat, _ = _built(C_)
+    nb = _lengths(C_, seg)
+    sums = {k: sum(t[k] for t in nb) for k in LAMBS}
+    assert len(set(sums.values())) == len(LAMBS)
+    for budget in (sums[LAMBS[2]], sums[LAMBS[2]] - 1, 10 * sums[LAMBS[0]]):
+        lamb, files = q.compress_latents_to_total_budget(lat, budget, LAMBS, segment=seg)
+        assert lamb == bs.smallest_rate_within(sums, budget)
+        assert sum(len(f) for f in files) == sums[lamb] <= budget
+        _same_files(files, q.compress_latents_to_bytes_batch(lat, lamb, segment=seg))
+        _same_files(files, [q.compress_latents_to_bytes(m, lv, lamb, segment=seg) for m, lv in lat])
+    with pytest.raises(ValueError, match=rf"no lambda fits in 1 bytes: the smallest file is {min(sums.values())} bytes"):
+        q.compress_latents_to_total_budget(lat, 1, LAMBS, segment=seg)
+
+
+def test_one_lambda_per_chunk_gives_the_same_table(monkeypatch):
+    from vbq_amd import ops, quantizer
+    C_, seg = 32, 64
+    q, lat, _ = _built(C_)
+    want = _lengths(C_, seg)
+    launches = []
+    real = ops.rans_sizes_files
+    monkeypatch.setattr(ops, "rans_sizes_files", lambda *a, **kw: launches.append(kw["totals"].shape[0]) or real(*a, **kw))
+    _same_tables(q.coded_nbytes_batch(lat, LAMBS, segment=seg), want)
+    assert launches == [len(LAMBS)]                               # unchunked: ONE sizes launch
+    del launches[:]
+    monkeypatch.setattr(quantizer, "RATE_SCRATCH_BYTES", 1)
+    _same_tables(q.coded_nbytes_batch(lat, LAMBS, segment=seg), want)
+    assert launches == [1] * len(LAMBS)
+
+
+def test_more_than_64_segments_across_files():
+    q, scale, rng = _gaussian_quantizer(2, 2)
+    lat = [_latents(rng, scale, (1, 1, 3, 2)) for _ in range(70)]
+    m, lv = _latents(rng, scale, (400, 2))
+    q.build_entropy_models_from_latents(m, lv, LAMBS[:2], add_n_smoothing=1, spread="logvar")
+    want = [q.coded_nbytes(m_, lv_, segment=2) for m_, lv_ in lat]
+    _same_tables(q.coded_nbytes_batch(lat, segment=2), want)
+    budgets = [w[LAMBS[f % 2]] for f, w in enumerate(want)]
+    _same_files(q.compress_latents_to_budget_batch(lat, budgets, segment=2),
+                [q.compress_latents_to_budget(m_, lv_, b, segment=2) for (m_, lv_), b in zip(lat, budgets)])
+
+
+def test_repeated_code_points():
+    from scipy.stats import norm
+    from vbq_amd import ChannelwisePriorCDFQuantizer
+
+    class Coarse:
+        def inverse_cdf(self, xi):
+            return np.round(norm.ppf(xi) * np.array([24.0, 64.0])) / np.array([24.0, 64.0])
+    q = ChannelwisePriorCDFQuantizer(2, N)
+    q.build_code_points(Coarse())
+    assert not q._strict
+    rng = np.random.default_rng(21)
+    lat = []
+    for shape in ((1, 40, 50, 2), (2, 7, 9, 2), (5, 2), (1, 40, 50, 2)):
+        lat.append((rng.normal(0, 1.1, shape).astype(np.float32), (2 * rng.normal(-2, 0.7, shape)).astype(np.float32)))
+    lambs = [0.01, 0.3, 4.0]
+    q.build_entropy_models_from_latents(lat[0][0].reshape(-1, 2), lat[0][1].reshape(-1, 2), lambs, add_n_smoothing=1, spread="logvar")
+    for seg in (64, 1024):
+        want = [q.coded_nbytes(m, lv, lambs, segment=seg) for m, lv in lat]
+        _same_tables(q.coded_nbytes_batch(lat, lambs, segment=seg), want)
+        budgets = [want[0][lambs[1]], want[1][lambs[2]], want[2][lambs[0]], want[3][lambs[1]] - 1]
+        _same_files(q.compress_latents_to_budget_batch(lat, budgets, lambs, segment=seg),
+                    [q.compress_latents_to_budget(m, lv, b, lambs, segment=seg) for (m, lv), b in zip(lat, budgets)])
+
+
+def test_compress_to_budget_batch_encodes_every_image():
+    C_, seg = 32, 64
+    q, lat, _ = _built(C_)
+    nb = _lengths(C_, seg)
+
+    class Stored:
+        """A stand-in VAE: `encode(i)` returns the stored latents of image i."""
+        def encode(self, i):
+            return lat[i]
+    order = [4, 0, 2]
+    budgets = [nb[4][LAMBS[0]], nb[0][LAMBS[1]], nb[2][LAMBS[2]] - 1]
+    want = [q.compress_to_budget(i, Stored(), b, LAMBS, segment=seg) for i, b in zip(order, budgets)]
+    assert len(set(_chosen(want))) == 3
+    _same_files(q.compress_to_budget_batch(order, Stored(), budgets, LAMBS, segment=seg), want)

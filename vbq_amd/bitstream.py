@@ -15,7 +15,8 @@ reads either through `parse_latent`.  A third format (magic b"VBQe", further dow
 vbq_amd.embeddings.compress_to_bytes / CompressedEmbeddings, and a fourth (magic b"VBQr", at the end) a matrix whose rows were
 quantized to one exact bit budget, as fixed-size records: compress_to_records / RecordEmbeddings.  latent_nbytes / compact_nbytes / embeddings_nbytes give the
 exact length of a file without building it, and smallest_rate_within is the byte-budget rule of the rate-control calls
-(coded_nbytes / *_to_budget on the quantizer and in vbq_amd.embeddings).
+(coded_nbytes / *_to_budget on the quantizer and in vbq_amd.embeddings; smallest_rates_within is the same rule for the F files
+of a batch at once).
 
 Layout of the two latent files, every field little-endian (version 1); `unit` is the segment or the part:
 
@@ -846,6 +847,45 @@ def smallest_rate_within(nbytes, max_bytes, name: str = "lambda"):
         return min(fits, key=lambda it: it[0])[2]
     _, least, rate = min(items, key=lambda it: (it[1], it[0]))
     raise ValueError(f"no {name} fits in {budget} bytes: the smallest file is {least} bytes, at {name} = {float(rate)!r}")
+
+
+def check_budgets(budgets):
+    """None for one budget for all files (an integer, checked), else the budgets of a sequence as a list, each checked by
+    check_budget."""
+    if np.ndim(budgets) == 0:
+        check_budget(budgets)
+        return None
+    return [check_budget(b) for b in budgets]
+
+
+def smallest_rates_within(nbytes, budgets, rates=None, name: str = "lambda") -> np.ndarray:
+    """smallest_rate_within for F files at once.  nbytes: exact file lengths int64 [F, L], the columns in ascending order of
+    the rate; budgets: one int for all files or a sequence of F (each checked by check_budget).  Returns int64 [F]: for every
+    file the FIRST column -- the numerically smallest rate -- whose length is <= the file's budget; no monotonicity along a
+    row is assumed.  ValueError naming the first file without a fit, its smallest length and that length's rate (rates[column]
+    where `rates` is given, else the column index)."""
+    nbytes = np.asarray(nbytes)
+    if nbytes.ndim != 2 or nbytes.dtype.kind not in "iu":
+        raise ValueError(f"nbytes must be an integer array [F, L], got {nbytes.dtype} {nbytes.shape}")
+    nbytes = nbytes.astype(np.int64, copy=False)
+    F, L = nbytes.shape
+    each = check_budgets(budgets)
+    budgets = [int(budgets)] * F if each is None else each
+    if len(budgets) != F:
+        raise ValueError(f"{len(budgets)} budgets for {F} files")
+    if F == 0:
+        return np.zeros(0, np.int64)
+    if L == 0:
+        raise ValueError(f"no candidate {name} to choose from")
+    if rates is not None and len(rates) != L:
+        raise ValueError(f"{len(rates)} rates for {L} columns")
+    fits = nbytes <= np.array([min(b, np.iinfo(np.int64).max) for b in budgets], np.int64)[:, None]
+    for f in np.flatnonzero(~fits.any(axis=1)):
+        col = int(np.argmin(nbytes[f]))                           # the first of equal lengths: the smaller rate
+        rate = repr(float(rates[col])) if rates is not None else f"column {col}"
+        raise ValueError(f"file {int(f)}: no {name} fits in {budgets[f]} bytes: the smallest file is {int(nbytes[f, col])} bytes, "
+                         f"at {name} = {rate}")
+    return np.argmax(fits, axis=1).astype(np.int64)
 
 
 def parse_embeddings(data) -> Tuple[EmbeddingHeader, np.ndarray, np.ndarray, int]:

@@ -84,6 +84,31 @@ __device__ __forceinline__ void stage_segment_table(const uint16_t *__restrict__
     if (lane == 63 && c_l) c_l[T] = (uint16_t)(incl == (1u << kPB) ? incl : 0u);
 }
 
+// fc_l[t] = fc_l[canon[t]] for every t, by the one wave that staged fc_l: the whole table through registers (T <= 2047: at
+// most 32 entries per lane) between two barriers, so that no entry is overwritten before it was read.  An encoder that reads
+// fc_l[sym] then codes symbol canon[sym] at no cost per symbol.  (An entry of canon outside the table counts as 0.)  For the
+// batch kernels (vbq_rans_files.hip, vbq_rans_sizes_files.hip).
+__device__ __forceinline__ void map_segment_table(const uint16_t *__restrict__ canon, int T, uint32_t *fc_l) {
+    const int lane = threadIdx.x;
+    uint32_t v[32];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        const int t = j * 64 + lane;
+        v[j] = 0u;
+        if (t < T) {
+            const unsigned s = canon[t];
+            v[j] = fc_l[s < (unsigned)T ? s : 0u];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        const int t = j * 64 + lane;
+        if (t < T) fc_l[t] = v[j];
+    }
+}
+
 // start[b] of rans_pop for slot = 16 b: the last symbol with c <= slot, by bisection over a valid row's c_l[0..T).
 __device__ __forceinline__ uint16_t bucket_start(const uint16_t *c_l, int T, unsigned slot) {
     int lo = 0, hi = T;

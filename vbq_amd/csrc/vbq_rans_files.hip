@@ -7,7 +7,7 @@
 // of 64 that share a frequency table (a lambda) and a workgroup takes one block of one channel: its lanes code segments of
 // DIFFERENT files with the one table it stages.  One lane codes one item in full, last symbol to first, with the state machine,
 // the renormalisation and the final-state flush of k_rans_encode: the words and the size of a segment are the same.
-// The constants, the per-symbol step and the table staging are vbq_rans_common.h's.
+// The constants, the per-symbol step, the table staging and the canon map are vbq_rans_common.h's.
 #include "vbq_rans_common.h"
 
 namespace vbq {
@@ -16,30 +16,6 @@ namespace {
 constexpr int kFilesThreads = 64;                                // one wave: stage_segment_table scans with wave shuffles alone
 constexpr int kEncFields = 6;                                    // idx_base, idx_stride, n, seg_base, table, reserved
 constexpr unsigned kBadFile = 128u;                              // status bit 7
-
-// fc_l[t] = fc_l[canon[t]] for every t, by the one wave that staged fc_l: the whole table through registers (T <= 2047: at
-// most 32 entries per lane) between two barriers, so that no entry is overwritten before it was read.  An encoder that reads
-// fc_l[sym] then codes symbol canon[sym] at no cost per symbol.  (An entry of canon outside the table counts as 0.)
-__device__ __forceinline__ void map_segment_table(const uint16_t *__restrict__ canon, int T, uint32_t *fc_l) {
-    const int lane = threadIdx.x;
-    uint32_t v[32];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int t = j * kFilesThreads + lane;
-        v[j] = 0u;
-        if (t < T) {
-            const unsigned s = canon[t];
-            v[j] = fc_l[s < (unsigned)T ? s : 0u];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int t = j * kFilesThreads + lane;
-        if (t < T) fc_l[t] = v[j];
-    }
-}
 
 // The descriptors and the items come from the caller's host plan; every index formed from them is range-checked without
 // overflow before it is used, and an item that fails writes nothing and sets bit 7 of its file's status word.  The checks of a

@@ -959,3 +959,45 @@ def rans_encode_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tenso
                                                _ptr(freq), n_tables, _ptr(canon), _ptr(words), _ptr(sizes), M, _ptr(status),
                                                _stream(idx)), "vbq_rans_encode_files_u16")
     return words, sizes, status
+
+
+def rans_sizes_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor, freq: torch.Tensor, *, lambda_stride: int,
+                     seg: int, N: int = 10, canon: Optional[torch.Tensor] = None, totals: Optional[torch.Tensor] = None,
+                     status: Optional[torch.Tensor] = None):
+    """vbq_rans_sizes_files_u16 (include/vbq.h, "Batch sizes"): the coded words of every file at every lambda in one launch.
+    idx u16 [n_idx], the rank indices of all files, one plane of lambda_stride indices per lambda; files int64 [F, 6] and items
+    int32 [n_items, 2] as rans_encode_files takes them (idx_base, idx_stride and n are read; a block's files need share
+    nothing); freq u16 [L, C, T]; canon u16 [C, T] or None.  Returns (totals u64 [L, F], status u32 [F]): totals[l, f] grows by
+    the words of every listed segment of every channel of file f at lambda l.  `totals` is added to and `status` OR-ed into:
+    zeroed here unless given."""
+    idx = _dev(idx, torch.uint16, "idx")
+    files = _dev(files, torch.int64, "files")
+    items = _dev(items, torch.int32, "items")
+    freq = _dev(freq, torch.uint16, "freq")
+    seg, N, lambda_stride = int(seg), int(N), int(lambda_stride)
+    T = table_size(N)
+    if files.dim() != 2 or files.shape[1] != 6:
+        raise ValueError(f"files must be [F, 6] (idx_base, idx_stride, n, seg_base, table, 0), got {tuple(files.shape)}")
+    if items.dim() != 2 or items.shape[1] != 2:
+        raise ValueError(f"items must be [n_items, 2] (file, segment), got {tuple(items.shape)}")
+    if freq.dim() != 3 or freq.shape[2] != T:
+        raise ValueError(f"expected freq [L, C, {T}], got {tuple(freq.shape)}")
+    F, L, n_ch = files.shape[0], freq.shape[0], freq.shape[1]
+    if canon is not None:
+        canon = _dev(canon, torch.uint16, "canon")
+        if tuple(canon.shape) != (n_ch, T):
+            raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
+    if totals is None:
+        totals = torch.zeros((L, F), dtype=torch.int64, device=idx.device).view(torch.uint64)
+    else:
+        totals = _out(totals, (L, F), torch.uint64, idx.device, "totals")
+    if status is None:
+        status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
+    else:
+        status = _dev(status, torch.uint32, "status")
+        if status.numel() != F:
+            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+    check(_lib.lib().vbq_rans_sizes_files_u16(_ptr(idx), idx.numel(), lambda_stride, _ptr(files), F, _ptr(items), items.shape[0],
+                                              n_ch, seg, N, _ptr(freq), L, _ptr(canon), _ptr(totals), _ptr(status),
+                                              _stream(idx)), "vbq_rans_sizes_files_u16")
+    return totals, status

@@ -30,6 +30,9 @@ from . import ops
 from .tables import n_bit_binary_floats
 
 
+RATE_SCRATCH_BYTES = 1 << 30                 # the batch rate calls: the u16 indices of one chunk of lambdas stay below this
+
+
 def _to_numpy(a):
     if isinstance(a, torch.Tensor):
         return a.detach().cpu().numpy()
@@ -885,15 +888,10 @@ class ChannelwisePriorCDFQuantizer:
         return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment, layout=layout, part=part)
 
     # ------------------------------------------------------------------ batches of files, written (include/vbq.h, "Batch encode")
-    def _batch_file_inputs(self, latents, lambs, segment):
-        """Every check of compress_latents_to_bytes_batch, before any device work -> (pairs, shapes, keys, segment)."""
-        self._check_coder_bits()
-        bitstream.check_segment(segment)
-        pairs = list(latents)
+    def _batch_file_shapes(self, pairs, segment):
+        """The latent shape of every file of a batch, channel-last; ValueError naming the file's index for what is not a pair
+        of one such shape, or for more than 65535 files."""
         F = len(pairs)
-        lambs = [lambs] * F if np.ndim(lambs) == 0 else list(lambs)
-        if len(lambs) != F:
-            raise ValueError(f"{len(lambs)} lambdas for {F} files")
         if F > bitstream.MAX_BATCH_FILES:
             raise ValueError(f"{F} files: one call takes at most {bitstream.MAX_BATCH_FILES}")
         shapes = []
@@ -908,6 +906,18 @@ class ChannelwisePriorCDFQuantizer:
                 raise ValueError(f"file {i}: {e}") from None
             if 0 in shapes[-1]:
                 raise ValueError(f"file {i}: empty latent shape {shapes[-1]}")
+        return shapes
+
+    def _batch_file_inputs(self, latents, lambs, segment):
+        """Every check of compress_latents_to_bytes_batch, before any device work -> (pairs, shapes, keys, segment)."""
+        self._check_coder_bits()
+        bitstream.check_segment(segment)
+        pairs = list(latents)
+        F = len(pairs)
+        lambs = [lambs] * F if np.ndim(lambs) == 0 else list(lambs)
+        if len(lambs) != F:
+            raise ValueError(f"{len(lambs)} lambdas for {F} files")
+        shapes = self._batch_file_shapes(pairs, segment)
         keys = [self._lambda_key(l) for l in lambs] if F else []
         return pairs, shapes, keys, int(segment)
 
@@ -967,8 +977,12 @@ class ChannelwisePriorCDFQuantizer:
         digests = {k: self._coder_tables(k, segment)[1] for k in tables}
         rows = [int(np.prod(sh[:-1], dtype=np.int64)) for sh in shapes]
         plan = bitstream.encode_plan(rows, [tables.index(k) for k in keys], segment, C, len(tables))
-        M, R = plan.M, plan.n_rows
-        back = 8 + 4 * M + 4 * F
+        return self._batch_stage(plan, shapes, keys, tables, digests, segment, rows, pairs, 8 + 4 * plan.M + 4 * F)
+
+    def _batch_stage(self, plan, shapes, keys, tables, digests, segment, rows, pairs, back):
+        """The ONE staging buffer of a batch call (see _encode_batch_plan), filled: `back` zeroed bytes that the device writes
+        and the host reads back | the plan's descriptors | its items | the latents unless every input is a device tensor."""
+        C, R = self.num_channels, plan.n_rows
         cut = [int(c) for c in np.cumsum([back + (-back % 8), plan.files.nbytes, plan.items.nbytes])]
         on_device = all(isinstance(a, torch.Tensor) and a.is_cuda for pair in pairs for a in pair)
         host_t = self._encode_stage(cut[2] + (0 if on_device else 8 * R * C))
@@ -1203,6 +1217,102 @@ class ChannelwisePriorCDFQuantizer:
         posterior_means, posterior_logvars = vae.encode(X)
         return self.compress_latents_to_budget(posterior_means, posterior_logvars, max_bytes, lambs=lambs, segment=segment,
                                                layout=layout, part=part)
+
+    # ------------------------------------------------------------------ rate control for batches (include/vbq.h, "Batch sizes")
+    def _rate_batch_inputs(self, latents, lambs, segment):
+        """Every check of the batch rate calls, before any device work: those of _batch_file_inputs for the files and of
+        _rate_keys for the candidate lambdas -> (pairs, shapes, keys, segment); no lambda is looked up when there is no file."""
+        self._check_coder_bits()
+        bitstream.check_segment(segment)
+        pairs = list(latents)
+        shapes = self._batch_file_shapes(pairs, segment)
+        keys = self._rate_keys(lambs) if pairs else []
+        return pairs, shapes, keys, int(segment)
+
+    def _coded_nbytes_batch(self, pairs, shapes, keys, segment):
+        """(nbytes int64 [F, L] with nbytes[f, l] = the exact file length of latent f at keys[l], the F latents as pairs of
+        device tensors shaped like the inputs): ONE plan with every file in table 0 (bitstream.encode_plan), ONE upload as the
+        batch encoder's (zeroed totals u64 [L, F] and status u32 [F], descriptors, items and -- unless every input is a device
+        tensor -- the latents), one vbq_prep_planes_f32 of all R rows, then per chunk of max(1, RATE_SCRATCH_BYTES // (2 C R))
+        lambdas one solve into [L_chunk, C, R] and ONE vbq_rans_sizes_files_u16 with that chunk's tables, and one copy of the
+        totals and the status words back."""
+        from . import _lib
+        F, L, C, N, dev = len(pairs), len(keys), self.num_channels, self.max_bits_per_coord, self.device
+        rows = [int(np.prod(sh[:-1], dtype=np.int64)) for sh in shapes]
+        plan = bitstream.encode_plan(rows, [0] * F, segment, C, 1)
+        R = plan.n_rows
+        b = self._batch_stage(plan, shapes, keys, None, None, segment, rows, pairs, 8 * L * F + 4 * F)
+        d_host, lat = self._encode_batch_upload(b)
+        d_status = d_host[8 * L * F:b.back].view(torch.uint32)
+        d_files = d_host[b.cut[0]:b.cut[1]].view(torch.int64).view(F, 6)
+        d_items = d_host[b.cut[1]:b.cut[2]].view(torch.int32).view(-1, 2)
+        canon = None if self._strict else self._dev("canon_u16", lambda: torch.from_numpy(self._canon.astype(np.uint16)))
+        mu_cb, sg_cb = self._prep(lat[0], lat[1], spread="logvar")
+        chunk = max(1, RATE_SCRATCH_BYTES // (2 * C * R))
+        for l0 in range(0, L, chunk):
+            ks = keys[l0:l0 + chunk]
+            idx = self._solve_idx(mu_cb, sg_cb, ks, self._level_len_dev(ks))                   # [L_chunk, C, R]
+            freq = self._coder_stack(ks, segment)._freq(dev).view(len(ks), C, -1)
+            ops.rans_sizes_files(idx.view(-1), d_files, d_items, freq, lambda_stride=C * R, seg=segment, N=N, canon=canon,
+                                 totals=d_host[8 * l0 * F:8 * (l0 + len(ks)) * F].view(torch.uint64).view(len(ks), F),
+                                 status=d_status)
+        h = d_host[:b.back].cpu().numpy()
+        totals, status = h[:8 * L * F].view(np.uint64).reshape(L, F), h[8 * L * F:].view(np.uint32)
+        for f in np.flatnonzero(status):
+            raise _lib.VBQError(f"file {int(f)}: the batch sizes kernel refused its descriptor (status {int(status[f])})")
+        nbytes = np.array([[bitstream.latent_nbytes(shapes[f], C, segment, int(totals[l, f])) for l in range(L)]
+                           for f in range(F)], dtype=np.int64).reshape(F, L)
+        row_base = plan.row0                                      # (one table: its group starts at row 0)
+        on_dev = [tuple(lat[w, int(row_base[f]):int(row_base[f]) + rows[f]].view(shapes[f]) for w in (0, 1)) for f in range(F)]
+        return nbytes, on_dev
+
+    def coded_nbytes_batch(self, latents, lambs=None, segment=1024) -> list:
+        """[coded_nbytes(means_f, logvars_f, lambs, segment=segment) for f]: a list of F dicts {lambda: exact file length}, the
+        same keys in the same order, with ONE solve and ONE vbq_rans_sizes_files_u16 launch for all files and lambdas (per
+        chunk of lambdas: see _coded_nbytes_batch).  `latents` as compress_latents_to_bytes_batch takes them; files in
+        segments only.  F == 0 returns [].  Errors before any device work: those of compress_latents_to_bytes_batch for the
+        files (ValueError naming the file's index), KeyError for a lambda without a model."""
+        pairs, shapes, keys, segment = self._rate_batch_inputs(latents, lambs, segment)
+        if not pairs:
+            return []
+        nbytes, _ = self._coded_nbytes_batch(pairs, shapes, keys, segment)
+        return [{k: int(b) for k, b in zip(keys, row)} for row in nbytes]
+
+    def compress_latents_to_budget_batch(self, latents, max_bytes, lambs=None, segment=1024) -> list:
+        """[compress_latents_to_budget(means_f, logvars_f, max_bytes[f], lambs, segment=segment) for f], byte for byte:
+        every file at the numerically smallest lambda of `lambs` whose exact length is within the file's budget.  `max_bytes`:
+        one integer >= 1 for all files or a sequence of F.  The lengths come from coded_nbytes_batch's one sizes launch, the
+        files from compress_latents_to_bytes_batch at the chosen lambdas on the latents already on the device (its solve
+        covers only the chosen lambdas).  ValueError (bitstream.smallest_rates_within) naming the first file that no lambda
+        fits, before anything is encoded.  F == 0 returns []."""
+        budgets = bitstream.check_budgets(max_bytes)
+        pairs, shapes, keys, segment = self._rate_batch_inputs(latents, lambs, segment)
+        if budgets is not None and len(budgets) != len(pairs):
+            raise ValueError(f"{len(budgets)} budgets for {len(pairs)} files")
+        if not pairs:
+            return []
+        nbytes, on_dev = self._coded_nbytes_batch(pairs, shapes, keys, segment)
+        order = sorted(range(len(keys)), key=lambda j: float(keys[j]))          # columns in ascending order of lambda
+        cols = bitstream.smallest_rates_within(nbytes[:, order], max_bytes if budgets is None else budgets,
+                                               rates=[float(keys[j]) for j in order])
+        return self.compress_latents_to_bytes_batch(on_dev, [keys[order[c]] for c in cols], segment=segment)
+
+    def compress_latents_to_total_budget(self, latents, max_total_bytes, lambs=None, segment=1024):
+        """(lamb, files): ONE lambda for all files -- the numerically smallest of `lambs` at which the F files together take
+        at most max_total_bytes (bitstream.smallest_rate_within on the column sums of the length table) -- and
+        files == compress_latents_to_bytes_batch(latents, lamb, segment).  ValueError for no files, or naming the smallest
+        achievable total and its lambda when nothing fits."""
+        bitstream.check_budget(max_total_bytes)
+        pairs, shapes, keys, segment = self._rate_batch_inputs(latents, lambs, segment)
+        if not pairs:
+            raise ValueError("no files: a total budget needs at least one")
+        nbytes, on_dev = self._coded_nbytes_batch(pairs, shapes, keys, segment)
+        lamb = bitstream.smallest_rate_within(dict(zip(keys, nbytes.sum(axis=0))), max_total_bytes, "lambda")
+        return lamb, self.compress_latents_to_bytes_batch(on_dev, lamb, segment=segment)
+
+    def compress_to_budget_batch(self, Xs, vae, max_bytes, lambs=None, segment=1024) -> list:
+        """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_budget_batch."""
+        return self.compress_latents_to_budget_batch([vae.encode(X) for X in Xs], max_bytes, lambs=lambs, segment=segment)
 
     def decompress(self, data, vae, clip=True, return_np=True):
         """decompress_latents, then `vae.decode` and the clip to [0, 1] of compress (quantizer.py:251-253).  The decoder
