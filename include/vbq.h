@@ -1041,6 +1041,74 @@ int vbq_rans_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, int64_t lambd
                              const uint16_t *d_freq, int32_t n_lambda, const uint16_t *d_canon, uint64_t *d_totals,
                              uint32_t *d_status, void *stream);
 
+/* ----------------------------------------------------------------------------------
+ * Compact batch: the parts of MANY compact latent files (vbq_amd/bitstream.py, magic "VBQc") sized, written or read in ONE
+ * launch each.  vbq_rans_il_sizes_u16 / _encode_u16 / _decode_u16 give a wave one part of ONE tensor: a small file has a few
+ * parts, so a few waves run and the call takes the time of one wave's steps.  Here the caller lists the work as items
+ * (file, part) and a wave (a workgroup of 64) takes one item: the parts of all files run side by side.  The format and the
+ * coder are those of vbq_rans_il_encode_u16 (one copy of the device code serves both); the three calls share one descriptor
+ * and one item list, so one plan serves writer and reader.
+ *   d_idx      u16 [n_idx]: the rank indices of all files.  A file has n_ch streams of n symbols; symbol i of stream c of file
+ *              f is d_idx[idx_base_f + c * idx_stride_f + i], 0 <= i < n_f.
+ *   d_files    int64 [n_files][8], per file: idx_base, idx_stride, n, part_base, table, part, word_base, n_words_f.  The first
+ *              five fields sit where the batch encoder's descriptor has them, part_base in the place of seg_base.  The file's
+ *              n_ch * n symbols in stream-major order are cut every `part` symbols (1 .. 2^24, any value per file) into
+ *              P_f = ceil(n_ch * n / part) parts; part p of the file is entry part_base + p of d_sizes / d_offsets; `table`
+ *              picks the block of d_freq (the file's lambda); the file's words are d_payload[word_base, word_base +
+ *              n_words_f).  The last two fields are the decoder's: the encode-side calls do not read them (an encoder's
+ *              offsets are the caller's own, and they are not known when the descriptors are made).
+ *   d_items    int32 [n_items][2]: (file, part within the file), in any order, any count: one wave handles one item, a lane is
+ *              not an item, so there is no multiple-of-64 rule.  An item with file == -1 is padding and skipped silently.
+ *   d_freq     u16 [n_tables][n_ch][T], T = 2^(N+1) - 1, every row summing to 2^15 (the encode side: every entry >= 1).
+ *   d_canon    u16 [n_ch][T] or NULL (the encode side), as in the batch encode: symbol d_canon[c][idx] is coded instead of
+ *              idx; the map is applied once to the staged table of a run, not per symbol.  An entry outside the table counts
+ *              as 0.
+ *   d_sizes    u32 [P_all], d_offsets int64 [P_all], d_payload u16 [n_words].
+ *   d_status   u32 [n_files], may be NULL, OR-ed into; zero it first.  Per file:
+ *                bits 0 - 3 as vbq_rans_il_decode_u16 (the decoder);
+ *                bit 4 (16)  the decoder: a part outside the file's words, or the file's last part not ending at word_base +
+ *                            n_words_f; the encoder: a part whose [offset, offset + size) leaves [0, n_words) or whose size is
+ *                            below 128 -- it is not written;
+ *                bit 7 (128) of the descriptor -- `table` outside [0, n_tables), n < 1, `part` outside [1, 2^24], symbols of
+ *                            some stream outside [0, n_idx), part_base + P_f outside [0, P_all], or (the decoder) a word range
+ *                            outside [0, n_words): every item of the file finds the same, so nothing of that file is read or
+ *                            written;
+ *                            of one item -- a part id outside [0, P_f): that item does nothing.
+ *              An item whose file id lies outside [0, n_files) (other than -1) does nothing and sets bit 7 of word 0: it has no
+ *              word of its own.
+ * Descriptors and items are range-checked on the device, without overflow, before anything is indexed with them.
+ *
+ * vbq_rans_il_sizes_files_u16   d_sizes[part_base_f + p] = the words of every listed part: exactly the entry
+ *                               vbq_rans_il_sizes_u16 gives for that file alone with the row block d_freq[table_f].  Entries no
+ *                               item names are left untouched.
+ * vbq_rans_il_encode_files_u16  every listed part backwards from d_offsets[.] + d_sizes[.] into d_payload, so that it begins at
+ *                               d_offsets[.] with its 128 state words: exactly the bytes of vbq_rans_il_encode_u16 for that
+ *                               file alone.  Sizes and offsets are the caller's own (the sizes call and an exclusive scan) and
+ *                               are checked for memory safety only.
+ * vbq_rans_il_decode_files_u16  payload, sizes and offsets are UNTRUSTED, with the rules of vbq_rans_il_decode_u16: no read
+ *                               leaves a part's [off, off + size), which is checked against the FILE's [word_base, word_base +
+ *                               n_words_f) within [0, n_words); every index written is below T; no write leaves the file's own
+ *                               index positions inside [0, n_idx).  Writes u16 indices to d_idx at the addresses above;
+ *                               positions that belong to no listed part are left untouched.  A part with any status bit
+ *                               decodes to zeros; the other parts of the file and the other files decode in full.
+ * Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): n_files <= 65535, n_ch in 1..65535, N in 1..10, n_tables >= 1,
+ * every size >= 0, n_items <= 2^31 - 1, n_ch * n_idx addressable, no null pointer (d_canon, d_status and, with n_words == 0,
+ * d_payload excepted).  n_files == 0 or n_items == 0 return VBQ_OK with no launch.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_il_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, const int64_t *d_files, int32_t n_files,
+                                const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t N, const uint16_t *d_freq,
+                                int32_t n_tables, const uint16_t *d_canon, uint32_t *d_sizes, int64_t P_all,
+                                uint32_t *d_status, void *stream);
+int vbq_rans_il_encode_files_u16(const uint16_t *d_idx, int64_t n_idx, const int64_t *d_files, int32_t n_files,
+                                 const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t N, const uint16_t *d_freq,
+                                 int32_t n_tables, const uint16_t *d_canon, const uint32_t *d_sizes, const int64_t *d_offsets,
+                                 int64_t P_all, uint16_t *d_payload, int64_t n_words, uint32_t *d_status, void *stream);
+int vbq_rans_il_decode_files_u16(const uint16_t *d_payload, int64_t n_words, const uint32_t *d_sizes, const int64_t *d_offsets,
+                                 int64_t P_all, const int64_t *d_files, int32_t n_files, const int32_t *d_items,
+                                 int64_t n_items, int32_t n_ch, int32_t N, const uint16_t *d_freq, int32_t n_tables,
+                                 uint16_t *d_idx, int64_t n_idx, uint32_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -428,6 +428,40 @@ MAX_BATCH_FILES = 65535                      # the kernel's limit (vbq_rans_enco
 EncodePlan = namedtuple("EncodePlan", "nseg seg_base M row0 group_rows group_row_base n_rows files items")
 
 
+def _plan_inputs(rows, tables, C, n_tables):
+    """The checks encode_plan and compact_plan share -> (C, rows int64 [F], tables int64 [F], F, n_tables)."""
+    C = int(C)
+    if C < 1:
+        raise ValueError("zero channels")
+    n = np.asarray(rows, dtype=np.int64).reshape(-1)
+    tab = np.asarray(tables, dtype=np.int64).reshape(-1)
+    F = n.size
+    if tab.size != F:
+        raise ValueError(f"{tab.size} tables for {F} files")
+    if F > MAX_BATCH_FILES:
+        raise ValueError(f"{F} files: one call takes at most {MAX_BATCH_FILES}")
+    if F and int(n.min()) < 1:
+        raise ValueError(f"file {int(np.flatnonzero(n < 1)[0])} has no rows")
+    n_tables = (int(tab.max()) + 1 if F else 0) if n_tables is None else int(n_tables)
+    if F and (int(tab.min()) < 0 or int(tab.max()) >= n_tables):
+        raise ValueError(f"table outside [0, {n_tables})")
+    return C, n, tab, F, n_tables
+
+
+def _row_groups(n, tab, n_tables):
+    """The row layout of a batch (see encode_plan) -> (row0 [F], group_rows [n_tables], group_row_base [n_tables]): the files
+    of a table next to each other in file order, each file's run of rows rounded up to ENCODE_ROW_ALIGN."""
+    padded = (n + ENCODE_ROW_ALIGN - 1) // ENCODE_ROW_ALIGN * ENCODE_ROW_ALIGN
+    row0 = np.zeros(n.size, np.int64)
+    group_rows = np.zeros(n_tables, np.int64)
+    for t in range(n_tables):
+        fs = np.flatnonzero(tab == t)
+        run = np.cumsum(padded[fs])
+        row0[fs] = run - padded[fs]
+        group_rows[t] = run[-1] if fs.size else 0
+    return row0, group_rows, np.cumsum(group_rows) - group_rows
+
+
 def encode_plan(rows, tables, segment, C, n_tables=None) -> EncodePlan:
     """What vbq_rans_encode_files_u16 reads, from the rows per channel n_f >= 1 of F files, their table numbers (the files'
     lambdas, 0 .. n_tables - 1; default n_tables: the largest + 1), the segment length and the number of channels C:
@@ -449,45 +483,72 @@ def encode_plan(rows, tables, segment, C, n_tables=None) -> EncodePlan:
 
     ValueError for a bad segment, C < 1, a row count < 1, a table outside [0, n_tables) or more than MAX_BATCH_FILES files."""
     check_segment(segment)
-    segment, C = int(segment), int(C)
-    if C < 1:
-        raise ValueError("zero channels")
-    n = np.asarray(rows, dtype=np.int64).reshape(-1)
-    tab = np.asarray(tables, dtype=np.int64).reshape(-1)
-    F = n.size
-    if tab.size != F:
-        raise ValueError(f"{tab.size} tables for {F} files")
-    if F > MAX_BATCH_FILES:
-        raise ValueError(f"{F} files: one call takes at most {MAX_BATCH_FILES}")
-    if F and int(n.min()) < 1:
-        raise ValueError(f"file {int(np.flatnonzero(n < 1)[0])} has no rows")
-    n_tables = (int(tab.max()) + 1 if F else 0) if n_tables is None else int(n_tables)
-    if F and (int(tab.min()) < 0 or int(tab.max()) >= n_tables):
-        raise ValueError(f"table outside [0, {n_tables})")
+    segment = int(segment)
+    C, n, tab, F, n_tables = _plan_inputs(rows, tables, C, n_tables)
     nseg = (n + segment - 1) // segment
     if F and int(nseg.max()) > np.iinfo(np.int32).max:
         raise ValueError(f"{int(nseg.max())} segments per stream are too many")
     per_file = C * nseg
     seg_base = np.cumsum(per_file) - per_file
-    padded = (n + ENCODE_ROW_ALIGN - 1) // ENCODE_ROW_ALIGN * ENCODE_ROW_ALIGN
-    row0 = np.zeros(F, np.int64)
-    group_rows = np.zeros(n_tables, np.int64)
+    row0, group_rows, group_row_base = _row_groups(n, tab, n_tables)
     lists = []
     for t in range(n_tables):
         fs = np.flatnonzero(tab == t)
-        run = np.cumsum(padded[fs])
-        row0[fs] = run - padded[fs]
-        group_rows[t] = run[-1] if fs.size else 0
         reps = nseg[fs]
         first = np.cumsum(reps) - reps
         item = np.stack([np.repeat(fs, reps), np.arange(int(reps.sum())) - np.repeat(first, reps)], axis=1)
         lists += [item, np.full((-item.shape[0] % ENCODE_BLOCK, 2), -1, np.int64)]
-    group_row_base = np.cumsum(group_rows) - group_rows
     items = (np.concatenate(lists) if lists else np.zeros((0, 2), np.int64)).astype(np.int32)
     files = np.stack([C * group_row_base[tab] + row0, group_rows[tab], n, seg_base, tab, np.zeros(F, np.int64)], axis=1) \
         if F else np.zeros((0, 6), np.int64)
     return EncodePlan(nseg, seg_base, int(per_file.sum()), row0, group_rows, group_row_base, int(group_rows.sum()),
                       np.ascontiguousarray(files, dtype=np.int64), np.ascontiguousarray(items))
+
+
+# ---- batches of compact files, written and read (ChannelwisePriorCDFQuantizer.compress_latents_to_compact_batch /
+# decompress_latents_compact_batch; include/vbq.h, "Compact batch").  One wave codes one part, so the plan lists every part of
+# every file; the rows lie as encode_plan lays them.
+COMPACT_FIELDS = 8                           # idx_base, idx_stride, n, part_base, table, part, word_base, n_words_f
+CompactPlan = namedtuple("CompactPlan", "n_parts part_base P_all row0 group_rows group_row_base n_rows files items")
+
+
+def compact_plan(rows, tables, parts, C, n_tables=None) -> CompactPlan:
+    """What vbq_rans_il_sizes_files_u16 / _encode_files_u16 / _decode_files_u16 read, from the rows per channel n_f >= 1 of F
+    files, their table numbers, their part lengths (one for all files or one per file) and the number of channels C:
+
+        n_parts         int64 [F]         P_f = ceil(C * n_f / part_f)
+        part_base, P_all  int64 [F], int  the file-major exclusive sum of P_f and its total: a file's size block is
+                                          sizes[part_base_f : part_base_f + P_f] of the P_all entries
+        row0, group_rows, group_row_base, n_rows   the row layout of encode_plan, unchanged: the files of a table next to each
+                                          other, every file's run of rows starting at a multiple of ENCODE_ROW_ALIGN
+        files           int64 [F, 8]      the descriptors: idx_base = C * group_row_base_g + row0_f, idx_stride = B_g, n_f,
+                                          part_base_f, table, part_f, and word_base = n_words_f = 0 -- the reader fills the
+                                          last two in from its files, the encode side does not read them
+        items           int32 [P_all, 2]  the work items (file, part), file by file and part by part; no padding
+
+    ValueError for a bad part, C < 1, a row count < 1, a table outside [0, n_tables) or more than MAX_BATCH_FILES files."""
+    C, n, tab, F, n_tables = _plan_inputs(rows, tables, C, n_tables)
+    part = np.asarray(parts).reshape(-1)
+    if part.size == 1:
+        part = np.repeat(part, F)
+    if part.size != F:
+        raise ValueError(f"{part.size} parts for {F} files")
+    for v in part.tolist():
+        check_part(v)
+    part = part.astype(np.int64)
+    n_parts = (C * n + part - 1) // part
+    part_base = np.cumsum(n_parts) - n_parts
+    P_all = int(n_parts.sum())
+    if P_all > np.iinfo(np.int32).max:
+        raise ValueError(f"{P_all} parts are too many")
+    row0, group_rows, group_row_base = _row_groups(n, tab, n_tables)
+    items = np.stack([np.repeat(np.arange(F), n_parts), np.arange(P_all) - np.repeat(part_base, n_parts)], axis=1) \
+        if F else np.zeros((0, 2), np.int64)
+    zero = np.zeros(F, np.int64)
+    files = np.stack([C * group_row_base[tab] + row0, group_rows[tab], n, part_base, tab, part, zero, zero], axis=1) \
+        if F else np.zeros((0, COMPACT_FIELDS), np.int64)
+    return CompactPlan(n_parts, part_base, P_all, row0, group_rows, group_row_base, int(group_rows.sum()),
+                       np.ascontiguousarray(files, dtype=np.int64), np.ascontiguousarray(items, dtype=np.int32))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

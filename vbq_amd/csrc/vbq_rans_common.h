@@ -3,7 +3,8 @@
 // of the encoder and of the decoder.  32-bit state, start state 2^16, 16-bit renormalisation words, 15 probability bits;
 // format: include/vbq.h.  The two segment coders also share, further down, how a frequency row reaches LDS, the bucket table
 // of the slot search, the rules for reading an untrusted segment and the host-side argument check; the interleaved coder maps
-// lanes to symbols differently and keeps its own staging and its own two-register word window.
+// lanes to symbols differently and keeps its own staging and its own two-register word window (vbq_rans_il_common.h, for
+// vbq_rans_il.hip and vbq_rans_il_files.hip).
 #pragma once
 #include "vbq_common.h"
 
@@ -87,7 +88,7 @@ __device__ __forceinline__ void stage_segment_table(const uint16_t *__restrict__
 // fc_l[t] = fc_l[canon[t]] for every t, by the one wave that staged fc_l: the whole table through registers (T <= 2047: at
 // most 32 entries per lane) between two barriers, so that no entry is overwritten before it was read.  An encoder that reads
 // fc_l[sym] then codes symbol canon[sym] at no cost per symbol.  (An entry of canon outside the table counts as 0.)  For the
-// batch kernels (vbq_rans_files.hip, vbq_rans_sizes_files.hip).
+// batch kernels (vbq_rans_files.hip, vbq_rans_sizes_files.hip, and per run vbq_rans_il_common.h's encoder).
 __device__ __forceinline__ void map_segment_table(const uint16_t *__restrict__ canon, int T, uint32_t *fc_l) {
     const int lane = threadIdx.x;
     uint32_t v[32];

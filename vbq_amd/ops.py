@@ -1001,3 +1001,100 @@ def rans_sizes_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor
                                               n_ch, seg, N, _ptr(freq), L, _ptr(canon), _ptr(totals), _ptr(status),
                                               _stream(idx)), "vbq_rans_sizes_files_u16")
     return totals, status
+
+
+# ---- batches of compact files (include/vbq.h, "Compact batch"): one wave per (file, part)
+def _il_files_args(idx, files, items, freq, N, status):
+    """What the three compact-batch calls check alike -> (idx, files, items, freq, status, F, n_tables, n_ch)."""
+    idx = _dev(idx, torch.uint16, "idx")
+    files = _dev(files, torch.int64, "files")
+    items = _dev(items, torch.int32, "items")
+    freq = _dev(freq, torch.uint16, "freq")
+    T = table_size(int(N))
+    if files.dim() != 2 or files.shape[1] != 8:
+        raise ValueError("files must be [F, 8] (idx_base, idx_stride, n, part_base, table, part, word_base, n_words_f), got "
+                         f"{tuple(files.shape)}")
+    if items.dim() != 2 or items.shape[1] != 2:
+        raise ValueError(f"items must be [n_items, 2] (file, part), got {tuple(items.shape)}")
+    if freq.dim() != 3 or freq.shape[2] != T:
+        raise ValueError(f"expected freq [n_tables, C, {T}], got {tuple(freq.shape)}")
+    F = files.shape[0]
+    if status is None:
+        status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
+    else:
+        status = _dev(status, torch.uint32, "status")
+        if status.numel() != F:
+            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+    return idx, files, items, freq, status, F, freq.shape[0], freq.shape[1]
+
+
+def _il_canon(canon, n_ch, N):
+    if canon is None:
+        return None
+    canon = _dev(canon, torch.uint16, "canon")
+    if tuple(canon.shape) != (n_ch, table_size(int(N))):
+        raise ValueError(f"canon must be [{n_ch}, {table_size(int(N))}], got {tuple(canon.shape)}")
+    return canon
+
+
+def rans_il_sizes_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor, freq: torch.Tensor, P_all: int, *,
+                        N: int = 10, canon: Optional[torch.Tensor] = None, sizes: Optional[torch.Tensor] = None,
+                        status: Optional[torch.Tensor] = None):
+    """vbq_rans_il_sizes_files_u16 (include/vbq.h, "Compact batch"): the words of every listed part of every file in one
+    launch.  idx u16 [n_idx]; files int64 [F, 8] and items int32 [n_items, 2] (file, part), file -1 = padding
+    (bitstream.compact_plan builds both); freq u16 [n_tables, C, T]; canon u16 [C, T] or None.  Returns (sizes u32 [P_all],
+    status u32 [F]): entry part_base_f + p is what RansCodec.sizes_interleaved gives for that file alone; entries no item names
+    keep what `sizes` held (a new one is zeroed).  `status` is OR-ed into: zeroed here unless given."""
+    idx, files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    canon = _il_canon(canon, n_ch, N)
+    P_all = int(P_all)
+    if P_all < 0:
+        raise ValueError(f"P_all = {P_all} parts")
+    if sizes is None:
+        sizes = torch.zeros(P_all, dtype=torch.uint32, device=idx.device)
+    else:
+        sizes = _out(sizes, (P_all,), torch.uint32, idx.device, "sizes")
+    check(_lib.lib().vbq_rans_il_sizes_files_u16(_ptr(idx), idx.numel(), _ptr(files), F, _ptr(items), items.shape[0], n_ch,
+                                                 int(N), _ptr(freq), n_tables, _ptr(canon), _ptr(sizes), P_all, _ptr(status),
+                                                 _stream(idx)), "vbq_rans_il_sizes_files_u16")
+    return sizes, status
+
+
+def rans_il_encode_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor, freq: torch.Tensor, sizes: torch.Tensor,
+                         offsets: torch.Tensor, payload: torch.Tensor, *, N: int = 10, canon: Optional[torch.Tensor] = None,
+                         status: Optional[torch.Tensor] = None):
+    """vbq_rans_il_encode_files_u16: every listed part into payload u16 [n_words] at offsets int64 [P_all], with sizes u32
+    [P_all] from rans_il_sizes_files (the same idx, files, items, freq and canon).  A part's words are those of
+    RansCodec.encode_interleaved for its file alone.  Returns (payload, status u32 [F])."""
+    idx, files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    canon = _il_canon(canon, n_ch, N)
+    sizes = _dev(sizes, torch.uint32, "sizes").reshape(-1)
+    offsets = _dev(offsets, torch.int64, "offsets").reshape(-1)
+    payload = _dev(payload, torch.uint16, "payload").reshape(-1)
+    if offsets.numel() != sizes.numel():
+        raise ValueError(f"{sizes.numel()} sizes and {offsets.numel()} offsets")
+    check(_lib.lib().vbq_rans_il_encode_files_u16(_ptr(idx), idx.numel(), _ptr(files), F, _ptr(items), items.shape[0], n_ch,
+                                                  int(N), _ptr(freq), n_tables, _ptr(canon), _ptr(sizes), _ptr(offsets),
+                                                  sizes.numel(), _ptr(payload), payload.numel(), _ptr(status), _stream(idx)),
+          "vbq_rans_il_encode_files_u16")
+    return payload, status
+
+
+def rans_il_decode_files(payload: torch.Tensor, sizes: torch.Tensor, offsets: torch.Tensor, files: torch.Tensor,
+                         items: torch.Tensor, freq: torch.Tensor, idx: torch.Tensor, *, N: int = 10,
+                         status: Optional[torch.Tensor] = None):
+    """vbq_rans_il_decode_files_u16: every listed part of every file from payload u16 [n_words], sizes u32 [P_all] and offsets
+    int64 [P_all] -- all UNTRUSTED -- into idx u16 [n_idx] at the positions the descriptors name (files [F, 8] with the word
+    fields filled in); positions of no listed part keep what `idx` held.  Returns (idx, status u32 [F]): a part with a status
+    bit decoded to zeros (read the words with coder._raise_status)."""
+    idx, files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    payload = _dev(payload, torch.uint16, "payload").reshape(-1)
+    sizes = _dev(sizes, torch.uint32, "sizes").reshape(-1)
+    offsets = _dev(offsets, torch.int64, "offsets").reshape(-1)
+    if offsets.numel() != sizes.numel():
+        raise ValueError(f"{sizes.numel()} sizes and {offsets.numel()} offsets")
+    check(_lib.lib().vbq_rans_il_decode_files_u16(_ptr(payload), payload.numel(), _ptr(sizes), _ptr(offsets), sizes.numel(),
+                                                  _ptr(files), F, _ptr(items), items.shape[0], n_ch, int(N), _ptr(freq),
+                                                  n_tables, _ptr(idx), idx.numel(), _ptr(status), _stream(idx)),
+          "vbq_rans_il_decode_files_u16")
+    return idx, status

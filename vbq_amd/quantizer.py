@@ -766,21 +766,28 @@ class ChannelwisePriorCDFQuantizer:
                        bitstream.MAPPED_MAGIC: "a lambda-map file (magic b'VBQm'): it has a table per symbol"}.get(magic)
             if foreign:
                 raise ValueError(f"file {i} is {foreign}; windows and batches read files in segments (magic b'VBQb')")
-            try:
-                h, sz, start = bitstream.parse(data)
-            except ValueError as e:
-                raise ValueError(f"file {i}: {e}") from None
-            if h.N != self.max_bits_per_coord or h.C != self.num_channels:
-                raise ValueError(f"file {i} is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
-                                 f"C = {self.num_channels}")
-            if heads and h.segment != heads[0].segment:
-                raise ValueError(f"file {i} is in segments of {h.segment} symbols, file 0 in segments of {heads[0].segment}: "
-                                 "one call decodes files of one segment length")
-            key = self._lambda_key(h.lamb)
-            if self._coder_tables(key, h.segment)[1] != h.digest:
-                raise ValueError(f"file {i} was compressed with a different quantizer or entropy model (digest mismatch)")
+            h, sz, start, key = self._batch_file_header(i, data, bitstream.parse, heads[0].segment if heads else None)
             heads.append(h), sizes.append(sz), starts.append(start), keys.append(key)
         return heads, sizes, starts, keys
+
+    def _batch_file_header(self, i, data, parse, segment=None):
+        """File i of a batch parsed by `parse` (bitstream.parse / parse_compact) with the checks of decompress_latents ->
+        (header, sizes, payload offset, key); ValueError naming i for a malformed file, one of another N or C, another segment
+        length than `segment` (where given) or another digest; KeyError for a lambda without a model."""
+        try:
+            h, sz, start = parse(data)
+        except ValueError as e:
+            raise ValueError(f"file {i}: {e}") from None
+        if h.N != self.max_bits_per_coord or h.C != self.num_channels:
+            raise ValueError(f"file {i} is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
+                             f"C = {self.num_channels}")
+        if segment is not None and h.segment != segment:
+            raise ValueError(f"file {i} is in segments of {h.segment} symbols, file 0 in segments of {segment}: "
+                             "one call decodes files of one segment length")
+        key = self._lambda_key(h.lamb)
+        if self._coder_tables(key, getattr(h, "segment", None))[1] != h.digest:
+            raise ValueError(f"file {i} was compressed with a different quantizer or entropy model (digest mismatch)")
+        return h, sz, start, key
 
     def decompress_latents_batch(self, files, regions=None, channels=None, return_np=False):
         """The same-sized boxes of many latent files in ONE launch: f32 [F, *extents, C_sel], every value bit-identical to
@@ -888,9 +895,9 @@ class ChannelwisePriorCDFQuantizer:
         return self.compress_latents_to_bytes(posterior_means, posterior_logvars, lamb, segment=segment, layout=layout, part=part)
 
     # ------------------------------------------------------------------ batches of files, written (include/vbq.h, "Batch encode")
-    def _batch_file_shapes(self, pairs, segment):
+    def _batch_file_shapes(self, pairs, unit, layout="segments"):
         """The latent shape of every file of a batch, channel-last; ValueError naming the file's index for what is not a pair
-        of one such shape, or for more than 65535 files."""
+        of one such shape, or for more than 65535 files.  `unit`: the segment, or the part of layout "interleaved"."""
         F = len(pairs)
         if F > bitstream.MAX_BATCH_FILES:
             raise ValueError(f"{F} files: one call takes at most {bitstream.MAX_BATCH_FILES}")
@@ -901,23 +908,24 @@ class ChannelwisePriorCDFQuantizer:
             except (TypeError, ValueError):
                 raise ValueError(f"file {i}: expected a pair (posterior_means, posterior_logvars)") from None
             try:
-                shapes.append(self._file_layout(means, logvars, "segments", segment, None)[0])
+                shapes.append(self._file_layout(means, logvars, layout, unit, unit)[0])
             except ValueError as e:
                 raise ValueError(f"file {i}: {e}") from None
             if 0 in shapes[-1]:
                 raise ValueError(f"file {i}: empty latent shape {shapes[-1]}")
         return shapes
 
-    def _batch_file_inputs(self, latents, lambs, segment):
-        """Every check of compress_latents_to_bytes_batch, before any device work -> (pairs, shapes, keys, segment)."""
+    def _batch_file_inputs(self, latents, lambs, segment, layout="segments"):
+        """Every check of compress_latents_to_bytes_batch, before any device work -> (pairs, shapes, keys, segment); with
+        layout "interleaved" those of compress_latents_to_compact_batch, `segment` being its part."""
         self._check_coder_bits()
-        bitstream.check_segment(segment)
+        _LAYOUTS[layout].check(segment)
         pairs = list(latents)
         F = len(pairs)
         lambs = [lambs] * F if np.ndim(lambs) == 0 else list(lambs)
         if len(lambs) != F:
             raise ValueError(f"{len(lambs)} lambdas for {F} files")
-        shapes = self._batch_file_shapes(pairs, segment)
+        shapes = self._batch_file_shapes(pairs, segment, layout)
         keys = [self._lambda_key(l) for l in lambs] if F else []
         return pairs, shapes, keys, int(segment)
 
@@ -1028,24 +1036,31 @@ class ChannelwisePriorCDFQuantizer:
                                   zeros[: -b.rows[f] % bitstream.ENCODE_ROW_ALIGN]]
         return d_host, torch.cat(pieces[0] + pieces[1]).view(2, plan.n_rows, C)
 
+    def _batch_solve(self, b, lat):
+        """Per distinct lambda one vbq_prep_planes_f32 and one solve of its files' rows into its planes of the one index array
+        -> (idx u16 [C * R], canon u16 [C, T] or None: the map a batch coder applies when the table has repeated code points)."""
+        plan, C = b.plan, self.num_channels
+        idx = torch.empty(C * plan.n_rows, dtype=torch.uint16, device=lat.device)
+        for t, key in enumerate(b.tables):
+            r0, B = int(plan.group_row_base[t]), int(plan.group_rows[t])
+            mu_cb, sg_cb = self._prep(lat[0, r0:r0 + B], lat[1, r0:r0 + B], spread="logvar")
+            self._solve_idx(mu_cb, sg_cb, [key], self._level_len_dev([key]), out_idx=idx[C * r0:C * (r0 + B)].view(1, C, B))
+        canon = None if self._strict else self._dev("canon_u16", lambda: torch.from_numpy(self._canon.astype(np.uint16)))
+        return idx, canon
+
     def _encode_batch_run(self, b, d_host, lat):
         """The device side: per distinct lambda one vbq_prep_planes_f32 and one solve of its files' rows into its planes of the
         one index array, ONE vbq_rans_encode_files_u16, ONE vbq_rans_pack_u16 -> the payload u16 (its first `total` words are
         valid); total, sizes and status land in d_host[:b.back].  Nothing is read back."""
         from . import _lib
         plan, C, N, dev, segment = b.plan, self.num_channels, self.max_bits_per_coord, d_host.device, b.segment
-        F, M, R, cut = len(b.keys), plan.M, plan.n_rows, b.cut
+        F, M, cut = len(b.keys), plan.M, b.cut
         d_total, d_sizes = d_host[:8].view(torch.uint64), d_host[8:8 + 4 * M].view(torch.uint32)
         d_status = d_host[8 + 4 * M:b.back].view(torch.uint32)
         d_files = d_host[cut[0]:cut[1]].view(torch.int64).view(F, 6)
         d_items = d_host[cut[1]:cut[2]].view(torch.int32).view(-1, 2)
-        idx = torch.empty(C * R, dtype=torch.uint16, device=dev)
-        for t, key in enumerate(b.tables):
-            r0, B = int(plan.group_row_base[t]), int(plan.group_rows[t])
-            mu_cb, sg_cb = self._prep(lat[0, r0:r0 + B], lat[1, r0:r0 + B], spread="logvar")
-            self._solve_idx(mu_cb, sg_cb, [key], self._level_len_dev([key]), out_idx=idx[C * r0:C * (r0 + B)].view(1, C, B))
+        idx, canon = self._batch_solve(b, lat)
         freq = self._coder_stack(b.tables, segment)._freq(dev).view(len(b.tables), C, -1)
-        canon = None if self._strict else self._dev("canon_u16", lambda: torch.from_numpy(self._canon.astype(np.uint16)))
         words = torch.empty((M, segment + 2), dtype=torch.uint16, device=dev)      # pack reads valid words only
         payload = torch.empty(M * (segment + 2), dtype=torch.uint16, device=dev)
         offsets = torch.empty(M, dtype=torch.int64, device=dev)
@@ -1058,6 +1073,143 @@ class ChannelwisePriorCDFQuantizer:
     def compress_to_bytes_batch(self, Xs, vae, lambs, segment=1024):
         """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_bytes_batch."""
         return self.compress_latents_to_bytes_batch([vae.encode(X) for X in Xs], lambs, segment=segment)
+
+    # ------------------------------------------------------------------ batches of compact files (include/vbq.h, "Compact batch")
+    # The one-file calls give the interleaved coder one wave per part: a Kodak-shaped latent is three parts, so three waves run
+    # and the call takes the time of one wave's steps.  Here the parts of all files of a batch run side by side, one launch
+    # per step.  Nothing routes here implicitly: one file stays with compress_latents_to_bytes / decompress_latents.
+    def compress_latents_to_compact_batch(self, latents, lambs, part=1 << 17):
+        """[compress_latents_to_bytes(means_f, logvars_f, lambs[f], layout="interleaved", part=part) for f], byte for byte, with
+        ONE sizes launch and ONE encode launch for all files.  `latents`, `lambs`, the errors and their order are those of
+        compress_latents_to_bytes_batch, with `part` checked by bitstream.check_part; the table may have repeated code points.
+        F == 0 returns [].
+        Work per call, L the number of DISTINCT lambdas: the one staging buffer and upload of the batch encoder (the plan of
+        bitstream.compact_plan, zeroed sizes and status words, the latents unless all are device tensors); per distinct
+        lambda one vbq_prep_planes_f32 and one solve; ONE vbq_rans_il_sizes_files_u16 over every part of every file; the
+        offsets by a device cumsum; ONE vbq_rans_il_encode_files_u16 into a payload buffer of the known upper bound,
+        sum(C * B_f) + 128 * P_all words.  Two device-to-host copies: the part sizes and the status words, then the valid
+        words.  The F files are assembled on the host (bitstream.CompactHeader / bitstream.write_compact)."""
+        from . import _lib
+        pairs, shapes, keys, part = self._batch_file_inputs(latents, lambs, part, "interleaved")
+        F, C, N = len(pairs), self.num_channels, self.max_bits_per_coord
+        if F == 0:
+            return []
+        tables = sorted(set(keys), key=float)                     # (a stable tag for the codec cache of _coder_stack)
+        digests = {k: self._coder_tables(k)[1] for k in tables}
+        rows = [int(np.prod(sh[:-1], dtype=np.int64)) for sh in shapes]
+        plan = bitstream.compact_plan(rows, [tables.index(k) for k in keys], part, C, len(tables))
+        P = plan.P_all
+        b = self._batch_stage(plan, shapes, keys, tables, digests, part, rows, pairs, 4 * P + 4 * F)
+        d_host, lat = self._encode_batch_upload(b)
+        d_sizes, d_status = d_host[:4 * P].view(torch.uint32), d_host[4 * P:b.back].view(torch.uint32)
+        d_files = d_host[b.cut[0]:b.cut[1]].view(torch.int64).view(F, bitstream.COMPACT_FIELDS)
+        d_items = d_host[b.cut[1]:b.cut[2]].view(torch.int32).view(-1, 2)
+        idx, canon = self._batch_solve(b, lat)
+        freq = self._coder_stack(tables, None)._freq(idx.device).view(len(tables), C, -1)
+        ops.rans_il_sizes_files(idx, d_files, d_items, freq, P, N=N, canon=canon, sizes=d_sizes, status=d_status)
+        s64 = d_sizes.view(torch.int32).to(torch.int64)                                   # (a size is at most 2^24 + 128)
+        payload = torch.empty(C * sum(rows) + bitstream.PART_STATE_WORDS * P, dtype=torch.uint16, device=idx.device)
+        ops.rans_il_encode_files(idx, d_files, d_items, freq, d_sizes, torch.cumsum(s64, 0) - s64, payload, N=N, canon=canon,
+                                 status=d_status)
+        h = d_host[:b.back].cpu().numpy()
+        sizes, status = h[:4 * P].view(np.uint32), h[4 * P:].view(np.uint32)
+        for f in np.flatnonzero(status):
+            raise _lib.VBQError(f"file {int(f)}: the batch encoder refused its descriptor (status {int(status[f])})")
+        ends = np.cumsum(sizes, dtype=np.int64)
+        pay = payload[:int(ends[-1])].cpu().numpy()
+        out = []
+        for f in range(F):
+            p0, p1 = int(plan.part_base[f]), int(plan.part_base[f] + plan.n_parts[f])
+            w0, w1 = int(ends[p0 - 1]) if p0 else 0, int(ends[p1 - 1])
+            hd = bitstream.CompactHeader(N=N, C=C, shape=shapes[f], lamb=float(keys[f]), digest=digests[keys[f]],
+                                         n_words=w1 - w0, part=part)
+            out.append(bitstream.write_compact(hd, sizes[p0:p1], pay[w0:w1]))
+        return out
+
+    def compress_to_compact_batch(self, Xs, vae, lambs, part=1 << 17):
+        """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_compact_batch."""
+        return self.compress_latents_to_compact_batch([vae.encode(X) for X in Xs], lambs, part=part)
+
+    def _compact_headers(self, files):
+        """The parsed headers of `files` with the checks of decompress_latents on each, (headers, sizes, payload offsets, keys);
+        ValueError naming the index of a file that is no b"VBQc" file of this quantizer."""
+        heads, sizes, starts, keys = [], [], [], []
+        for i, data in enumerate(files):
+            magic = bytes(memoryview(data).cast("B")[:4])
+            foreign = {bitstream.MAGIC: "a file in segments (magic b'VBQb')",
+                       bitstream.MAPPED_MAGIC: "a lambda-map file (magic b'VBQm')"}.get(magic)
+            if foreign:
+                raise ValueError(f"file {i} is {foreign}; compact batches read compact files (magic b'VBQc')")
+            h, sz, start, key = self._batch_file_header(i, data, bitstream.parse_compact)
+            heads.append(h), sizes.append(sz), starts.append(start), keys.append(key)
+        return heads, sizes, starts, keys
+
+    def decompress_latents_compact_batch(self, files, stack=True, return_np=False):
+        """Many compact latent files decoded in full in ONE launch, every value bit-identical to decompress_latents(files[f]).
+        `files`: b"VBQc" byte strings of this quantizer -- any built lambdas, any latent shapes, any `part` per file; each
+        gets the checks of decompress_latents (ValueError naming the file's index, also for a b"VBQb" or b"VBQm" file;
+        KeyError for a lambda without a model).  stack=True: one f32 [F, *shape]; ValueError naming the first file whose shape
+        differs from file 0's.  stack=False: a list of F tensors, each shaped like its latents, all views of one allocation.
+        F == 0 returns an empty tensor or list with no launch.
+        Work per call: one staging buffer and ONE upload (descriptors, part offsets -- the exclusive sum of the part sizes,
+        which the parser has validated, taken on the host --, items, all part sizes, all payloads), ONE
+        vbq_rans_il_decode_files_u16 into the columns of one [C, sum B_f] index matrix, ONE gather of it into channel-last
+        values, one read of the status words.  A damaged file raises VBQError naming the index of the first one."""
+        from . import _lib, coder
+        self._check_coder_bits()
+        files = list(files)
+        F, C, N = len(files), self.num_channels, self.max_bits_per_coord
+        heads, sizes, starts, keys = self._compact_headers(files)
+        if stack:
+            for i, h in enumerate(heads):
+                if h.shape != heads[0].shape:
+                    raise ValueError(f"file {i} has latent shape {h.shape}, file 0 has {heads[0].shape}: stack=False returns "
+                                     "a list")
+        if F == 0:
+            if not stack:
+                return []
+            out = torch.empty((0,), dtype=torch.float32, device=self.device)
+            return out.cpu().numpy() if return_np else out
+        dev = self.device
+        tables = sorted(set(keys), key=float)                      # (a stable tag for the codec cache of _coder_stack)
+        rows = [h.n_rows for h in heads]
+        plan = bitstream.compact_plan(rows, [tables.index(k) for k in keys], [h.part for h in heads], C, len(tables))
+        P, B = plan.P_all, int(sum(rows))
+        desc = plan.files.copy()
+        n_words_f = np.array([h.n_words for h in heads], np.int64)
+        # the files side by side as columns of ONE [C, B] index matrix, so that one gather serves them all
+        desc[:, 0], desc[:, 1] = np.cumsum(rows) - rows, B
+        desc[:, 6], desc[:, 7] = np.cumsum(n_words_f) - n_words_f, n_words_f
+        all_sizes = np.concatenate(sizes).astype(np.uint32)
+        offsets = np.cumsum(all_sizes, dtype=np.int64) - all_sizes
+        n_words = int(n_words_f.sum())
+        raws = [np.frombuffer(memoryview(d).cast("B"), dtype=np.uint8) for d in files]
+        head = [desc.view(np.uint8).reshape(-1), offsets.view(np.uint8), plan.items.view(np.uint8).reshape(-1),
+                all_sizes.view(np.uint8), np.zeros(4 * (P & 1), np.uint8)]
+        host = np.concatenate(head + [r[s: s + 2 * h.n_words] for r, h, s in zip(raws, heads, starts)])
+        cut = [int(c) for c in np.cumsum([0] + [a.size for a in head])]
+        d = torch.from_numpy(host).to(dev)
+        d_files = d[cut[0]:cut[1]].view(torch.int64).view(F, bitstream.COMPACT_FIELDS)
+        d_offsets = d[cut[1]:cut[2]].view(torch.int64)
+        d_items = d[cut[2]:cut[3]].view(torch.int32).view(P, 2)
+        d_sizes = d[cut[3]:cut[4]].view(torch.uint32)
+        d_payload = d[cut[5]:cut[5] + 2 * n_words].view(torch.uint16)
+        freq = self._coder_stack(tables, None)._freq(dev).view(len(tables), C, -1)
+        idx = torch.empty((C, B), dtype=torch.uint16, device=dev)                       # every position lies in a listed part
+        _, status = ops.rans_il_decode_files(d_payload, d_sizes, d_offsets, d_files, d_items, freq, idx, N=N)
+        zhat = ops.gather(idx[None], self._sorted_dev(), C, N=N, layout="cb", out_layout="bc").view(B, C)
+        st = status.cpu().numpy()
+        for f in np.flatnonzero(st):
+            try:
+                coder._raise_status(int(st[f]))
+            except _lib.VBQError as e:
+                raise _lib.VBQError(f"file {int(f)}: {e}") from None
+        if stack:
+            out = zhat.view((F,) + heads[0].shape)
+            return out.cpu().numpy() if return_np else out
+        col = desc[:, 0]
+        out = [zhat[int(col[f]): int(col[f]) + rows[f]].view(heads[f].shape) for f in range(F)]
+        return [o.cpu().numpy() for o in out] if return_np else out
 
     # ------------------------------------------------------------------ lambda maps (vbq_amd.bitstream, magic b"VBQm")
     # A palette `lambs` of 1..4 distinct built lambdas and `classes`, integers in [0, P) shaped like the latents without the
