@@ -7,6 +7,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import adversarial_tables as AT  # noqa: E402
 from oracle import c_oracle as CO
 from vbq_amd import bitstream as bs
 
@@ -27,9 +28,10 @@ class Batch:
     tables and index planes: every file in table 0 of bitstream.encode_plan, one plane of lambda_stride indices per lambda;
     what no file owns holds T - 1, which no check may ever see coded.  tight: the files follow each other without padding
     rows and every plane starts one element in, so that plane bases are no multiples of 8 symbols (descriptors of the test's
-    own; segments and items stay the plan's)."""
+    own; segments and items stay the plan's).  adversarial: tables and draws that do not fit each other
+    (adversarial_tables.mixed_model) instead of the fitted ones."""
 
-    def __init__(self, rows, L, C_, seg, bits, seed, canon=False, tight=False):
+    def __init__(self, rows, L, C_, seg, bits, seed, canon=False, tight=False, adversarial=False):
         from vbq_amd.coder import quantize_frequencies
         rng = np.random.default_rng(seed)
         T = 2 ** (bits + 1) - 1
@@ -37,8 +39,11 @@ class Batch:
         centre = rng.integers(T // 8, T - T // 8, (L, C_))
         spread = np.array([0.3, 2.0, 25.0, 300.0])[rng.integers(0, 4, (L, C_))] * T / 2047
         draw = lambda l, n: np.clip(np.rint(rng.normal(centre[l, :, None], spread[l, :, None], (C_, n))), 0, T - 1).astype(np.uint16)
-        self.freq = np.stack([quantize_frequencies(np.stack([np.bincount(r, minlength=T) for r in draw(l, 4000)]))
-                              for l in range(L)])                                      # [L, C, T]
+        if adversarial:
+            self.freq, draw = AT.mixed_model(L, C_, bits, seed)
+        else:
+            self.freq = np.stack([quantize_frequencies(np.stack([np.bincount(r, minlength=T) for r in draw(l, 4000)]))
+                                  for l in range(L)])                                  # [L, C, T]
         self.idx = [[draw(l, n) for n in rows] for l in range(L)]                      # [l][f] -> [C, n]
         # pairs of ranks mapped to the first of each pair: not the identity
         self.canon = np.tile((np.arange(T) & ~1).astype(np.uint16), (C_, 1)) if canon else None
@@ -88,6 +93,8 @@ KERNEL_CASES = {  # rows, L, C, seg, bits, canon
     # bases that are multiples of 8 and segments of 1024: the 16-byte loads
     "aligned-vector-path": ([1536, 1536], 2, 32, 1024, N, False),
     "canonical-map": ([1, 7, 64, 65, 200], 3, 3, 64, N, True),
+    # tables that do not fit the data: a spike, the ramp and half_ones across the lambdas; at lambda 0 frequency-1 symbols only
+    "mismatched-tables": ([1, 7, 64, 65, 200], 3, 3, 64, 7, False),
 }
 _BATCHES = {}
 
@@ -96,7 +103,8 @@ def _batch(case):
     """The batch of a case and its reference: built once, shared, never changed."""
     if case not in _BATCHES:
         rows, L, C_, seg, bits, canon = KERNEL_CASES[case]
-        _BATCHES[case] = Batch(rows, L, C_, seg, bits, seed=len(case), canon=canon, tight=case in ("rows-and-lambdas", "canonical-map"))
+        _BATCHES[case] = Batch(rows, L, C_, seg, bits, seed=len(case), canon=canon, tight=case in ("rows-and-lambdas", "canonical-map"),
+                               adversarial=case == "mismatched-tables")
     return _BATCHES[case]
 
 
@@ -114,6 +122,10 @@ def test_kernel_totals_equal_the_sum_of_the_checkers_sizes(case):
     if case == "canonical-map":                                   # the map changes what is coded
         plain = [[int(CO.rans_encode(i, k.freq[l], k.seg)[1].sum()) for i in k.idx[l]] for l in range(k.L)]
         assert plain != k.want.tolist()
+    if case == "mismatched-tables":
+        assert [k.freq[l, 0].tobytes() for l in range(3)] == [r.tobytes() for r in (AT.spike(7, 0), AT.ramp(), AT.half_ones(7))]
+        assert all(np.all(np.take_along_axis(k.freq[0], i.astype(np.int64), axis=1) == 1) for i in k.idx[0])
+        assert np.all(k.sizes[0][3][:, 0] == 2 + (15 * 64) // 16)  # a full segment of them: 62 of at most 66 words
     totals, st = k.run()
     assert st == [0] * k.F
     assert totals.dtype == np.uint64 and totals.shape == (k.L, k.F)

@@ -7,6 +7,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import adversarial_tables as AT  # noqa: E402
 import interleaved_reference as IR  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -89,7 +90,11 @@ class Batch:
         return _u32(st).tolist(), _u16(out)
 
 
-def _three(N):
+def _three(N, adversarial=False):
+    """adversarial: tables and draws that do not fit each other (adversarial_tables.mixed_model) instead of the fitted ones."""
+    if adversarial:
+        freq, draw = AT.mixed_model(2, 3, N)
+        return [draw(t, n) for n, _, t in FILES3], [t for _, _, t in FILES3], [p for _, p, _ in FILES3], freq
     cases = [IR.make_case(3, n, N, seed=s) for s, (n, _, _) in enumerate(FILES3)]
     freq = np.stack([cases[0][1], cases[1][1]])                  # table 0 from file 0, table 1 from file 1: every entry >= 1
     return [c[0] for c in cases], [t for _, _, t in FILES3], [p for _, p, _ in FILES3], freq
@@ -126,6 +131,21 @@ def test_three_files_in_one_launch_match_the_numpy_coder(N):
     st, got = b.decode()
     assert st == [0, 0, 0]
     assert np.array_equal(got, b.matrix)                          # every index, and every sentinel intact
+    _check_all_three(b)
+
+
+def test_three_files_of_mismatched_tables_match_the_numpy_coder():
+    """A spike, the ramp and half_ones across the streams of the two tables, none fitted to the data; files 0 and 2 hold
+    frequency-1 symbols only: 15 bits a symbol on top of the 16 of a lane's start state, so a lane with k symbols takes
+    15 k // 16 words.  File 0's one part has three runs of 100 symbols: lanes 0 .. 35 own six symbols, the others three."""
+    N = 7
+    b = Batch(*_three(N, adversarial=True), N)
+    assert [b.freq[0, c].tobytes() for c in range(3)] == [r.tobytes() for r in (AT.spike(7, 0), AT.ramp(), AT.half_ones(7))]
+    assert all(np.all(np.take_along_axis(b.freq[0], b.idxs[f].astype(np.int64), axis=1) == 1) for f in (0, 2))
+    assert b.n_parts == [1, 37, 1] and int(b.sizes[0]) == 128 + 36 * (15 * 6 // 16) + 28 * (15 * 3 // 16) == 364
+    st, got = b.decode()
+    assert st == [0, 0, 0]
+    assert np.array_equal(got, b.matrix)
     _check_all_three(b)
 
 

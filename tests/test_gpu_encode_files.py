@@ -8,6 +8,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import adversarial_tables as AT  # noqa: E402
 from oracle import c_oracle as CO
 from vbq_amd import bitstream as bs
 
@@ -28,9 +29,10 @@ class Batch:
     """Synthetic indices and frequency tables (built as `Coded` of test_gpu_window.py builds them), one file per (rows, table),
     laid out by bitstream.encode_plan; the padding rows between files hold T - 1, which no check may ever see coded.  tight:
     the files of a table follow each other without padding rows and the whole array starts one element in, so that plane bases
-    are no multiples of 8 symbols (descriptors of the test's own; segments and items stay the plan's)."""
+    are no multiples of 8 symbols (descriptors of the test's own; segments and items stay the plan's).  adversarial: tables and
+    draws that do not fit each other (adversarial_tables.mixed_model) instead of the fitted ones."""
 
-    def __init__(self, rows, tables, n_tables, C_, seg, bits, seed, canon=False, tight=False):
+    def __init__(self, rows, tables, n_tables, C_, seg, bits, seed, canon=False, tight=False, adversarial=False):
         from vbq_amd.coder import quantize_frequencies
         rng = np.random.default_rng(seed)
         T = 2 ** (bits + 1) - 1
@@ -38,8 +40,11 @@ class Batch:
         centre = rng.integers(T // 8, T - T // 8, (n_tables, C_))
         spread = np.array([0.3, 2.0, 25.0, 300.0])[rng.integers(0, 4, (n_tables, C_))] * T / 2047
         draw = lambda t, n: np.clip(np.rint(rng.normal(centre[t, :, None], spread[t, :, None], (C_, n))), 0, T - 1).astype(np.uint16)
-        self.freq = np.stack([quantize_frequencies(np.stack([np.bincount(r, minlength=T) for r in draw(t, 4000)]))
-                              for t in range(n_tables)])
+        if adversarial:
+            self.freq, draw = AT.mixed_model(n_tables, C_, bits, seed)
+        else:
+            self.freq = np.stack([quantize_frequencies(np.stack([np.bincount(r, minlength=T) for r in draw(t, 4000)]))
+                                  for t in range(n_tables)])
         self.idx = [draw(t, n) for n, t in zip(rows, tables)]
         # pairs of ranks mapped to the first of each pair: not the identity
         self.canon = np.tile((np.arange(T) & ~1).astype(np.uint16), (C_, 1)) if canon else None
@@ -102,14 +107,21 @@ KERNEL_CASES = {  # rows, tables, n_tables, C, seg, bits, canon
     # bases that are multiples of 8 and segments of 1024: the 16-byte loads
     "aligned-vector-path": ([1536, 1536], [0, 1], 2, 32, 1024, N, False),
     "canonical-map": ([1, 7, 64, 65, 200], [1, 0, 1, 0, 1], 2, 3, 64, N, True),
+    # tables that do not fit the data: a spike, the ramp and half_ones across the files; files 1 and 3 hold frequency-1 symbols only
+    "mismatched-tables": ([1, 7, 64, 65, 200], [1, 0, 2, 0, 1], 3, 3, 64, 7, False),
 }
 
 
 @pytest.mark.parametrize("case", list(KERNEL_CASES))
 def test_kernel_words_and_sizes_equal_the_checker(case):
     rows, tables, n_tables, C_, seg, bits, canon = KERNEL_CASES[case]
-    k = Batch(rows, tables, n_tables, C_, seg, bits, seed=len(case), canon=canon, tight=case == "rows-and-tables")
+    k = Batch(rows, tables, n_tables, C_, seg, bits, seed=len(case), canon=canon, tight=case == "rows-and-tables",
+              adversarial=case == "mismatched-tables")
     p = k.plan
+    if case == "mismatched-tables":
+        assert [k.freq[t, 0].tobytes() for t in range(3)] == [r.tobytes() for r in (AT.spike(7, 0), AT.ramp(), AT.half_ones(7))]
+        assert all(np.all(np.take_along_axis(k.freq[0], k.idx[f].astype(np.int64), axis=1) == 1) for f in (1, 3))
+        assert np.all(k.want[3][1][:, 0] == 2 + (15 * 64) // 16)  # a full segment of them: 62 of at most 66 words
     if case == "several-blocks":
         assert p.items.shape[0] == 128 and {int(f) for f in p.items[64:128, 0]} == {0, 1, 2, 3, -1}
     if case == "aligned-vector-path":

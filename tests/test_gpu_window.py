@@ -8,6 +8,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import adversarial_tables as AT  # noqa: E402
 from oracle import c_oracle as CO
 
 pytestmark = pytest.mark.gpu
@@ -24,9 +25,11 @@ def _need_gpu():
 
 # ---------------------------------------------------------------------------------------------------------------- kernel level
 class Coded:
-    """Files coded with RansCodec.encode_packed, staged as the window decode reads them: one file per (leading shape, table)."""
+    """Files coded with RansCodec.encode_packed, staged as the window decode reads them: one file per (leading shape, table).
+    adversarial: tables and draws that do not fit each other (adversarial_tables.mixed_model) instead of the fitted ones; what
+    the encoder made of them is compared with the C checker before anything decodes it."""
 
-    def __init__(self, shapes, tables, n_tables, C_, seg, bits, seed):
+    def __init__(self, shapes, tables, n_tables, C_, seg, bits, seed, adversarial=False):
         from vbq_amd import _lib, ops
         from vbq_amd.coder import RansCodec, quantize_frequencies
         rng = np.random.default_rng(seed)
@@ -36,12 +39,19 @@ class Coded:
         centre = rng.integers(T // 8, T - T // 8, (n_tables, C_))
         spread = np.array([0.3, 2.0, 25.0, 300.0])[rng.integers(0, 4, (n_tables, C_))] * T / 2047
         draw = lambda t, n: np.clip(np.rint(rng.normal(centre[t, :, None], spread[t, :, None], (C_, n))), 0, T - 1).astype(np.uint16)
-        self.freq = np.stack([quantize_frequencies(np.stack([np.bincount(r, minlength=T) for r in draw(t, 4000)]))
-                              for t in range(n_tables)])
+        if adversarial:
+            self.freq, draw = AT.mixed_model(n_tables, C_, bits, seed)
+        else:
+            self.freq = np.stack([quantize_frequencies(np.stack([np.bincount(r, minlength=T) for r in draw(t, 4000)]))
+                                  for t in range(n_tables)])
         self.idx, sizes, payloads, self.seg_base = [], [], [], []
         for shape, t in zip(shapes, tables):
             idx = draw(t, int(np.prod(shape)))
             sz, pay = RansCodec(self.freq[t], N=bits, segment=seg).encode_packed(torch.from_numpy(idx).cuda())
+            if adversarial:
+                w_ref, s_ref = CO.rans_encode(idx, self.freq[t], seg)
+                assert np.array_equal(sz, s_ref)
+                assert np.array_equal(pay, w_ref[np.arange(seg + 2)[None, None, :] < s_ref[..., None].astype(np.int64)])
             self.idx.append(idx)
             self.seg_base.append(sum(s.size for s in sizes))
             sizes.append(sz.reshape(-1).astype(np.uint16))
@@ -144,6 +154,28 @@ def test_kernel_batch_of_three_files_and_damage_in_one():
     assert st[0] == 0 and st[2] == 0 and st[1] != 0 and st[1] & ~(2 | 4) == 0, st
     assert np.array_equal(_bits(got[[0, 2]]), _bits(want[[0, 2]]))
     assert np.array_equal(_bits(np.delete(got[1], 4, axis=-1)), _bits(np.delete(want[1], 4, axis=-1)))
+
+
+def test_kernel_batch_of_three_files_with_mismatched_tables():
+    """A spike, the ramp and half_ones in the first channel of the three files (and cycling over the channels), none fitted to
+    the data; every stream of file 0 holds only frequency-1 symbols, so its segments come close to seg + 2 words."""
+    shapes = [(1, 17, 23), (1, 20, 30), (2, 9, 11)]
+    regions = [(S(None), S(3, 11), S(5, 13)), (S(0, 1), S(12, 20), S(22, 30)), (S(1, 2), S(0, 8), S(2, 10))]
+    k = Coded(shapes, [0, 1, 2], 3, 8, 64, 7, seed=13, adversarial=True)
+    assert [k.freq[t, 0].tobytes() for t in range(3)] == [r.tobytes() for r in (AT.spike(7, 0), AT.ramp(), AT.half_ones(7))]
+    assert np.all(np.take_along_axis(k.freq[0], k.idx[0].astype(np.int64), axis=1) == 1)         # file 0: all-rare data
+    nseg0 = (17 * 23 + 63) // 64
+    assert np.all(k.sizes_host[:8 * nseg0].reshape(8, nseg0)[:, :-1] == 2 + (15 * 64) // 16)     # 62 of at most 66 words
+    got, st, lists = k.decode(regions, fill=-7.0)
+    assert st == [0, 0, 0] and got.shape == (3, 1, 8, 8, 8)
+    assert np.array_equal(_bits(got), _bits(k.want(regions)))
+    got, st, _ = k.decode(regions, [7, 0, 7])
+    assert st == [0, 0, 0] and np.array_equal(_bits(got), _bits(k.want(regions, [7, 0, 7])))
+    for f, shape in enumerate(shapes):                           # every segment of every file
+        one = Coded([shape], [f], 3, 8, 64, 7, seed=13 + f, adversarial=True)
+        whole = (S(None),) * 3
+        got, st, _ = one.decode([whole])
+        assert st == [0] and np.array_equal(_bits(got), _bits(one.want([whole]))), f
 
 
 def test_direct_c_call_sets_bits_5_and_7_per_file():
