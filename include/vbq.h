@@ -1095,6 +1095,28 @@ int vbq_rans_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, int64_t lambd
  * every size >= 0, n_items <= 2^31 - 1, n_ch * n_idx addressable, no null pointer (d_canon, d_status and, with n_words == 0,
  * d_payload excepted).  n_files == 0 or n_items == 0 return VBQ_OK with no launch.
  * Added without an ABI version bump: nothing that existed before changed.
+ *
+ * vbq_rans_il_rates_files_u16   the parts of MANY compact files sized at SEVERAL lambdas in ONE launch -- rate control over a
+ *                               compact batch.  Every file is sized at every lambda.
+ *   d_idx      u16 [n_idx]: one plane of lambda_stride indices per lambda.  Symbol i of stream c of file f at lambda l is
+ *              d_idx[l * lambda_stride + idx_base_f + c * idx_stride_f + i].
+ *   d_files    int64 [n_files][8], the descriptor above, unchanged: idx_base, idx_stride, n, part_base and part are read;
+ *              `table` must be 0 -- the row block of lambda l is d_freq[l], not a table the file names, and any other value is
+ *              a bad descriptor (bit 7); the two word fields are not read.
+ *   d_items    int32 [n_items][2]: (file, part), any order, any count, file == -1 padding.  The same item serves every lambda.
+ *   d_freq     u16 [n_lambda][n_ch][T], every entry >= 1, every row summing to 2^15.   d_canon as above.
+ *   d_sizes    u32 [n_lambda][P_all]: entry [l][part_base_f + p] = exactly what vbq_rans_il_sizes_files_u16 gives for that file
+ *              alone on plane l with the row block d_freq[l].  Entries no item names are left untouched.  No atomics and no
+ *              totals: the result does not depend on scheduling; the host sums a file's parts.
+ *   d_status   u32 [n_files], may be NULL, OR-ed into; zero it first.  Bit 7 with the meanings above, but a file's symbols are
+ *              checked against its lambda's plane [0, lambda_stride), not against [0, n_idx): a file that fits the whole array
+ *              but crosses into the next lambda's plane is refused, at every lambda alike.  An unknown file id other than -1
+ *              sets bit 7 of word 0.
+ * The grid is (n_items, n_lambda), one wave (a workgroup of 64) per (item, lambda); the coder over a part is the one copy the
+ * other calls use.  Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): what the three calls above check (with one
+ * table), n_lambda in 1..65535, lambda_stride >= 0, n_lambda * lambda_stride <= n_idx (tested without forming the product),
+ * n_lambda * P_all addressable, no null pointer (d_canon and d_status excepted).  n_files == 0 or n_items == 0 return VBQ_OK
+ * with no launch.  Added without an ABI version bump: nothing that existed before changed.
  * ---------------------------------------------------------------------------------- */
 int vbq_rans_il_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, const int64_t *d_files, int32_t n_files,
                                 const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t N, const uint16_t *d_freq,
@@ -1108,6 +1130,10 @@ int vbq_rans_il_decode_files_u16(const uint16_t *d_payload, int64_t n_words, con
                                  int64_t P_all, const int64_t *d_files, int32_t n_files, const int32_t *d_items,
                                  int64_t n_items, int32_t n_ch, int32_t N, const uint16_t *d_freq, int32_t n_tables,
                                  uint16_t *d_idx, int64_t n_idx, uint32_t *d_status, void *stream);
+int vbq_rans_il_rates_files_u16(const uint16_t *d_idx, int64_t n_idx, int64_t lambda_stride, const int64_t *d_files,
+                                int32_t n_files, const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t N,
+                                const uint16_t *d_freq, int32_t n_lambda, const uint16_t *d_canon, uint32_t *d_sizes,
+                                int64_t P_all, uint32_t *d_status, void *stream);
 
 #ifdef __cplusplus
 }

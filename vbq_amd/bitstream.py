@@ -551,6 +551,17 @@ def compact_plan(rows, tables, parts, C, n_tables=None) -> CompactPlan:
                        np.ascontiguousarray(files, dtype=np.int64), np.ascontiguousarray(items, dtype=np.int32))
 
 
+def compact_file_words(sizes, plan: CompactPlan) -> np.ndarray:
+    """The words of every file of `plan` from the part sizes u32 [..., P_all] (vbq_rans_il_sizes_files_u16, or one row per
+    lambda from vbq_rans_il_rates_files_u16) -> int64 [..., F]: the sum of sizes[..., part_base_f : part_base_f + P_f]."""
+    sizes = np.asarray(sizes)
+    if sizes.ndim < 1 or sizes.shape[-1] != plan.P_all or sizes.dtype.kind not in "iu":
+        raise ValueError(f"sizes must be an integer array [..., {plan.P_all}], got {sizes.dtype} {sizes.shape}")
+    run = np.zeros(sizes.shape[:-1] + (plan.P_all + 1,), np.int64)
+    np.cumsum(sizes, axis=-1, dtype=np.int64, out=run[..., 1:])
+    return run[..., plan.part_base + plan.n_parts] - run[..., plan.part_base]
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # The lambda-map latent file: ONE latent tensor coded at up to four lambdas (ChannelwisePriorCDFQuantizer.
 # compress_latents_to_bytes_mapped).  A palette of P lambdas and a class per latent POSITION (the latent shape without its

@@ -93,6 +93,23 @@ k_il_encode_files(const uint16_t *__restrict__ idx, long n_idx, const int64_t *_
                            kWrite ? nullptr : sizes_out + it.slot, fc_l);
 }
 
+// One wave per (item, lambda): the parts of every file sized at SEVERAL lambdas in one launch (rate control over a compact
+// batch).  The index array holds one plane of lambda_stride indices per lambda and freq one row block per lambda; an item is
+// opened against its lambda's plane alone -- il_open_item with n_idx = lambda_stride and the one table 0 -- so a file that
+// crosses into the next plane is refused, at every lambda alike.  The coder over the part is il_encode_part<false>, as above:
+// sizes[l][slot] is what k_il_encode_files<false> gives on plane l with the row block freq[l].
+__global__ void __launch_bounds__(kLanes)
+k_il_rates_files(const uint16_t *__restrict__ idx, long lambda_stride, const int64_t *__restrict__ files, int n_files,
+                 const int32_t *__restrict__ items, long n_ch, int T, const uint16_t *__restrict__ freq,
+                 const uint16_t *__restrict__ canon, long P_all, uint32_t *__restrict__ sizes, uint32_t *__restrict__ status) {
+    __shared__ uint32_t fc_l[2048];
+    const long l = blockIdx.y;
+    IlItem it;
+    if (!il_open_item<false>(it, files, n_files, items, lambda_stride, n_ch, T, freq + l * n_ch * T, 1, P_all, 0L, status)) return;
+    il_encode_part<false>(idx + l * lambda_stride + it.idx_base, it.stride, it.n, it.a, it.b, T, it.freq, canon, nullptr, 0L, 0L,
+                          sizes + l * P_all + it.slot, fc_l);
+}
+
 // One wave per item, as k_il_decode reads a part: sizes, offsets and words are UNTRUSTED.  A part's [off, off + size) is
 // checked against the FILE's words, which the descriptor check placed inside [0, n_words); no read leaves it.
 __global__ void __launch_bounds__(kLanes)
@@ -118,7 +135,7 @@ k_il_decode_files(const uint16_t *__restrict__ payload, long n_words, const uint
     }
 }
 
-// What the three entry points check before any device work.
+// What the entry points check before any device work.
 int check_il_files(const char *who, int64_t n_idx, int32_t n_files, int64_t n_items, int32_t n_ch, int32_t N, int32_t n_tables,
                    int64_t P_all, int64_t n_words) {
     VBQ_REQUIRE(n_idx >= 0 && n_files >= 0 && n_files <= 65535 && n_items >= 0 && n_ch >= 1 && n_ch <= 65535 && N >= 1 &&
@@ -148,6 +165,29 @@ extern "C" int vbq_rans_il_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx,
                        table_size(N), d_freq, (int)n_tables, d_canon, nullptr, nullptr, (long)P_all, 0L, nullptr, d_sizes,
                        d_status);
     VBQ_CHECK_LAUNCH("rans_il_sizes_files");
+    return VBQ_OK;
+}
+
+extern "C" int vbq_rans_il_rates_files_u16(const uint16_t *d_idx, int64_t n_idx, int64_t lambda_stride, const int64_t *d_files,
+                                           int32_t n_files, const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t N,
+                                           const uint16_t *d_freq, int32_t n_lambda, const uint16_t *d_canon, uint32_t *d_sizes,
+                                           int64_t P_all, uint32_t *d_status, void *stream) {
+    using namespace vbq;
+    if (int r = check_il_files("vbq_rans_il_rates_files_u16", n_idx, n_files, n_items, n_ch, N, 1, P_all, 0)) return r;
+    VBQ_REQUIRE(n_lambda >= 1 && n_lambda <= 65535 && lambda_stride >= 0, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_il_rates_files_u16: bad sizes n_lambda=%d lambda_stride=%lld", n_lambda, (long long)lambda_stride);
+    VBQ_REQUIRE(lambda_stride <= n_idx / n_lambda, VBQ_ERR_INVALID_ARGUMENT,     // n_lambda * lambda_stride <= n_idx, no product
+                "vbq_rans_il_rates_files_u16: n_lambda=%d planes of lambda_stride=%lld indices do not fit in n_idx=%lld", n_lambda,
+                (long long)lambda_stride, (long long)n_idx);
+    VBQ_REQUIRE(P_all <= (INT64_MAX >> 2) / n_lambda, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_il_rates_files_u16: n_lambda=%d rows of P_all=%lld sizes are too many", n_lambda, (long long)P_all);
+    if (n_files == 0 || n_items == 0) return VBQ_OK;
+    VBQ_REQUIRE(d_idx && d_files && d_items && d_freq && d_sizes, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_rans_il_rates_files_u16: null pointer argument");
+    hipLaunchKernelGGL(k_il_rates_files, dim3((unsigned)n_items, (unsigned)n_lambda), dim3(kLanes), 0,
+                       reinterpret_cast<hipStream_t>(stream), d_idx, (long)lambda_stride, d_files, (int)n_files, d_items,
+                       (long)n_ch, table_size(N), d_freq, d_canon, (long)P_all, d_sizes, d_status);
+    VBQ_CHECK_LAUNCH("rans_il_rates_files");
     return VBQ_OK;
 }
 

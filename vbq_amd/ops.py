@@ -1060,6 +1060,30 @@ def rans_il_sizes_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Ten
     return sizes, status
 
 
+def rans_il_rates_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor, freq: torch.Tensor, P_all: int, *,
+                        lambda_stride: int, N: int = 10, canon: Optional[torch.Tensor] = None,
+                        sizes: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """vbq_rans_il_rates_files_u16 (include/vbq.h, "Compact batch"): the words of every listed part of every file at every
+    lambda in one launch.  idx u16 [n_idx], one plane of lambda_stride indices per lambda; files int64 [F, 8] (every `table`
+    0) and items int32 [n_items, 2] as rans_il_sizes_files takes them; freq u16 [L, C, T], one row block per lambda; canon u16
+    [C, T] or None.  Returns (sizes u32 [L, P_all], status u32 [F]): sizes[l] is what rans_il_sizes_files gives on plane l
+    with freq[l]; entries no item names keep what `sizes` held (a new one is zeroed).  `status` is OR-ed into: zeroed here
+    unless given."""
+    idx, files, items, freq, status, F, L, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    canon = _il_canon(canon, n_ch, N)
+    P_all, lambda_stride = int(P_all), int(lambda_stride)
+    if P_all < 0:
+        raise ValueError(f"P_all = {P_all} parts")
+    if sizes is None:
+        sizes = torch.zeros((L, P_all), dtype=torch.uint32, device=idx.device)
+    else:
+        sizes = _out(sizes, (L, P_all), torch.uint32, idx.device, "sizes")
+    check(_lib.lib().vbq_rans_il_rates_files_u16(_ptr(idx), idx.numel(), lambda_stride, _ptr(files), F, _ptr(items),
+                                                 items.shape[0], n_ch, int(N), _ptr(freq), L, _ptr(canon), _ptr(sizes), P_all,
+                                                 _ptr(status), _stream(idx)), "vbq_rans_il_rates_files_u16")
+    return sizes, status
+
+
 def rans_il_encode_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor, freq: torch.Tensor, sizes: torch.Tensor,
                          offsets: torch.Tensor, payload: torch.Tensor, *, N: int = 10, canon: Optional[torch.Tensor] = None,
                          status: Optional[torch.Tensor] = None):

@@ -1089,8 +1089,16 @@ class ChannelwisePriorCDFQuantizer:
         offsets by a device cumsum; ONE vbq_rans_il_encode_files_u16 into a payload buffer of the known upper bound,
         sum(C * B_f) + 128 * P_all words.  Two device-to-host copies: the part sizes and the status words, then the valid
         words.  The F files are assembled on the host (bitstream.CompactHeader / bitstream.write_compact)."""
-        from . import _lib
         pairs, shapes, keys, part = self._batch_file_inputs(latents, lambs, part, "interleaved")
+        return self._compact_batch(pairs, shapes, keys, part)
+
+    def _compact_batch(self, pairs, shapes, keys, part, part_sizes=None):
+        """The device side and the assembly of compress_latents_to_compact_batch, its inputs checked.  part_sizes: u32 [P_all]
+        on the host, the words of every part of every file, file-major as bitstream.compact_plan lays them, from a caller
+        that has sized the parts already (the budget calls: a row per file of the rate kernel's table).  Given, they ride in
+        the front region of the staging buffer in the place of the zeros, and there is no vbq_rans_il_sizes_files_u16 launch:
+        the encode kernel takes sizes and offsets as the caller's own and checks them for memory safety only."""
+        from . import _lib
         F, C, N = len(pairs), self.num_channels, self.max_bits_per_coord
         if F == 0:
             return []
@@ -1100,13 +1108,16 @@ class ChannelwisePriorCDFQuantizer:
         plan = bitstream.compact_plan(rows, [tables.index(k) for k in keys], part, C, len(tables))
         P = plan.P_all
         b = self._batch_stage(plan, shapes, keys, tables, digests, part, rows, pairs, 4 * P + 4 * F)
+        if part_sizes is not None:
+            b.host.numpy()[:4 * P] = np.ascontiguousarray(part_sizes, dtype=np.uint32).reshape(P).view(np.uint8)
         d_host, lat = self._encode_batch_upload(b)
         d_sizes, d_status = d_host[:4 * P].view(torch.uint32), d_host[4 * P:b.back].view(torch.uint32)
         d_files = d_host[b.cut[0]:b.cut[1]].view(torch.int64).view(F, bitstream.COMPACT_FIELDS)
         d_items = d_host[b.cut[1]:b.cut[2]].view(torch.int32).view(-1, 2)
         idx, canon = self._batch_solve(b, lat)
         freq = self._coder_stack(tables, None)._freq(idx.device).view(len(tables), C, -1)
-        ops.rans_il_sizes_files(idx, d_files, d_items, freq, P, N=N, canon=canon, sizes=d_sizes, status=d_status)
+        if part_sizes is None:
+            ops.rans_il_sizes_files(idx, d_files, d_items, freq, P, N=N, canon=canon, sizes=d_sizes, status=d_status)
         s64 = d_sizes.view(torch.int32).to(torch.int64)                                   # (a size is at most 2^24 + 128)
         payload = torch.empty(C * sum(rows) + bitstream.PART_STATE_WORDS * P, dtype=torch.uint16, device=idx.device)
         ops.rans_il_encode_files(idx, d_files, d_items, freq, d_sizes, torch.cumsum(s64, 0) - s64, payload, N=N, canon=canon,
@@ -1371,13 +1382,14 @@ class ChannelwisePriorCDFQuantizer:
                                                layout=layout, part=part)
 
     # ------------------------------------------------------------------ rate control for batches (include/vbq.h, "Batch sizes")
-    def _rate_batch_inputs(self, latents, lambs, segment):
+    def _rate_batch_inputs(self, latents, lambs, segment, layout="segments"):
         """Every check of the batch rate calls, before any device work: those of _batch_file_inputs for the files and of
-        _rate_keys for the candidate lambdas -> (pairs, shapes, keys, segment); no lambda is looked up when there is no file."""
+        _rate_keys for the candidate lambdas -> (pairs, shapes, keys, segment); no lambda is looked up when there is no file.
+        With layout "interleaved" `segment` is the part of the compact rate calls."""
         self._check_coder_bits()
-        bitstream.check_segment(segment)
+        _LAYOUTS[layout].check(segment)
         pairs = list(latents)
-        shapes = self._batch_file_shapes(pairs, segment)
+        shapes = self._batch_file_shapes(pairs, segment, layout)
         keys = self._rate_keys(lambs) if pairs else []
         return pairs, shapes, keys, int(segment)
 
@@ -1465,6 +1477,105 @@ class ChannelwisePriorCDFQuantizer:
     def compress_to_budget_batch(self, Xs, vae, max_bytes, lambs=None, segment=1024) -> list:
         """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_budget_batch."""
         return self.compress_latents_to_budget_batch([vae.encode(X) for X in Xs], max_bytes, lambs=lambs, segment=segment)
+
+    # ------------------------------------------------------------------ rate control for batches of compact files (include/vbq.h,
+    # "Compact batch", vbq_rans_il_rates_files_u16).  The four calls above, for the compact file: `part` in the place of
+    # `segment`.  A sizes pass of the interleaved coder costs about what the encode costs, so the writers hand the part sizes
+    # the rate kernel computed to _compact_batch and nothing is sized twice.  Nothing routes here implicitly.
+    def _coded_nbytes_compact_batch(self, pairs, shapes, keys, part):
+        """(nbytes int64 [F, L] with nbytes[f, l] = the exact compact file length of latent f at keys[l], the F latents as
+        pairs of device tensors shaped like the inputs, the part sizes u32 [L, P_all] on the host, the plan): ONE plan with
+        every file in table 0 (bitstream.compact_plan), ONE upload as the batch encoder's (zeroed sizes u32 [L, P_all] and
+        status u32 [F], descriptors, items and -- unless every input is a device tensor -- the latents), one
+        vbq_prep_planes_f32 of all R rows, then per chunk of max(1, RATE_SCRATCH_BYTES // (2 C R)) lambdas one solve into
+        [L_chunk, C, R] and ONE vbq_rans_il_rates_files_u16 with that chunk's tables, and one copy of the sizes and the
+        status words back."""
+        from . import _lib
+        F, L, C, N, dev = len(pairs), len(keys), self.num_channels, self.max_bits_per_coord, self.device
+        rows = [int(np.prod(sh[:-1], dtype=np.int64)) for sh in shapes]
+        plan = bitstream.compact_plan(rows, [0] * F, part, C, 1)
+        R, P = plan.n_rows, plan.P_all
+        b = self._batch_stage(plan, shapes, keys, None, None, part, rows, pairs, 4 * L * P + 4 * F)
+        d_host, lat = self._encode_batch_upload(b)
+        d_status = d_host[4 * L * P:b.back].view(torch.uint32)
+        d_files = d_host[b.cut[0]:b.cut[1]].view(torch.int64).view(F, bitstream.COMPACT_FIELDS)
+        d_items = d_host[b.cut[1]:b.cut[2]].view(torch.int32).view(-1, 2)
+        canon = None if self._strict else self._dev("canon_u16", lambda: torch.from_numpy(self._canon.astype(np.uint16)))
+        mu_cb, sg_cb = self._prep(lat[0], lat[1], spread="logvar")
+        chunk = max(1, RATE_SCRATCH_BYTES // (2 * C * R))
+        for l0 in range(0, L, chunk):
+            ks = keys[l0:l0 + chunk]
+            idx = self._solve_idx(mu_cb, sg_cb, ks, self._level_len_dev(ks))                   # [L_chunk, C, R]
+            freq = self._coder_stack(ks, None)._freq(dev).view(len(ks), C, -1)
+            ops.rans_il_rates_files(idx.view(-1), d_files, d_items, freq, P, lambda_stride=C * R, N=N, canon=canon,
+                                    sizes=d_host[4 * l0 * P:4 * (l0 + len(ks)) * P].view(torch.uint32).view(len(ks), P),
+                                    status=d_status)
+        h = d_host[:b.back].cpu().numpy()
+        sizes, status = h[:4 * L * P].view(np.uint32).reshape(L, P), h[4 * L * P:].view(np.uint32)
+        for f in np.flatnonzero(status):
+            raise _lib.VBQError(f"file {int(f)}: the compact rate kernel refused its descriptor (status {int(status[f])})")
+        words = bitstream.compact_file_words(sizes, plan)                                      # [L, F]
+        nbytes = np.array([[bitstream.compact_nbytes(shapes[f], C, part, int(words[l, f])) for l in range(L)]
+                           for f in range(F)], dtype=np.int64).reshape(F, L)
+        row_base = plan.row0                                      # (one table: its group starts at row 0)
+        on_dev = [tuple(lat[w, int(row_base[f]):int(row_base[f]) + rows[f]].view(shapes[f]) for w in (0, 1)) for f in range(F)]
+        return nbytes, on_dev, sizes, plan
+
+    @staticmethod
+    def _chosen_part_sizes(sizes, plan, cols):
+        """The part sizes u32 [P_all] of every file at its own lambda: file f's block from row cols[f] of sizes [L, P_all]."""
+        return sizes[np.repeat(np.asarray(cols, np.int64), plan.n_parts), np.arange(plan.P_all)]
+
+    def coded_nbytes_compact_batch(self, latents, lambs=None, part=1 << 17) -> list:
+        """[coded_nbytes(means_f, logvars_f, lambs, layout="interleaved", part=part) for f]: a list of F dicts {lambda: exact
+        compact file length}, the same keys in the same order, with ONE solve and ONE vbq_rans_il_rates_files_u16 launch for
+        all files and lambdas (per chunk of lambdas: see _coded_nbytes_compact_batch).  `latents` as
+        compress_latents_to_compact_batch takes them.  F == 0 returns [].  Errors before any device work: those of
+        compress_latents_to_compact_batch for the files (ValueError naming the file's index; `part` by bitstream.check_part),
+        KeyError for a lambda without a model."""
+        pairs, shapes, keys, part = self._rate_batch_inputs(latents, lambs, part, "interleaved")
+        if not pairs:
+            return []
+        nbytes = self._coded_nbytes_compact_batch(pairs, shapes, keys, part)[0]
+        return [{k: int(b) for k, b in zip(keys, row)} for row in nbytes]
+
+    def compress_latents_to_compact_budget_batch(self, latents, max_bytes, lambs=None, part=1 << 17) -> list:
+        """[compress_latents_to_budget(means_f, logvars_f, max_bytes[f], lambs, layout="interleaved", part=part) for f], byte
+        for byte: every file at the numerically smallest lambda of `lambs` whose exact length is within the file's budget.
+        `max_bytes`: one integer >= 1 for all files or a sequence of F.  The lengths come from
+        coded_nbytes_compact_batch's one rate launch; the files from the compact batch writer at the chosen lambdas on the
+        latents already on the device, with the part sizes the rate launch computed at those lambdas: its solve covers only
+        the chosen lambdas and it runs no sizes launch.  ValueError (bitstream.smallest_rates_within) naming the first file
+        that no lambda fits, before anything is encoded.  F == 0 returns []."""
+        budgets = bitstream.check_budgets(max_bytes)
+        pairs, shapes, keys, part = self._rate_batch_inputs(latents, lambs, part, "interleaved")
+        if budgets is not None and len(budgets) != len(pairs):
+            raise ValueError(f"{len(budgets)} budgets for {len(pairs)} files")
+        if not pairs:
+            return []
+        nbytes, on_dev, sizes, plan = self._coded_nbytes_compact_batch(pairs, shapes, keys, part)
+        order = sorted(range(len(keys)), key=lambda j: float(keys[j]))          # columns in ascending order of lambda
+        cols = bitstream.smallest_rates_within(nbytes[:, order], max_bytes if budgets is None else budgets,
+                                               rates=[float(keys[j]) for j in order])
+        chosen = [order[c] for c in cols]
+        return self._compact_batch(on_dev, shapes, [keys[j] for j in chosen], part, self._chosen_part_sizes(sizes, plan, chosen))
+
+    def compress_latents_to_compact_total_budget(self, latents, max_total_bytes, lambs=None, part=1 << 17):
+        """(lamb, files): ONE lambda for all files -- the numerically smallest of `lambs` at which the F files together take
+        at most max_total_bytes (bitstream.smallest_rate_within on the column sums of the length table) -- and
+        files == compress_latents_to_compact_batch(latents, lamb, part), written without a second sizes launch.  ValueError
+        for no files, or naming the smallest achievable total and its lambda when nothing fits."""
+        bitstream.check_budget(max_total_bytes)
+        pairs, shapes, keys, part = self._rate_batch_inputs(latents, lambs, part, "interleaved")
+        if not pairs:
+            raise ValueError("no files: a total budget needs at least one")
+        nbytes, on_dev, sizes, plan = self._coded_nbytes_compact_batch(pairs, shapes, keys, part)
+        lamb = bitstream.smallest_rate_within(dict(zip(keys, nbytes.sum(axis=0))), max_total_bytes, "lambda")
+        return lamb, self._compact_batch(on_dev, shapes, [lamb] * len(pairs), part, sizes[keys.index(lamb)])
+
+    def compress_to_compact_budget_batch(self, Xs, vae, max_bytes, lambs=None, part=1 << 17) -> list:
+        """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_compact_budget_batch."""
+        return self.compress_latents_to_compact_budget_batch([vae.encode(X) for X in Xs], max_bytes, lambs=lambs, part=part)
 
     def decompress(self, data, vae, clip=True, return_np=True):
         """decompress_latents, then `vae.decode` and the clip to [0, 1] of compress (quantizer.py:251-253).  The decoder
