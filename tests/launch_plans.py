@@ -9,6 +9,7 @@ shapes have to move.
     *_grid          vbq_moments_f32, vbq_rd_sums_u16, vbq_index_max_u16, vbq_check_inputs_f32
                                                                         vbq_amd/csrc/vbq_reduce.hip
                     launch_hist (k_hist_tiled)                          vbq_amd/csrc/vbq_hist.hip
+    solve_kernel    launch_quantize: which solve kernel a lambda chunk takes     vbq_amd/csrc/vbq_quantize.hip, vbq_quantize_fast.hip
 """
 from collections import namedtuple
 
@@ -40,6 +41,16 @@ HIST_TILED_WGS = 512             # gx = 512 / (groups * L) + 1
 HIST_TILED_ROWS = 64             # rows per pass of a k_hist_tiled workgroup (1024 threads / 16 channels)
 HIST_TILE_CH = 16                # kTileChannels
 THREADS = 256                    # workgroup size of the reductions and scans
+# ---- vbq_common.h, vbq_quantize.hip, vbq_quantize_fast.hip: the solve
+SOLVE_DEPTHS = (12, 11, 10, 9, 8, 7, 6, 5, 4)      # VBQ_FOR_EACH_N: the bit depths the solve kernels are built for
+MAX_LAMBDA_CHUNK = 32            # kMaxLambdaChunk: lambdas per launch
+PRUNED_MAX_L = 2                 # kPrunedMaxL: lambdas up to which the pruned descent K1p takes an indices-only call
+PRUNED_BUILT_L = (1, 2, 3, 4)    # VBQ_PRUNED_CASE: the K1p instances that are compiled (3 and 4 are not reached)
+HULL_IDX_MIN_L = 16              # `if (L < 16) return 1;` of launch_quant_hull_idx10: K1e from this many lambdas
+FAST_LAMBDA_RANGE = (1.9e-12, 1.8e19)              # fast_ok: every lambda of the chunk inside, as doubles
+SWEEP_KEY_SHIFT = 16             # build_sweep_table<16>: a bucket is one value of (f32 bits >> 16)
+SWEEP_KEYS = 2048                # kHullKeys: buckets, 16 octaves of 128
+TILED_MAX_N = 10                 # `else if constexpr (N > 10)`: channel-last with n_ch > 1 is refused above
 
 
 def cdiv(a, b):
@@ -177,3 +188,67 @@ def hist_tiled_grid(rows, n_ch, L):
     iters = cdiv(rows, HIST_TILED_ROWS)
     gx = max(1, min(HIST_TILED_WGS // (groups * L) + 1, iters))
     return gx, groups, cdiv(iters, gx)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the solve
+def sweep_eligible(lam):
+    """build_sweep_table<16> on the chunk's lambdas as f32 (the threshold kernels K1t and K1e): at most 32 values inside the fast
+    range, no two in one bucket of 7 mantissa bits (equal ones among them), no more octaves than there are buckets."""
+    import struct
+    if not 1 <= len(lam) <= MAX_LAMBDA_CHUNK:
+        return False
+    v = sorted(struct.unpack("f", struct.pack("f", x))[0] for x in lam)
+    lo, hi = (struct.unpack("f", struct.pack("f", x))[0] for x in FAST_LAMBDA_RANGE)
+    if not all(lo <= x <= hi for x in v):
+        return False
+    keys = [struct.unpack("I", struct.pack("f", x))[0] >> SWEEP_KEY_SHIFT for x in v]
+    if any(b <= a for a, b in zip(keys, keys[1:])):
+        return False
+    return keys[-1] - keys[0] + 2 <= SWEEP_KEYS
+
+
+def solve_kernel(N, lam, layout, n_ch, mode="f32", level_len=False, want_idx=True, want_zhat=False, want_bits=False,
+                 counting=False, workgroups_per_cu=0, elements=0):
+    """launch_quantize for ONE chunk of lambdas (`lam`, at most 32 doubles) -> the kernel it launches:
+        "tiled"     k_quant_tiled         channel-last input with n_ch > 1 (the literal scan)
+        "flat"      k_quant_flat          planes / one code book, the literal scan
+        "K1t"       k_level_counts_hull   counting, raw lengths, N = 10, an eligible sweep
+        "K1e"       k_quant_hull_idx      indices only, raw lengths, N = 10, 16 or more lambdas, an eligible sweep
+        "K1p<LL>"   k_quant_pruned        indices only, LL <= kPrunedMaxL lambdas, workgroups_per_cu == 0; any lambda
+        "K1<MODE>"  k_quant_fast          MODE 0 indices, 1 with Z_hat / lengths, 2 counting; every lambda in the fast range
+        "refused"   VBQ_ERR_UNSUPPORTED
+    layout: "bc", "cb" or "bc->cb"; level_len: a caller length table is given; elements: rows x n_ch (K1e's 4 GB plane limit).
+    counting: vbq_level_counts_f32 (no per-element output, f32 mode)."""
+    assert N in SOLVE_DEPTHS and 1 <= len(lam) <= MAX_LAMBDA_CHUNK and layout in ("bc", "cb", "bc->cb") and mode in ("f32", "f64")
+    L = len(lam)
+    if counting:
+        want_idx = want_zhat = want_bits = False
+        if n_ch > 1 and layout == "bc":
+            return "refused"
+    if mode == "f64" and level_len:
+        return "refused"
+    bc_to_cb = layout == "bc->cb" and n_ch > 1
+    flat = n_ch == 1 or layout == "cb" or bc_to_cb
+    if not flat:
+        return "refused" if N > TILED_MAX_N else "tiled"
+    f32 = mode == "f32"
+    fast_ok = f32 and all(FAST_LAMBDA_RANGE[0] <= x <= FAST_LAMBDA_RANGE[1] for x in lam)
+    idx_only = not counting and want_idx and not want_zhat and not want_bits
+    if f32 and N == 10 and fast_ok and not level_len:
+        if counting and sweep_eligible(lam):
+            return "K1t"
+        if idx_only and L >= HULL_IDX_MIN_L and 2 * elements <= 0xffffffff and sweep_eligible(lam):
+            return "K1e"
+    if f32 and idx_only and workgroups_per_cu == 0 and L <= PRUNED_MAX_L:
+        return f"K1p<{L}>"
+    if fast_ok:
+        return "K1<2>" if counting else ("K1<1>" if want_zhat or want_bits else "K1<0>")
+    if counting or bc_to_cb:
+        return "refused"
+    return "flat"
+
+
+def solve_kernels(N, lam, layout, n_ch, **kw):
+    """solve_kernel for every chunk of a sweep of any length (the l0 loop of launch_quantize); a per-lambda flag list
+    level_len is not needed: the table is given for all chunks or for none."""
+    return [solve_kernel(N, list(lam[l0:l0 + MAX_LAMBDA_CHUNK]), layout, n_ch, **kw) for l0 in range(0, len(lam), MAX_LAMBDA_CHUNK)]

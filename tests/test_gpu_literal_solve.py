@@ -30,6 +30,7 @@ from oracle import c_oracle as CO
 from oracle import rd_f64 as R
 from oracle import vbq_oracle as O
 from oracle.mode_split import SPLIT_LAMS, mode_splitting_set
+from solve_cases import latents            # the edge data: hits, nextafter neighbours, mid-points, both rims, extreme sigmas
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -60,33 +61,6 @@ def tables(rng, C, Nb):
     orc = O.ChannelwiseOracle(C, Nb)
     orc.build_code_points(O.factored_gaussian_icdf(rng.normal(0, 0.2, C), np.exp(rng.uniform(-1, 1, C))))
     return orc.all_code_points
-
-
-def latents(rng, rows, C, tab):
-    """mu, sigma [rows, C] with exact code-point hits, nextafter neighbours, midpoints of adjacent points (L/R ties at
-    lambda = 0), points beyond both ends (the deepest level has no edge padding), sigma at 1e-4 and 10 and the
-    all-ones mantissa mixed in."""
-    srt = np.sort(tab, axis=1)
-    T = srt.shape[1]
-    scale = np.abs(srt[:, -1] - srt[:, 0]) / 6
-    mu = (scale * rng.normal(0, 1.0, (rows, C))).astype(F32)
-    sg = np.clip(np.exp(rng.normal(-2.5, 1.0, (rows, C))), 1e-4, 10).astype(F32)
-    k = rng.integers(0, T - 1, (rows, C))
-    pick = np.take_along_axis(srt.T, k, axis=0)
-    nxt = np.take_along_axis(srt.T, k + 1, axis=0)
-    kind = rng.integers(0, 12, (rows, C))
-    mu = np.where(kind == 0, pick, mu)
-    mu = np.where(kind == 1, np.nextafter(pick, F32(np.inf)), mu)
-    mu = np.where(kind == 2, np.nextafter(pick, F32(-np.inf)), mu)
-    mu = np.where(kind == 3, F32(0.5) * (pick + nxt), mu)
-    mu = np.where(kind == 4, srt[:, -1] + np.abs(mu), mu)
-    mu = np.where(kind == 5, srt[:, 0] - np.abs(mu), mu)
-    mu = np.where(kind == 6, np.nextafter(srt[:, -1], F32(np.inf))[None], mu)
-    sg = np.where(kind == 7, F32(1e-4), sg)
-    sg = np.where(kind == 8, F32(10.0), sg)
-    sg = np.where(kind == 9, F32(2.0) - F32(2.0 ** -23), sg)
-    mu = np.where(kind == 10, F32(1.0) - F32(2.0 ** -24), mu)        # all-ones mantissa
-    return mu.astype(F32), sg.astype(F32)
 
 
 def solve(ops, mu, sg, tab, lam, Nb, layout, mode, want_zhat=True, want_bits=True, level_len=None, view=False, **kw):

@@ -162,14 +162,26 @@ def test_quantize_duplicate_code_points(ops):
 
 @pytest.mark.parametrize("Nbits", [4, 5, 6, 7, 8, 9])
 def test_quantize_other_bit_depths(ops, Nbits):
+    """Eight lambdas inside the fast range, indices only.  Channel-last with two channels takes k_quant_tiled<N, float>, the
+    literal scan; the same data as planes (layout "cb") and one channel of it as one code book take k_quant_fast<N, 0>
+    (tests/launch_plans.solve_kernel states the dispatch)."""
+    import launch_plans as LP
     rng = np.random.default_rng(Nbits)
     orc = O.ChannelwiseOracle(2, Nbits)
     orc.build_code_points(O.factored_gaussian_icdf(np.zeros(2), np.array([1.0, 0.5])))
     mu = rng.normal(0, 1, (500, 2)).astype(np.float32)
     sg = np.exp(rng.normal(-2, 0.7, (500, 2))).astype(np.float32)
-    want = CO.quantize(mu, sg, orc.all_code_points, LAM32[::4], N=Nbits)
-    got = ops.quantize(dev(mu), dev(sg), dev(orc.all_code_points), LAM32[::4], N=Nbits)
+    lam = LAM32[::4]
+    want = CO.quantize(mu, sg, orc.all_code_points, lam, N=Nbits)
+    assert LP.solve_kernel(Nbits, lam, "bc", 2) == "tiled"
+    got = ops.quantize(dev(mu), dev(sg), dev(orc.all_code_points), lam, N=Nbits)
     assert np.array_equal(host(got), want)
+    assert LP.solve_kernel(Nbits, lam, "cb", 2) == "K1<0>"
+    got = ops.quantize(dev(mu.T), dev(sg.T), dev(orc.all_code_points), lam, N=Nbits, layout="cb")
+    assert np.array_equal(host(got).transpose(0, 2, 1), want)
+    assert LP.solve_kernel(Nbits, lam, "bc", 1) == "K1<0>"
+    got = ops.quantize(dev(mu[:, 1]), dev(sg[:, 1]), dev(orc.all_code_points[1:2]), lam, N=Nbits)
+    assert np.array_equal(host(got), want[:, :, 1])
 
 
 def test_notebook_vs_oracle(ops):

@@ -84,6 +84,91 @@ def test_reduction_caps_match_the_source():
     assert int(_one(r"constexpr int kTileChannels = (\d+);", _src("vbq_common.h") + s, "kTileChannels")) == LP.HIST_TILE_CH
 
 
+def test_solve_constants_match_the_source():
+    c, q, f = _src("vbq_common.h"), _src("vbq_quantize.hip"), _src("vbq_quantize_fast.hip")
+    depths = _one(r"#else\s*#define VBQ_FOR_EACH_N\(X\) ((?:X\(\d+\) ?)+)\s*#endif", c, "VBQ_FOR_EACH_N")
+    assert tuple(int(v) for v in re.findall(r"X\((\d+)\)", depths)) == LP.SOLVE_DEPTHS
+    assert int(_one(r"constexpr int kMaxLambdaChunk = (\d+);", c, "kMaxLambdaChunk")) == LP.MAX_LAMBDA_CHUNK
+    assert int(_one(r"constexpr int kPrunedMaxL = (\d+);", f, "kPrunedMaxL")) == LP.PRUNED_MAX_L
+    built = _one(r"switch \(L\) \{\s*((?:VBQ_PRUNED_CASE\(\d+\) ?)+)\s*default: return 1;", f, "VBQ_PRUNED_CASE")
+    assert tuple(int(v) for v in re.findall(r"\((\d+)\)", built)) == LP.PRUNED_BUILT_L and LP.PRUNED_MAX_L <= max(LP.PRUNED_BUILT_L)
+    assert int(_one(r"if \(L < (\d+)\) return 1; +// below that the thresholds cost more", f, "K1e's shortest sweep")) == LP.HULL_IDX_MIN_L
+    lo, hi = _one(r"fast_ok = fast_ok && \(lc\.lam\[i\] >= ([0-9.e+-]+) && lc\.lam\[i\] <= ([0-9.e+-]+)\);", q, "fast_ok")
+    assert (float(lo), float(hi)) == LP.FAST_LAMBDA_RANGE
+    shift, lo, hi = _one(r"return build_sweep_table<(\d+)>\(v, L, ([0-9.e+-]+)f, ([0-9.e+-]+)f, sw\);", f, "build_lambda_sweep")
+    assert int(shift) == LP.SWEEP_KEY_SHIFT and (float(lo), float(hi)) == LP.FAST_LAMBDA_RANGE
+    assert int(_one(r"constexpr int kHullKeys = (\d+);", f, "kHullKeys")) == LP.SWEEP_KEYS
+    assert int(_one(r"\} else if constexpr \(N > (\d+)\) \{\s*set_error\(\"vbq_quantize_f32: N=%d is built for channel-major", q,
+                    "tiled limit")) == LP.TILED_MAX_N
+    # the order of the dispatch and its conditions: the lines solve_kernel restates are still there, in this order
+    marks = [r"const bool flat = \(n_ch == 1\) \|\| \(layout == VBQ_LAYOUT_CB\) \|\| bc_to_cb;",
+             r"if constexpr \(sizeof\(PenT\) == 4 && N == 10\) \{\s*// first entropy-model pass[^\n]*\s*if \(fast_ok && lc_out && !len_c\) \{",
+             r"if \(fast_ok && !lc_out && !len_c && oi && !oz && !ob\) \{\s*const int r = launch_quant_hull_idx10",
+             r"if \(!lc_out && oi && !oz && !ob && wg_per_cu == 0\) \{\s*const int r = launch_quant_pruned<N>",
+             r"if \(fast_ok\) \{\s*const int r = launch_quant_fast<N>",
+             r"hipLaunchKernelGGL\(\(k_quant_flat<N, PenT>\)"]
+    at = [re.search(m, q) for m in marks]
+    assert all(at), [m for m, a in zip(marks, at) if not a]
+    assert [a.start() for a in at] == sorted(a.start() for a in at)
+    _one(r"if \(L < 1 \|\| L > kPrunedMaxL\) return 1;", f, "K1p's limit")
+    _one(r"if \(2 \* \(uint64_t\)E > 0xffffffffull\) return 1;", f, "K1e's plane limit")
+    _one(r"if \(level_counts\)\s*hipLaunchKernelGGL\(\(k_quant_fast<N, 2>\)", f, "K1 mode 2")
+    _one(r"else if \(out_zhat \|\| out_bits\)\s*hipLaunchKernelGGL\(\(k_quant_fast<N, 1>\)", f, "K1 mode 1")
+
+
+def test_solve_kernel_routes():
+    """The routes the docstring of tests/test_gpu_literal_solve.py states, and the ones tests/test_gpu_fast_solve_variants.py
+    is built on."""
+    K = LP.solve_kernel
+    lam6 = [0.0, 2.0 ** -8 * 2 ** 0.5, 0.1, 1.0, 37.0, 300.0]
+    inside = [0.01, 0.1, 1.0, 4.0, 37.0]
+    for N in LP.SOLVE_DEPTHS:
+        # test_gpu_literal_solve.py: "k_quant_tiled<N, double / float>  layout bc, n_ch > 1.  N <= 10."
+        for mode in ("f32", "f64"):
+            assert K(N, lam6, "bc", 3, mode=mode, want_bits=True) == ("tiled" if N <= 10 else "refused")
+            # "k_quant_flat<N, double>  mode f64, layout cb or n_ch == 1"; f32 with lambda = 0 and L >= 5 likewise
+            assert K(N, lam6, "cb", 3, mode=mode, want_zhat=True, want_bits=True) == "flat"
+            assert K(N, lam6, "bc", 1, mode=mode) == "flat" and K(N, lam6, "cb", 3, mode=mode) == "flat"
+        assert K(N, inside, "cb", 3, mode="f64") == "flat"
+        # "... and not the pruned descent: L >= 5, Z_hat / bits wanted, or workgroups_per_cu != 0"
+        for L in (1, 2, 3, 4):
+            out = [0.0, 1e25, 1e-13, 0.2][:L]
+            assert K(N, out, "cb", 2, want_zhat=True) == "flat" and K(N, out, "cb", 2, want_bits=True) == "flat"
+            assert K(N, out, "cb", 2, workgroups_per_cu=4) == "flat" and K(N, out, "bc", 1, workgroups_per_cu=4) == "flat"
+            assert K(N, out, "cb", 2) == (f"K1p<{L}>" if L <= LP.PRUNED_MAX_L else "flat")
+            assert K(N, out, "bc->cb", 2) == (f"K1p<{L}>" if L <= LP.PRUNED_MAX_L else "refused")
+            ins = inside[:L]
+            assert K(N, ins, "cb", 2) == K(N, ins, "bc", 1) == K(N, ins, "cb", 2, level_len=True) == (f"K1p<{L}>" if L <= 2 else "K1<0>")
+            assert K(N, ins, "cb", 2, workgroups_per_cu=4) == "K1<0>"
+            assert K(N, ins, "cb", 2, want_bits=True) == K(N, ins, "bc->cb", 2, want_zhat=True, level_len=True) == "K1<1>"
+        # the fast kernels
+        assert K(N, inside, "cb", 2) == K(N, inside, "bc->cb", 2) == K(N, inside, "bc", 1) == "K1<0>"
+        assert K(N, inside, "bc->cb", 1) == "K1<0>"                      # one channel: the layout does not matter
+        assert K(N, inside, "cb", 2, counting=True, level_len=True) == "K1<2>"
+        assert K(N, inside, "cb", 2, counting=True) == ("K1t" if N == 10 else "K1<2>")
+        assert K(N, inside, "bc", 2, counting=True) == "refused" and K(N, lam6, "cb", 2, counting=True) == "refused"
+        assert K(N, lam6, "bc->cb", 2) == "refused" and K(N, inside, "cb", 2, mode="f64", level_len=True) == "refused"
+        sweep32 = [2.0 ** (-8 + 0.5 * i) for i in range(32)]
+        for L in (15, 16, 32):
+            assert K(N, sweep32[:L], "cb", 2, elements=4002) == ("K1e" if N == 10 and L >= 16 else "K1<0>")
+            assert K(N, sweep32[:L], "cb", 2, level_len=True) == "K1<0>" and K(N, sweep32[:L], "cb", 2, want_zhat=True) == "K1<1>"
+        assert K(N, sweep32[:16], "cb", 2, elements=1 << 31) == "K1<0>"
+        assert LP.solve_kernels(N, sweep32 + [1.0], "cb", 2) == ["K1e" if N == 10 else "K1<0>", "K1p<1>"]
+        assert LP.solve_kernels(N, sweep32 + [1.0], "cb", 2, level_len=True) == ["K1<0>", "K1p<1>"]
+        assert LP.solve_kernels(N, sweep32 + [1.0], "cb", 2, want_zhat=True) == ["K1<1>", "K1<1>"]
+        # per chunk: the four lambdas after the first 32 hold no zero and go fast
+        assert LP.solve_kernels(N, lam6 * 6, "cb", 2, want_bits=True) == ["flat", "K1<1>"]
+        assert LP.solve_kernels(N, lam6 * 6 + [0.0], "cb", 2, want_bits=True) == ["flat", "flat"]
+    # sweeps the threshold kernels hand on (test_threshold_kernel_on_ties_and_odd_sweeps): repeated values, one bucket, octaves
+    assert LP.sweep_eligible([0.37]) and LP.sweep_eligible([2.0 ** k for k in range(-7, 9)])      # 15 octaves: 1922 buckets
+    assert not LP.sweep_eligible([2.0 ** k for k in range(-7, 10)])                              # 16 octaves: 2050
+    assert not LP.sweep_eligible([1.0, 1.0, 2.0]) and not LP.sweep_eligible([1.0, 1.0 + 2.0 ** -9, 4.0])
+    assert not LP.sweep_eligible([1e-9, 1.0, 1e9]) and LP.sweep_eligible([1.0, 1.0 + 2.0 ** -7, 4.0])
+    assert K(10, [1.0, 1.0, 2.0], "bc", 1, counting=True) == "K1<2>"
+    # the eight-lambda sweeps of solve_cases cycled to 33: repeats, so N = 10 stays on K1 for raw lengths as well
+    assert LP.solve_kernels(10, [1.0, 8.0] * 16 + [1.0], "cb", 2, elements=4002) == ["K1<0>", "K1p<1>"]
+
+
 # ------------------------------------------------------------------------------------------------ worked numbers, 256 CUs
 def test_lookup_plan_worked_numbers():
     p = LP.lookup_plan(8, 256, 20740, 10, CUS)
