@@ -959,6 +959,43 @@ int vbq_rans_decode_window_f32(const uint16_t *d_payload, int64_t n_words, const
                                int64_t w2, float *d_out, uint32_t *d_status, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Mapped window decode: the window decode for lambda-map files (vbq_amd/bitstream.py, magic "VBQm") and files in segments
+ * at one lambda ("VBQb") together -- the class-mapped twin of vbq_rans_decode_window_f32, with the same geometry and work
+ * split (blocks of 64 listed segments x selected channel x file, one lane per listed segment, decoded in full).  Every
+ * argument it shares with that call means what it means there; what differs:
+ *   d_files    int64 [n_files][16], per file: seg_base, n, D1, D2, a0, a1, a2 as there; P, the classes of the file's palette
+ *              (1..4, at most max_classes); table[0..3], the blocks of d_freq of classes 0..3 (those at p >= P are unused,
+ *              = 0); cls_base, the byte offset of the file's class block inside d_cls, or -1: every position has class 0;
+ *              three reserved fields, = 0.  Symbol i of channel c pops from the row d_freq[table[class of position i]][c].
+ *   d_cls      u8 [cls_bytes], aligned to 8 bytes: the class blocks as the files store them -- 2 bits per position, position
+ *              b of a file in byte cls_base + b / 4 at bits 2 (b % 4), a block 8 ceil(n / 32) bytes long.  Nothing is
+ *              unpacked: a lane reads one aligned 64-bit word per 32 symbols, the first one from the bit its segment starts
+ *              at.  May be NULL when cls_bytes == 0 (every file then has cls_base == -1).
+ *   max_classes  the largest P of the launch, 1..4: it sizes the tables in LDS, 8192 + 8196 max_classes bytes per
+ *              workgroup (per class c[0..T] and the 2048 search starts; the code points once, they do not depend on lambda).
+ *              A file with a smaller P stages only its own tables.
+ *   d_status   u32 [n_files]: bits 0 - 3 and bit 5 (32) as vbq_rans_decode_window_f32; bit 6 (64) a class >= P met while
+ *              decoding -- it is compared with P before it indexes anything, and the segment writes zeros from there on, as a
+ *              starved one does; bit 7 (128) as there, and also P outside [1, max_classes], a table[p], p < P, outside
+ *              [0, n_tables), or a cls_base that is neither -1 nor a multiple of 8 with cls_base >= 0 and cls_base +
+ *              8 ceil(n / 32) <= cls_bytes: nothing of that file is written.  The values of a file whose status is non-zero
+ *              are unspecified; every store still lies inside that file's box.
+ * A file with P == 1 and cls_base == -1 decodes bit for bit as vbq_rans_decode_window_f32 does with table = table[0].
+ * Payload, sizes, offsets, descriptors, id lists and class blocks are UNTRUSTED: the rules of vbq_rans_decode_window_f32, and
+ * no read leaves [0, cls_bytes) of d_cls.
+ * Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): what vbq_rans_decode_window_f32 checks, max_classes in 1..4,
+ * cls_bytes a multiple of 8 and >= 0; then, unless there is nothing to launch, d_cls non-null when cls_bytes > 0 and aligned
+ * to 8 bytes.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_map_decode_window_f32(const uint16_t *d_payload, int64_t n_words, const uint16_t *d_sizes, const int64_t *d_offsets,
+                                   int64_t M, const int64_t *d_files, int32_t n_files, const int32_t *d_segs, int32_t n_sel,
+                                   const int32_t *d_channels, int32_t n_ch_sel, int32_t n_ch, int32_t seg, int32_t N,
+                                   const uint16_t *d_freq, int32_t n_tables, const float *d_values, const uint8_t *d_cls,
+                                   int64_t cls_bytes, int32_t max_classes, int64_t w0, int64_t w1, int64_t w2, float *d_out,
+                                   uint32_t *d_status, void *stream);
+
+/* ----------------------------------------------------------------------------------
  * Batch encode: every segment of MANY latent files in segments (vbq_amd/bitstream.py, magic "VBQb") in ONE launch -- the
  * writer's counterpart of the window decode.  vbq_rans_encode_u16 gives a workgroup 64 consecutive segments of one stream;
  * a small file has a few segments per channel and leaves most lanes idle.  Here the caller lists the work as items

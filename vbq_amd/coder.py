@@ -112,7 +112,7 @@ def ideal_bits(counts, freq, prob_bits: int = PROB_BITS) -> float:
 
 def _raise_status(st: int):
     """The OR-ed status word of vbq_rans_decode_u16 / vbq_rans_unpack_u16 / vbq_rans_map_decode_u16 /
-    vbq_rans_decode_window_f32 / vbq_rans_il_decode_u16 / vbq_rans_il_decode_files_u16 (a part counts as a segment in the
+    vbq_rans_decode_window_f32 / vbq_rans_map_decode_window_f32 / vbq_rans_il_decode_u16 / vbq_rans_il_decode_files_u16 (a part counts as a segment in the
     messages) -> VBQError (nothing when 0)."""
     if st:
         what = [m for b, m in ((1, "segment size out of range"), (2, "segment ran out of words"),

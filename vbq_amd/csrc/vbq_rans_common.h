@@ -120,6 +120,12 @@ __device__ __forceinline__ uint16_t bucket_start(const uint16_t *c_l, int T, uns
     return (uint16_t)lo;
 }
 
+// A decoder with a table per class (vbq_rans_map.hip, vbq_rans_map_window.hip) keeps, per class in use, c[0..T] and start[] in LDS.
+constexpr int kMapMaxClasses = 4;
+constexpr int kMapT = 2048;                                      // table stride in LDS (T <= 2047)
+constexpr int kMapCStride = kMapT + 2;                           // c[0..T], an even count of u16
+constexpr int kMapBuckets = (1 << kPB) / 16;
+
 // Reading one segment, whose words are UNTRUSTED: words[0 .. k - 3] renormalisation words in emission order, words[k - 2],
 // words[k - 1] the final state (low, high half).  The decoder starts from that state and consumes the words backwards.  What a
 // kernel decodes after a starved segment, and which flag it keeps, is the kernel's own business.

@@ -15,10 +15,6 @@ namespace vbq {
 namespace {
 
 constexpr int kMapThreads = 64;
-constexpr int kMapMaxClasses = 4;
-constexpr int kMapT = 2048;                                      // table stride in LDS (T <= 2047)
-constexpr int kMapCStride = kMapT + 2;                           // c[0..T], an even count of u16
-constexpr int kMapBuckets = (1 << kPB) / 16;
 
 struct MapEncodeArgs {
     const uint16_t *idx;                                         // [n_planes][S][n]

@@ -9,12 +9,11 @@
 // in the file's three-level geometry by increment and carry and stores the symbols that fall inside the box.  The 64 lanes of a
 // workgroup belong to one (file, channel) and share its tables in LDS: fc, c, start and the values, 24 KB.  Table staging, the
 // bucket table and the rules for untrusted words are vbq_rans_common.h's.
-#include "vbq_rans_common.h"
+#include "vbq_rans_window_common.h"
 
 namespace vbq {
 namespace {
 
-constexpr int kWinThreads = 64;                                  // one wave: stage_segment_table scans with wave shuffles alone
 constexpr int kFileFields = 8;                                   // seg_base, n, D1, D2, a0, a1, a2, table
 
 // Untrusted: payload, sizes, offsets (as k_rans_decode_values) and, defensively, the descriptors and the two id lists -- every
@@ -128,28 +127,15 @@ extern "C" int vbq_rans_decode_window_f32(const uint16_t *d_payload, int64_t n_w
                                           const float *d_values, int64_t w0, int64_t w1, int64_t w2, float *d_out,
                                           uint32_t *d_status, void *stream) {
     using namespace vbq;
-    VBQ_REQUIRE(n_words >= 0 && M >= 0 && n_files >= 0 && n_files <= 65535 && n_sel >= 0 && n_ch_sel >= 0 && n_ch_sel <= 65535 &&
-                    n_ch >= 1 && seg >= 1 && seg <= 65533 && N >= 1 && N <= 10 && n_tables >= 1 && w0 >= 0 && w1 >= 0 && w2 >= 0,
-                VBQ_ERR_INVALID_ARGUMENT,
-                "vbq_rans_decode_window_f32: bad sizes n_words=%lld M=%lld n_files=%d n_sel=%d n_ch_sel=%d n_ch=%d seg=%d N=%d "
-                "n_tables=%d box=%lld x %lld x %lld", (long long)n_words, (long long)M, n_files, n_sel, n_ch_sel, n_ch, seg, N,
-                n_tables, (long long)w0, (long long)w1, (long long)w2);
-    VBQ_REQUIRE(d_channels || n_ch_sel == 0 || n_ch_sel == n_ch, VBQ_ERR_INVALID_ARGUMENT,
-                "vbq_rans_decode_window_f32: without d_channels every channel is decoded, n_ch_sel=%d must be n_ch=%d", n_ch_sel,
-                n_ch);
-    long long total = 0;                                         // elements of d_out
-    VBQ_REQUIRE(!__builtin_smulll_overflow(w0, w1, &total) && !__builtin_smulll_overflow(total, w2, &total) &&
-                    !__builtin_smulll_overflow(total, n_ch_sel, &total) && !__builtin_smulll_overflow(total, n_files, &total) &&
-                    total <= INT64_MAX / 4,
-                VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_decode_window_f32: an output of %d x %lld x %lld x %lld x %d values is too large",
-                n_files, (long long)w0, (long long)w1, (long long)w2, n_ch_sel);
+    long long total;                                             // elements of d_out
+    if (int r = check_window("vbq_rans_decode_window_f32", n_words, M, n_files, n_sel, d_channels != nullptr, n_ch_sel, n_ch, seg, N,
+                             n_tables, w0, w1, w2, total))
+        return r;
     if (n_files == 0 || n_sel == 0 || n_ch_sel == 0 || total == 0) return VBQ_OK;
     VBQ_REQUIRE(d_sizes && d_offsets && d_files && d_segs && d_freq && d_values && d_out, VBQ_ERR_INVALID_ARGUMENT,
                 "vbq_rans_decode_window_f32: null pointer argument");
     VBQ_REQUIRE(n_words == 0 || d_payload, VBQ_ERR_INVALID_ARGUMENT, "vbq_rans_decode_window_f32: null d_payload");
-    hipLaunchKernelGGL(k_rans_decode_window,
-                       dim3((unsigned)(((int64_t)n_sel + kWinThreads - 1) / kWinThreads), (unsigned)n_ch_sel, (unsigned)n_files),
-                       dim3(kWinThreads), 0, reinterpret_cast<hipStream_t>(stream), d_payload, (long)n_words, d_sizes, d_offsets,
+    hipLaunchKernelGGL(k_rans_decode_window, window_grid(n_sel, n_ch_sel, n_files), dim3(kWinThreads), 0, reinterpret_cast<hipStream_t>(stream), d_payload, (long)n_words, d_sizes, d_offsets,
                        (long)M, d_files, d_segs, (int)n_sel, d_channels, (int)n_ch_sel, (int)n_ch, table_size(N), (int)seg, d_freq,
                        (int)n_tables, d_values, (long)w0, (long)w1, (long)w2, d_out, d_status);
     VBQ_CHECK_LAUNCH("rans_decode_window");

@@ -858,16 +858,9 @@ def bag(emb: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, *, weights:
 WINDOW_BAD_SEGMENT, WINDOW_BAD_FILE = 32, 128    # status bits 5 and 7 of the window decode (bits 0..3: the segment decoder's)
 
 
-def rans_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: torch.Tensor, files: torch.Tensor,
-                       segs: torch.Tensor, freq: torch.Tensor, values: torch.Tensor, box: Sequence[int], *, seg: int, N: int = 10,
-                       channels: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
-                       out: Optional[torch.Tensor] = None):
-    """vbq_rans_decode_window_f32 (include/vbq.h, "Window decode"): the box of extents box = (w0, w1, w2) of every listed file,
-    straight from the concatenated payloads.  payload u16 [n_words]; sizes u16 [M] and offsets int64 [M] (their exclusive prefix
-    sum) over all files; files int64 [F, 8] (seg_base, n, D1, D2, a0, a1, a2, table); segs int32 [F, n_sel], -1 = skip; freq
-    u16 [n_tables, C, T]; values f32 [C, T]; channels int32 [C_sel] or None for all C in order.  Returns (out f32
-    [F, w0, w1, w2, C_sel], status u32 [F]); positions no listed segment covers keep what `out` held.  `status` is OR-ed into:
-    zeroed here unless given."""
+def _window_args(payload, sizes, offsets, files, fields, segs, freq, values, box, seg, N, channels, status, out):
+    """The checks rans_decode_window and rans_map_decode_window share; `fields` = (count, names) of a descriptor.  -> the
+    tensors as given or made (status zeroed, out empty), the box and F, n_ch_sel, n_ch, n_tables."""
     payload = _dev(payload, torch.uint16, "payload")
     sizes = _dev(sizes, torch.uint16, "sizes")
     offsets = _dev(offsets, torch.int64, "offsets")
@@ -875,13 +868,12 @@ def rans_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: torc
     segs = _dev(segs, torch.int32, "segs")
     freq = _dev(freq, torch.uint16, "freq")
     values = _dev(values, torch.float32, "values")
-    seg, N = int(seg), int(N)
     T = table_size(N)
     if payload.dim() != 1 or sizes.dim() != 1 or offsets.shape != sizes.shape:
         raise ValueError(f"expected payload [n_words], sizes [M] and offsets [M], got {tuple(payload.shape)}, {tuple(sizes.shape)} "
                          f"and {tuple(offsets.shape)}")
-    if files.dim() != 2 or files.shape[1] != 8:
-        raise ValueError(f"files must be [F, 8] (seg_base, n, D1, D2, a0, a1, a2, table), got {tuple(files.shape)}")
+    if files.dim() != 2 or files.shape[1] != fields[0]:
+        raise ValueError(f"files must be [F, {fields[0]}] ({fields[1]}), got {tuple(files.shape)}")
     F = files.shape[0]
     if segs.dim() != 2 or segs.shape[0] != F:
         raise ValueError(f"segs must be [F = {F}, n_sel], got {tuple(segs.shape)}")
@@ -903,10 +895,57 @@ def rans_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: torc
         if status.numel() != F:
             raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
     out = _out(out, (F,) + box + (n_ch_sel,), torch.float32, payload.device, "out")
+    return payload, sizes, offsets, files, segs, freq, values, box, channels, status, out, F, n_ch_sel, n_ch, n_tables
+
+
+def rans_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: torch.Tensor, files: torch.Tensor,
+                       segs: torch.Tensor, freq: torch.Tensor, values: torch.Tensor, box: Sequence[int], *, seg: int, N: int = 10,
+                       channels: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None):
+    """vbq_rans_decode_window_f32 (include/vbq.h, "Window decode"): the box of extents box = (w0, w1, w2) of every listed file,
+    straight from the concatenated payloads.  payload u16 [n_words]; sizes u16 [M] and offsets int64 [M] (their exclusive prefix
+    sum) over all files; files int64 [F, 8] (seg_base, n, D1, D2, a0, a1, a2, table); segs int32 [F, n_sel], -1 = skip; freq
+    u16 [n_tables, C, T]; values f32 [C, T]; channels int32 [C_sel] or None for all C in order.  Returns (out f32
+    [F, w0, w1, w2, C_sel], status u32 [F]); positions no listed segment covers keep what `out` held.  `status` is OR-ed into:
+    zeroed here unless given."""
+    seg, N = int(seg), int(N)
+    payload, sizes, offsets, files, segs, freq, values, box, channels, status, out, F, n_ch_sel, n_ch, n_tables = _window_args(
+        payload, sizes, offsets, files, (8, "seg_base, n, D1, D2, a0, a1, a2, table"), segs, freq, values, box, seg, N, channels,
+        status, out)
     check(_lib.lib().vbq_rans_decode_window_f32(_ptr(payload), payload.numel(), _ptr(sizes), _ptr(offsets), sizes.numel(),
                                                 _ptr(files), F, _ptr(segs), segs.shape[1], _ptr(channels), n_ch_sel, n_ch, seg,
                                                 N, _ptr(freq), n_tables, _ptr(values), box[0], box[1], box[2], _ptr(out),
                                                 _ptr(status), _stream(payload)), "vbq_rans_decode_window_f32")
+    return out, status
+
+
+WINDOW_BAD_CLASS = 64                            # status bit 6 of the mapped window decode: a class outside the file's palette
+
+
+def rans_map_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: torch.Tensor, files: torch.Tensor,
+                           segs: torch.Tensor, freq: torch.Tensor, values: torch.Tensor, classes: Optional[torch.Tensor],
+                           box: Sequence[int], *, seg: int, max_classes: int, N: int = 10,
+                           channels: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                           out: Optional[torch.Tensor] = None):
+    """vbq_rans_map_decode_window_f32 (include/vbq.h, "Mapped window decode"): rans_decode_window with a table per symbol.
+    files int64 [F, 16] (seg_base, n, D1, D2, a0, a1, a2, P, table[0..3], cls_base, 0, 0, 0); classes u8 [cls_bytes], a multiple
+    of 8 bytes at an address that is one: the packed class blocks of the files (bitstream.pack_classes), file f's at byte
+    cls_base_f -- or None when every file has cls_base = -1; max_classes the largest P of `files`, 1..4.  Everything else, and
+    the result (out, status), as rans_decode_window."""
+    seg, N, max_classes = int(seg), int(N), int(max_classes)
+    payload, sizes, offsets, files, segs, freq, values, box, channels, status, out, F, n_ch_sel, n_ch, n_tables = _window_args(
+        payload, sizes, offsets, files, (16, "seg_base, n, D1, D2, a0, a1, a2, P, table[0..3], cls_base, 0, 0, 0"), segs, freq,
+        values, box, seg, N, channels, status, out)
+    if classes is not None:
+        classes = _dev(classes, torch.uint8, "classes")
+        if classes.dim() != 1:
+            raise ValueError(f"classes must be one-dimensional, got shape {tuple(classes.shape)}")
+    check(_lib.lib().vbq_rans_map_decode_window_f32(_ptr(payload), payload.numel(), _ptr(sizes), _ptr(offsets), sizes.numel(),
+                                                    _ptr(files), F, _ptr(segs), segs.shape[1], _ptr(channels), n_ch_sel, n_ch,
+                                                    seg, N, _ptr(freq), n_tables, _ptr(values), _ptr(classes),
+                                                    0 if classes is None else classes.numel(), max_classes, box[0], box[1],
+                                                    box[2], _ptr(out), _ptr(status), _stream(payload)),
+          "vbq_rans_map_decode_window_f32")
     return out, status
 
 

@@ -778,16 +778,24 @@ class ChannelwisePriorCDFQuantizer:
             h, sz, start = parse(data)
         except ValueError as e:
             raise ValueError(f"file {i}: {e}") from None
+        return h, sz, start, self._batch_header_keys(i, h, segment)[0]
+
+    def _batch_header_keys(self, i, h, segment=None):
+        """The checks of _batch_file_header on the parsed header h of file i -> the keys of its lambdas: one, or the palette of
+        a lambda-map file, whose digests are checked class by class."""
         if h.N != self.max_bits_per_coord or h.C != self.num_channels:
             raise ValueError(f"file {i} is for N = {h.N}, C = {h.C}; this quantizer has N = {self.max_bits_per_coord}, "
                              f"C = {self.num_channels}")
         if segment is not None and h.segment != segment:
             raise ValueError(f"file {i} is in segments of {h.segment} symbols, file 0 in segments of {segment}: "
                              "one call decodes files of one segment length")
-        key = self._lambda_key(h.lamb)
-        if self._coder_tables(key, getattr(h, "segment", None))[1] != h.digest:
-            raise ValueError(f"file {i} was compressed with a different quantizer or entropy model (digest mismatch)")
-        return h, sz, start, key
+        palette = isinstance(h, bitstream.MappedHeader)
+        keys = [self._lambda_key(l) for l in (h.lambs if palette else (h.lamb,))]
+        for p, (key, dig) in enumerate(zip(keys, h.digests if palette else (h.digest,))):
+            if self._coder_tables(key, getattr(h, "segment", None))[1] != dig:
+                where = f"digest mismatch in class {p} of its palette" if palette else "digest mismatch"
+                raise ValueError(f"file {i} was compressed with a different quantizer or entropy model ({where})")
+        return keys
 
     def decompress_latents_batch(self, files, regions=None, channels=None, return_np=False):
         """The same-sized boxes of many latent files in ONE launch: f32 [F, *extents, C_sel], every value bit-identical to
@@ -799,12 +807,16 @@ class ChannelwisePriorCDFQuantizer:
         allowed.  Work: one staging buffer and one upload, one vbq_rans_segment_offsets_u16 over all sizes, one
         vbq_rans_decode_window_f32 over the segments that hold a row of a box, one read of the status words.  A damaged
         file raises VBQError naming the index of the first one; damage in segments no box touches is not seen."""
+        return self._window_call(self._window_plan(files, regions, channels), self._window_run, return_np)
+
+    def _window_call(self, plan, run, return_np):
+        """The one upload of plan.host, `run` (_window_run or _mapped_window_run) and the one read of the status words:
+        VBQError naming the first damaged file."""
         from . import _lib, coder
-        plan = self._window_plan(files, regions, channels)
         if plan.host is None:                                      # no file, no channel or an empty extent: nothing to launch
             out = torch.empty(plan.shape, dtype=torch.float32, device=self.device)
             return out.cpu().numpy() if return_np else out
-        out, status = self._window_run(plan, torch.from_numpy(plan.host).to(self.device))
+        out, status = run(plan, torch.from_numpy(plan.host).to(self.device))
         st = status.cpu().numpy()
         for f in np.flatnonzero(st[:-1]):
             try:
@@ -821,6 +833,29 @@ class ChannelwisePriorCDFQuantizer:
         (plan.host, u8; None when there is nothing to decode): descriptors int64 [F, 8], segment lists int32 [F, n_sel] and
         channels int32 [C_sel] (each padded to 8 bytes), then all sizes u16 [M], then all payloads u16 -- the last two straight
         from the files.  plan.cut: where each part starts."""
+        files, regions, ch, C_sel = self._window_inputs(files, regions, channels)
+        heads, sizes, starts, keys = self._window_headers(files)
+        F = len(files)
+        shape, boxes, geometry, seg_ids, chans, n_sel = self._window_geometry(heads, regions, ch, C_sel)
+        if seg_ids is None:
+            return self._WindowPlan(shape, None, None, F, 0, C_sel, 0, 0, None, [], None)
+        segment = heads[0].segment
+        tables = sorted(set(keys), key=float)                      # (a stable tag for the codec cache of _coder_stack)
+        M, n_words = sum(h.n_sizes for h in heads), sum(h.n_words for h in heads)
+        desc = np.empty((F, 8), np.int64)
+        desc[:, :7] = geometry
+        desc[:, 7] = [tables.index(k) for k in keys]
+        head = [desc.view(np.uint8).reshape(-1), seg_ids.view(np.uint8), chans.view(np.uint8)]
+        raws = [np.frombuffer(memoryview(d).cast("B"), dtype=np.uint8) for d in files]
+        host = np.concatenate(head + [r[h.nbytes: h.nbytes + 2 * h.n_sizes] for r, h in zip(raws, heads)]
+                              + [r[s: s + 2 * h.n_words] for r, h, s in zip(raws, heads, starts)])
+        cut = [int(c) for c in np.cumsum([0, head[0].size, head[1].size, head[2].size, 2 * M, 2 * n_words])]
+        box = tuple(h - l for l, h in zip(boxes[0][1], boxes[0][2]))
+        return self._WindowPlan(shape, host, cut, F, n_sel, C_sel, M, n_words, segment, tables, box)
+
+    def _window_inputs(self, files, regions, channels):
+        """What both window plans do before they read a file: (files as a list, one region per file, the channel list as int32
+        or None, C_sel); ValueError for a wrong count of regions or a channel outside [0, C)."""
         self._check_coder_bits()
         files = list(files)
         F, C = len(files), self.num_channels
@@ -835,59 +870,151 @@ class ChannelwisePriorCDFQuantizer:
             if ch.size and (ch.dtype.kind not in "iu" or int(ch.min()) < 0 or int(ch.max()) >= C):
                 raise ValueError(f"channels must be integers in [0, {C})")
             ch = ch.astype(np.int32)
-        C_sel = C if ch is None else int(ch.size)
-        heads, sizes, starts, keys = self._window_headers(files)
+        return files, regions, ch, C if ch is None else int(ch.size)
+
+    @staticmethod
+    def _window_geometry(heads, regions, ch, C_sel):
+        """What both window plans stage alike, from the parsed headers (of one segment length): (output shape, boxes, the
+        descriptors' first seven fields int64 [F, 7] -- seg_base, n, D1, D2, a0, a1, a2 --, segment lists int32 padded with -1 to
+        [F, n_sel] and to 8 bytes, channels int32 padded to 8 bytes, n_sel).  Everything after the shape is None when there is
+        nothing to decode: no file, no channel or an empty extent."""
+        F = len(heads)
         boxes, extents = bitstream.region_boxes([h.shape[:-1] for h in heads], regions)
         shape = (F,) + tuple(extents) + (C_sel,)
         if F == 0 or C_sel == 0 or 0 in extents:
-            return self._WindowPlan(shape, None, None, F, 0, C_sel, 0, 0, None, [], None)
-        segment = heads[0].segment
-        tables = sorted(set(keys), key=float)                      # (a stable tag for the codec cache of _coder_stack)
-        lists = [bitstream.box_segments(dims, lo, hi, segment) for dims, lo, hi in boxes]
+            return shape, None, None, None, None, 0
+        lists = [bitstream.box_segments(dims, lo, hi, heads[0].segment) for dims, lo, hi in boxes]
         n_sel = max(l.size for l in lists)
-        M, n_words = sum(h.n_sizes for h in heads), sum(h.n_words for h in heads)
-        desc = np.empty((F, 8), np.int64)
+        geometry = np.empty((F, 7), np.int64)
         base = 0
         for f, (h, (dims, lo, hi)) in enumerate(zip(heads, boxes)):
-            desc[f] = (base, h.n_rows, dims[1], dims[2], lo[0], lo[1], lo[2], tables.index(keys[f]))
+            geometry[f] = (base, h.n_rows, dims[1], dims[2], lo[0], lo[1], lo[2])
             base += h.n_sizes
         seg_ids = np.full(F * n_sel + (F * n_sel & 1), -1, np.int32)
         for f, l in enumerate(lists):
             seg_ids[f * n_sel: f * n_sel + l.size] = l
         chans = np.zeros(0, np.int32) if ch is None else np.concatenate([ch, np.zeros(C_sel & 1, np.int32)])
-        head = [desc.view(np.uint8).reshape(-1), seg_ids.view(np.uint8), chans.view(np.uint8)]
-        raws = [np.frombuffer(memoryview(d).cast("B"), dtype=np.uint8) for d in files]
-        host = np.concatenate(head + [r[h.nbytes: h.nbytes + 2 * h.n_sizes] for r, h in zip(raws, heads)]
-                              + [r[s: s + 2 * h.n_words] for r, h, s in zip(raws, heads, starts)])
-        cut = [int(c) for c in np.cumsum([0, head[0].size, head[1].size, head[2].size, 2 * M, 2 * n_words])]
-        box = tuple(h - l for l, h in zip(boxes[0][1], boxes[0][2]))
-        return self._WindowPlan(shape, host, cut, F, n_sel, C_sel, M, n_words, segment, tables, box)
+        return shape, boxes, geometry, seg_ids, chans, n_sel
 
     def _window_run(self, plan, dev):
         """The device side: `dev` is plan.host on the device.  One vbq_rans_segment_offsets_u16 over all sizes and one
         vbq_rans_decode_window_f32 -> (out f32 plan.shape, status u32 [F + 1]: per file, then the scan's); nothing is read
         back."""
+        d_files, d_segs, d_ch, d_sizes, d_payload, offsets, status, freq = self._window_device(plan, dev, 8, 3)
+        out, _ = ops.rans_decode_window(d_payload, d_sizes, offsets, d_files, d_segs, freq, self._sorted_dev(), plan.box,
+                                        seg=plan.segment, N=self.max_bits_per_coord, channels=d_ch, status=status[:plan.F])
+        return out.view(plan.shape), status
+
+    def _window_device(self, plan, dev, fields, k):
+        """The views of a window plan's staging buffer on the device -- descriptors [F, fields], segment lists, channels (None
+        for all), sizes and payload at plan.cut[k:] --, the offsets of vbq_rans_segment_offsets_u16 over the sizes, the zeroed
+        status words u32 [F + 1] (the last one the scan's) and the frequency stack [n_tables, C, T]."""
         from . import _lib
         F, C, cut = plan.F, self.num_channels, plan.cut
-        d_files = dev[cut[0]:cut[1]].view(torch.int64).view(F, 8)
+        d_files = dev[cut[0]:cut[1]].view(torch.int64).view(F, fields)
         d_segs = dev[cut[1]:cut[1] + 4 * F * plan.n_sel].view(torch.int32).view(F, plan.n_sel)
         d_ch = dev[cut[2]:cut[2] + 4 * plan.C_sel].view(torch.int32) if cut[3] > cut[2] else None
-        d_sizes, d_payload = dev[cut[3]:cut[4]].view(torch.uint16), dev[cut[4]:cut[5]].view(torch.uint16)
+        d_sizes, d_payload = dev[cut[k]:cut[k + 1]].view(torch.uint16), dev[cut[k + 1]:cut[k + 2]].view(torch.uint16)
         offsets = torch.empty(plan.M, dtype=torch.int64, device=dev.device)
         status = torch.zeros(F + 1, dtype=torch.uint32, device=dev.device)
         _lib.check(_lib.lib().vbq_rans_segment_offsets_u16(ops._ptr(d_sizes), plan.M, plan.segment, plan.n_words,
                                                             ops._ptr(offsets), ops._ptr(status[F:]), ops._stream(dev)),
                    "vbq_rans_segment_offsets_u16")
         freq = self._coder_stack(plan.tables, plan.segment)._freq(dev.device).view(len(plan.tables), C, -1)
-        out, _ = ops.rans_decode_window(d_payload, d_sizes, offsets, d_files, d_segs, freq, self._sorted_dev(), plan.box,
-                                        seg=plan.segment, N=self.max_bits_per_coord, channels=d_ch, status=status[:F])
-        return out.view(plan.shape), status
+        return d_files, d_segs, d_ch, d_sizes, d_payload, offsets, status, freq
 
     def decompress_latents_window(self, data, region, channels=None, return_np=True):
         """decompress_latents(data)[region][..., channels] without decoding the rest: the batch of one file
         (decompress_latents_batch) with the file axis dropped.  Only the segments that hold a row of the region are decoded --
         and checked: damage elsewhere in the file goes unseen."""
         return self.decompress_latents_batch([data], regions=[region], channels=channels, return_np=return_np)[0]
+
+    # ------------------------------------------------------- windows and batches of lambda-map files ("Mapped window decode")
+    def decompress_latents_mapped_batch(self, files, regions=None, channels=None, return_np=False):
+        """decompress_latents_batch for lambda-map files: f32 [F, *extents, C_sel], every value bit-identical to
+        decompress_latents(files[f])[regions[f]][..., channels].  `files`: b"VBQm" files (compress_latents_to_bytes_mapped) and
+        b"VBQb" files of this quantizer, mixed in any order -- any built lambdas, any palettes of 1..4 of them, any latent
+        shapes, one `segment`; each gets the checks of decompress_latents, the digest of every class of a palette included
+        (ValueError naming the file's index, also for a compact file; KeyError for a lambda without a model).  `regions` and
+        `channels` as in decompress_latents_batch.  Work: one staging buffer and one upload -- the class blocks go as the
+        files pack them, 2 bits per position --, one vbq_rans_segment_offsets_u16, one vbq_rans_map_decode_window_f32, one read
+        of the status words.  A damaged file raises VBQError naming the index of the first one; damage in segments no box
+        touches is not seen."""
+        return self._window_call(self._mapped_window_plan(files, regions, channels), self._mapped_window_run, return_np)
+
+    def decompress_latents_mapped_window(self, data, region, channels=None, return_np=True):
+        """decompress_latents(data)[region][..., channels] of a lambda-map file (or a file in segments) without decoding the
+        rest: the batch of one file (decompress_latents_mapped_batch) with the file axis dropped."""
+        return self.decompress_latents_mapped_batch([data], regions=[region], channels=channels, return_np=return_np)[0]
+
+    def _mapped_window_headers(self, files):
+        """_window_headers for lambda-map files and files in segments mixed: (headers, payload offsets, the keys of each file's
+        palette -- one key for a b"VBQb" file); ValueError naming the index of a file that is neither, is not of this quantizer
+        or has another segment."""
+        heads, starts, keys = [], [], []
+        for i, data in enumerate(files):
+            segment = heads[0].segment if heads else None
+            magic = bytes(memoryview(data).cast("B")[:4])
+            if magic == bitstream.COMPACT_MAGIC:
+                raise ValueError(f"file {i} is a compact file (magic b'VBQc'): its parts are not addressable; windows and batches "
+                                 "read lambda-map files (magic b'VBQm') and files in segments (magic b'VBQb')")
+            if magic == bitstream.MAPPED_MAGIC:
+                try:
+                    h, _, _, start = bitstream.parse_mapped(data)
+                except ValueError as e:
+                    raise ValueError(f"file {i}: {e}") from None
+                palette = self._batch_header_keys(i, h, segment)
+            else:
+                h, _, start, key = self._batch_file_header(i, data, bitstream.parse, segment)
+                palette = [key]
+            heads.append(h), starts.append(start), keys.append(palette)
+        return heads, starts, keys
+
+    _MappedWindowPlan = namedtuple("_MappedWindowPlan", "shape host cut F n_sel C_sel M n_words segment tables box max_P cls_bytes")
+
+    def _mapped_window_plan(self, files, regions, channels):
+        """The host side of decompress_latents_mapped_batch, as _window_plan: every check and the ONE staging buffer (plan.host,
+        u8; None when there is nothing to decode): descriptors int64 [F, 16], segment lists int32 [F, n_sel] and channels int32
+        [C_sel] (each padded to 8 bytes), then the class blocks of the lambda-map files (each a multiple of 8 bytes), all sizes
+        u16 [M] and all payloads u16 -- the last three straight from the files.  plan.cut: where each part starts;
+        plan.tables: the distinct lambdas of all files and palettes, the rows of the frequency stack."""
+        files, regions, ch, C_sel = self._window_inputs(files, regions, channels)
+        heads, starts, keys = self._mapped_window_headers(files)
+        F = len(files)
+        shape, boxes, geometry, seg_ids, chans, n_sel = self._window_geometry(heads, regions, ch, C_sel)
+        if seg_ids is None:
+            return self._MappedWindowPlan(shape, None, None, F, 0, C_sel, 0, 0, None, [], None, 0, 0)
+        tables = sorted({k for palette in keys for k in palette}, key=float)
+        M, n_words = sum(h.n_sizes for h in heads), sum(h.n_words for h in heads)
+        desc = np.zeros((F, 16), np.int64)
+        desc[:, :7] = geometry
+        raws = [np.frombuffer(memoryview(d).cast("B"), dtype=np.uint8) for d in files]
+        blocks, cls_bytes = [], 0
+        for f, (h, r, palette) in enumerate(zip(heads, raws, keys)):
+            desc[f, 7] = len(palette)
+            desc[f, 8: 8 + len(palette)] = [tables.index(k) for k in palette]
+            desc[f, 12] = -1
+            if isinstance(h, bitstream.MappedHeader):
+                desc[f, 12] = cls_bytes
+                blocks.append(r[h.nbytes: h.sizes_offset])
+                cls_bytes += h.classes_nbytes
+        head = [desc.view(np.uint8).reshape(-1), seg_ids.view(np.uint8), chans.view(np.uint8)]
+        host = np.concatenate(head + blocks + [r[s - 2 * h.n_sizes: s] for r, h, s in zip(raws, heads, starts)]    # (the sizes end
+                              + [r[s: s + 2 * h.n_words] for r, h, s in zip(raws, heads, starts)])                 # where the payload starts)
+        cut = [int(c) for c in np.cumsum([0, head[0].size, head[1].size, head[2].size, cls_bytes, 2 * M, 2 * n_words])]
+        box = tuple(h - l for l, h in zip(boxes[0][1], boxes[0][2]))
+        return self._MappedWindowPlan(shape, host, cut, F, n_sel, C_sel, M, n_words, heads[0].segment, tables, box,
+                                      max(len(p) for p in keys), cls_bytes)
+
+    def _mapped_window_run(self, plan, dev):
+        """The device side, as _window_run: one vbq_rans_segment_offsets_u16 over all sizes and one
+        vbq_rans_map_decode_window_f32 -> (out f32 plan.shape, status u32 [F + 1]); nothing is read back."""
+        d_files, d_segs, d_ch, d_sizes, d_payload, offsets, status, freq = self._window_device(plan, dev, 16, 4)
+        d_cls = dev[plan.cut[3]:plan.cut[4]] if plan.cls_bytes else None
+        out, _ = ops.rans_map_decode_window(d_payload, d_sizes, offsets, d_files, d_segs, freq, self._sorted_dev(), d_cls, plan.box,
+                                            seg=plan.segment, max_classes=plan.max_P, N=self.max_bits_per_coord, channels=d_ch,
+                                            status=status[:plan.F])
+        return out.view(plan.shape), status
 
     def compress_to_bytes(self, X, vae, lamb, segment=1024, layout="segments", part=1 << 17) -> bytes:
         """`vae.encode(X)`, then compress_latents_to_bytes."""
