@@ -1079,6 +1079,67 @@ int vbq_rans_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, int64_t lambd
                              uint32_t *d_status, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Mapped batch encode: every segment of MANY lambda-map files (vbq_amd/bitstream.py, magic "VBQm") in ONE launch -- the batch
+ * encode with a frequency table per symbol, and the writer's counterpart of the mapped window decode.
+ * vbq_rans_map_encode_u16 gives a workgroup 64 consecutive segments of one stream and stages up to four tables for them; a
+ * small file leaves most lanes idle.  Here the caller lists the work as items (file, segment) in blocks of 64 that share a
+ * PALETTE -- an ordered list of 1..4 blocks of d_freq, one per class --, and a workgroup codes one block of one channel: it
+ * stages the palette's tables once and its lanes take segments of different files, each following its own file's classes.
+ *   d_idx      u16 [n_idx]: the rank indices of all files, one plane per class of a file's palette.  Symbol i of channel c of
+ *              file f is d_idx[idx_base_f + cls * plane_stride_f + c * idx_stride_f + i] with cls = d_cls[cls_base_f + i],
+ *              0 <= i < n_f.  plane_stride_f == 0 reads every class from one plane.
+ *   d_cls      u8 [n_cls]: the class bytes, one per position of a file, shared by its channels.  A class byte >= P of the
+ *              file's palette is coded as class 0, as vbq_rans_map_encode_u16 does: the caller checks its map.
+ *   d_files    int64 [n_files][8], per file: idx_base, idx_stride, plane_stride, n, seg_base, palette, cls_base, 0.  The file has
+ *              n symbols per channel in nseg_f = ceil(n / seg) segments; `palette` picks the row of d_palettes; the last field
+ *              is reserved.
+ *   d_palettes int32 [n_palettes][4]: per palette the blocks of d_freq of its classes, class 0 first; the first -1 ends the row
+ *              (P = the entries before it, 1..4; what follows it is not read).
+ *   max_classes  the largest P of the palettes in use, 1..4: the launch's dynamic LDS is max_classes tables of 8 KB (at most 32 KB
+ *              of the CU's 160 KiB).  A palette with more classes is refused as a defective one.
+ *   d_items    int32 [n_items][2]: (file, segment within a stream), exactly as in "Batch encode" with the palette in the place of
+ *              the table: n_items a multiple of 64, the files of one block share one `palette` (the block's palette is that of
+ *              its first item whose file names a valid one), file == -1 is padding and skipped silently.
+ *   d_freq     u16 [n_tables][n_ch][T], T = 2^(N+1) - 1, every entry >= 1, every row summing to 2^15.
+ *   d_canon    u16 [n_ch][T] or NULL, as in "Batch encode": applied once to every staged table, not per symbol.
+ *   d_words    u16 [M][seg + 2], d_sizes u32 [M].  Segment g of channel c of file f goes to slot seg_base_f + c * nseg_f + g:
+ *              its words and its size are exactly what vbq_rans_map_encode_u16 writes for the same symbols, classes and
+ *              palette -- and, for a file whose classes are all p, what vbq_rans_encode_files_u16 writes with the table
+ *              palette[p]; an index outside the table is coded as symbol 0.  Slots that no item names, and the words of a slot
+ *              past its size, are left untouched.  With seg_base the file-major exclusive sum of n_ch * nseg_f, ONE
+ *              vbq_rans_pack_u16(d_words, d_sizes, n_streams = 1, n = M * seg, seg, ...) packs all files, in file order.
+ *   d_status   u32 [n_files], may be NULL, OR-ed into; zero it first.  Bit 7 (128) for a file:
+ *                of the descriptor -- `palette` outside [0, n_palettes); a palette row whose first entry is -1, with an entry
+ *                before its first -1 outside [0, n_tables), or with more than max_classes classes; n < 1; symbols of some plane
+ *                and channel outside [0, n_idx); classes outside [0, n_cls); slots outside [0, M): every item of the file
+ *                finds the same, so nothing of that file is written;
+ *                of one item -- a segment id outside [0, nseg_f), or a file whose palette is not the block's: that item writes
+ *                nothing.
+ *              An item whose file id lies outside [0, n_files) (other than -1) writes nothing and sets bit 7 of word 0: it has
+ *              no word of its own.
+ * vbq_rans_map_sizes_files_u16: the d_sizes of vbq_rans_map_encode_files_u16 for the same arguments, without the words.
+ * Descriptors, palettes and items are range-checked on the device, without overflow, before anything is indexed with them.
+ * Eight classes are read in one 8-byte load where a segment's class address allows it and, when the eight agree and that class's
+ * plane is 16-byte aligned there, their symbols in one 16-byte load; narrow loads otherwise: words and sizes do not depend on
+ * the alignment.
+ * Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): n_files <= 65535, n_ch <= 65535, seg in 1..65533, N in 1..10,
+ * n_tables >= 1, n_palettes >= 1, max_classes in 1..4, every size >= 0 (n_cls too), n_items a multiple of 64, M * (seg + 2) words
+ * addressable, no null pointer (d_canon and d_status excepted).  n_files == 0, n_items == 0 or n_ch == 0 return VBQ_OK with no
+ * launch.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_map_encode_files_u16(const uint16_t *d_idx, int64_t n_idx, const uint8_t *d_cls, int64_t n_cls,
+                                  const int64_t *d_files, int32_t n_files, const int32_t *d_palettes, int32_t n_palettes,
+                                  int32_t max_classes, const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t seg,
+                                  int32_t N, const uint16_t *d_freq, int32_t n_tables, const uint16_t *d_canon,
+                                  uint16_t *d_words, uint32_t *d_sizes, int64_t M, uint32_t *d_status, void *stream);
+int vbq_rans_map_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, const uint8_t *d_cls, int64_t n_cls,
+                                 const int64_t *d_files, int32_t n_files, const int32_t *d_palettes, int32_t n_palettes,
+                                 int32_t max_classes, const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t seg,
+                                 int32_t N, const uint16_t *d_freq, int32_t n_tables, const uint16_t *d_canon, uint32_t *d_sizes,
+                                 int64_t M, uint32_t *d_status, void *stream);
+
+/* ----------------------------------------------------------------------------------
  * Compact batch: the parts of MANY compact latent files (vbq_amd/bitstream.py, magic "VBQc") sized, written or read in ONE
  * launch each.  vbq_rans_il_sizes_u16 / _encode_u16 / _decode_u16 give a wave one part of ONE tensor: a small file has a few
  * parts, so a few waves run and the call takes the time of one wave's steps.  Here the caller lists the work as items

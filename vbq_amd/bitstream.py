@@ -723,6 +723,57 @@ def mapped_nbytes(shape, C, segment, n_words, P) -> int:
                                        digests=(bytes(16),) * P, n_words=n_words)).total_nbytes
 
 
+# ---- batches of lambda-map files, written (ChannelwisePriorCDFQuantizer.compress_latents_to_bytes_mapped_batch; include/vbq.h,
+# "Mapped batch encode").  encode_plan with a palette where it has a table: the files of a palette are solved together at the
+# palette's P lambdas, and a block of items shares the palette's tables.
+MAPPED_ENCODE_FIELDS = 8                     # idx_base, idx_stride, plane_stride, n, seg_base, palette, cls_base, 0
+CLASS_ALIGN = 8                              # a file's class bytes start at a multiple of 8 bytes: one 8-byte load is 8 classes
+MappedEncodePlan = namedtuple("MappedEncodePlan", "nseg seg_base M row0 group_rows group_row_base n_rows group_idx_base n_idx "
+                                                  "cls_base n_cls files palettes items")
+
+
+def mapped_encode_plan(rows, palettes, palette_sizes, segment, C) -> MappedEncodePlan:
+    """What vbq_rans_map_encode_files_u16 / vbq_rans_map_sizes_files_u16 read, from the rows per channel n_f >= 1 of F files,
+    their palette numbers (0 .. G - 1), the number of classes P_g (1..MAX_CLASSES) of each of the G palettes, the segment
+    length and the number of channels C:
+
+        nseg, seg_base, M   exactly encode_plan's: ceil(n_f / segment), the file-major exclusive sum of C * nseg_f, its total
+        row0, group_rows, group_row_base, n_rows   the row layout of encode_plan with the palette in the place of the table: the
+                                          files of a palette sit next to each other, in file order, in that palette's group of
+                                          B_g rows, every file's run starting at a multiple of ENCODE_ROW_ALIGN (the latents
+                                          of all groups are one array of n_rows rows)
+        group_idx_base, n_idx  int64 [G], int  group g owns [P_g, C, B_g] index planes of the one index array, starting at
+                                          element group_idx_base_g = the sum of P_h * C * B_h over the groups h before it;
+                                          n_idx their total
+        cls_base, n_cls     int64 [F], int  the file-major exclusive sum of the files' positions n_f, each rounded up to
+                                          CLASS_ALIGN bytes, and its total: file f's class bytes are cls[cls_base_f : + n_f]
+        files               int64 [F, 8]  the descriptors: idx_base = group_idx_base_g + row0_f, idx_stride = B_g, plane_stride
+                                          = C * B_g, n_f, seg_base_f, palette, cls_base_f, 0
+        palettes            int32 [G, 4]  a template of the kernel's palette rows: 0 for a class below P_g, -1 past it -- the
+                                          caller writes its table numbers over the zeros
+        items               int32 [n_items, 2]  exactly encode_plan's, palette by palette: every block of ENCODE_BLOCK items
+                                          holds one palette only, padded with (-1, -1)
+
+    ValueError for a bad segment, C < 1, a row count < 1, a palette outside [0, G), a palette size outside [1, MAX_CLASSES] or
+    more than MAX_BATCH_FILES files."""
+    P = np.asarray(palette_sizes, dtype=np.int64).reshape(-1)
+    G = P.size
+    if G and (int(P.min()) < 1 or int(P.max()) > MAX_CLASSES):
+        raise ValueError(f"palette sizes {P.tolist()} outside [1, {MAX_CLASSES}]")
+    base = encode_plan(rows, palettes, segment, C, G)
+    C, n, pal, F, _ = _plan_inputs(rows, palettes, C, G)
+    per_group = P * C * base.group_rows
+    group_idx_base = np.cumsum(per_group) - per_group
+    padded = (n + CLASS_ALIGN - 1) // CLASS_ALIGN * CLASS_ALIGN
+    cls_base = np.cumsum(padded) - padded
+    files = np.stack([group_idx_base[pal] + base.row0, base.group_rows[pal], C * base.group_rows[pal], n, base.seg_base, pal,
+                      cls_base, np.zeros(F, np.int64)], axis=1) if F else np.zeros((0, MAPPED_ENCODE_FIELDS), np.int64)
+    rows4 = np.where(np.arange(MAX_CLASSES)[None, :] < P[:, None], 0, -1).astype(np.int32)
+    return MappedEncodePlan(base.nseg, base.seg_base, base.M, base.row0, base.group_rows, base.group_row_base, base.n_rows,
+                            group_idx_base, int(per_group.sum()), cls_base, int(padded.sum()),
+                            np.ascontiguousarray(files, dtype=np.int64), np.ascontiguousarray(rows4), base.items)
+
+
 def parse_mapped(data) -> Tuple[MappedHeader, np.ndarray, np.ndarray, int]:
     """bytes -> (header, classes u8 [B], sizes u16 [C * nseg] (a read-only view into `data`), byte offset of the payload).
     ValueError on anything malformed."""

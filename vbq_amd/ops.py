@@ -1042,6 +1042,87 @@ def rans_sizes_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor
     return totals, status
 
 
+def _map_files_args(idx, classes, files, palettes, items, freq, M, seg, N, canon, words, sizes, status):
+    """What rans_map_encode_files and rans_map_sizes_files share: the checks and the outputs; `words` is False for the sizes
+    entry.  -> (words or None, sizes, status)."""
+    idx = _dev(idx, torch.uint16, "idx")
+    classes = _dev(classes, torch.uint8, "classes")
+    files = _dev(files, torch.int64, "files")
+    palettes = _dev(palettes, torch.int32, "palettes")
+    items = _dev(items, torch.int32, "items")
+    freq = _dev(freq, torch.uint16, "freq")
+    seg, N, M = int(seg), int(N), int(M)
+    T = table_size(N)
+    if files.dim() != 2 or files.shape[1] != 8:
+        raise ValueError("files must be [F, 8] (idx_base, idx_stride, plane_stride, n, seg_base, palette, cls_base, 0), got "
+                         f"{tuple(files.shape)}")
+    if palettes.dim() != 2 or palettes.shape[1] != 4:
+        raise ValueError(f"palettes must be [n_palettes, 4] (tables, class 0 first, -1 past P), got {tuple(palettes.shape)}")
+    if items.dim() != 2 or items.shape[1] != 2:
+        raise ValueError(f"items must be [n_items, 2] (file, segment), got {tuple(items.shape)}")
+    if freq.dim() != 3 or freq.shape[2] != T:
+        raise ValueError(f"expected freq [n_tables, C, {T}], got {tuple(freq.shape)}")
+    F, n_tables, n_ch = files.shape[0], freq.shape[0], freq.shape[1]
+    if canon is not None:
+        canon = _dev(canon, torch.uint16, "canon")
+        if tuple(canon.shape) != (n_ch, T):
+            raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
+    if M < 0:
+        raise ValueError(f"M = {M} slots")
+    given = words is not None
+    if words is not False:
+        words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words")
+    if sizes is None:
+        sizes = torch.zeros(M, dtype=torch.uint32, device=idx.device)
+        if words is not False and not given:
+            words.zero_()
+    else:
+        sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes")
+    if status is None:
+        status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
+    else:
+        status = _dev(status, torch.uint32, "status")
+        if status.numel() != F:
+            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+    return idx, classes, files, palettes, items, freq, canon, words, sizes, status, F, n_tables, n_ch, M, seg, N
+
+
+def rans_map_encode_files(idx: torch.Tensor, classes: torch.Tensor, files: torch.Tensor, palettes: torch.Tensor,
+                          items: torch.Tensor, freq: torch.Tensor, M: int, *, seg: int, max_classes: int, N: int = 10,
+                          canon: Optional[torch.Tensor] = None, words: Optional[torch.Tensor] = None,
+                          sizes: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """vbq_rans_map_encode_files_u16 (include/vbq.h, "Mapped batch encode"): rans_encode_files with a table per symbol.  idx u16
+    [n_idx], the index planes of all files; classes u8 [n_cls], their class bytes; files int64 [F, 8] (idx_base, idx_stride,
+    plane_stride, n, seg_base, palette, cls_base, 0); palettes int32 [n_palettes, 4] (blocks of freq, class 0 first, -1 past P);
+    items int32 [n_items, 2] (file, segment), n_items a multiple of 64, a block of 64 of one palette, file -1 = padding
+    (bitstream.mapped_encode_plan builds all three); freq u16 [n_tables, C, T]; canon u16 [C, T] or None; max_classes the
+    largest P in use, 1..4.  Returns (words u16 [M, seg + 2], sizes u32 [M], status u32 [F]): slot seg_base_f + c nseg_f + g
+    holds segment g of channel c of file f as MappedRansCodec.encode writes it; slots no item names keep what `words` / `sizes`
+    held (new ones are zeroed).  `status` is OR-ed into: zeroed here unless given."""
+    idx, classes, files, palettes, items, freq, canon, words, sizes, status, F, n_tables, n_ch, M, seg, N = _map_files_args(
+        idx, classes, files, palettes, items, freq, M, seg, N, canon, words, sizes, status)
+    check(_lib.lib().vbq_rans_map_encode_files_u16(_ptr(idx), idx.numel(), _ptr(classes), classes.numel(), _ptr(files), F,
+                                                   _ptr(palettes), palettes.shape[0], int(max_classes), _ptr(items),
+                                                   items.shape[0], n_ch, seg, N, _ptr(freq), n_tables, _ptr(canon), _ptr(words),
+                                                   _ptr(sizes), M, _ptr(status), _stream(idx)), "vbq_rans_map_encode_files_u16")
+    return words, sizes, status
+
+
+def rans_map_sizes_files(idx: torch.Tensor, classes: torch.Tensor, files: torch.Tensor, palettes: torch.Tensor,
+                         items: torch.Tensor, freq: torch.Tensor, M: int, *, seg: int, max_classes: int, N: int = 10,
+                         canon: Optional[torch.Tensor] = None, sizes: Optional[torch.Tensor] = None,
+                         status: Optional[torch.Tensor] = None):
+    """vbq_rans_map_sizes_files_u16: the sizes of rans_map_encode_files for the same arguments, without the words.  Returns
+    (sizes u32 [M], status u32 [F])."""
+    idx, classes, files, palettes, items, freq, canon, _, sizes, status, F, n_tables, n_ch, M, seg, N = _map_files_args(
+        idx, classes, files, palettes, items, freq, M, seg, N, canon, False, sizes, status)
+    check(_lib.lib().vbq_rans_map_sizes_files_u16(_ptr(idx), idx.numel(), _ptr(classes), classes.numel(), _ptr(files), F,
+                                                  _ptr(palettes), palettes.shape[0], int(max_classes), _ptr(items),
+                                                  items.shape[0], n_ch, seg, N, _ptr(freq), n_tables, _ptr(canon), _ptr(sizes),
+                                                  M, _ptr(status), _stream(idx)), "vbq_rans_map_sizes_files_u16")
+    return sizes, status
+
+
 # ---- batches of compact files (include/vbq.h, "Compact batch"): one wave per (file, part)
 def _il_files_args(idx, files, items, freq, N, status):
     """What the three compact-batch calls check alike -> (idx, files, items, freq, status, F, n_tables, n_ch)."""

@@ -1096,7 +1096,7 @@ class ChannelwisePriorCDFQuantizer:
             out.append(bitstream.write(hd, sz, pay[int(ends[f]) - n_words: int(ends[f])]))
         return out
 
-    _EncodeBatch = namedtuple("_EncodeBatch", "plan shapes keys tables digests segment rows pairs on_device host cut back")
+    _EncodeBatch = namedtuple("_EncodeBatch", "plan shapes keys tables digests segment rows pairs on_device host cut back group")
 
     def _encode_batch_plan(self, latents, lambs, segment):
         """The host side of compress_latents_to_bytes_batch: every check, the plan of bitstream.encode_plan and the ONE staging
@@ -1114,26 +1114,31 @@ class ChannelwisePriorCDFQuantizer:
         plan = bitstream.encode_plan(rows, [tables.index(k) for k in keys], segment, C, len(tables))
         return self._batch_stage(plan, shapes, keys, tables, digests, segment, rows, pairs, 8 + 4 * plan.M + 4 * F)
 
-    def _batch_stage(self, plan, shapes, keys, tables, digests, segment, rows, pairs, back):
+    def _batch_stage(self, plan, shapes, keys, tables, digests, segment, rows, pairs, back, group=None, extra=()):
         """The ONE staging buffer of a batch call (see _encode_batch_plan), filled: `back` zeroed bytes that the device writes
-        and the host reads back | the plan's descriptors | its items | the latents unless every input is a device tensor."""
+        and the host reads back | the plan's descriptors | its items | every array of `extra` (u8, each a multiple of 8 bytes:
+        b.cut[3:] say where they end) | the latents unless every input is a device tensor.  `group`: the row group of every
+        file (default: the table of its descriptor)."""
         C, R = self.num_channels, plan.n_rows
-        cut = [int(c) for c in np.cumsum([back + (-back % 8), plan.files.nbytes, plan.items.nbytes])]
+        group = plan.files[:, 4] if group is None else group
+        cut = [int(c) for c in np.cumsum([back + (-back % 8), plan.files.nbytes, plan.items.nbytes] + [e.nbytes for e in extra])]
         on_device = all(isinstance(a, torch.Tensor) and a.is_cuda for pair in pairs for a in pair)
-        host_t = self._encode_stage(cut[2] + (0 if on_device else 8 * R * C))
+        host_t = self._encode_stage(cut[-1] + (0 if on_device else 8 * R * C))
         host = host_t.numpy()
         host[:cut[0]] = 0
         host[cut[0]:cut[1]] = plan.files.view(np.uint8).reshape(-1)
         host[cut[1]:cut[2]] = plan.items.view(np.uint8).reshape(-1)
+        for k, e in enumerate(extra):
+            host[cut[2 + k]:cut[3 + k]] = e
         if not on_device:
-            stage = host[cut[2]:].view(np.float32).reshape(2, R, C)
-            row_base = plan.group_row_base[plan.files[:, 4]] + plan.row0          # of every file among the R staged rows
+            stage = host[cut[-1]:].view(np.float32).reshape(2, R, C)
+            row_base = plan.group_row_base[group] + plan.row0                     # of every file among the R staged rows
             for f, (means, logvars) in enumerate(pairs):
                 r0, r1 = int(row_base[f]), int(row_base[f]) + rows[f]
                 stage[0, r0:r1] = _to_numpy(means).reshape(-1, C)
                 stage[1, r0:r1] = _to_numpy(logvars).reshape(-1, C)
                 stage[:, r1:r1 + (-rows[f] % bitstream.ENCODE_ROW_ALIGN)] = 0     # the padding rows: mean 0, logvar 0
-        return self._EncodeBatch(plan, shapes, keys, tables, digests, segment, rows, pairs, on_device, host_t, cut, back)
+        return self._EncodeBatch(plan, shapes, keys, tables, digests, segment, rows, pairs, on_device, host_t, cut, back, group)
 
     def _encode_stage(self, nbytes: int) -> torch.Tensor:
         """The staging buffer of _encode_batch_plan, a host tensor u8 [nbytes]: a view of ONE pinned block kept between calls and grown on
@@ -1153,8 +1158,8 @@ class ChannelwisePriorCDFQuantizer:
         dev, C, plan = self.device, self.num_channels, b.plan
         d_host = b.host.to(dev)
         if not b.on_device:
-            return d_host, d_host[b.cut[2]:].view(torch.float32).view(2, plan.n_rows, C)
-        row_base = plan.group_row_base[plan.files[:, 4]] + plan.row0
+            return d_host, d_host[b.cut[-1]:].view(torch.float32).view(2, plan.n_rows, C)
+        row_base = plan.group_row_base[b.group] + plan.row0
         zeros = self._dev("_pad_rows", lambda: torch.zeros((bitstream.ENCODE_ROW_ALIGN, C), dtype=torch.float32))
         pieces = [[], []]
         for f in np.argsort(row_base, kind="stable"):
@@ -1434,6 +1439,162 @@ class ChannelwisePriorCDFQuantizer:
         """`vae.encode(X)`, then compress_latents_to_bytes_mapped; `classes` is at latent resolution."""
         posterior_means, posterior_logvars = vae.encode(X)
         return self.compress_latents_to_bytes_mapped(posterior_means, posterior_logvars, lambs, classes, segment=segment)
+
+    # ------------------------------------------------------------------ batches of lambda maps, written (include/vbq.h, "Mapped
+    # batch encode").  The one-file call gives a workgroup the 64 consecutive segments of one stream and up to four tables to
+    # stage for them; here the segments of all files of a batch share workgroups, palette by palette.  Nothing routes here
+    # implicitly: one file stays with compress_latents_to_bytes_mapped.
+    _MappedBatch = namedtuple("_MappedBatch", "b groups palette_of cls max_classes")
+
+    def _mapped_batch_plan(self, latents, lambs, classes, segment):
+        """The host side of the mapped batch calls: every check of the one-file call per file (the file's index in the
+        message), the plan of bitstream.mapped_encode_plan and the ONE staging buffer of _batch_stage with the palettes int32
+        [G, 4] and the class bytes u8 [n_cls] after the items.  b.tables: the distinct lambdas of all palettes; groups: the
+        distinct palettes as tuples of keys, in order of first use.  None when there is no file."""
+        self._check_coder_bits()
+        bitstream.check_segment(segment)
+        segment = int(segment)
+        pairs, classes, lambs = list(latents), list(classes), list(lambs)
+        F, C = len(pairs), self.num_channels
+        if len(classes) != F:
+            raise ValueError(f"{len(classes)} class maps for {F} files")
+        scalar = [np.ndim(l) == 0 for l in lambs]
+        if all(scalar):
+            palettes = [lambs] * F                                # one palette for all files
+        elif any(scalar) or len(lambs) != F:
+            raise ValueError(f"`lambs` must be one palette (a sequence of numbers) or a sequence of {F} palettes, one per file")
+        else:
+            palettes = lambs
+        shapes = self._batch_file_shapes(pairs, segment)
+        if F == 0:
+            return None
+        groups, palette_of, cls = [], [], []
+        for f in range(F):
+            try:
+                keys, cl = self._map_inputs(pairs[f][0], palettes[f], classes[f])
+            except ValueError as e:
+                raise ValueError(f"file {f}: {e}") from None
+            except KeyError as e:
+                raise KeyError(f"file {f}: no entropy model for lambda {e.args[0]!r}") from None
+            keys = tuple(keys)
+            if keys not in groups:
+                groups.append(keys)
+            palette_of.append(groups.index(keys))
+            cls.append(cl)
+        tables = sorted({k for g in groups for k in g}, key=float)    # (a stable tag for the codec cache of _coder_stack)
+        digests = {k: self._coder_tables(k, segment)[1] for k in tables}
+        rows = [int(np.prod(sh[:-1], dtype=np.int64)) for sh in shapes]
+        plan = bitstream.mapped_encode_plan(rows, palette_of, [len(g) for g in groups], segment, C)
+        rows4 = plan.palettes.copy()
+        for g, keys in enumerate(groups):
+            rows4[g, :len(keys)] = [tables.index(k) for k in keys]
+        cls_bytes = np.zeros(plan.n_cls, np.uint8)
+        for f in range(F):
+            cls_bytes[int(plan.cls_base[f]): int(plan.cls_base[f]) + rows[f]] = cls[f]
+        b = self._batch_stage(plan, shapes, [groups[g] for g in palette_of], tables, digests, segment, rows, pairs,
+                              8 + 4 * plan.M + 4 * F, group=np.asarray(palette_of, np.int64),
+                              extra=(rows4.view(np.uint8).reshape(-1), cls_bytes))
+        return self._MappedBatch(b, groups, palette_of, cls, max(len(g) for g in groups))
+
+    def _mapped_batch_run(self, mb, d_host, lat, words: bool):
+        """The device side, after the one upload (_encode_batch_upload(mb.b) -> d_host, lat): per distinct palette one
+        vbq_prep_planes_f32 and one solve of its files' rows at its P lambdas into its [P, C, B_g] planes of the one index
+        array, then ONE vbq_rans_map_encode_files_u16 and ONE vbq_rans_pack_u16 (words=True) or ONE
+        vbq_rans_map_sizes_files_u16 -> the payload u16 or None; total, sizes and status land in d_host[:b.back].  Nothing is
+        read back."""
+        from . import _lib
+        b = mb.b
+        plan, C, N, segment, cut = b.plan, self.num_channels, self.max_bits_per_coord, b.segment, b.cut
+        dev, F, M = d_host.device, len(b.keys), plan.M
+        d_total, d_sizes = d_host[:8].view(torch.uint64), d_host[8:8 + 4 * M].view(torch.uint32)
+        d_status = d_host[8 + 4 * M:b.back].view(torch.uint32)
+        d_files = d_host[cut[0]:cut[1]].view(torch.int64).view(F, bitstream.MAPPED_ENCODE_FIELDS)
+        d_items = d_host[cut[1]:cut[2]].view(torch.int32).view(-1, 2)
+        d_palettes = d_host[cut[2]:cut[3]].view(torch.int32).view(-1, bitstream.MAX_CLASSES)
+        d_cls = d_host[cut[3]:cut[4]]
+        idx = torch.empty(plan.n_idx, dtype=torch.uint16, device=dev)
+        for g, keys in enumerate(mb.groups):
+            r0, B, P, i0 = int(plan.group_row_base[g]), int(plan.group_rows[g]), len(keys), int(plan.group_idx_base[g])
+            mu_cb, sg_cb = self._prep(lat[0, r0:r0 + B], lat[1, r0:r0 + B], spread="logvar")
+            self._solve_idx(mu_cb, sg_cb, list(keys), self._level_len_dev(list(keys)),
+                            out_idx=idx[i0:i0 + P * C * B].view(P, C, B))
+        canon = None if self._strict else self._dev("canon_u16", lambda: torch.from_numpy(self._canon.astype(np.uint16)))
+        freq = self._coder_stack(b.tables, segment)._freq(dev).view(len(b.tables), C, -1)
+        if not words:
+            ops.rans_map_sizes_files(idx, d_cls, d_files, d_palettes, d_items, freq, M, seg=segment, max_classes=mb.max_classes,
+                                     N=N, canon=canon, sizes=d_sizes, status=d_status)
+            return None
+        buf = torch.empty((M, segment + 2), dtype=torch.uint16, device=dev)           # pack reads valid words only
+        payload = torch.empty(M * (segment + 2), dtype=torch.uint16, device=dev)
+        offsets = torch.empty(M, dtype=torch.int64, device=dev)
+        ops.rans_map_encode_files(idx, d_cls, d_files, d_palettes, d_items, freq, M, seg=segment, max_classes=mb.max_classes,
+                                  N=N, canon=canon, words=buf, sizes=d_sizes, status=d_status)
+        _lib.check(_lib.lib().vbq_rans_pack_u16(ops._ptr(buf), ops._ptr(d_sizes), 1, M * segment, segment, ops._ptr(payload),
+                                                ops._ptr(offsets), ops._ptr(d_total), ops._stream(buf)), "vbq_rans_pack_u16")
+        return payload
+
+    def _mapped_batch_back(self, mb, d_host):
+        """The first copy back -> (total, sizes u32 [M], the end of every file's words among all words int64 [F]); VBQError
+        naming the file whose descriptor the kernel refused."""
+        from . import _lib
+        plan, M = mb.b.plan, mb.b.plan.M
+        h = d_host[:mb.b.back].cpu().numpy()
+        total, sizes, status = int(h[:8].view(np.uint64)[0]), h[8:8 + 4 * M].view(np.uint32), h[8 + 4 * M:].view(np.uint32)
+        for f in np.flatnonzero(status):
+            raise _lib.VBQError(f"file {int(f)}: the mapped batch encoder refused its descriptor (status {int(status[f])})")
+        return total, sizes, np.cumsum(sizes, dtype=np.int64)[plan.seg_base + self.num_channels * plan.nseg - 1]
+
+    def compress_latents_to_bytes_mapped_batch(self, latents, lambs, classes, segment=1024):
+        """[compress_latents_to_bytes_mapped(means_f, logvars_f, lambs_f, classes[f], segment=segment) for f], byte for byte,
+        with ONE encode launch for all files.  `latents`: F pairs as compress_latents_to_bytes_batch takes them (any shapes,
+        NumPy or tensors, host or device).  `lambs`: one palette for all files (a sequence of 1..4 distinct built lambdas) or a
+        sequence of F palettes; palettes are grouped as ordered tuples, so (a, b) and (b, a) are two groups.  `classes`: a
+        sequence of F integer arrays, classes[f] shaped like file f's latents without the channel axis.  The table may have
+        repeated code points (the canonical map is applied to the staged tables: no int64 gather).  F == 0 returns [].
+        Errors are those of the one-file call, raised before any device work with the file's index in the message; also
+        ValueError for len(classes) != F, for a wrong number of palettes and for more than 65535 files.
+        Work per call, G the number of DISTINCT palettes: one staging buffer and one upload (the plan of
+        bitstream.mapped_encode_plan, zeroed sizes and status words, descriptors, items, palettes, class bytes and -- for
+        inputs that are not all device tensors -- the latents); per palette one vbq_prep_planes_f32 and one solve of its
+        files' rows at its P lambdas; ONE vbq_rans_map_encode_files_u16; ONE vbq_rans_pack_u16 (two launches): 2 G + 3
+        launches.  Two device-to-host copies: the total, all segment sizes and the status words, then the first `total`
+        payload words.  The files are assembled on the host (bitstream.MappedHeader / bitstream.write_mapped)."""
+        mb = self._mapped_batch_plan(latents, lambs, classes, segment)
+        if mb is None:
+            return []
+        b, plan, C = mb.b, mb.b.plan, self.num_channels
+        d_host, lat = self._encode_batch_upload(b)
+        payload = self._mapped_batch_run(mb, d_host, lat, words=True)
+        total, sizes, ends = self._mapped_batch_back(mb, d_host)
+        pay = payload[:total].cpu().numpy()
+        out = []
+        for f, keys in enumerate(b.keys):
+            n_words = int(ends[f] - (ends[f - 1] if f else 0))
+            hd = bitstream.MappedHeader(N=self.max_bits_per_coord, C=C, shape=b.shapes[f], segment=b.segment,
+                                        lambs=tuple(float(k) for k in keys), digests=tuple(b.digests[k] for k in keys),
+                                        n_words=n_words)
+            sz = sizes[int(plan.seg_base[f]): int(plan.seg_base[f] + C * plan.nseg[f])]
+            out.append(bitstream.write_mapped(hd, mb.cls[f], sz, pay[int(ends[f]) - n_words: int(ends[f])]))
+        return out
+
+    def compress_to_bytes_mapped_batch(self, Xs, vae, lambs, classes, segment=1024):
+        """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_bytes_mapped_batch; `classes` at latent resolution."""
+        return self.compress_latents_to_bytes_mapped_batch([vae.encode(X) for X in Xs], lambs, classes, segment=segment)
+
+    def coded_nbytes_mapped_batch(self, latents, lambs, classes, segment=1024) -> list:
+        """[coded_nbytes_mapped(means_f, logvars_f, lambs_f, classes[f], segment=segment) for f], exact, without building a
+        file: the plan, the upload and the solves of compress_latents_to_bytes_mapped_batch, ONE
+        vbq_rans_map_sizes_files_u16 (segment sizes only, no words) and one copy of the sizes and the status words back; the
+        lengths come from bitstream.mapped_nbytes.  Arguments and errors as compress_latents_to_bytes_mapped_batch."""
+        mb = self._mapped_batch_plan(latents, lambs, classes, segment)
+        if mb is None:
+            return []
+        d_host, lat = self._encode_batch_upload(mb.b)
+        self._mapped_batch_run(mb, d_host, lat, words=False)
+        _, _, ends = self._mapped_batch_back(mb, d_host)
+        n_words = np.diff(ends, prepend=0)
+        return [bitstream.mapped_nbytes(mb.b.shapes[f], self.num_channels, mb.b.segment, int(n_words[f]), len(keys))
+                for f, keys in enumerate(mb.b.keys)]
 
     def _decompress_latents_mapped(self, data, return_np):
         """decompress_latents of a lambda-map file: the digest of every class, the mapped decoder, the gather."""
