@@ -1140,6 +1140,60 @@ int vbq_rans_map_sizes_files_u16(const uint16_t *d_idx, int64_t n_idx, const uin
                                  int64_t M, uint32_t *d_status, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Mapped batch rates: the coded length of MANY lambda-map files under SEVERAL candidate palettes in ONE launch -- rate control
+ * over lambda maps.  "Batch sizes" with a frequency table per symbol, and vbq_rans_map_sizes_files_u16 with a candidate axis:
+ * the caller solves every distinct lambda of its candidates ONCE into one plane of indices per lambda, and a candidate is a
+ * list of 1..4 of those planes, one per class.  The work is listed as items (file, segment) in blocks of 64; a workgroup
+ * sizes one block of one channel under one candidate: it stages the candidate's tables once and its lanes take segments of
+ * different files, each following its own file's classes.  Every file is sized under every candidate.
+ *   d_idx      u16 [n_idx]: the rank indices of all files at all lambdas, one plane of lambda_stride indices per lambda.
+ *              Symbol i of channel c of file f under candidate k is d_idx[t * lambda_stride + idx_base_f + c * idx_stride_f + i]
+ *              with t = d_palettes[k][cls] and cls = d_cls[cls_base_f + i], 0 <= i < n_f.
+ *   d_cls      u8 [n_cls]: the class bytes, one per position of a file, shared by its channels and by all candidates.  A class
+ *              byte >= P of the candidate is coded as class 0, as in "Mapped batch encode": the caller checks its maps.
+ *   d_files    int64 [n_files][8], the mapped batch encoder's descriptors: idx_base, idx_stride, n and cls_base are read;
+ *              plane_stride, seg_base, palette and the reserved field are ignored (a plan with every file in one palette group
+ *              serves).  The file has nseg_f = ceil(n / seg) segments per channel.
+ *   d_palettes int32 [n_palettes][4]: per candidate the planes of d_idx -- and the blocks of d_freq -- of its classes, class 0
+ *              first; the first -1 ends the row (P = the entries before it, 1..4; what follows it is not read).  Candidates may
+ *              share planes, and the same planes in another order are another candidate.
+ *   max_classes  the largest P of the candidates, 1..4: the launch's dynamic LDS is max_classes tables of 8 KB (at most 32 KB).
+ *   d_items    int32 [n_items][2]: (file, segment within a stream), n_items a multiple of 64, exactly as in "Batch sizes": the
+ *              files of a block need share nothing, file == -1 is padding and skipped silently, and the same item serves
+ *              every channel and every candidate.
+ *   d_freq     u16 [n_lambda][n_ch][T], T = 2^(N+1) - 1, every entry >= 1, every row summing to 2^15: block t belongs to plane t.
+ *   d_canon    u16 [n_ch][T] or NULL, as in "Batch encode": applied once to every staged table, not per symbol.
+ *   d_totals   u64 [n_palettes][n_files], ADDED to: zero it first.  d_totals[k][f] grows, per listed segment and channel, by
+ *              exactly the d_sizes entry vbq_rans_map_sizes_files_u16 writes for the same symbols, classes and palette (the
+ *              renormalisation words + the two words of the final state); an index outside the table is coded as symbol 0.
+ *              One 64-bit atomic add per (candidate, channel, item); integer adds commute: the result does not depend on
+ *              scheduling.
+ *   d_status   u32 [n_files], may be NULL, OR-ed into; zero it first.  Bit 7 (128) for a file:
+ *                of the descriptor -- n < 1; symbols of some plane t < n_lambda and some channel outside [0, n_idx), that is
+ *                idx_base < 0, idx_stride < 0 or idx_base + (n_ch - 1) * idx_stride + n > n_idx - (n_lambda - 1) *
+ *                lambda_stride; classes outside [0, n_cls): nothing of that file is added, under any candidate;
+ *                of one item -- a segment id outside [0, nseg_f): that item adds nothing.
+ *              An item whose file id lies outside [0, n_files) (other than -1) adds nothing and sets bit 7 of word 0.
+ *              A defective candidate row -- a first entry of -1, an entry before the first -1 outside [0, n_lambda), or more
+ *              classes than max_classes -- sets bit 7 of every listed file of its blocks and adds nothing to its row of
+ *              d_totals; the other rows are not affected.
+ * Descriptors, candidate rows and items are range-checked on the device, without overflow, before anything is indexed with
+ * them.  A lane walks its segment exactly as in "Mapped batch encode" (one copy of the device code serves both): eight classes
+ * per 8-byte load where the class address allows it and, when the eight agree and that class's plane is 16-byte aligned there,
+ * their symbols in one 16-byte load; narrow loads otherwise: the totals do not depend on the alignment.
+ * Checked before any device work (VBQ_ERR_INVALID_ARGUMENT): n_files <= 65535, n_ch <= 65535, seg in 1..65533, N in 1..10,
+ * n_lambda in 1..65535, n_palettes in 1..65535, max_classes in 1..4, every size >= 0 (n_cls and lambda_stride too), n_items a
+ * multiple of 64, n_lambda * lambda_stride <= n_idx (tested without forming the product), no null pointer (d_canon and d_status
+ * excepted).  n_files == 0, n_items == 0 or n_ch == 0 return VBQ_OK with no launch.
+ * Added without an ABI version bump: nothing that existed before changed.
+ * ---------------------------------------------------------------------------------- */
+int vbq_rans_map_rates_files_u16(const uint16_t *d_idx, int64_t n_idx, int64_t lambda_stride, const uint8_t *d_cls, int64_t n_cls,
+                                 const int64_t *d_files, int32_t n_files, const int32_t *d_palettes, int32_t n_palettes,
+                                 int32_t max_classes, const int32_t *d_items, int64_t n_items, int32_t n_ch, int32_t seg,
+                                 int32_t N, const uint16_t *d_freq, int32_t n_lambda, const uint16_t *d_canon,
+                                 uint64_t *d_totals, uint32_t *d_status, void *stream);
+
+/* ----------------------------------------------------------------------------------
  * Compact batch: the parts of MANY compact latent files (vbq_amd/bitstream.py, magic "VBQc") sized, written or read in ONE
  * launch each.  vbq_rans_il_sizes_u16 / _encode_u16 / _decode_u16 give a wave one part of ONE tensor: a small file has a few
  * parts, so a few waves run and the call takes the time of one wave's steps.  Here the caller lists the work as items

@@ -774,6 +774,57 @@ def mapped_encode_plan(rows, palettes, palette_sizes, segment, C) -> MappedEncod
                             np.ascontiguousarray(files, dtype=np.int64), np.ascontiguousarray(rows4), base.items)
 
 
+# ---- byte budgets over lambda maps (ChannelwisePriorCDFQuantizer.coded_nbytes_mapped_palettes_batch and the budget calls over
+# it; include/vbq.h, "Mapped batch rates").  A budget call takes an ordered list of candidate palettes of one size P and keeps,
+# per file, the FIRST candidate of the list whose file fits (smallest_rates_within(..., name="palette")): palettes have no natural
+# order, so the order is the caller's.
+def palette_ladder(lambs, steps):
+    """The usual list of candidates: the relative quality between the classes held fixed while the whole palette slides up a
+    ladder of lambdas.  lambs: the ladder, sorted ascending; steps: P (1..MAX_CLASSES) distinct non-negative integers, the rung
+    of every class above the candidate's first.  Candidate j is tuple(lambs[j + s] for s in steps), for j = 0 .. len(lambs) - 1
+    - max(steps).  ValueError for an empty result, repeated or negative steps, a ladder that is not ascending or P outside
+    1..MAX_CLASSES."""
+    lambs = [float(l) for l in lambs]
+    for s in steps:
+        if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)):
+            raise ValueError(f"steps must be integers, got {s!r}")
+    steps = [int(s) for s in steps]
+    if not 1 <= len(steps) <= MAX_CLASSES:
+        raise ValueError(f"{len(steps)} steps: a palette has 1..{MAX_CLASSES} lambdas")
+    if min(steps) < 0:
+        raise ValueError(f"negative step in {steps}")
+    if len(set(steps)) != len(steps):
+        raise ValueError(f"repeated step in {steps}: the lambdas of a palette are distinct")
+    if any(b <= a for a, b in zip(lambs, lambs[1:])):
+        raise ValueError("the ladder of lambdas must be sorted ascending, without repeats")
+    count = len(lambs) - max(steps)
+    if count < 1:
+        raise ValueError(f"a ladder of {len(lambs)} lambdas has no candidate with steps {steps}")
+    return [tuple(lambs[j + s] for s in steps) for j in range(count)]
+
+
+def candidate_chunks(rows, max_tables):
+    """Cut a list of candidates into runs that can be sized from one solve.  rows: int [K, P], the candidates as indices into
+    the L distinct lambdas; max_tables: how many lambdas one solve may hold.  Yields (k0, k1, tables): greedy runs [k0, k1) of
+    consecutive candidates whose distinct lambdas -- tables, a sorted list -- number at most max_tables.  A chunk always holds
+    at least one candidate, so a single candidate may bring up to P tables whatever the cap.  Every candidate is yielded once,
+    in order."""
+    rows = np.asarray(rows, dtype=np.int64)
+    if rows.ndim != 2:
+        raise ValueError(f"rows must be [K, P], got shape {rows.shape}")
+    max_tables = int(max_tables)
+    K = rows.shape[0]
+    k0 = 0
+    while k0 < K:
+        tables = set(rows[k0].tolist())
+        k1 = k0 + 1
+        while k1 < K and len(tables | set(rows[k1].tolist())) <= max_tables:
+            tables |= set(rows[k1].tolist())
+            k1 += 1
+        yield k0, k1, sorted(tables)
+        k0 = k1
+
+
 def parse_mapped(data) -> Tuple[MappedHeader, np.ndarray, np.ndarray, int]:
     """bytes -> (header, classes u8 [B], sizes u16 [C * nseg] (a read-only view into `data`), byte offset of the payload).
     ValueError on anything malformed."""

@@ -22,7 +22,8 @@ INCLUDE = os.path.join(ROOT, "include")
 HIP_SOURCES = ["vbq_api.hip", "vbq_quantize.hip", "vbq_quantize_fast.hip", "vbq_hist.hip", "vbq_notebook.hip", "vbq_bmshj.hip",
                "vbq_candidates.hip", "vbq_latents.hip", "vbq_host.hip", "vbq_rans.hip", "vbq_comm.hip", "vbq_xi.hip", "vbq_baselines.hip", "vbq_ranks.hip", "vbq_metrics.hip",
                "vbq_budget.hip", "vbq_reduce.hip", "vbq_transpose.hip", "vbq_rans_il.hip", "vbq_records.hip", "vbq_topk.hip", "vbq_bag.hip", "vbq_rans_map.hip", "vbq_rans_window.hip", "vbq_rans_map_window.hip",
-               "vbq_rans_files.hip", "vbq_rans_sizes_files.hip", "vbq_rans_il_files.hip", "vbq_rans_map_files.hip"]
+               "vbq_rans_files.hip", "vbq_rans_sizes_files.hip", "vbq_rans_il_files.hip", "vbq_rans_map_files.hip",
+               "vbq_rans_map_rates_files.hip"]
 LINK_LIBS = ["-ldl"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                # every f32/f64 op of the reference is a separately rounded op: never contract a*b+c

@@ -9,8 +9,8 @@
 // and a workgroup takes one block of one channel: it stages the palette's tables once and its lanes code segments of DIFFERENT
 // files, each following its own file's class bytes.  One lane codes one item in full, last symbol to first: the words and the
 // size of a segment are those of k_rans_map_encode.  The constants, the per-symbol step, the table staging and the canon map
-// are vbq_rans_common.h's.
-#include "vbq_rans_common.h"
+// are vbq_rans_common.h's; the walk of a lane over its segment is vbq_rans_map_common.h's.
+#include "vbq_rans_map_common.h"
 
 namespace vbq {
 namespace {
@@ -132,37 +132,8 @@ __global__ void __launch_bounds__(kMapFilesThreads) k_rans_map_encode_files(cons
         }
         x = rans_push(x, fr, cu);
     };
-    auto cls_of = [&](unsigned v) -> unsigned { return v < (unsigned)P ? v : 0u; };   // (a class outside the palette: class 0)
-    long i = hi;
-    // the tail down to an 8-byte boundary of the classes by narrow loads, then eight classes per 8-byte load -- and, when the
-    // eight agree and that class's plane is 16-byte aligned there, their symbols in one 16-byte load --, then the head: the same
-    // symbols in the same order whatever the alignment of the file
-    while (i > lo && reinterpret_cast<uintptr_t>(cl + i) % 8 != 0) {
-        --i;
-        const unsigned p = cls_of(cl[i]);
-        put(src[p * plane + i], p);
-    }
-    for (; i - 8 >= lo; i -= 8) {
-        const uint2 cv = *reinterpret_cast<const uint2 *>(cl + i - 8);
-        const unsigned c0 = cv.x & 0xffu;
-        const unsigned p0 = cls_of(c0);
-        const uint16_t *s8 = src + p0 * plane + i - 8;
-        if (cv.x == c0 * 0x01010101u && cv.y == cv.x && reinterpret_cast<uintptr_t>(s8) % 16 == 0) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(s8);
-            put(v.w >> 16, p0); put(v.w & 0xffffu, p0); put(v.z >> 16, p0); put(v.z & 0xffffu, p0);
-            put(v.y >> 16, p0); put(v.y & 0xffffu, p0); put(v.x >> 16, p0); put(v.x & 0xffffu, p0);
-        } else {
-#pragma unroll
-            for (int j = 7; j >= 0; --j) {
-                const unsigned p = cls_of(((j < 4 ? cv.x : cv.y) >> (8 * (j & 3))) & 0xffu);
-                put(src[p * plane + i - 8 + j], p);
-            }
-        }
-    }
-    for (--i; i >= lo; --i) {
-        const unsigned p = cls_of(cl[i]);
-        put(src[p * plane + i], p);
-    }
+    // (the order of the symbols and the width of the loads: map_segment_walk, shared with the rates kernel)
+    map_segment_walk(cl, lo, hi, P, [&](unsigned p) { return src + p * plane; }, put);
     if (kWords) {
         out[k] = (uint16_t)(x & 0xffffu);
         out[k + 1] = (uint16_t)(x >> 16);

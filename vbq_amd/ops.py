@@ -1123,6 +1123,57 @@ def rans_map_sizes_files(idx: torch.Tensor, classes: torch.Tensor, files: torch.
     return sizes, status
 
 
+def rans_map_rates_files(idx: torch.Tensor, classes: torch.Tensor, files: torch.Tensor, palettes: torch.Tensor,
+                         items: torch.Tensor, freq: torch.Tensor, *, lambda_stride: int, seg: int, max_classes: int,
+                         N: int = 10, canon: Optional[torch.Tensor] = None, totals: Optional[torch.Tensor] = None,
+                         status: Optional[torch.Tensor] = None):
+    """vbq_rans_map_rates_files_u16 (include/vbq.h, "Mapped batch rates"): the coded words of every file under every candidate
+    palette in one launch -- rans_sizes_files with a table per symbol.  idx u16 [n_idx], the rank indices of all files, one
+    plane of lambda_stride indices per lambda; classes u8 [n_cls], the files' class bytes; files int64 [F, 8] and items int32
+    [n_items, 2] as rans_map_encode_files takes them (idx_base, idx_stride, n and cls_base are read; a block's files need share
+    nothing); palettes int32 [K, 4], per candidate the planes of idx (= the blocks of freq) of its classes, class 0 first, -1
+    past P; freq u16 [L, C, T]; canon u16 [C, T] or None; max_classes the largest P of the candidates, 1..4.  Returns (totals
+    u64 [K, F], status u32 [F]): totals[k, f] grows by the words of every listed segment of every channel of file f under
+    candidate k.  `totals` is added to and `status` OR-ed into: zeroed here unless given."""
+    idx = _dev(idx, torch.uint16, "idx")
+    classes = _dev(classes, torch.uint8, "classes")
+    files = _dev(files, torch.int64, "files")
+    palettes = _dev(palettes, torch.int32, "palettes")
+    items = _dev(items, torch.int32, "items")
+    freq = _dev(freq, torch.uint16, "freq")
+    seg, N, lambda_stride = int(seg), int(N), int(lambda_stride)
+    T = table_size(N)
+    if files.dim() != 2 or files.shape[1] != 8:
+        raise ValueError("files must be [F, 8] (idx_base, idx_stride, plane_stride, n, seg_base, palette, cls_base, 0), got "
+                         f"{tuple(files.shape)}")
+    if palettes.dim() != 2 or palettes.shape[1] != 4:
+        raise ValueError(f"palettes must be [K, 4] (planes, class 0 first, -1 past P), got {tuple(palettes.shape)}")
+    if items.dim() != 2 or items.shape[1] != 2:
+        raise ValueError(f"items must be [n_items, 2] (file, segment), got {tuple(items.shape)}")
+    if freq.dim() != 3 or freq.shape[2] != T:
+        raise ValueError(f"expected freq [L, C, {T}], got {tuple(freq.shape)}")
+    F, K, L, n_ch = files.shape[0], palettes.shape[0], freq.shape[0], freq.shape[1]
+    if canon is not None:
+        canon = _dev(canon, torch.uint16, "canon")
+        if tuple(canon.shape) != (n_ch, T):
+            raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
+    if totals is None:
+        totals = torch.zeros((K, F), dtype=torch.int64, device=idx.device).view(torch.uint64)
+    else:
+        totals = _out(totals, (K, F), torch.uint64, idx.device, "totals")
+    if status is None:
+        status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
+    else:
+        status = _dev(status, torch.uint32, "status")
+        if status.numel() != F:
+            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+    check(_lib.lib().vbq_rans_map_rates_files_u16(_ptr(idx), idx.numel(), lambda_stride, _ptr(classes), classes.numel(),
+                                                  _ptr(files), F, _ptr(palettes), K, int(max_classes), _ptr(items), items.shape[0],
+                                                  n_ch, seg, N, _ptr(freq), L, _ptr(canon), _ptr(totals), _ptr(status),
+                                                  _stream(idx)), "vbq_rans_map_rates_files_u16")
+    return totals, status
+
+
 # ---- batches of compact files (include/vbq.h, "Compact batch"): one wave per (file, part)
 def _il_files_args(idx, files, items, freq, N, status):
     """What the three compact-batch calls check alike -> (idx, files, items, freq, status, F, n_tables, n_ch)."""

@@ -1596,6 +1596,172 @@ class ChannelwisePriorCDFQuantizer:
         return [bitstream.mapped_nbytes(mb.b.shapes[f], self.num_channels, mb.b.segment, int(n_words[f]), len(keys))
                 for f, keys in enumerate(mb.b.keys)]
 
+    # ------------------------------------------------------------------ byte budgets over lambda maps (include/vbq.h, "Mapped
+    # batch rates").  The caller gives an ORDERED list of K candidate palettes, each of the same P distinct built lambdas
+    # (bitstream.palette_ladder builds the usual one), and one class map per file; a budget call keeps the FIRST candidate of
+    # the list whose exact file length fits -- palettes have no natural order, and no monotonicity is assumed.  Every distinct
+    # lambda of the candidates is solved once and ONE launch sizes every file under every candidate.  Nothing routes here
+    # implicitly.
+    def _mapped_palettes_inputs(self, latents, palettes, classes, segment):
+        """Every check of the calls below, before any device work -> (pairs, shapes, candidates as K tuples of P keys, the
+        class maps as F u8 arrays, the class maps as given, segment)."""
+        self._check_coder_bits()
+        bitstream.check_segment(segment)
+        pairs, classes = list(latents), list(classes)
+        F, C = len(pairs), self.num_channels
+        if len(classes) != F:
+            raise ValueError(f"{len(classes)} class maps for {F} files")
+        given = list(palettes)
+        if not given:
+            raise ValueError("no candidate palette to choose from")
+        if any(np.ndim(p) != 1 for p in given):
+            raise ValueError("`palettes` must be a sequence of candidate palettes, each a sequence of lambdas")
+        nothing = (np.zeros((0, C), np.float32), np.zeros(0, np.int64))
+        cands = []
+        for k, pal in enumerate(given):
+            if len(pal) != len(given[0]):
+                raise ValueError(f"palette {k}: {len(pal)} lambdas, palette 0 has {len(given[0])}: the candidates of one call "
+                                 "have one size")
+            try:
+                cands.append(tuple(self._map_inputs(nothing[0], pal, nothing[1])[0]))      # (the palette's own checks)
+            except ValueError as e:
+                raise ValueError(f"palette {k}: {e}") from None
+            except KeyError as e:
+                raise KeyError(f"palette {k}: no entropy model for lambda {e.args[0]!r}") from None
+        shapes = self._batch_file_shapes(pairs, segment)
+        cls = []
+        for f in range(F):
+            try:
+                cls.append(self._map_inputs(pairs[f][0], cands[0], classes[f])[1])           # (the classes: P alone matters)
+            except ValueError as e:
+                raise ValueError(f"file {f}: {e}") from None
+        return pairs, shapes, cands, cls, classes, int(segment)
+
+    def _coded_nbytes_mapped_palettes(self, pairs, shapes, cands, cls, segment):
+        """(nbytes int64 [F, K] with nbytes[f, k] = the exact lambda-map file length of latent f under cands[k], the F latents
+        as pairs of device tensors shaped like the inputs): ONE plan with every file in one palette group
+        (bitstream.mapped_encode_plan), ONE upload as the batch encoder's (zeroed totals u64 [K, F] and status u32 [F],
+        descriptors, items, candidate rows, class bytes and -- unless every input is a device tensor -- the latents), one
+        vbq_prep_planes_f32 of all R rows, then per chunk of candidates (bitstream.candidate_chunks with max(1,
+        RATE_SCRATCH_BYTES // (2 C R)) tables) one solve of the chunk's distinct lambdas into [L_chunk, C, R] and ONE
+        vbq_rans_map_rates_files_u16, and one copy of the totals and the status words back."""
+        from . import _lib
+        F, K, P, C, N, dev = len(pairs), len(cands), len(cands[0]), self.num_channels, self.max_bits_per_coord, self.device
+        rows = [int(np.prod(sh[:-1], dtype=np.int64)) for sh in shapes]
+        plan = bitstream.mapped_encode_plan(rows, [0] * F, [P], segment, C)
+        R = plan.n_rows
+        lambs = sorted({k for cand in cands for k in cand}, key=float)                         # the L distinct lambdas
+        chunks = list(bitstream.candidate_chunks([[lambs.index(k) for k in cand] for cand in cands],
+                                                 max(1, RATE_SCRATCH_BYTES // (2 * C * R))))
+        rows4 = np.full((K, bitstream.MAX_CLASSES), -1, np.int32)                              # planes of the candidate's own chunk
+        for k0, k1, tables in chunks:
+            rows4[k0:k1, :P] = [[tables.index(lambs.index(k)) for k in cand] for cand in cands[k0:k1]]
+        cls_bytes = np.zeros(plan.n_cls, np.uint8)
+        for f in range(F):
+            cls_bytes[int(plan.cls_base[f]): int(plan.cls_base[f]) + rows[f]] = cls[f]
+        b = self._batch_stage(plan, shapes, cands, None, None, segment, rows, pairs, 8 * K * F + 4 * F,
+                              group=np.zeros(F, np.int64), extra=(rows4.view(np.uint8).reshape(-1), cls_bytes))
+        d_host, lat = self._encode_batch_upload(b)
+        cut = b.cut
+        d_totals = d_host[:8 * K * F].view(torch.uint64).view(K, F)
+        d_status = d_host[8 * K * F:b.back].view(torch.uint32)
+        d_files = d_host[cut[0]:cut[1]].view(torch.int64).view(F, bitstream.MAPPED_ENCODE_FIELDS)
+        d_items = d_host[cut[1]:cut[2]].view(torch.int32).view(-1, 2)
+        d_rows4 = d_host[cut[2]:cut[3]].view(torch.int32).view(K, bitstream.MAX_CLASSES)
+        d_cls = d_host[cut[3]:cut[4]]
+        canon = None if self._strict else self._dev("canon_u16", lambda: torch.from_numpy(self._canon.astype(np.uint16)))
+        mu_cb, sg_cb = self._prep(lat[0], lat[1], spread="logvar")
+        for k0, k1, tables in chunks:
+            ks = [lambs[t] for t in tables]
+            idx = self._solve_idx(mu_cb, sg_cb, ks, self._level_len_dev(ks))                   # [L_chunk, C, R]
+            freq = self._coder_stack(ks, segment)._freq(dev).view(len(ks), C, -1)
+            ops.rans_map_rates_files(idx.view(-1), d_cls, d_files, d_rows4[k0:k1], d_items, freq, lambda_stride=C * R,
+                                     seg=segment, max_classes=P, N=N, canon=canon, totals=d_totals[k0:k1], status=d_status)
+        h = d_host[:b.back].cpu().numpy()
+        totals, status = h[:8 * K * F].view(np.uint64).reshape(K, F), h[8 * K * F:].view(np.uint32)
+        for f in np.flatnonzero(status):
+            raise _lib.VBQError(f"file {int(f)}: the mapped rates kernel refused its descriptor (status {int(status[f])})")
+        nbytes = np.array([[bitstream.mapped_nbytes(shapes[f], C, segment, int(totals[k, f]), P) for k in range(K)]
+                           for f in range(F)], dtype=np.int64).reshape(F, K)
+        on_dev = [tuple(lat[w, int(plan.row0[f]):int(plan.row0[f]) + rows[f]].view(shapes[f]) for w in (0, 1)) for f in range(F)]
+        return nbytes, on_dev
+
+    def coded_nbytes_mapped_palettes_batch(self, latents, palettes, classes, segment=1024) -> np.ndarray:
+        """int64 [F, K]: entry [f, k] == coded_nbytes_mapped(means_f, logvars_f, palettes[k], classes[f], segment=segment),
+        exact, with every distinct lambda of the candidates solved ONCE and ONE vbq_rans_map_rates_files_u16 launch for all
+        files and candidates (per chunk of candidates: see _coded_nbytes_mapped_palettes).  `latents`: F pairs as
+        compress_latents_to_bytes_mapped_batch takes them; `palettes`: K >= 1 candidates, each a sequence of the same P
+        (1..4) distinct built lambdas, in the caller's order -- (a, b) and (b, a) are two candidates; `classes`: F integer
+        arrays in [0, P), classes[f] shaped like file f's latents without the channel axis.  F == 0 returns an empty [0, K]
+        array.  Errors before any device work: those of compress_latents_to_bytes_mapped per candidate ("palette k: ...":
+        a size outside 1..4, a repeated lambda; KeyError for a lambda without a model) and per file ("file f: ...": a bad
+        shape pair, classes of the wrong shape or dtype or outside [0, P)); ValueError for candidates of unequal length, for no
+        candidate, for len(classes) != F, for a bad `segment` and for more than 65535 files."""
+        pairs, shapes, cands, cls, _, segment = self._mapped_palettes_inputs(latents, palettes, classes, segment)
+        if not pairs:
+            return np.zeros((0, len(cands)), np.int64)
+        return self._coded_nbytes_mapped_palettes(pairs, shapes, cands, cls, segment)[0]
+
+    def compress_latents_to_budget_mapped_batch(self, latents, max_bytes, palettes, classes, segment=1024) -> list:
+        """F lambda-map files: file f is, byte for byte, compress_latents_to_bytes_mapped(means_f, logvars_f, palettes[k_f],
+        classes[f], segment=segment) with k_f the FIRST candidate of `palettes` whose exact length is within the file's
+        budget.  `max_bytes`: one integer >= 1 for all files or a sequence of F.  The lengths come from
+        coded_nbytes_mapped_palettes_batch's one rates launch, the files from compress_latents_to_bytes_mapped_batch on the
+        latents already on the device with every file's chosen palette (its solves cover only the chosen palettes).
+        ValueError (bitstream.smallest_rates_within) naming the first file that no candidate fits, before anything is
+        encoded.  F == 0 returns []."""
+        budgets = bitstream.check_budgets(max_bytes)
+        pairs, shapes, cands, cls, classes, segment = self._mapped_palettes_inputs(latents, palettes, classes, segment)
+        if budgets is not None and len(budgets) != len(pairs):
+            raise ValueError(f"{len(budgets)} budgets for {len(pairs)} files")
+        if not pairs:
+            return []
+        nbytes, on_dev = self._coded_nbytes_mapped_palettes(pairs, shapes, cands, cls, segment)
+        cols = bitstream.smallest_rates_within(nbytes, max_bytes if budgets is None else budgets, name="palette")
+        return self.compress_latents_to_bytes_mapped_batch(on_dev, [list(cands[c]) for c in cols], classes, segment=segment)
+
+    def compress_latents_to_total_budget_mapped(self, latents, max_total_bytes, palettes, classes, segment=1024):
+        """(k, files): ONE candidate for all files -- the first of `palettes` under which the F files together take at most
+        max_total_bytes -- and files == compress_latents_to_bytes_mapped_batch(latents, palettes[k], classes, segment).
+        ValueError for no files, or naming the smallest achievable total and its candidate when nothing fits."""
+        budget = bitstream.check_budget(max_total_bytes)
+        pairs, shapes, cands, cls, classes, segment = self._mapped_palettes_inputs(latents, palettes, classes, segment)
+        if not pairs:
+            raise ValueError("no files: a total budget needs at least one")
+        nbytes, on_dev = self._coded_nbytes_mapped_palettes(pairs, shapes, cands, cls, segment)
+        sums = nbytes.sum(axis=0)
+        fits = np.flatnonzero(sums <= budget)
+        if not fits.size:
+            raise ValueError(f"no palette fits in {budget} bytes in total: the smallest total is {int(sums.min())} bytes, at "
+                             f"palette {int(np.argmin(sums))}")
+        k = int(fits[0])
+        return k, self.compress_latents_to_bytes_mapped_batch(on_dev, list(cands[k]), classes, segment=segment)
+
+    def coded_nbytes_mapped_palettes(self, posterior_means, posterior_logvars, palettes, classes, segment=1024) -> list:
+        """[coded_nbytes_mapped(posterior_means, posterior_logvars, p, classes, segment=segment) for p in palettes], K ints:
+        coded_nbytes_mapped_palettes_batch for one file."""
+        return [int(v) for v in self.coded_nbytes_mapped_palettes_batch([(posterior_means, posterior_logvars)], palettes,
+                                                                        [classes], segment=segment)[0]]
+
+    def compress_latents_to_budget_mapped(self, posterior_means, posterior_logvars, max_bytes, palettes, classes,
+                                          segment=1024) -> bytes:
+        """The lambda-map file of the first candidate of `palettes` whose exact length is <= max_bytes:
+        compress_latents_to_budget_mapped_batch for one file."""
+        bitstream.check_budget(max_bytes)
+        return self.compress_latents_to_budget_mapped_batch([(posterior_means, posterior_logvars)], max_bytes, palettes,
+                                                            [classes], segment=segment)[0]
+
+    def compress_to_budget_mapped(self, X, vae, max_bytes, palettes, classes, segment=1024) -> bytes:
+        """`vae.encode(X)`, then compress_latents_to_budget_mapped; `classes` is at latent resolution."""
+        posterior_means, posterior_logvars = vae.encode(X)
+        return self.compress_latents_to_budget_mapped(posterior_means, posterior_logvars, max_bytes, palettes, classes,
+                                                      segment=segment)
+
+    def compress_to_budget_mapped_batch(self, Xs, vae, max_bytes, palettes, classes, segment=1024) -> list:
+        """`vae.encode(X)` for every X of `Xs`, then compress_latents_to_budget_mapped_batch; `classes` at latent resolution."""
+        return self.compress_latents_to_budget_mapped_batch([vae.encode(X) for X in Xs], max_bytes, palettes, classes,
+                                                            segment=segment)
+
     def _decompress_latents_mapped(self, data, return_np):
         """decompress_latents of a lambda-map file: the digest of every class, the mapped decoder, the gather."""
         h, classes, _, _ = bitstream.parse_mapped(data)
