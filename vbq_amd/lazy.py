@@ -88,7 +88,10 @@ class HostStager:
             h = self.blocks[stack.name] = torch.empty(max(t.numel(), 1), dtype=t.dtype, pin_memory=True)
         st = torch.cuda.current_stream(t.device)
         if stack.stream is not None and stack.stream != st.cuda_stream:
-            st.wait_stream(torch.cuda.ExternalStream(stack.stream, device=t.device))      # produced on another stream
+            # produced on another stream.  Handle 0 is the default stream and has to be named as such: a wait on
+            # ExternalStream(0) orders nothing (measured: a copy behind it reads what the default stream has not yet written)
+            st.wait_stream(torch.cuda.default_stream(t.device) if stack.stream == 0 else
+                           torch.cuda.ExternalStream(stack.stream, device=t.device))
             # ... and tell the caching allocator that this stream reads the block: a stack dropped while a prefetched copy is
             # still queued must not have its memory handed out again (on the producing stream) before the copy has run
             t.record_stream(st)
