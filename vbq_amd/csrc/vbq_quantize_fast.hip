@@ -36,6 +36,7 @@
 #include <stddef.h>
 
 #include "vbq_common.h"
+#include "vbq_index_planes.h"
 #include "vbq_sweep.h"
 
 namespace vbq {
@@ -52,6 +53,12 @@ constexpr int kFastThreads = 256;
 #define VBQ_SLOW_INLINE __noinline__
 #endif
 constexpr int kFastNE = VBQ_FAST_NE;      // elements per thread: 4 (16-B loads) or 2 (8-B loads)
+// 1: the lambda loop of k_quant_fast without six instructions the answers do not need (an address copy, a 64-bit pointer add, a
+// second tie compare, two masks and a shift-or: see its phase B; two elements per thread only); 0: the loop as it was
+#ifndef VBQ_K1_TRIM
+#define VBQ_K1_TRIM 1
+#endif
+constexpr bool kK1Trim = VBQ_K1_TRIM != 0 && VBQ_FAST_NE == 2;
 
 // Correctly rounded f32 quotient d / sigma without an f32 division: RN32(RN64(d * RN64(1/sigma))).
 // The f64 product is within 2^-52 (relative) of the true quotient, and a quotient of two f32 numbers
@@ -163,7 +170,9 @@ __device__ VBQ_SLOW_INLINE uint32_t exact_rank_scan(const float *tb, float z, fl
 // first entropy-model pass needs: no 2 B per solve written, no K2 pass reading them back.  The LDS column that
 // parks the packed rank / gap words in modes 0 / 1 holds the counters instead: [L][N+1] x 32 sixteen-bit copies
 // (16 words x 2 halves per (lambda, level); lane & 15 picks the word, lane & 16 the half).
-template <int N, int MODE>
+// BUF (MODE 0 only): every index plane of the launch ends within 4 GB of out_idx (index_planes_within_4gb, the launcher asks):
+// the full-pair store goes through one buffer descriptor with the plane's byte offset as the instruction's scalar offset.
+template <int N, int MODE, bool BUF = false>
 __global__ void __launch_bounds__(kFastThreads, VBQ_FAST_WAVES)
 k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_per_ch, long ch_stride, int C,
              const float *__restrict__ table, Lambdas32 lam, const float *__restrict__ len,
@@ -237,6 +246,12 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
     if (q0 < nquads) load_group(q0, mn, sn);
     const bool resident = (vec_ok & 4) != 0;                // the launcher sized the grid to the resident workgroups
     unsigned int rot = wave_slot();
+    // The penalty row's LDS address lives in a vector register and advances by the row pitch (a 2-cycle add): as a function of
+    // the scalar loop counter it was copied into one with a 4-cycle v_mov from an SGPR at every lambda.
+    uint32_t prow0 = 0;
+    asm volatile("" : "+v"(prow0));
+    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(out_idx, 0, -1 /* 4 GB */, 0x00020000);
+    const uint32_t plane_bytes = (uint32_t)(2 * E);
     for (long q = q0; q < nquads; q += qstep) {
         if (resident) __builtin_amdgcn_s_setprio(3);          // phase A (a chain of LDS round trips) goes first
         const long i0 = q * NE;
@@ -308,11 +323,27 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
             set_issue_priority(rot);                            // with three (0..2 under phase A's) two of the four waves always
             rot += 3u;                                          // shared a level and age decided between them: 350 -> 335 us
         }
-        for (int l = 0; l < L; ++l) {
-            const float *pp = penl + l * PS;
-            float p[N1];
+        // A lane whose level-0 distortion is not a number (mu or sigma is not) takes the literal scan at every lambda: the
+        // merged tie test below counts the two elements' masks together, and only a solve with no number among its costs
+        // could hide a neighbour's tie from that count.
+        uint64_t nan0[NE];
 #pragma unroll
-            for (int n = 0; n < N1; ++n) p[n] = pp[n];
+        for (int k = 0; k < NE; ++k) nan0[k] = kK1Trim ? __builtin_amdgcn_ballot_w64(du[k][0] != du[k][0]) : 0ull;
+        uint32_t prow = prow0, plane_off = 0;
+        for (int l = 0; l < L; ++l, prow += 4u * PS, plane_off += plane_bytes) {
+            if constexpr (kK1Trim) asm volatile("" : "+v"(prow));      // stays a register of its own: not l * pitch again
+            const float *pp = kK1Trim ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(penl) + prow) : penl + l * PS;
+            float p[PS];
+            if constexpr (kK1Trim) {                           // rows are whole 16-byte reads, which the opaque offset no longer shows
+#pragma unroll
+                for (int n = 0; n < PS; n += 4) {
+                    const float4 v = *reinterpret_cast<const float4 *>(pp + n);
+                    p[n] = v.x; p[n + 1] = v.y; p[n + 2] = v.z; p[n + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int n = 0; n < N1; ++n) p[n] = pp[n];
+            }
             uint32_t rank[NE];
             // The NE solves are written level-by-level across elements so that neighbouring
             // instructions are independent (one element's chain alone issues ~1 op / 8 cycles).
@@ -340,10 +371,12 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
                 // reference's L-before-R order decides: literal scan).  Which SIDE wins never changes the level.
                 uint64_t any_multi = 0;
                 uint32_t lvl[NE];
+                uint64_t multi2 = 0;                            // either element of the lane: see the index modes below
+                if constexpr (kK1Trim) multi2 = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[0]) + (uint32_t)__popc(ne[NE - 1]), 2u * N, 33);
 #pragma unroll
                 for (int k = 0; k < NE; ++k) {
                     lvl[k] = (uint32_t)__builtin_ctz(~ne[k]);
-                    const uint64_t multi = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[k]), (uint32_t)N, 33);
+                    const uint64_t multi = kK1Trim ? (multi2 | nan0[k]) : __builtin_amdgcn_uicmp((uint32_t)__popc(ne[k]), (uint32_t)N, 33);
                     fmk[k] = never_flag ? 0ull : (force_slow ? ~0ull : multi);
                     any_multi |= fmk[k];
                 }
@@ -370,17 +403,24 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
             // Flags are kept as 64-bit lane masks in SGPRs (v_cmp writes them there): OR-ing them and testing
             // for "any" is scalar work, no VALU op.  LLVM icmp predicates: 33 = ne, 37 = ule.
             uint64_t fm[NE];
+            // More than one level attains S in EITHER element of the lane: every mask has at most N bits (the level that
+            // attains S clears its own, unless no cost is a number: nan0), so the two counts sum to 2 N exactly when both are N
+            // -- v_bcnt accumulates, one compare instead of two.  The partner of a tie is re-solved with it: the same answer.
+            uint64_t multi2 = 0;
+            if constexpr (kK1Trim) multi2 = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[0]) + (uint32_t)__popc(ne[NE - 1]), 2u * N, 33);
 #pragma unroll
             for (int k = 0; k < NE; ++k) {
                 // more than one level attains S
-                const uint64_t multi = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[k]), (uint32_t)N, 33);
+                const uint64_t multi = kK1Trim ? (multi2 | nan0[k]) : __builtin_amdgcn_uicmp((uint32_t)__popc(ne[k]), (uint32_t)N, 33);
                 // The gap sits at the float's own bit positions [31:21]: compare bit patterns directly.
                 // fl(dL + pen) can meet fl(dR + pen) only if dL - dR <= ulp(S) <= 2^-22 S.  The test
                 // (word & 0xffe00000) <= bits(2^-20 S) is implied by word <= bits(2^-19 S) without the mask
                 // (doubling a float adds 2^23 to its bit pattern, more than the 21 low bits can hold).
                 const uint32_t thr = __float_as_uint(__fmul_rn(S[k], 1.9073486328125e-06f));
                 const uint64_t lr_close = __builtin_amdgcn_uicmp(pk[k], thr, 37);
-                rank[k] = pk[k] & ((2u << N) - 1u);                // ranks need N + 1 bits, the gap sits above bit 21
+                // ranks need N + 1 <= 13 bits, the gap sits above bit 21 and bits 15 .. N + 1 are zero: where only the low
+                // half of the word leaves (the index stores below) the mask is not needed
+                rank[k] = (kK1Trim && !EXTRA) ? pk[k] : pk[k] & ((2u << N) - 1u);
                 fm[k] = never_flag ? 0ull : (force_slow ? ~0ull : (multi | lr_close));
             }
             uint64_t any_flag = 0;
@@ -416,6 +456,14 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
                         if (out_bits) *reinterpret_cast<float4 *>(out_bits + o) = make_float4(bt[0], bt[1], bt[2], bt[3]);
                     }
                 } else {
+                    if constexpr (kK1Trim && !EXTRA) {
+                        // the low halves of both words as one: v_perm_b32 (bytes 0, 1 of rank[0]; 4, 5 = bytes 0, 1 of rank[1])
+                        const uint32_t two = __builtin_amdgcn_perm(rank[NE - 1], rank[0], 0x05040100u);
+                        if constexpr (BUF)
+                            __builtin_amdgcn_raw_buffer_store_b32(two, orsrc, (uint32_t)(2 * (base + i0)), plane_off, 0);
+                        else
+                            store_idx2<false>(reinterpret_cast<uint32_t *>(out_idx + o), two);
+                    } else
                     store_idx2<false>(reinterpret_cast<uint32_t *>(out_idx + o), rank[0] | (rank[1] << 16));
                     if (EXTRA) {
                         if (out_zhat) *reinterpret_cast<float2 *>(out_zhat + o) = make_float2(zh[0], zh[1]);
@@ -426,6 +474,11 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
 #pragma unroll
                 for (int k = 0; k < NE; ++k) {
                     if (i0 + k < n_per_ch) {
+                        // BUF: the short store through the descriptor as well -- a plain one keeps a 64-bit pointer per lane
+                        // alive that every lambda advances, whether a lane stores through it or not
+                        if constexpr (kK1Trim && !EXTRA && BUF)
+                            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)rank[k], orsrc, (uint32_t)(2 * (base + i0 + k)), plane_off, 0);
+                        else
                         out_idx[o + k] = (uint16_t)rank[k];
                         if (EXTRA) {
                             if (out_zhat) out_zhat[o + k] = zh[k];
@@ -486,6 +539,11 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
 constexpr int kHullThreads = VBQ_HULL_THREADS;
 #ifndef VBQ_HULL_COPIES
 #define VBQ_HULL_COPIES 16
+#endif
+// Records in flight per stage of K1t's position phase (10: all of an element's at once; 2, 5 and 10 measured alike, 113 us
+// against 118 us for 0, one position after the other as sweep_position has it)
+#ifndef VBQ_K1T_STAGE
+#define VBQ_K1T_STAGE 10
 #endif
 constexpr int kHullKeys = 2048;         // 16 octaves of 128 buckets
 constexpr int kFixQueue = 192;          // K1t: deferred fix-ups per workgroup (about ten are expected per 2 300 elements)
@@ -691,6 +749,33 @@ k_level_counts_hull(const float *__restrict__ mu, const float *__restrict__ sg, 
             float Tn[N];
             sweep_thresholds<N>(du[k], Tn);
             fix[k] = __builtin_amdgcn_ballot_w64(!(sweep_max_du<N>(du[k]) < kSweepBig)) | (force_slow ? ~0ull : 0ull);
+#if VBQ_K1T_STAGE
+            // The positions in stages (sweep_position taken apart, as K1e does): all ten bucket reads, then the records
+            // VBQ_K1T_STAGE at a time, the compares and bands behind them, the ten counter updates last -- LDS returns in
+            // order, so a read issued behind an atomic waits for it, and one position after the other drained the counter at
+            // every read.
+            uint32_t apos[N];
+#pragma unroll
+            for (int n = 0; n < N; ++n) apos[n] = lut[sweep_bucket<16>(Tn[n], key0, nkeys)];
+#pragma unroll
+            for (int h = 0; h < N; h += VBQ_K1T_STAGE) {
+                float4 nbs[VBQ_K1T_STAGE];
+#pragma unroll
+                for (int i = 0; i < VBQ_K1T_STAGE; ++i)
+                    if (h + i < N) nbs[i] = rec[apos[h + i]];
+#pragma unroll
+                for (int i = 0; i < VBQ_K1T_STAGE; ++i) {
+                    const int n = h + i;
+                    if (n >= N) break;
+                    apos[n] += nbs[i].y < Tn[n] ? 1u : 0u;      // val_(a-1) < T <= val_(a)
+                    const float G = sweep_band(Tn[n], n, du[k][n]);
+                    const float dist = sweep_distance(Tn[n], nbs[i]);
+                    fix[k] |= __builtin_amdgcn_ballot_w64(dist <= G);
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < N; ++n) atomicAdd(&H[((uint32_t)n * LB + apos[n]) * (unsigned)KC + copy], vinc);
+#else
 #pragma unroll
             for (int n = 0; n < N; ++n) {
                 float4 nb;
@@ -700,6 +785,7 @@ k_level_counts_hull(const float *__restrict__ mu, const float *__restrict__ sg, 
                 fix[k] |= __builtin_amdgcn_ballot_w64(dist <= G);
                 atomicAdd(&H[((uint32_t)n * LB + a) * (unsigned)KC + copy], vinc);
             }
+#endif
             fix[k] &= __builtin_amdgcn_ballot_w64(valid);      // lane masks are scalars: no branch inside the block
         }
         uint64_t any_fix = 0;
@@ -1384,6 +1470,9 @@ int launch_quant_fast(const float *mu, const float *sg, int64_t n_per_ch, int64_
     else if (out_zhat || out_bits)
         hipLaunchKernelGGL((k_quant_fast<N, 1>), grid, block, 0, st, mu, sg, (long)n_per_ch, (long)ch_stride, (int)n_ch, table,
                            lam, len, (int)L, out_idx, out_zhat, out_bits, (long)E, vec_ok, dbg, level_counts);
+    else if (kK1Trim && index_planes_within_4gb(L, E))
+        hipLaunchKernelGGL((k_quant_fast<N, 0, true>), grid, block, 0, st, mu, sg, (long)n_per_ch, (long)ch_stride, (int)n_ch, table,
+                           lam, len, (int)L, out_idx, out_zhat, out_bits, (long)E, vec_ok, dbg, level_counts);
     else
         hipLaunchKernelGGL((k_quant_fast<N, 0>), grid, block, 0, st, mu, sg, (long)n_per_ch, (long)ch_stride, (int)n_ch, table,
                            lam, len, (int)L, out_idx, out_zhat, out_bits, (long)E, vec_ok, dbg, level_counts);
@@ -1499,7 +1588,7 @@ int launch_quant_hull_idx10(const float *mu, const float *sg, int64_t n_per_ch, 
     Lambdas32 l32;
     for (int i = 0; i < kMaxLambdaChunk; ++i) l32.lam[i] = i < L ? (float)lam[i] : 0.0f;
     // all L planes within 4 GB: the emission addresses them through one buffer descriptor (32-bit scalar plane offsets)
-    const bool buf = (uint64_t)L * 2ull * (uint64_t)E <= 0xffffffffull;
+    const bool buf = index_planes_within_4gb(L, E);
 #define VBQ_K1E_LAUNCH(LF, BF)                                                                                                \
     hipLaunchKernelGGL((k_quant_hull_idx<10, LF, BF>), dim3((unsigned)gx, (unsigned)n_ch), dim3(256), 0, st, mu, sg,          \
                        (long)n_per_ch, (long)ch_stride, (int)n_ch, table, l32, sw, vec_ok, out_idx, (long)E, dbg)
