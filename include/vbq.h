@@ -52,6 +52,10 @@ enum {
     VBQ_ERR_LAUNCH = -3,
     VBQ_ERR_WORKSPACE = -4
 };
+/* Refusals.  A call that returns VBQ_ERR_INVALID_ARGUMENT, VBQ_ERR_UNSUPPORTED or VBQ_ERR_WORKSPACE has enqueued nothing:
+ * outputs, outputs that are "ADDED to", status words and the workspace hold what they held, whichever of the lambdas, the bit
+ * depth or an inner step of a composite call the refusal is about.  VBQ_ERR_LAUNCH is a failure of the runtime in mid-call
+ * and is exempt: work enqueued before it stays enqueued. */
 
 enum {
     VBQ_LAYOUT_BC = 0,

@@ -13,9 +13,12 @@ documented errors (KeyError, ValueError, TypeError, VBQError), `same` compares t
 INPUTS hold the latents of a few files, class maps, palettes and budgets; the budgets are derived from a fresh quantizer's own
 coded_nbytes* answers (a length strictly between two rungs), never constants.
 
+FAILED_ATTEMPTS are the calls that raise -- transitions refused half way, probes asked what they must refuse -- each with the
+exception type it raises; tests/test_gpu_failed_calls.py holds the quantizer to answering every probe afterwards as before.
 PROBED / EXEMPT say, for every public method of the class, which probes call it or why none does;
 tests/test_quantizer_histories_host.py holds them against the class.  A NEW PUBLIC METHOD OF THE QUANTIZER GOES INTO ONE OF THE
 TWO.  Importable without a GPU."""
+import zipfile
 from collections import namedtuple
 
 import numpy as np
@@ -586,3 +589,236 @@ EXEMPT = {
 def public_methods(cls):
     """The public callables of the class (properties are not callable)."""
     return sorted(name for name in dir(cls) if not name.startswith("_") and callable(getattr(cls, name)))
+
+
+# ------------------------------------------------------------------------------------------------------------------ failed attempts
+FAILED_ATTEMPTS = {}
+"""'<public method>:<what is wrong>' -> (function(q, inputs), the exception type the call raises).  The function makes ONE public
+call that raises; what it needs before -- a file to damage, a saved state -- it gets from public calls that succeed.  It
+restores what it set on the quantizer itself (validate_inputs) and nothing else.  A type given as a string names a class of
+vbq_amd._lib (the module imports without the native library); expected_type resolves it."""
+UNBUILT = 0.123                                # a lambda no state has a model for
+OTHER_STATE = {"A": "E", "E": "A"}             # the state whose files `inputs.foreign` holds in a test of the key
+MIDDLE = 2                                     # of the five files of FILE_SHAPES
+NEW_IMAGE_SHAPE = (1, 5, 7, 3)                 # not in IMAGE_SHAPES: compress_replay has to capture it
+
+
+def _attempt(name, exc):
+    def register(fn):
+        assert name not in FAILED_ATTEMPTS, name
+        FAILED_ATTEMPTS[name] = (fn, exc)
+        return fn
+    return register
+
+
+def expected_type(exc):
+    if isinstance(exc, str):
+        from vbq_amd import _lib
+        return getattr(_lib, exc)
+    return exc
+
+
+def _with(i, **changes):
+    new = i._copy()
+    new.__dict__.update(changes)
+    return new
+
+
+def _host(a):
+    return np.asarray(a.cpu() if hasattr(a, "cpu") else a)
+
+
+# ---- transitions that fail
+@_attempt("build_entropy_models_from_latents:lambda_zero", "VBQError")
+def t_lambda_zero(q, i):
+    # 0.0 is outside the range pass 1's kernels serve: vbq_level_counts_f32 refuses it
+    q.build_entropy_models_from_latents(*fit_latents("B"), [0.3, 0.0], 1, spread="logvar")
+
+
+@_attempt("build_entropy_models_from_latents:33_lambdas_the_last_1e25", "VBQError")
+def t_late_lambda(q, i):
+    # the offending lambda is in the second chunk of 32; the first chunk is eligible on its own
+    q.build_entropy_models_from_latents(*fit_latents("B"), [float(v) for v in np.geomspace(0.01, 30.0, 32)] + [1e25], 1,
+                                        spread="logvar")
+
+
+@_attempt("build_entropy_models_from_latents:one_channel_too_many", ValueError)
+def t_channels(q, i):
+    means, logvars = (np.pad(a, ((0, 0), (0, 1))) for a in fit_latents("B"))
+    q.build_entropy_models_from_latents(means, logvars, list(LAMBS_A), 1, spread="logvar")
+
+
+@_attempt("build_entropy_models_from_latents:nan_mean_with_validate_inputs", ValueError)
+def t_nan_mean(q, i):
+    means, logvars = fit_latents("B")
+    means = means.copy()
+    means[1234, 2] = np.nan
+    before, q.validate_inputs = q.validate_inputs, True
+    try:
+        q.build_entropy_models_from_latents(means, logvars, list(LAMBS_A), 1, spread="logvar")
+    finally:
+        q.validate_inputs = before
+
+
+class BadPrior(Grid):
+    """Grid(1.25) -- a table of no state -- made wrong in one way: "order" (the two points either side of the median of level 3
+    trade places in channel 1: not monotone in xi, before and after the float32 cast), "shape" (a row short), "raises"."""
+
+    def __init__(self, how):
+        Grid.__init__(self, 1.25)
+        self.how = how
+
+    def inverse_cdf(self, xi):
+        if self.how == "raises":
+            raise ArithmeticError("this prior has no inverse CDF")
+        pts = Grid.inverse_cdf(self, xi)
+        if self.how == "shape":
+            return pts[:-1]
+        lo = 2 ** 3 - 1 + 3
+        pts[[lo, lo + 1], 1] = pts[[lo + 1, lo], 1]
+        return pts
+
+
+@_attempt("build_code_points:not_monotone_after_the_f32_cast", ValueError)
+def t_not_monotone(q, i):
+    q.build_code_points(BadPrior("order"))
+
+
+@_attempt("build_code_points:wrong_shape", ValueError)
+def t_wrong_shape(q, i):
+    q.build_code_points(BadPrior("shape"))
+
+
+@_attempt("build_code_points:inverse_cdf_raises", ArithmeticError)
+def t_prior_raises(q, i):
+    q.build_code_points(BadPrior("raises"))
+
+
+def _state_file(q):
+    import os
+    import tempfile
+    path = os.path.join(tempfile.mkdtemp(prefix="vbq_failed_"), "quantizer.npz")
+    q.save(path)
+    return path
+
+
+@_attempt("load:truncated_file", zipfile.BadZipFile)
+def t_load_truncated(q, i):
+    path = _state_file(q)
+    with open(path, "rb") as f:
+        data = f.read()
+    with open(path, "wb") as f:
+        f.write(data[:len(data) // 2])              # the archive's directory, which stands at its end, is gone
+    type(q).load(path)
+
+
+@_attempt("load:unknown_format", ValueError)
+def t_load_unknown(q, i):
+    path = _state_file(q)
+    with np.load(path, allow_pickle=False) as z:
+        d = {k: z[k] for k in z.files}
+    d["format"] = np.array("vbq_amd.quantizer/99")
+    np.savez_compressed(path, **d)
+    type(q).load(path)
+
+
+@_attempt("save:missing_directory", FileNotFoundError)
+def t_save_nowhere(q, i):
+    import os
+    import tempfile
+    q.save(os.path.join(tempfile.mkdtemp(prefix="vbq_failed_"), "no", "such", "directory", "quantizer.npz"))
+
+
+# ---- probes that raise
+@_attempt("compress_latents:unbuilt_lambda", KeyError)
+def f_unbuilt(q, i):
+    m, lv = _one(i)
+    q.compress_latents(m[None], lv[None], [i.lamb, UNBUILT])
+
+
+@_attempt("compress_replay:unbuilt_lambda_on_a_new_image_shape", KeyError)
+def f_replay_abandoned(q, i):
+    v_replay(q, _with(i, lambs=[i.lamb, UNBUILT]), NEW_IMAGE_SHAPE)
+
+
+def _no_rung(probe, key, at=None):
+    """The probe with a budget of one byte, which no rung fits (in a batch: for the file in the middle alone)."""
+    def fn(q, i):
+        b = 1
+        if at is not None:
+            b = list(i.budgets[key])
+            b[at] = 1
+        probe(q, _with(i, budgets={**i.budgets, key: b}))
+    return fn
+
+
+for _name, _probe, _key, _at in (
+        ("compress_latents_to_budget:no_rung_fits_segments", p_to_budget, "one", None),
+        ("compress_latents_to_budget:no_rung_fits_interleaved", p_to_budget_c, "one_c", None),
+        ("compress_latents_to_budget_mapped:no_rung_fits", p_to_budget_mapped, "one_m", None),
+        ("compress_latents_to_budget_batch:no_rung_fits_the_middle_file", b_to_budget, "batch", MIDDLE),
+        ("compress_latents_to_total_budget:no_rung_fits", b_total_budget, "total", None),
+        ("compress_latents_to_compact_budget_batch:no_rung_fits_the_middle_file", b_compact_budget, "compact", MIDDLE),
+        ("compress_latents_to_compact_total_budget:no_rung_fits", b_compact_total_budget, "compact_total", None),
+        ("compress_latents_to_budget_mapped_batch:no_rung_fits_the_middle_file", b_mapped_budget, "mapped", MIDDLE),
+        ("compress_latents_to_total_budget_mapped:no_rung_fits", b_mapped_total_budget, "mapped_total", None)):
+    _attempt(_name, ValueError)(_no_rung(_probe, _key, _at))
+
+
+def _bad_file_in_the_middle(probe):
+    """A batch writer whose file in the middle has C + 1 channels."""
+    def fn(q, i):
+        files = list(i.files)
+        files[MIDDLE] = tuple(np.concatenate([_host(a), _host(a)[..., :1]], axis=-1) for a in files[MIDDLE])
+        probe(q, _with(i, files=files))
+    return fn
+
+
+for _name, _probe in BATCHES.items():
+    (_method,) = [m for m, ps in PROBED.items() if _name in ps]
+    _attempt(_method + ":bad_file_in_the_middle", ValueError)(_bad_file_in_the_middle(_probe))
+
+# The file each reader is given in place of a good one: (kind, index) -- for the one-file readers the SECOND file they read, for
+# the batch readers a file that stands in the middle of a list (r_batch reads [b1, b4, b4], r_mapped_batch [m1, b4, m4],
+# r_compact_batch all five).
+BAD_FILE_OF = {"r_decompress_b": ("b", 3), "r_decompress_c": ("c", 3), "r_decompress_m": ("m", 3), "r_window": ("b", 0),
+               "r_mapped_window": ("m", 0), "r_batch": ("b", 4), "r_mapped_batch": ("b", 4), "r_compact_batch": ("c", MIDDLE)}
+
+
+def _reader_given(reader, name, bad):
+    """The reader on files this quantizer wrote itself, one of them replaced by bad(that file, inputs, kind, index)."""
+    def fn(q, i):
+        given = written_all(q, i)
+        kind, f = BAD_FILE_OF[name]
+        given[kind][f] = bad(given[kind][f], i, kind, f)
+        reader(q, i.reading(given, "bad"))
+    return fn
+
+
+def _truncated(data, i, kind, f):
+    return bytes(data[:len(data) // 2])
+
+
+def _foreign(data, i, kind, f):
+    assert i.foreign is not None, "the test sets inputs.foreign to the files of OTHER_STATE"
+    assert i.foreign[kind][f] != data
+    return i.foreign[kind][f]
+
+
+for _name, _reader in READERS.items():
+    (_method,) = [m for m, ps in PROBED.items() if _name in ps]
+    _kind = BAD_FILE_OF[_name][0]
+    _attempt(f"{_method}:damaged_file_{_name}", ValueError)(_reader_given(_reader, _name, _truncated))
+    _attempt(f"{_method}:file_of_another_state_{_name}", ValueError)(_reader_given(_reader, _name, _foreign))
+
+
+@_attempt("decompress_latents_window:region_of_three_axes_in_a_file_of_two", ValueError)
+def f_window_axes(q, i):
+    # (a slice past the end of an axis is clamped as NumPy clamps it and selects nothing: only a region with an axis the file
+    # does not have lies outside it in a way the reader refuses)
+    q.decompress_latents_window(written(q, i, "b", 0), (slice(3, 17), slice(5, 20), slice(0, 2)), None)
+
+
+@_attempt("decompress_latents_mapped_window:channel_outside_the_file", ValueError)
+def f_window_channel(q, i):
+    q.decompress_latents_mapped_window(written(q, i, "m", 0), (slice(3, 17), slice(5, 20)), [1, C])

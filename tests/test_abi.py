@@ -68,7 +68,9 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 
 
 def test_argument_validation_of_the_newer_entry_points(built_lib):
-    """Every entry point validates sizes and pointers before touching the device: callable on a CPU-only host."""
+    """Sizes and pointers are refused on a CPU-only host: these checks stand before any device work.  That EVERY refusal
+    stands before the first enqueue is held by tests/test_refusal_order_host.py (the sources) and
+    tests/test_gpu_refused_calls.py (the bytes)."""
     import ctypes as C
     from vbq_amd import _lib
     h = _lib.lib()

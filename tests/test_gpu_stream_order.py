@@ -975,14 +975,43 @@ def _control_cases():
     }
 
 
+def runs_beside(s, t, spin):
+    """True when work on t does not wait for work enqueued on s before it.  Streams share the runtime's few hardware queues, and
+    two that were given the same one run in order by accident: t then only returns once the delay on s is over."""
+    torch.cuda.synchronize()
+    busy, word = torch.cuda.Event(), torch.zeros(1, device="cuda")
+    with torch.cuda.stream(s):
+        spin.enqueue(SO.FLOOR_MS)
+        busy.record(s)
+    with torch.cuda.stream(t):
+        word.add_(1)
+    t.synchronize()
+    beside = not busy.query()
+    torch.cuda.synchronize()
+    return beside
+
+
+def two_streams_that_run_side_by_side(spin, candidates=8):
+    """The premise of the control, checked instead of assumed: s, and the first of a few streams that runs beside it (which
+    hardware queue a stream has depends on every stream the process made before)."""
+    s = torch.cuda.Stream()
+    for _ in range(candidates):
+        t = torch.cuda.Stream()
+        if runs_beside(s, t, spin):
+            return s, t
+    pytest.fail(f"none of {candidates} streams runs beside another one: the control cannot be armed")
+
+
 @pytest.mark.parametrize("name", ["transpose", "quantize", "histogram"])
 def test_control_a_misrouted_launch_is_seen(name, spin, monkeypatch):
     """ops._stream redirected to a third stream t: the one launch of the call does not wait for the delay, reads the stale
     inputs, and the harness sees it -- the answer is not the fresh one, and once everything has run it is exactly the stale
-    one.  Only calls that are one launch each, with their outputs (and workspace) given: nothing else is enqueued."""
+    one.  Only calls that are one launch each, with their outputs (and workspace) given: nothing else is enqueued.  t is a
+    stream that does run beside s (two_streams_that_run_side_by_side): on a hardware queue shared with s the misrouted launch
+    would wait for the delay like a correct one, and the control would fail for a reason that is none of the library's."""
     from vbq_amd import ops
     call, make, reset = _control_cases()[name]
-    s, t = torch.cuda.Stream(), torch.cuda.Stream()
+    s, t = two_streams_that_run_side_by_side(spin)
     handle = t.cuda_stream
     routed = {"on": False, "calls": 0}
     real = ops._stream

@@ -57,6 +57,49 @@ def test_exempt_holds_only_the_allowed_reasons():
             assert f"self.{target}(" in src and ("vae.encode(" in src or "self._encode(X, vae)" in src), f"{method} is no wrapper of {target}"
 
 
+def test_every_transition_has_a_failed_attempt_and_every_attempt_a_method():
+    methods = set(QH.public_methods(_cls()))
+    attempted = {}
+    for name, (fn, exc) in QH.FAILED_ATTEMPTS.items():
+        method, sep, what = name.partition(":")
+        assert sep and what and method in methods, f"FAILED_ATTEMPTS[{name!r}] names no public method of the class"
+        assert callable(fn) and (isinstance(exc, str) or (isinstance(exc, type) and issubclass(exc, Exception))), name
+        assert not isinstance(exc, str) or isinstance(QH.expected_type(exc), type), name
+        attempted.setdefault(method, []).append(what)
+    transitions = sorted(m for m, reason in QH.EXEMPT.items() if reason == QH.TRANSITION)
+    assert transitions == ["build_code_points", "build_entropy_models_from_latents", "load", "save"]
+    missing = [m for m in transitions if m not in attempted]
+    assert not missing, f"transitions without a failed attempt in FAILED_ATTEMPTS of tests/quantizer_histories.py: {missing}"
+    # the families the harness is held to: every budget call, every reader twice, every batch writer
+    budget = sorted(m for m in QH.PROBED if "_budget" in m)
+    assert len(budget) == 8 and all(any(w.startswith("no_rung_fits") for w in attempted.get(m, [])) for m in budget), budget
+    for reader in QH.READERS:
+        (method,) = [m for m, ps in QH.PROBED.items() if reader in ps]
+        assert {f"damaged_file_{reader}", f"file_of_another_state_{reader}"} <= set(attempted[method]), reader
+    for writer in QH.BATCHES:
+        (method,) = [m for m, ps in QH.PROBED.items() if writer in ps]
+        assert "bad_file_in_the_middle" in attempted[method], writer
+    assert set(QH.BAD_FILE_OF) == set(QH.READERS) and set(QH.OTHER_STATE) == {"A", "E"}
+    assert QH.NEW_IMAGE_SHAPE not in QH.IMAGE_SHAPES and QH.UNBUILT not in QH.LAMBS_A + QH.LAMBS_SUB
+
+
+def test_the_bad_priors_are_bad_in_the_way_they_say():
+    from vbq_amd.tables import n_bit_binary_floats, rank_of_slot
+    xi = np.repeat(np.hstack([n_bit_binary_floats(n) for n in range(QH.N + 1)])[:, None], QH.C, axis=1)
+    good = QH.Grid(1.25).inverse_cdf(xi)
+    for st in QH.STATES.values():                      # the table of no state: a half-applied build would show
+        assert good.astype(np.float32).T.tobytes() != QH.code_points(st).tobytes()
+    order = QH.BadPrior("order").inverse_cdf(xi)
+    assert order.shape == good.shape == (QH.T, QH.C) and (order != good).sum() == 2
+    for pts, monotone in ((good, True), (order, False)):
+        ranked = np.empty((QH.C, QH.T), np.float32)
+        ranked[:, rank_of_slot(QH.N)] = pts.astype(np.float32).T
+        assert bool(np.all(np.diff(ranked, axis=1) >= 0)) == monotone
+    assert QH.BadPrior("shape").inverse_cdf(xi).shape == (QH.T - 1, QH.C)
+    with pytest.raises(ArithmeticError):
+        QH.BadPrior("raises").inverse_cdf(xi)
+
+
 def test_recipes_are_deterministic():
     for kind in ("A", "B"):
         a, b = QH.fit_latents(kind), QH.fit_latents(kind)

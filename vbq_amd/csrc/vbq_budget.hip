@@ -163,6 +163,9 @@ extern "C" int vbq_budget_dp_f64(const double *d_fhat, int64_t n_rows, int32_t K
     const BudgetPlan p = budget_plan(K, N, budget);
     VBQ_REQUIRE(p.ok, VBQ_ERR_UNSUPPORTED, "vbq_budget_dp_f64: two value rows of budget+1 = %lld float64 do not fit the LDS",
                 (long long)budget + 1);
+    VBQ_REQUIRE(p.bp_in_lds || (d_workspace && workspace_bytes >= p.bp_row_bytes), VBQ_ERR_WORKSPACE,
+                "vbq_budget_dp_f64: workspace of %zu bytes holds no row's back-pointers (%zu bytes each; "
+                "vbq_budget_dp_workspace_bytes gives the full size)", workspace_bytes, p.bp_row_bytes);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int64_t grid = n_rows < (1 << 20) ? n_rows : (1 << 20);          // the rest of the rows: the kernel's row loop
     if (p.bp_in_lds) {
@@ -173,9 +176,6 @@ extern "C" int vbq_budget_dp_f64(const double *d_fhat, int64_t n_rows, int32_t K
         hipLaunchKernelGGL(k_budget_dp<true>, dim3((unsigned)grid), dim3(p.threads), p.lds_bytes, st, d_fhat, (long)n_rows, (int)K,
                            (int)N, (int)budget, d_out_bits, d_out_obj, d_status, (unsigned char *)nullptr, p.bp_row_bytes);
     } else {
-        VBQ_REQUIRE(d_workspace && workspace_bytes >= p.bp_row_bytes, VBQ_ERR_WORKSPACE,
-                    "vbq_budget_dp_f64: workspace of %zu bytes holds no row's back-pointers (%zu bytes each; "
-                    "vbq_budget_dp_workspace_bytes gives the full size)", workspace_bytes, p.bp_row_bytes);
         // as many workgroups as the workspace has slices, each walking over its share of the rows
         const int64_t slices = (int64_t)(workspace_bytes / p.bp_row_bytes);
         const int64_t resident = (int64_t)num_cus() * kBudgetWsWgPerCu;

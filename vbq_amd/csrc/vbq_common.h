@@ -87,6 +87,18 @@ __device__ __forceinline__ float neg_half_sq_err(float P, float mu, float sigma)
 #define VBQ_FOR_EACH_N(X) X(12) X(11) X(10) X(9) X(8) X(7) X(6) X(5) X(4)
 #endif
 
+// True for the bit depths above.  A refusal enqueues nothing (include/vbq.h): every entry point asks this BEFORE its first launch,
+// memset or inner call, so the dispatch switches below it cannot miss.
+inline bool n_is_built(int N) {
+#define VBQ_N_CASE(NN) case NN:
+    switch (N) {
+        VBQ_FOR_EACH_N(VBQ_N_CASE)
+        return true;
+        default: return false;
+    }
+#undef VBQ_N_CASE
+}
+
 // The lambdas of one launch rounded to f32 (TF casts the Python scalar to the tensor dtype), passed in the kernel arguments:
 // the fast kernels form their penalties fl32(lambda) * len in the prologue instead of reading a table another kernel prepared.
 struct Lambdas32 {
@@ -102,6 +114,15 @@ int launch_quant_fast(const float *mu, const float *sg, int64_t n_per_ch, int64_
                       const Lambdas32 &lam, const float *len, int32_t L, uint16_t *out_idx, float *out_zhat,
                       float *out_bits, int64_t E, int vec_ok,
                       unsigned long long *level_counts, int wg_per_cu, int reserved, hipStream_t st);
+
+// The solve's refusals that depend on no pointer, decided for ALL lambda chunks before anything is enqueued (vbq_quantize.hip):
+// N built at all, N built for this layout (channel-last tiles: N <= 10), and -- counting mode and VBQ_LAYOUT_BC_TO_CB, which only
+// the fast f32 kernels serve -- every chunk of 32 lambdas within the fast range or of K1p's kind.  -> VBQ_OK, or
+// VBQ_ERR_UNSUPPORTED with the message set.  The composite calls (vbq_latents.hip) ask it before their first launch.
+// idx_only: indices are the only element output; counting: vbq_level_counts_f32.
+int quantize_kernel_refusal(const char *who, int32_t n_ch, int32_t layout, const double *h_lambdas, int32_t n_lambda, int32_t N,
+                            int32_t mode, bool counting, bool idx_only, int32_t wg_per_cu);
+int pruned_max_lambdas();                            // kPrunedMaxL of vbq_quantize_fast.hip: the most lambdas K1p takes per call
 
 // K1p (vbq_quantize_fast.hip): one to four lambdas per call with exact pruning of the descent; indices only.  Returns 1 when the
 // call is not of that kind (the caller takes launch_quant_fast).  Valid for ANY penalties (literal comparisons only).

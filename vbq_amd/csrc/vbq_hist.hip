@@ -354,10 +354,7 @@ int launch_hist(const uint16_t *idx, int64_t n_rows, int32_t n_ch, int32_t layou
         hipLaunchKernelGGL((k_hist_flat<N, CountT>), dim3((unsigned)gx, (unsigned)n_ch, (unsigned)L), dim3(kHistThreads), 0, st,
                            src, (long)n_per_ch, (long)n_rows, (int)n_ch, (long)E, counts, vec_ok);
         VBQ_CHECK_LAUNCH("hist_flat");
-    } else if constexpr (N > 10) {
-        set_error("histogram: N=%d is built for channel-major planes only (VBQ_LAYOUT_CB, or n_ch = 1)", N);
-        return VBQ_ERR_UNSUPPORTED;
-    } else {
+    } else if constexpr (N <= 10) {                              // (N > 10: refused by histogram_entry)
         constexpr int T = table_size(N);
         const size_t lds = sizeof(unsigned int) * kTileChannels * (T + 2);
         {   // per device and cheap: set on every call (a process may drive several GPUs)
@@ -380,9 +377,8 @@ int launch_hist(const uint16_t *idx, int64_t n_rows, int32_t n_ch, int32_t layou
     return VBQ_OK;
 }
 
-template <typename CountT>
 int histogram_entry(const char *who, const uint16_t *d_idx, int64_t n_rows, int32_t n_ch, int32_t layout,
-                    int32_t n_lambda, int32_t N, CountT *cnt, int64_t row_begin, int64_t row_end, void *stream) {
+                    int32_t n_lambda, int32_t N, void *cnt, bool counts_are_i32, int64_t row_begin, int64_t row_end, void *stream) {
     VBQ_REQUIRE(n_rows >= 0 && n_ch >= 1 && n_lambda >= 1 && n_lambda <= 65535 && n_ch <= 65535,
                 VBQ_ERR_INVALID_ARGUMENT, "%s: bad sizes n_rows=%lld n_ch=%d n_lambda=%d", who, (long long)n_rows, n_ch,
                 n_lambda);
@@ -391,17 +387,23 @@ int histogram_entry(const char *who, const uint16_t *d_idx, int64_t n_rows, int3
     VBQ_REQUIRE(row_begin == row_end || (d_idx && cnt), VBQ_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
     VBQ_REQUIRE(layout == VBQ_LAYOUT_BC || layout == VBQ_LAYOUT_CB, VBQ_ERR_INVALID_ARGUMENT, "%s: unknown layout %d",
                 who, layout);
-    VBQ_REQUIRE(sizeof(CountT) == 8 || n_rows <= 0x7fffffffLL, VBQ_ERR_INVALID_ARGUMENT,
+    VBQ_REQUIRE(!counts_are_i32 || n_rows <= 0x7fffffffLL, VBQ_ERR_INVALID_ARGUMENT,
                 "%s: %lld rows per channel can overflow 32-bit counters", who, (long long)n_rows);
     if (row_begin == row_end) return VBQ_OK;
+    VBQ_REQUIRE(n_is_built(N), VBQ_ERR_UNSUPPORTED, "%s: max_bits_per_coord N=%d not built (have 4 ... 12; only 10 with VBQ_ONLY_N10)",
+                who, N);
+    VBQ_REQUIRE(n_ch == 1 || layout == VBQ_LAYOUT_CB || N <= 10, VBQ_ERR_UNSUPPORTED,
+                "histogram: N=%d is built for channel-major planes only (VBQ_LAYOUT_CB, or n_ch = 1)", N);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define VBQ_DISPATCH_N(NN) \
-    case NN: return launch_hist<NN, CountT>(d_idx, n_rows, n_ch, layout, n_lambda, cnt, row_begin, row_end, st);
+#define VBQ_DISPATCH_N(NN)                                                                                                       \
+    case NN:                                                                                                                     \
+        return counts_are_i32 ? launch_hist<NN, unsigned int>(d_idx, n_rows, n_ch, layout, n_lambda, static_cast<unsigned int *>(cnt), \
+                                                              row_begin, row_end, st)                                            \
+                              : launch_hist<NN, unsigned long long>(d_idx, n_rows, n_ch, layout, n_lambda,                      \
+                                                                    static_cast<unsigned long long *>(cnt), row_begin, row_end, st);
     switch (N) {
         VBQ_FOR_EACH_N(VBQ_DISPATCH_N)
-        default:
-            set_error("%s: max_bits_per_coord N=%d not built (have 4 ... 12; only 10 with VBQ_ONLY_N10)", who, N);
-            return VBQ_ERR_UNSUPPORTED;
+        default: return VBQ_ERR_UNSUPPORTED;                 // not reached: n_is_built(N) was asked above
     }
 #undef VBQ_DISPATCH_N
 }
@@ -410,24 +412,19 @@ int histogram_entry(const char *who, const uint16_t *d_idx, int64_t n_rows, int3
 
 extern "C" int vbq_histogram_u16(const uint16_t *d_idx, int64_t n_rows, int32_t n_ch, int32_t layout,
                                  int32_t n_lambda, int32_t N, int64_t *d_counts, void *stream) {
-    return vbq::histogram_entry<unsigned long long>("vbq_histogram_u16", d_idx, n_rows, n_ch, layout, n_lambda, N,
-                                                    reinterpret_cast<unsigned long long *>(d_counts), 0, n_rows, stream);
+    return vbq::histogram_entry("vbq_histogram_u16", d_idx, n_rows, n_ch, layout, n_lambda, N, d_counts, false, 0, n_rows, stream);
 }
 
 extern "C" int vbq_histogram_u16_i32(const uint16_t *d_idx, int64_t n_rows, int32_t n_ch, int32_t layout,
                                      int32_t n_lambda, int32_t N, int32_t *d_counts, void *stream) {
-    return vbq::histogram_entry<unsigned int>("vbq_histogram_u16_i32", d_idx, n_rows, n_ch, layout, n_lambda, N,
-                                              reinterpret_cast<unsigned int *>(d_counts), 0, n_rows, stream);
+    return vbq::histogram_entry("vbq_histogram_u16_i32", d_idx, n_rows, n_ch, layout, n_lambda, N, d_counts, true, 0, n_rows, stream);
 }
 
 extern "C" int vbq_histogram_rows_u16(const uint16_t *d_idx, int64_t n_rows, int32_t n_ch, int32_t layout,
                                       int32_t n_lambda, int32_t N, void *d_counts, int32_t counts_are_i32,
                                       int64_t row_begin, int64_t row_end, void *stream) {
-    if (counts_are_i32)
-        return vbq::histogram_entry<unsigned int>("vbq_histogram_rows_u16", d_idx, n_rows, n_ch, layout, n_lambda, N,
-                                                  reinterpret_cast<unsigned int *>(d_counts), row_begin, row_end, stream);
-    return vbq::histogram_entry<unsigned long long>("vbq_histogram_rows_u16", d_idx, n_rows, n_ch, layout, n_lambda, N,
-                                                    reinterpret_cast<unsigned long long *>(d_counts), row_begin, row_end, stream);
+    return vbq::histogram_entry("vbq_histogram_rows_u16", d_idx, n_rows, n_ch, layout, n_lambda, N, d_counts, counts_are_i32 != 0,
+                                row_begin, row_end, stream);
 }
 
 namespace vbq {
@@ -462,6 +459,8 @@ extern "C" int vbq_histogram_models_u16(const uint16_t *d_idx, int64_t n_rows, i
                 "vbq_histogram_models_u16: null pointer argument");
     VBQ_REQUIRE(!counts_are_i32 || n_rows <= 0x7fffffffLL, VBQ_ERR_INVALID_ARGUMENT,
                 "vbq_histogram_models_u16: %lld rows per channel can overflow 32-bit counters", (long long)n_rows);
+    // (before the memset of d_counts below: the plain histogram would find an N that is not built only after it)
+    VBQ_REQUIRE(n_rows == 0 || n_is_built(N), VBQ_ERR_UNSUPPORTED, "vbq_histogram_models_u16: max_bits_per_coord N=%d not built", N);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t n_bins = (int64_t)n_lambda * n_ch * table_size(N);
     // one workgroup per (lambda, channel) is the launch shape of the plain histogram whenever there are at least 2048 rows of
@@ -478,11 +477,9 @@ extern "C" int vbq_histogram_models_u16(const uint16_t *d_idx, int64_t n_rows, i
                                                                            d_lut, lut_n, d_models, st);
         switch (N) {
             VBQ_FOR_EACH_N(VBQ_DISPATCH_N)
-            default: break;
+            default: return VBQ_ERR_UNSUPPORTED;             // not reached: n_is_built(N) was asked above
         }
 #undef VBQ_DISPATCH_N
-        set_error("vbq_histogram_models_u16: max_bits_per_coord N=%d not built", N);
-        return VBQ_ERR_UNSUPPORTED;
     }
     if (hipMemsetAsync(d_counts, 0, (size_t)n_bins * (counts_are_i32 ? 4 : 8), st) != hipSuccess) {
         set_error("vbq_histogram_models_u16: hipMemsetAsync failed");

@@ -341,8 +341,23 @@ int lookup_lds_passes(const uint16_t *idx, int64_t B, int32_t C, int32_t L, cons
     }
 }
 
+// Tiles of the generic pass (k_gather_latents_vec: 64 x 64 when everything is 16-byte aligned, else k_gather_latents' smaller ones).
+int64_t gather_latents_tiles(const uint16_t *idx, int64_t B, int32_t C, const float *out_z, const void *out_raw, const float *out_nb,
+                             const uint16_t *out_idx, bool *is_vec) {
+    const uintptr_t all = reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(out_z) | reinterpret_cast<uintptr_t>(out_raw) |
+                          reinterpret_cast<uintptr_t>(out_nb) | reinterpret_cast<uintptr_t>(out_idx);
+    const bool vec = B % 8 == 0 && C % 4 == 0 && (all & 15) == 0;
+    if (is_vec) *is_vec = vec;
+    return vec ? ((B + 63) / 64) * ((C + 63) / 64) : ((B + kGlRows - 1) / kGlRows) * ((C + kGlCh - 1) / kGlCh);
+}
+
 int gather_latents(const uint16_t *idx, int64_t B, int32_t C, int32_t L, int32_t N, const float *tab_sorted, const float *level_len,
                    const float *models, float *out_z, void *out_raw, float *out_nb, uint16_t *out_idx, hipStream_t st) {
+    VBQ_REQUIRE(n_is_built(N), VBQ_ERR_UNSUPPORTED, "vbq_gather_latents_u16: max_bits_per_coord N=%d not built", N);
+    // The generic pass's grid, bounded before the LDS passes are launched: they only take outputs away from it, which can turn
+    // the scalar form (more, smaller tiles) into the vector form and never the other way round.
+    VBQ_REQUIRE(gather_latents_tiles(idx, B, C, out_z, out_raw, out_nb, out_idx, nullptr) <= 0x7fffffffll && L <= 65535,
+                VBQ_ERR_UNSUPPORTED, "vbq_gather_latents_u16: grid too large");
     {   // large batches: tables in the LDS for the outputs that pay for it, the generic kernel for what is left
         bool did_z = false, did_nb = false;
         int rc = VBQ_OK;
@@ -360,11 +375,8 @@ int gather_latents(const uint16_t *idx, int64_t B, int32_t C, int32_t L, int32_t
         if (did_nb) out_nb = nullptr;
         if (!out_z && !out_raw && !out_nb && !out_idx) return VBQ_OK;
     }
-    const uintptr_t all = reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(out_z) | reinterpret_cast<uintptr_t>(out_raw) |
-                          reinterpret_cast<uintptr_t>(out_nb) | reinterpret_cast<uintptr_t>(out_idx);
-    const bool vec = B % 8 == 0 && C % 4 == 0 && (all & 15) == 0;
-    const int64_t tiles = vec ? ((B + 63) / 64) * ((C + 63) / 64) : ((B + kGlRows - 1) / kGlRows) * ((C + kGlCh - 1) / kGlCh);
-    VBQ_REQUIRE(tiles <= 0x7fffffffll && L <= 65535, VBQ_ERR_UNSUPPORTED, "vbq_gather_latents_u16: grid too large");
+    bool vec = false;
+    const int64_t tiles = gather_latents_tiles(idx, B, C, out_z, out_raw, out_nb, out_idx, &vec);
     const dim3 grid((unsigned)tiles, (unsigned)L);
     const int raw_as_int = level_len == nullptr;
 #define VBQ_DISPATCH_N(NN)                                                                                                  \
@@ -378,9 +390,7 @@ int gather_latents(const uint16_t *idx, int64_t B, int32_t C, int32_t L, int32_t
         break;
     switch (N) {
         VBQ_FOR_EACH_N(VBQ_DISPATCH_N)
-        default:
-            set_error("vbq_gather_latents_u16: max_bits_per_coord N=%d not built", N);
-            return VBQ_ERR_UNSUPPORTED;
+        default: return VBQ_ERR_UNSUPPORTED;                 // not reached: n_is_built(N) was asked above
     }
 #undef VBQ_DISPATCH_N
     VBQ_CHECK_LAUNCH("gather_latents");
@@ -488,6 +498,25 @@ extern "C" int vbq_gather_f32(const uint16_t *d_idx, int64_t n_rows, int32_t n_c
     return VBQ_OK;
 }
 
+namespace vbq {
+namespace {
+// What the calls inside vbq_compress_latents_f32 and vbq_build_entropy_models_f32 could refuse once the planes are written --
+// the solve (sizes, pointers the composite does not own, N, every lambda chunk's kernel: quantize_kernel_refusal), the planes'
+// and the lookups' grids, the histogram's sizes -- asked before the first launch.  counting: pass 1 of the build.
+int latents_call_refusal(const char *who, int64_t n_rows, int32_t n_ch, const float *d_table_lm, const double *h_lambdas,
+                         int32_t n_lambda, int32_t N, bool counting) {
+    VBQ_REQUIRE(d_table_lm && h_lambdas, VBQ_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+    VBQ_REQUIRE(n_ch <= 65535 && n_lambda <= 65535, VBQ_ERR_UNSUPPORTED, "%s: n_ch=%d or n_lambda=%d exceeds 65535", who, n_ch, n_lambda);
+    VBQ_REQUIRE(((n_rows + 63) / 64) * (((int64_t)n_ch + 63) / 64) <= 0x7fffffffll / 4, VBQ_ERR_UNSUPPORTED,
+                "%s: more tiles than a grid holds", who);
+    int rc = VBQ_OK;
+    if (counting) rc = quantize_kernel_refusal(who, n_ch, VBQ_LAYOUT_CB, h_lambdas, n_lambda, N, VBQ_MODE_F32, true, false, 0);
+    if (rc != VBQ_OK) return rc;
+    return quantize_kernel_refusal(who, n_ch, VBQ_LAYOUT_CB, h_lambdas, n_lambda, N, VBQ_MODE_F32, false, true, 0);
+}
+}  // namespace
+}  // namespace vbq
+
 extern "C" size_t vbq_compress_latents_workspace_bytes(int64_t n_rows, int32_t n_ch, int32_t n_lambda, int32_t N) {
     if (n_rows < 0 || n_ch <= 0 || n_lambda <= 0 || N < 0) return 0;
     const size_t E = (size_t)n_rows * (size_t)n_ch;
@@ -517,7 +546,12 @@ extern "C" int vbq_compress_latents_f32(const float *d_means_bc, const float *d_
     uint16_t *idx = reinterpret_cast<uint16_t *>(w);
     w += align256((size_t)n_lambda * E * sizeof(uint16_t));
     const size_t qws = vbq_quantize_workspace_bytes(n_ch, n_lambda, N);
-    int rc = vbq_prep_planes_f32(d_means_bc, d_spread_bc, spread_kind, n_rows, n_ch, mu_cb, sg_cb, stream);
+    int rc = latents_call_refusal("vbq_compress_latents_f32", n_rows, n_ch, d_table_lm, h_lambdas, n_lambda, N, false);
+    if (rc != VBQ_OK) return rc;
+    VBQ_REQUIRE(d_out_zhat || d_out_raw_bits || d_out_num_bits, VBQ_ERR_INVALID_ARGUMENT, "vbq_compress_latents_f32: no output asked for");
+    VBQ_REQUIRE((!d_out_zhat || d_table_sorted) && (!d_out_num_bits || d_models), VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_compress_latents_f32: an output without its table");
+    rc = vbq_prep_planes_f32(d_means_bc, d_spread_bc, spread_kind, n_rows, n_ch, mu_cb, sg_cb, stream);
     if (rc != VBQ_OK) return rc;
     rc = vbq_quantize_f32(mu_cb, sg_cb, n_rows, n_ch, VBQ_LAYOUT_CB, d_table_lm, d_level_len, h_lambdas, n_lambda, N, VBQ_MODE_F32,
                           idx, nullptr, nullptr, w, qws, stream);
@@ -563,7 +597,12 @@ extern "C" int vbq_build_entropy_models_f32(const float *d_means_bc, const float
     w += align256((size_t)n_lambda * E * sizeof(uint16_t));
     const size_t qws = vbq_quantize_workspace_bytes(n_ch, n_lambda, N);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rc = vbq_prep_planes_f32(d_means_bc, d_spread_bc, spread_kind, n_rows, n_ch, mu_cb, sg_cb, stream);
+    // the caller's d_level_counts is zeroed below: everything an inner call could refuse is asked before
+    int rc = latents_call_refusal("vbq_build_entropy_models_f32", n_rows, n_ch, d_table_lm, h_lambdas, n_lambda, N, true);
+    if (rc != VBQ_OK) return rc;
+    VBQ_REQUIRE(!counts_are_i32 || n_rows <= 0x7fffffffLL, VBQ_ERR_INVALID_ARGUMENT,
+                "vbq_build_entropy_models_f32: %lld rows per channel can overflow 32-bit counters", (long long)n_rows);
+    rc = vbq_prep_planes_f32(d_means_bc, d_spread_bc, spread_kind, n_rows, n_ch, mu_cb, sg_cb, stream);
     if (rc != VBQ_OK) return rc;
     hipError_t e = hipMemsetAsync(d_level_counts, 0, sizeof(int64_t) * (size_t)n_lambda * (size_t)n_ch * (size_t)N1, st);
     if (e != hipSuccess) {

@@ -161,14 +161,15 @@ extern "C" int vbq_image_sqerr_u8(const uint8_t *d_img1, const uint8_t *d_img2, 
                 "vbq_image_sqerr_u8: bad shape %lld x %lld", (long long)n_images, (long long)n_per_image);
     if (n_images == 0) return VBQ_OK;
     VBQ_REQUIRE(d_out_sum, VBQ_ERR_INVALID_ARGUMENT, "vbq_image_sqerr_u8: null output");
+    // (before the memset of d_out_sum: a refusal leaves the sums as they were)
+    VBQ_REQUIRE(n_per_image == 0 || (d_img1 && d_img2), VBQ_ERR_INVALID_ARGUMENT, "vbq_image_sqerr_u8: null input");
+    VBQ_REQUIRE(n_per_image == 0 || n_images <= 65535, VBQ_ERR_UNSUPPORTED, "vbq_image_sqerr_u8: at most 65535 images per call");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (hipMemsetAsync(d_out_sum, 0, sizeof(int64_t) * n_images, st) != hipSuccess) {
         set_error("vbq_image_sqerr_u8: hipMemsetAsync failed");
         return VBQ_ERR_LAUNCH;
     }
     if (n_per_image == 0) return VBQ_OK;
-    VBQ_REQUIRE(d_img1 && d_img2, VBQ_ERR_INVALID_ARGUMENT, "vbq_image_sqerr_u8: null input");
-    VBQ_REQUIRE(n_images <= 65535, VBQ_ERR_UNSUPPORTED, "vbq_image_sqerr_u8: at most 65535 images per call");
     int64_t gx = (n_per_image + 256 * 16 - 1) / (256 * 16);
     if (gx > 1024) gx = 1024;
     if (gx < 1) gx = 1;

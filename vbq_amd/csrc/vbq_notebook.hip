@@ -950,6 +950,8 @@ extern "C" int vbq_quantize_notebook_f64(const float *d_means, const float *d_st
     VBQ_REQUIRE(n == 0 || (d_means && d_stds && d_codebook_lm && h_betas && d_out_idx), VBQ_ERR_INVALID_ARGUMENT,
                 "vbq_quantize_notebook_f64: null pointer argument");
     if (n == 0) return VBQ_OK;
+    VBQ_REQUIRE(n_is_built(N) && N <= 10, VBQ_ERR_UNSUPPORTED,
+                "vbq_quantize_notebook_f64: max_codepoint_length N=%d not built (have 4 ... 10)", N);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     switch (N) {
         case 10: return launch_notebook<10>(d_means, d_stds, n, d_codebook_lm, h_betas, n_beta, d_out_idx, d_out_val, st);
@@ -961,8 +963,6 @@ extern "C" int vbq_quantize_notebook_f64(const float *d_means, const float *d_st
         case 5: return launch_notebook<5>(d_means, d_stds, n, d_codebook_lm, h_betas, n_beta, d_out_idx, d_out_val, st);
         case 4: return launch_notebook<4>(d_means, d_stds, n, d_codebook_lm, h_betas, n_beta, d_out_idx, d_out_val, st);
 #endif
-        default:
-            set_error("vbq_quantize_notebook_f64: max_codepoint_length N=%d not built (have 4 ... 10)", N);
-            return VBQ_ERR_UNSUPPORTED;
+        default: return VBQ_ERR_UNSUPPORTED;                 // not reached: asked above
     }
 }

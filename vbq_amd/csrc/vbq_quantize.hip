@@ -358,6 +358,48 @@ k_intervals(const float *__restrict__ z_cb, long n_rows, const float *__restrict
     }
 }
 
+// The fast kernel's tie certificate needs lambda*len to be 0 or comfortably normal: every lambda of the chunk in its range.
+// One statement, asked by the dispatch of launch_quantize and, for all chunks before the first launch, by quantize_kernel_refusal.
+bool chunk_in_fast_range(const LambdaChunk &lc, int Lc) {
+    bool fast_ok = true;
+    // (vbq_quantize_fast.hip: the equality mask needs every lambda*len >= 2^-39 for len >= 1)
+    for (int i = 0; i < Lc; ++i) fast_ok = fast_ok && (lc.lam[i] >= 1.9e-12 && lc.lam[i] <= 1.8e19);
+    return fast_ok;
+}
+}  // namespace
+
+// vbq_common.h.  The chunks are those of launch_quantize, and so are the conditions: a chunk is served by the fast kernels when
+// every lambda of it is in their range, by K1p when it holds at most kPrunedMaxL (pruned_max_lambdas) lambdas and indices are all that is asked for,
+// and by the literal kernels otherwise -- which know neither the counting mode nor the transposing read.
+int quantize_kernel_refusal(const char *who, int32_t n_ch, int32_t layout, const double *h_lambdas, int32_t n_lambda, int32_t N,
+                            int32_t mode, bool counting, bool idx_only, int32_t wg_per_cu) {
+    VBQ_REQUIRE(n_is_built(N), VBQ_ERR_UNSUPPORTED, "%s: max_bits_per_coord N=%d not built (have 4 ... 12; only 10 with VBQ_ONLY_N10)",
+                who, N);
+    const bool bc_to_cb = layout == VBQ_LAYOUT_BC_TO_CB && n_ch > 1;
+    const bool flat = (n_ch == 1) || (layout == VBQ_LAYOUT_CB) || bc_to_cb;
+    VBQ_REQUIRE(flat || N <= 10, VBQ_ERR_UNSUPPORTED,
+                "vbq_quantize_f32: N=%d is built for channel-major planes only (VBQ_LAYOUT_CB, or n_ch = 1): "
+                "16 tables of %d points do not fit the LDS; transpose with vbq_transpose_f32 first", N, table_size(N));
+    if (!counting && !bc_to_cb) return VBQ_OK;
+    for (int l0 = 0; l0 < n_lambda; l0 += kMaxLambdaChunk) {
+        const int Lc = (n_lambda - l0 < kMaxLambdaChunk) ? (n_lambda - l0) : kMaxLambdaChunk;
+        LambdaChunk lc;
+        for (int i = 0; i < kMaxLambdaChunk; ++i) lc.lam[i] = i < Lc ? h_lambdas[l0 + i] : 0.0;
+        const bool fast_ok = mode == VBQ_MODE_F32 && chunk_in_fast_range(lc, Lc);
+        const bool pruned = mode == VBQ_MODE_F32 && !counting && idx_only && wg_per_cu == 0 && Lc <= pruned_max_lambdas();
+        if (fast_ok || pruned) continue;
+        if (counting)
+            set_error("vbq_level_counts_f32 is served by the fast f32 kernel only (every lambda in [1.9e-12, 1.8e19]); "
+                      "use vbq_quantize_f32 + vbq_histogram_u16 instead");
+        else
+            set_error("vbq_quantize_f32: VBQ_LAYOUT_BC_TO_CB is served by the fast f32 kernel only (VBQ_MODE_F32, every "
+                      "lambda in [1.9e-12, 1.8e19]); transpose with vbq_transpose_f32 and use VBQ_LAYOUT_CB instead");
+        return VBQ_ERR_UNSUPPORTED;
+    }
+    return VBQ_OK;
+}
+
+namespace {
 // Rows [row_begin, row_end) of the full [n_rows x n_ch] arrays are processed; outputs keep the full arrays'
 // addressing (lambda planes E = n_rows * n_ch apart).  level_counts != NULL: counting mode of the fast kernel.
 template <int N, typename PenT>
@@ -371,6 +413,14 @@ int launch_quantize(const float *mu, const float *sg, int64_t n_rows, int32_t n_
     PenT *pen = reinterpret_cast<PenT *>(ws);
     const bool bc_to_cb = layout == VBQ_LAYOUT_BC_TO_CB && n_ch > 1;
     const bool flat = (n_ch == 1) || (layout == VBQ_LAYOUT_CB) || bc_to_cb;
+
+    if (flat) {
+        // (which kernel serves a chunk is decided per chunk below; that one does was asked by quantize_kernel_refusal)
+    } else if constexpr (N > 10) {
+        set_error("vbq_quantize_f32: N=%d is built for channel-major planes only (VBQ_LAYOUT_CB, or n_ch = 1): "
+                  "16 tables of %d points do not fit the LDS; transpose with vbq_transpose_f32 first", N, table_size(N));
+        return VBQ_ERR_UNSUPPORTED;
+    }
 
     for (int l0 = 0; l0 < L; l0 += kMaxLambdaChunk) {
         const int Lc = (L - l0 < kMaxLambdaChunk) ? (L - l0) : kMaxLambdaChunk;
@@ -419,10 +469,7 @@ int launch_quantize(const float *mu, const float *sg, int64_t n_rows, int32_t n_
             const int64_t cap = (int64_t)num_cus() * 8 / (n_ch < 8 ? n_ch : 8) + 1;   // ~8 resident workgroups per CU in total
             if (gx > cap) gx = cap;
             if (gx < 1) gx = 1;
-            // The fast kernel's tie certificate needs lambda*len to be 0 or comfortably normal.
-            bool fast_ok = sizeof(PenT) == 4;
-            // (vbq_quantize_fast.hip: the equality mask needs every lambda*len >= 2^-39 for len >= 1)
-            for (int i = 0; i < Lc; ++i) fast_ok = fast_ok && (lc.lam[i] >= 1.9e-12 && lc.lam[i] <= 1.8e19);
+            const bool fast_ok = sizeof(PenT) == 4 && chunk_in_fast_range(lc, Lc);
             if constexpr (sizeof(PenT) == 4 && N == 10) {
                 // first entropy-model pass (raw lengths, levels only): thresholds instead of a per-lambda loop
                 if (fast_ok && lc_out && !len_c) {
@@ -458,25 +505,13 @@ int launch_quantize(const float *mu, const float *sg, int64_t n_rows, int32_t n_
                     continue;
                 }
             }
-            if (level_counts) {
-                set_error("vbq_level_counts_f32 is served by the fast f32 kernel only (every lambda in [1.9e-12, 1.8e19]); "
-                          "use vbq_quantize_f32 + vbq_histogram_u16 instead");
-                return VBQ_ERR_UNSUPPORTED;
-            }
-            if (bc_to_cb) {
-                set_error("vbq_quantize_f32: VBQ_LAYOUT_BC_TO_CB is served by the fast f32 kernel only (VBQ_MODE_F32, every "
-                          "lambda in [1.9e-12, 1.8e19]); transpose with vbq_transpose_f32 and use VBQ_LAYOUT_CB instead");
-                return VBQ_ERR_UNSUPPORTED;
-            }
+            // (counting mode and VBQ_LAYOUT_BC_TO_CB never come here: quantize_kernel_refusal turned them away before the
+            // first chunk was launched)
             if (const int r = prepare(); r != VBQ_OK) return r;
             hipLaunchKernelGGL((k_quant_flat<N, PenT>), dim3((unsigned)gx, (unsigned)n_ch), dim3(256), 0, st, mu_r, sg_r,
                                (long)n_per_ch, (long)ch_stride, (int)n_ch, table, pen, len_c, Lc, oi, oz, ob, (long)E, vec_ok);
             VBQ_CHECK_LAUNCH("quant_flat");
-        } else if constexpr (N > 10) {
-            set_error("vbq_quantize_f32: N=%d is built for channel-major planes only (VBQ_LAYOUT_CB, or n_ch = 1): "
-                      "16 tables of %d points do not fit the LDS; transpose with vbq_transpose_f32 first", N, table_size(N));
-            return VBQ_ERR_UNSUPPORTED;
-        } else {
+        } else if constexpr (N <= 10) {                          // (N > 10: refused above, before the first chunk)
             constexpr int T = table_size(N);
             constexpr int PS = (N1 + 3) & ~3;
             const size_t lds = sizeof(float) * kTileChannels * (T + 2) + 16 +
@@ -539,6 +574,10 @@ int quantize_entry(const char *who, const float *d_mu, const float *d_sigma, int
     VBQ_REQUIRE(d_workspace && workspace_bytes >= need, VBQ_ERR_WORKSPACE, "%s: workspace of %zu bytes given, %zu needed", who,
                 workspace_bytes, need);
     if (row_begin == row_end) return VBQ_OK;
+    // every lambda chunk's kernel, N and the layout it is built for: decided before the first chunk is launched
+    if (const int rc = quantize_kernel_refusal(who, n_ch, layout, h_lambdas, n_lambda, N, mode, counting,
+                                               d_out_idx && !d_out_zhat && !d_out_bits, wg_per_cu); rc != VBQ_OK)
+        return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int reserved = reserved_wgs < 0 ? 0 : reserved_wgs;
 #define VBQ_DISPATCH_N(NN)                                                                                         \
@@ -552,9 +591,7 @@ int quantize_entry(const char *who, const float *d_mu, const float *d_sigma, int
                                                  d_workspace, row_begin, row_end, level_counts, wg_per_cu, reserved, st);
     switch (N) {
         VBQ_FOR_EACH_N(VBQ_DISPATCH_N)
-        default:
-            set_error("%s: max_bits_per_coord N=%d not built (have 4 ... 12; only 10 with VBQ_ONLY_N10)", who, N);
-            return VBQ_ERR_UNSUPPORTED;
+        default: return VBQ_ERR_UNSUPPORTED;                 // not reached: n_is_built(N) was asked above
     }
 #undef VBQ_DISPATCH_N
 }
@@ -599,6 +636,7 @@ extern "C" int vbq_n_bit_intervals_f32(const float *d_z_cb, int64_t n_rows, int3
     VBQ_REQUIRE(n_rows >= 0 && n_ch >= 1 && n_ch <= 65535, VBQ_ERR_INVALID_ARGUMENT, "vbq_n_bit_intervals_f32: bad sizes");
     if (n_rows == 0) return VBQ_OK;
     VBQ_REQUIRE(d_z_cb && d_table_lm && d_left && d_right, VBQ_ERR_INVALID_ARGUMENT, "vbq_n_bit_intervals_f32: null pointer argument");
+    VBQ_REQUIRE(n_is_built(N), VBQ_ERR_UNSUPPORTED, "vbq_n_bit_intervals_f32: max_bits_per_coord N=%d not built", N);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int64_t gx = (n_rows + 255) / 256;
     const int64_t cap = 2048 / n_ch + 1;
@@ -610,9 +648,7 @@ extern "C" int vbq_n_bit_intervals_f32(const float *d_z_cb, int64_t n_rows, int3
         break;
     switch (N) {
         VBQ_FOR_EACH_N(VBQ_DISPATCH_N)
-        default:
-            set_error("vbq_n_bit_intervals_f32: max_bits_per_coord N=%d not built", N);
-            return VBQ_ERR_UNSUPPORTED;
+        default: return VBQ_ERR_UNSUPPORTED;                 // not reached: n_is_built(N) was asked above
     }
 #undef VBQ_DISPATCH_N
     VBQ_CHECK_LAUNCH("n_bit_intervals");

@@ -1480,6 +1480,8 @@ int launch_quant_fast(const float *mu, const float *sg, int64_t n_per_ch, int64_
     return VBQ_OK;
 }
 
+int pruned_max_lambdas() { return kPrunedMaxL; }
+
 // Host side of K1p: one to four lambdas, indices the only output.  Returns 1 when the call is not its kind.
 template <int N>
 int launch_quant_pruned(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch, const float *table,

@@ -174,6 +174,13 @@ class DeviceModels(MutableMapping):
 
 
 class ChannelwisePriorCDFQuantizer:
+    """The reference's quantizer (quantizer.py) on HIP kernels: code points from a prior, entropy models fitted on latents,
+    compression of latents and images to arrays, byte strings and files.
+
+    A public call that raises leaves the quantizer answering every later call exactly as it did before the failed one: the
+    transitions (build_code_points, build_entropy_models*, load) compute into locals and assign their state only once every
+    step has succeeded, and a refused probe changes no table, model or cache entry another call's answer depends on."""
+
     def __init__(self, num_channels, max_bits_per_coord, float_type="float32", int_type="int32", device=None,
                  validate_inputs=False):
         if float_type != "float32":
@@ -272,28 +279,29 @@ class ChannelwisePriorCDFQuantizer:
         pts = _to_numpy(prior_model.inverse_cdf(all_bin_floats_rep, **kwargs))
         if pts.shape != (self.quantization_levels, C):
             raise ValueError(f"prior.inverse_cdf returned shape {pts.shape}, expected {(self.quantization_levels, C)}")
-        self.all_code_points = np.ascontiguousarray(pts.astype(np.float32).T)       # C x T, level-major
-        self.code_points_by_channel = np.sort(self.all_code_points, axis=1)         # MUST BE SORTED (:37)
-        self.code_points_by_bits = [[self.all_code_points[c, 2 ** n - 1: 2 ** (n + 1) - 1] for n in range(N + 1)]
-                                    for c in range(C)]
+        # everything is computed into locals and checked first: a prior that is refused leaves the quantizer as it was
+        all_code_points = np.ascontiguousarray(pts.astype(np.float32).T)            # C x T, level-major
+        code_points_by_channel = np.sort(all_code_points, axis=1)                   # MUST BE SORTED (:37)
+        code_points_by_bits = [[all_code_points[c, 2 ** n - 1: 2 ** (n + 1) - 1] for n in range(N + 1)] for c in range(C)]
         grids = np.empty((C, N + 1, 2 ** N), dtype=np.float32)
         for c in range(C):
             for n in range(N + 1):
-                lvl = self.code_points_by_bits[c][n]
+                lvl = code_points_by_bits[c][n]
                 pad = 2 ** (N - 1) - 1 if n == 0 else 2 ** (N - 1) - 2 ** (n - 1)
                 grids[c, n] = np.pad(np.array([lvl[0]] * 2) if n == 0 else lvl, (pad,), "edge")
-        self._search_grids = grids
         # The kernels need the merged table to be non-decreasing in xi (then rank order == sorted order).
         from .tables import rank_of_slot
-        in_rank_order = np.empty_like(self.all_code_points)
-        in_rank_order[:, rank_of_slot(N)] = self.all_code_points
+        in_rank_order = np.empty_like(all_code_points)
+        in_rank_order[:, rank_of_slot(N)] = all_code_points
         if not np.all(np.diff(in_rank_order, axis=1) >= 0):
             raise ValueError("prior.inverse_cdf is not monotone in xi after the float32 cast; the reference's "
                              "per-level searchsorted (quantizer.py:74) is undefined on such tables")
-        self._strict = bool(np.all(np.diff(in_rank_order, axis=1) > 0))
+        strict = bool(np.all(np.diff(in_rank_order, axis=1) > 0))
         # canonical index of quantizer.py:135/223: first sorted position holding the same value
-        self._canon = (np.stack([np.searchsorted(r, r, side="left") for r in in_rank_order]).astype(np.int64)
-                       if not self._strict else None)
+        canon = (np.stack([np.searchsorted(r, r, side="left") for r in in_rank_order]).astype(np.int64)
+                 if not strict else None)
+        self.all_code_points, self.code_points_by_channel, self.code_points_by_bits = all_code_points, code_points_by_channel, code_points_by_bits
+        self._search_grids, self._strict, self._canon = grids, strict, canon
         self._dev_cache = {}
 
     def _table_dev(self):
@@ -468,7 +476,8 @@ class ChannelwisePriorCDFQuantizer:
                                   global_rows=B_global, distributed=distributed, group=self.process_group,
                                   counts_dtype=torch.int32 if B_global < 2 ** 31 else torch.int64, keep_models=self._strict,
                                   buffers=self._dev_cache.setdefault("_build_buffers", {}))
-        self.raw_code_length_entropy_models = None
+        # (a rebuild starts from raw lengths: both passes below get their lengths as arguments and never read
+        # self.raw_code_length_entropy_models, which -- like everything else of the quantizer -- changes only once they succeeded)
         if build.one_call_ok and B > 0:
             # one GPU, tabulated -log2: planes, both passes, the histogram and the models behind ONE C call
             build.run_one_call(mu_bc, sp_bc, spread)
@@ -480,9 +489,6 @@ class ChannelwisePriorCDFQuantizer:
             # pass 2: corrected lengths -> per-channel histogram of the code points (:118-148)
             _, counts = build.pass2(mu_cb, sg_cb, level_len)
         models_dev = build.finish_models()
-        self._add_n_smoothing = add_n_smoothing
-        self._dev_cache.pop("entropy_models", None)
-        self._dev_cache.pop("level_len", None)
         if models_dev is not None:
             state = {"done": False}
 
@@ -493,6 +499,9 @@ class ChannelwisePriorCDFQuantizer:
 
             if build.has_host_stages:        # a failed NumPy stage must not go unnoticed by device-only callers either
                 deferred_checks()
+            self._add_n_smoothing = add_n_smoothing
+            self._dev_cache.pop("entropy_models", None)
+            self._dev_cache.pop("level_len", None)
             self.raw_code_length_entropy_models = DeviceModels(lambs, raw_models, {"level_len": level_len}, deferred_checks)
             self.entropy_models = DeviceModels(lambs, models_dev, None, deferred_checks)
             # kept for the entropy coder (vbq_amd.coder): the integer histograms behind the models
@@ -503,7 +512,6 @@ class ChannelwisePriorCDFQuantizer:
         torch.cuda.synchronize(self.device)
         build.check()
         raw_models = raw_models.cpu().numpy()
-        self.raw_code_length_entropy_models = {lamb: raw_models[i] for i, lamb in enumerate(lambs)}
         counts = counts.cpu().numpy()
         if not self._strict:   # qidx is the FIRST sorted position of a repeated value (:135)
             merged = np.zeros_like(counts)
@@ -511,6 +519,9 @@ class ChannelwisePriorCDFQuantizer:
                 np.add.at(merged[:, c, :], (slice(None), self._canon[c]), counts[:, c, :])
             counts = merged
         models = _entropy.neg_log2_freq(counts, add_n_smoothing)                    # [L, C, T] f32
+        self._add_n_smoothing = add_n_smoothing
+        self._dev_cache.pop("entropy_models", None)
+        self.raw_code_length_entropy_models = {lamb: raw_models[i] for i, lamb in enumerate(lambs)}
         self.entropy_models = {lamb: models[i] for i, lamb in enumerate(lambs)}
         self._code_counts = {lamb: counts[i] for i, lamb in enumerate(lambs)}
         self._dev_cache["level_len"] = ([self.raw_code_length_entropy_models[lamb] for lamb in lambs], level_len)
