@@ -1,6 +1,6 @@
 """Build the HIP extension (and, for tests only, the C oracle) in-tree.
 
-    python -m vbq_amd.build            # libvbq_hip.so for gfx950
+    python -m vbq_amd.build            # libvbq_hip.so and libvbq_ext.so for gfx950
     python -m vbq_amd.build --oracle   # also oracle/_build/libvbq_oracle.so
 
 hipcc cross-compiles gfx950 without a GPU; the resulting .so is git-ignored but travels
@@ -24,6 +24,8 @@ HIP_SOURCES = ["vbq_api.hip", "vbq_quantize.hip", "vbq_quantize_fast.hip", "vbq_
                "vbq_budget.hip", "vbq_reduce.hip", "vbq_transpose.hip", "vbq_rans_il.hip", "vbq_records.hip", "vbq_topk.hip", "vbq_bag.hip", "vbq_rans_map.hip", "vbq_rans_window.hip", "vbq_rans_map_window.hip",
                "vbq_rans_files.hip", "vbq_rans_sizes_files.hip", "vbq_rans_il_files.hip", "vbq_rans_map_files.hip",
                "vbq_rans_map_rates_files.hip"]
+EXT = os.path.join(PKG, "ext")
+EXT_LIB = os.path.join(LIBDIR, "libvbq_ext.so")
 LINK_LIBS = ["-ldl"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                # every f32/f64 op of the reference is a separately rounded op: never contract a*b+c
@@ -31,6 +33,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                # no SLP vectorisation: the v_pk_add/mul_f32 pairs it forms issue at the rate of two scalar ops but need
                # their operands in aligned register pairs -- the moves cost K1t 3 %, K1e 5 %, the one-lambda kernel 7 %
                "-fno-slp-vectorize"]
+EXT_HIPCC_FLAGS = HIPCC_FLAGS + ["-fvisibility=hidden"]
 
 
 def _newer(target, deps):
@@ -57,9 +60,9 @@ def _tmp(path):
     return f"{path}.{os.getpid()}.{threading.get_ident()}.tmp"
 
 
-def _compile_one(hipcc, src, obj, extra):
+def _compile_one(hipcc, src, obj, extra, flags=None):
     tmp = _tmp(obj)
-    cmd = [hipcc] + HIPCC_FLAGS + extra + ["-I", INCLUDE, "-I", CSRC, "-c", src, "-o", tmp]
+    cmd = [hipcc] + (HIPCC_FLAGS if flags is None else flags) + extra + ["-I", INCLUDE, "-I", CSRC, "-c", src, "-o", tmp]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed on " + os.path.basename(src) + ":\n" + r.stdout + r.stderr)
@@ -74,49 +77,65 @@ def extra_flags():
     return extra
 
 
-def build_hip(force: bool = False, verbose: bool = False) -> str:
-    """One object per .hip source (rebuilt only when it or a header changed, in parallel), one link."""
+def _build_library(lib, srcs, headers, objdir, flags, force, verbose):
+    """One object per source under `objdir` (rebuilt only when it or a header changed, in parallel), one link into `lib`; the
+    flags the library was built with are written beside it as <name>.flags.txt -- flags.txt for libvbq_hip.so."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = hip_sources()
-    headers = hip_headers()
     extra = extra_flags()
-    objdir = os.path.join(LIBDIR, "obj")
     flags_tag = os.path.join(objdir, "flags.txt")
-    lib_tag = os.path.join(LIBDIR, "flags.txt")                 # travels with the library (the object cache does not)
-    tag = " ".join(HIPCC_FLAGS + extra)
+    # travels with the library (the object cache does not): flags.txt, vbq_ext.flags.txt
+    lib_tag = os.path.join(LIBDIR, "flags.txt" if lib == LIB else os.path.basename(lib)[3:-3] + ".flags.txt")
+    tag = " ".join(flags + extra)
     # A tree that arrived with its library but without the object cache (the GPU box: vbq_amd/lib/obj is not shipped) is up
     # to date when the library is newer than every source AND was built with these flags: nothing to do, and nothing
     # that needs hipcc.
-    if not force and not os.path.isdir(objdir) and not _newer(LIB, srcs + headers) and \
+    if not force and not os.path.isdir(objdir) and not _newer(lib, srcs + headers) and \
             os.path.exists(lib_tag) and open(lib_tag).read() == tag:
-        return LIB
+        return lib
     os.makedirs(objdir, exist_ok=True)
     if not os.path.exists(flags_tag) or open(flags_tag).read() != tag:
         force = True
     objs = [os.path.join(objdir, os.path.basename(s)[:-4] + ".o") for s in srcs]
     todo = [(s, o) for s, o in zip(srcs, objs) if force or _newer(o, [s] + headers)]
-    if not todo and not _newer(LIB, objs) and os.path.exists(lib_tag) and open(lib_tag).read() == tag:
-        return LIB
+    if not todo and not _newer(lib, objs) and os.path.exists(lib_tag) and open(lib_tag).read() == tag:
+        return lib
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
-        raise RuntimeError("hipcc not found: cannot build libvbq_hip.so (ROCm toolchain required)")
+        raise RuntimeError("hipcc not found: cannot build " + os.path.basename(lib) + " (ROCm toolchain required)")
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        for line in ex.map(lambda so: _compile_one(hipcc, so[0], so[1], extra), todo):
+        for line in ex.map(lambda so: _compile_one(hipcc, so[0], so[1], extra, flags), todo):
             if verbose:
                 print(line)
     open(flags_tag, "w").write(tag)
-    tmp = _tmp(LIB)
+    tmp = _tmp(lib)
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + LINK_LIBS + ["-o", tmp]
     if verbose:
         print(" ".join(cmd))
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("link failed:\n" + r.stdout + r.stderr)
-    os.replace(tmp, LIB)
+    os.replace(tmp, lib)
     tmp = _tmp(lib_tag)
     open(tmp, "w").write(tag)
     os.replace(tmp, lib_tag)
-    return LIB
+    return lib
+
+
+def build_hip(force: bool = False, verbose: bool = False) -> str:
+    """libvbq_hip.so (include/vbq.h): one object per .hip source of vbq_amd/csrc under vbq_amd/lib/obj, one link."""
+    return _build_library(LIB, hip_sources(), hip_headers(), os.path.join(LIBDIR, "obj"), HIPCC_FLAGS, force, verbose)
+
+
+def ext_sources():
+    import glob
+    return sorted(glob.glob(os.path.join(EXT, "*.hip")))
+
+
+def build_ext(force: bool = False, verbose: bool = False) -> str:
+    """libvbq_ext.so (include/vbq_ext.h): the sources of vbq_amd/ext, with the headers of vbq_amd/csrc on the include path
+    and hidden visibility -- only the extern "C" entry points leave the library.  Objects under vbq_amd/lib/obj/ext."""
+    headers = hip_headers() + [os.path.join(INCLUDE, "vbq_ext.h")]
+    return _build_library(EXT_LIB, ext_sources(), headers, os.path.join(LIBDIR, "obj", "ext"), EXT_HIPCC_FLAGS, force, verbose)
 
 
 def build_oracle(force: bool = False) -> str:
@@ -130,5 +149,6 @@ def build_oracle(force: bool = False) -> str:
 
 if __name__ == "__main__":
     print(build_hip(force="--force" in sys.argv, verbose=True))
+    print(build_ext(force="--force" in sys.argv, verbose=True))
     if "--oracle" in sys.argv:
         print(build_oracle(force="--force" in sys.argv))

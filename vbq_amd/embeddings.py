@@ -17,6 +17,9 @@
                                                              top-k, vbq_topk.hip): the records are searched as they are stored
     bag / RecordEmbeddings.bag                               (ours) pooled rows -- the sum, mean or max of a list of rows per
                                                              output, torch.nn.EmbeddingBag on the compressed table (vbq_bag.hip)
+    scores / similarity / rerank, also of RecordEmbeddings   (ours) the scores of the rows the caller names per query -- word-pair
+                                                             similarity, reranking -- in one launch, bit for bit the search's
+                                                             scores (vbq_amd/ext/vbqx_scores.hip, the second library)
 """
 from __future__ import annotations
 
@@ -434,6 +437,19 @@ def _search_args(queries, K: int, k, metric, exclude, device):
     k = operator.index(k)
     if not 1 <= k <= 64:
         raise ValueError(f"k = {k} outside 1..64")
+    q = _query_args(queries, K, metric, device)
+    if exclude is not None:
+        exclude = ops.upload(exclude, device, torch.int64)
+        if exclude.dim() == 1 and q.shape[0] == 1:
+            exclude = exclude[None, :]
+        if exclude.dim() != 2 or exclude.shape[0] != q.shape[0] or exclude.shape[1] > 8:
+            raise ValueError(f"exclude must be [{q.shape[0]}, E] with E <= 8, got shape {tuple(exclude.shape)}")
+    return q, k, exclude
+
+
+def _query_args(queries, K: int, metric, device):
+    """The queries of a most_similar or scores call as the kernels take them: f32 [Q, K] on the device, for the cosine divided
+    by 1e-8 + |q| in f32; ValueError for an unknown metric, a query of the wrong width or with a non-finite coordinate."""
     if metric not in ("dot", "cosine"):
         raise ValueError(f"metric {metric!r} is neither 'dot' nor 'cosine'")
     q = ops.upload(queries, device, torch.float32)
@@ -445,13 +461,7 @@ def _search_args(queries, K: int, k, metric, exclude, device):
         raise ValueError("queries hold a NaN or an infinity")
     if metric == "cosine":
         q = q / (1e-8 + torch.sqrt(torch.sum(q * q, dim=1, keepdim=True)))
-    if exclude is not None:
-        exclude = ops.upload(exclude, device, torch.int64)
-        if exclude.dim() == 1 and q.shape[0] == 1:
-            exclude = exclude[None, :]
-        if exclude.dim() != 2 or exclude.shape[0] != q.shape[0] or exclude.shape[1] > 8:
-            raise ValueError(f"exclude must be [{q.shape[0]}, E] with E <= 8, got shape {tuple(exclude.shape)}")
-    return q.contiguous(), k, exclude
+    return q.contiguous()
 
 
 def most_similar(emb, queries, k: int = 10, metric: str = "cosine", exclude=None):
@@ -541,6 +551,125 @@ def bag(emb, ids, offsets=None, *, mode: str = "sum", weights=None):
     args = _bag_args(ids, offsets, weights, mode, shape[0])                         # the host checks need no device
     e = _dev(emb)
     return _bag_call(lambda *a, **kw: ops.bag(e, *a, **kw), e.device, args, mode, shape[1:])
+
+
+# ------------------------------------------------------------------------ listed rows (vbq_amd/ext/vbqx_scores.hip)
+def _listed_ids(queries, ids, V: int):
+    """The ids of a `scores` call -> (int64 [Q, M] tensor, whether their range was checked here), Q the number of `queries`
+    ([Q, K] or [K]).  ids: [Q, M], or [M] with one query; negative ids are padding.  Host-side ids (lists, NumPy, CPU tensors)
+    that reach V raise IndexError here, before any device work; a device tensor is not read back -- the kernel's status bit
+    reports its range.  IndexError for ids that are not integers, ValueError for another shape.  Needs no device."""
+    on_device = isinstance(ids, torch.Tensor) and ids.is_cuda
+    if on_device:
+        if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+            raise IndexError(f"row ids must be integers, got {ids.dtype}")
+        t = ids.to(torch.int64)
+    else:
+        a = np.asarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids)
+        if a.size and a.dtype.kind not in "iu":
+            raise IndexError(f"row ids must be integers, got {a.dtype}")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a.size and int(a.max()) >= V:
+            raise IndexError(f"row {int(a[a >= V][0])} outside [0, {V}) (negative ids are padding)")
+        t = torch.from_numpy(a)
+    qs = tuple(np.shape(queries))
+    Q = 1 if len(qs) == 1 else (int(qs[0]) if qs else 0)
+    if t.dim() == 1 and Q == 1:
+        t = t[None, :]
+    if t.dim() != 2 or t.shape[0] != Q:
+        raise ValueError(f"ids must be [{Q}, M] (or [M] with one query), got shape {tuple(t.shape)}")
+    return t, not on_device
+
+
+def _scores_call(call, queries, listed, K: int, V: int, metric, device):
+    """The query checks of a `scores` call, the one launch `call(queries, ids, metric, status=)` on what _listed_ids returned
+    and -- for ids that were not checked on the host -- the look at the status word, after the launch -> (scores f32 [Q, M],
+    ids int64 [Q, M] on the device)."""
+    q = _query_args(queries, K, metric, device)
+    ids = listed[0].to(device).contiguous()
+    status = None if listed[1] else torch.zeros(1, dtype=torch.uint32, device=device)
+    out = call(q, ids, metric, status=status)
+    # ids checked on the host and records validated at load: no status bit is due, none is asked for, nothing is waited for
+    if status is not None and int(status.cpu().item()) & ops.SCORES_BAD_ROW:
+        raise IndexError(f"a row id outside [0, {V}) (negative ids are padding)")
+    return out, ids
+
+
+def _pair_ids(a, b, V: int):
+    """The ids of a `similarity` call as two int64 host arrays [P] and their common shape; IndexError unless every id is an
+    integer in [0, V), ValueError for two shapes.  Needs no device."""
+    a, b = (np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x) for x in (a, b))
+    if a.shape != b.shape:
+        raise ValueError(f"a {a.shape} and b {b.shape} differ in shape")
+    return _row_ids(a.reshape(-1), V), _row_ids(b.reshape(-1), V), a.shape
+
+
+def _rerank_k(k, M: int) -> int:
+    import operator
+    k = M if k is None else operator.index(k)
+    if not (1 <= k <= M or k == M == 0):
+        raise ValueError(f"k = {k} outside 1..M = {M}")
+    return k
+
+
+def _rerank(s: torch.Tensor, ids: torch.Tensor, k: int):
+    """(ids, scores) [Q, k] of the scores s [Q, M] of the rows ids [Q, M] in most_similar's total order: score descending, then
+    id ascending, -0.0 == 0.0; padding (negative ids, score -inf) at the tail as -1 / -inf.  Two stable torch sorts."""
+    key = torch.where(ids < 0, torch.iinfo(torch.int64).max, ids)
+    by_id = torch.argsort(key, dim=1, stable=True)
+    by_score = torch.argsort(s.gather(1, by_id) + 0.0, dim=1, descending=True, stable=True)       # + 0.0: -0.0 sorts as 0.0
+    order = by_id.gather(1, by_score)[:, :k]
+    out_ids = ids.gather(1, order)
+    return torch.where(out_ids < 0, -1, out_ids), s.gather(1, order)
+
+
+def _dense_shape(emb):
+    shape = tuple(int(d) for d in np.shape(emb))
+    if len(shape) != 2:
+        raise ValueError("emb must be [V, K]")
+    return shape
+
+
+def _dense_scores(emb, shape, queries, listed, metric):
+    e = _dev(emb)
+    return _scores_call(lambda *a, **kw: ops.scores(e, *a, **kw), queries, listed, shape[1], shape[0], metric, e.device)
+
+
+def scores(emb, queries, ids, metric: str = "cosine"):
+    """The score of each query against the rows it lists, on the dense matrix `emb` ([V, K], tensor or ndarray) -> f32 device
+    tensor [Q, M], in one launch and without a [Q * M, K] matrix of the listed rows (vbqx_scores_f32; the semantics are those
+    of include/vbq_ext.h, "Listed rows").  queries: [Q, K] or [K]; ids: integers [Q, M], or [M] with one query.  The scores are
+    those `most_similar` reports for the same (query, row), bit for bit: metric "cosine" is q . v / ((1e-8 + |q|)(1e-8 + |v|)),
+    "dot" is q . v.  A negative id is padding and scores -inf, so the -1 tail of a most_similar result can be fed back in.
+    IndexError for ids that are not integers or reach V: host-side ids (lists, NumPy) before any device work, a device tensor
+    -- which is not read back first -- after the launch.  ValueError for a query of the wrong width or with a non-finite
+    coordinate, an unknown metric, ids of another shape.  A "VBQe" file is served as scores(CompressedEmbeddings(data).tensor(),
+    ...), a "VBQr" file without decoding it by RecordEmbeddings.scores, bit for bit the same."""
+    shape = _dense_shape(emb)
+    listed = _listed_ids(queries, ids, shape[0])                                    # the host checks need no device
+    return _dense_scores(emb, shape, queries, listed, metric)[0]
+
+
+def similarity(emb, a, b, metric: str = "cosine"):
+    """The score of row a[i] against row b[i] of the dense matrix `emb` -> f32 device tensor shaped like `a`: word-pair
+    similarity.  `a` and `b` are integer arrays of one shape, every id in [0, V) (IndexError otherwise).  Row a is the QUERY
+    -- for the cosine divided by 1e-8 + |row a| as most_similar does with a query --, row b the candidate, scored as `scores`
+    with one id per query.  The two roles round differently: the result is NOT bitwise symmetric in (a, b)."""
+    shape = _dense_shape(emb)
+    a, b, out_shape = _pair_ids(a, b, shape[0])
+    e = _dev(emb)
+    queries = e.index_select(0, torch.from_numpy(a).to(e.device))
+    return _dense_scores(e, shape, queries, (torch.from_numpy(b)[:, None], True), metric)[0].view(out_shape)
+
+
+def rerank(emb, queries, ids, k=None, metric: str = "cosine"):
+    """`scores(emb, queries, ids, metric)` put into most_similar's order -> (ids int64 [Q, k or M], scores f32 [Q, k or M])
+    device tensors: score descending, then id ascending, -0.0 == 0.0; padding (negative ids) goes to the tail as -1 / -inf;
+    an id listed twice stays twice.  ValueError for k outside 1..M.  A torch sort over the scores."""
+    shape = _dense_shape(emb)
+    listed = _listed_ids(queries, ids, shape[0])
+    k = _rerank_k(k, listed[0].shape[1])
+    return _rerank(*_dense_scores(emb, shape, queries, listed, metric), k)
 
 
 # ------------------------------------------------------------------------ fixed-size records (vbq_amd.bitstream, "VBQr")
@@ -680,3 +809,38 @@ class RecordEmbeddings:
         args = _bag_args(ids, offsets, weights, mode, h.n_rows)
         return _bag_call(lambda *a, **kw: ops.records_bag(self._words, h.row_length, h.N, h.total_bits, self._table, *a, **kw),
                          self.device, args, mode, h.shape[1:])
+
+    def _scores(self, queries, listed, metric):
+        h = self.header
+        return _scores_call(lambda *a, **kw: ops.records_scores(self._words, h.row_length, h.N, h.total_bits, self._table, *a, **kw),
+                            queries, listed, h.row_length, h.n_rows, metric, self.device)
+
+    def scores(self, queries, ids, metric: str = "cosine"):
+        """The score of each query against the rows it lists -> f32 device tensor [Q, M], as the module's `scores` on tensor()
+        bit for bit, but straight from the records in one launch: no [Q * M, K] float32 matrix is written or read, nothing
+        but the result is allocated.  queries: [Q, K] or [K]; ids: integers [Q, M], or [M] with one query.  The scores are those
+        `most_similar` reports for the same (query, row), bit for bit; a negative id is padding and scores -inf, so the -1 tail
+        of a most_similar result can be fed back in.  IndexError for ids that are not integers or reach V: host-side ids
+        (lists, NumPy) before any device work, a device tensor -- which is not read back first -- after the launch.
+        ValueError for the queries most_similar refuses and for ids of another shape.  Records too long for the kernel's LDS
+        (K above 3500 can be) raise VBQError naming the limit."""
+        return self._scores(queries, _listed_ids(queries, ids, self.header.n_rows), metric)[0]
+
+    def similarity(self, a, b, metric: str = "cosine"):
+        """The score of row a[i] against row b[i] -> f32 device tensor shaped like `a`: word-pair similarity.  `a` and `b` are
+        integer arrays of one shape, every id in [0, V) (IndexError otherwise).  Row a is the QUERY -- rows(a), for the cosine
+        divided by 1e-8 + |row a| as most_similar(ids=a) does --, row b the candidate, scored as `scores` with one id per
+        query.  The two roles round differently: the result is NOT bitwise symmetric in (a, b)."""
+        h = self.header
+        a, b, out_shape = _pair_ids(a, b, h.n_rows)
+        queries = self.rows(a).reshape(a.size, h.row_length)
+        return self._scores(queries, (torch.from_numpy(b)[:, None], True), metric)[0].view(out_shape)
+
+    def rerank(self, queries, ids, k=None, metric: str = "cosine"):
+        """`scores(queries, ids, metric)` put into most_similar's order -> (ids int64 [Q, k or M], scores f32 [Q, k or M]) device
+        tensors: score descending, then id ascending, -0.0 == 0.0; padding (negative ids) goes to the tail as -1 / -inf; an id
+        listed twice stays twice.  ValueError for k outside 1..M.  A torch sort over the scores: rerank of most_similar's own
+        output returns it unchanged."""
+        listed = _listed_ids(queries, ids, self.header.n_rows)
+        k = _rerank_k(k, listed[0].shape[1])
+        return _rerank(*self._scores(queries, listed, metric), k)

@@ -1,0 +1,26 @@
+// libvbq_ext.so: the library's own error string and ABI version (include/vbq_ext.h).  The sources of this directory share the
+// headers of vbq_amd/csrc but are built with hidden visibility: vbq::set_error below is this library's own, and no C++ symbol
+// of either library is visible to the other.  gfx950 / ROCm only.
+#include <stdarg.h>
+#include <stdio.h>
+
+#include "vbq_common.h"
+#include "vbq_ext.h"
+
+namespace vbq {
+namespace {
+thread_local char g_err[512] = "";
+}
+void set_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+}  // namespace vbq
+
+#pragma GCC visibility push(default)
+extern "C" int vbqx_abi_version(void) { return VBQX_ABI_VERSION; }
+
+extern "C" const char *vbqx_last_error(void) { return vbq::g_err; }
+#pragma GCC visibility pop

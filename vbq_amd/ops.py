@@ -855,6 +855,59 @@ def bag(emb: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, *, weights:
     return out
 
 
+SCORES_BAD_ROW = 8                               # status bit 3 of the scores calls (bits 0..2: RECORDS_UNPACK_STATUS)
+
+
+def _scores_args(queries, ids, K, metric, status, out):
+    """What records_scores and scores take alike -> (queries [Q, K], ids [Q, M], metric code, status, out [Q, M])."""
+    queries = _dev(queries, torch.float32, "queries")
+    if queries.dim() != 2 or queries.shape[1] != K:
+        raise ValueError(f"queries must be [Q, {K}], got shape {tuple(queries.shape)}")
+    ids = _dev(ids, torch.int64, "ids")
+    if ids.dim() != 2 or ids.shape[0] != queries.shape[0]:
+        raise ValueError(f"ids must be [{queries.shape[0]}, M], got shape {tuple(ids.shape)}")
+    if metric not in _METRICS:
+        raise ValueError(f"metric {metric!r} is neither 'dot' nor 'cosine'")
+    if status is not None:
+        status = _dev(status, torch.uint32, "status")
+    return queries, ids, _METRICS[metric], status, _out(out, tuple(ids.shape), torch.float32, queries.device, "out")
+
+
+def records_scores(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: torch.Tensor, queries: torch.Tensor,
+                   ids: torch.Tensor, metric="cosine", *, status: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vbqx_records_scores_f32: the score of query q against each row ids[q, m] of the records uint32 [V, record_words], in one
+    launch and without a [Q * M, K] matrix of the listed rows (semantics: include/vbq_ext.h, "Listed rows"; the scores are
+    those records_topk reports, bit for bit).  queries f32 [Q, K], taken as given; ids int64 [Q, M]; metric "dot" or "cosine"
+    (the score divided by 1e-8 + |row|).  Returns f32 [Q, M].  A negative id is padding and scores -inf; an id >= V scores
+    -inf and sets bit 3 of `status` (uint32 [1], zeroed by the caller), a damaged record counts as a row of zeros and sets the
+    unpack's bits 0..2."""
+    from . import _lib_ext
+    words = _dev(words, torch.uint32, "words")
+    K, N, total_bits = int(K), int(N), int(total_bits)
+    n_tables, table_sorted = _records_inputs(words, "V", K, N, total_bits, table_sorted)
+    queries, ids, metric, status, out = _scores_args(queries, ids, K, metric, status, out)
+    _lib_ext.check(_lib_ext.lib().vbqx_records_scores_f32(_ptr(words), words.shape[0], K, N, total_bits, _ptr(table_sorted),
+                                                          n_tables, _ptr(queries), ids.shape[0], _ptr(ids), ids.shape[1], metric,
+                                                          _ptr(out), _ptr(status), _stream(words)), "vbqx_records_scores_f32")
+    return out
+
+
+def scores(emb: torch.Tensor, queries: torch.Tensor, ids: torch.Tensor, metric="cosine", *,
+           status: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vbqx_scores_f32: records_scores on a dense f32 [V, K] matrix -- the same kernel with a dense row loader, the same
+    scores bit for bit."""
+    from . import _lib_ext
+    emb = _dev(emb, torch.float32, "emb")
+    if emb.dim() != 2:
+        raise ValueError(f"emb must be [V, K], got shape {tuple(emb.shape)}")
+    V, K = emb.shape
+    queries, ids, metric, status, out = _scores_args(queries, ids, K, metric, status, out)
+    _lib_ext.check(_lib_ext.lib().vbqx_scores_f32(_ptr(emb), V, K, _ptr(queries), ids.shape[0], _ptr(ids), ids.shape[1], metric,
+                                                  _ptr(out), _ptr(status), _stream(emb)), "vbqx_scores_f32")
+    return out
+
+
 WINDOW_BAD_SEGMENT, WINDOW_BAD_FILE = 32, 128    # status bits 5 and 7 of the window decode (bits 0..3: the segment decoder's)
 
 
