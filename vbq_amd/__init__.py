@@ -6,6 +6,7 @@ ROCm device the ops raise.
 
     vbq_amd.quantize(mu, sigma, lmbda, table=...)          one-call surface (api.py)
     vbq_amd.quantize_rows_to_budget(mu, sigma, total_bits) every row at exactly total_bits raw bits (rows_budget.py)
+    vbq_amd.quantize_rows_to_budgets(mu, sigma, budgets)   the same at many budgets from one DP pass (include/vbq_budget.h)
     vbq_amd.ChannelwisePriorCDFQuantizer                   img-compression/quantizer.py:13-256
     vbq_amd.utils                                          img-compression/utils.py solvers
     vbq_amd.embeddings                                     word-embeddings notebook cells 25-30; compress_to_bytes / decompress /
@@ -20,7 +21,7 @@ from . import ops  # noqa: F401
 from .api import gaussian_table, quantize  # noqa: F401
 from .lazy import LazyArray, device_tensor  # noqa: F401
 from .quantizer import ChannelwisePriorCDFQuantizer  # noqa: F401
-from .rows_budget import quantize_rows_to_budget  # noqa: F401
+from .rows_budget import quantize_rows_to_budget, quantize_rows_to_budgets  # noqa: F401
 
 __all__ = ["VBQError", "lib", "library_path", "ops", "quantize", "gaussian_table", "ChannelwisePriorCDFQuantizer", "LazyArray",
-           "device_tensor", "quantize_rows_to_budget"]
+           "device_tensor", "quantize_rows_to_budget", "quantize_rows_to_budgets"]

@@ -1,6 +1,6 @@
 """Build the HIP extension (and, for tests only, the C oracle) in-tree.
 
-    python -m vbq_amd.build            # libvbq_hip.so and libvbq_ext.so for gfx950
+    python -m vbq_amd.build            # libvbq_hip.so, libvbq_ext.so and libvbq_budget.so for gfx950
     python -m vbq_amd.build --oracle   # also oracle/_build/libvbq_oracle.so
 
 hipcc cross-compiles gfx950 without a GPU; the resulting .so is git-ignored but travels
@@ -26,6 +26,8 @@ HIP_SOURCES = ["vbq_api.hip", "vbq_quantize.hip", "vbq_quantize_fast.hip", "vbq_
                "vbq_rans_map_rates_files.hip"]
 EXT = os.path.join(PKG, "ext")
 EXT_LIB = os.path.join(LIBDIR, "libvbq_ext.so")
+BUDGET = os.path.join(PKG, "budget")
+BUDGET_LIB = os.path.join(LIBDIR, "libvbq_budget.so")
 LINK_LIBS = ["-ldl"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                # every f32/f64 op of the reference is a separately rounded op: never contract a*b+c
@@ -83,7 +85,7 @@ def _build_library(lib, srcs, headers, objdir, flags, force, verbose):
     from concurrent.futures import ThreadPoolExecutor
     extra = extra_flags()
     flags_tag = os.path.join(objdir, "flags.txt")
-    # travels with the library (the object cache does not): flags.txt, vbq_ext.flags.txt
+    # travels with the library (the object cache does not): flags.txt, vbq_ext.flags.txt, vbq_budget.flags.txt
     lib_tag = os.path.join(LIBDIR, "flags.txt" if lib == LIB else os.path.basename(lib)[3:-3] + ".flags.txt")
     tag = " ".join(flags + extra)
     # A tree that arrived with its library but without the object cache (the GPU box: vbq_amd/lib/obj is not shipped) is up
@@ -138,6 +140,19 @@ def build_ext(force: bool = False, verbose: bool = False) -> str:
     return _build_library(EXT_LIB, ext_sources(), headers, os.path.join(LIBDIR, "obj", "ext"), EXT_HIPCC_FLAGS, force, verbose)
 
 
+def budget_sources():
+    import glob
+    return sorted(glob.glob(os.path.join(BUDGET, "*.hip")))
+
+
+def build_budget(force: bool = False, verbose: bool = False) -> str:
+    """libvbq_budget.so (include/vbq_budget.h): the sources of vbq_amd/budget, built as build_ext builds vbq_amd/ext -- the
+    headers of vbq_amd/csrc on the include path, hidden visibility.  Objects under vbq_amd/lib/obj/budget."""
+    headers = hip_headers() + [os.path.join(INCLUDE, "vbq_budget.h")]
+    return _build_library(BUDGET_LIB, budget_sources(), headers, os.path.join(LIBDIR, "obj", "budget"), EXT_HIPCC_FLAGS, force,
+                          verbose)
+
+
 def build_oracle(force: bool = False) -> str:
     """gcc build of oracle/vbq_oracle.c (test infrastructure, never loaded by vbq_amd)."""
     odir = os.path.join(ROOT, "oracle")
@@ -150,5 +165,6 @@ def build_oracle(force: bool = False) -> str:
 if __name__ == "__main__":
     print(build_hip(force="--force" in sys.argv, verbose=True))
     print(build_ext(force="--force" in sys.argv, verbose=True))
+    print(build_budget(force="--force" in sys.argv, verbose=True))
     if "--oracle" in sys.argv:
         print(build_oracle(force="--force" in sys.argv))

@@ -20,6 +20,10 @@
     scores / similarity / rerank, also of RecordEmbeddings   (ours) the scores of the rows the caller names per query -- word-pair
                                                              similarity, reranking -- in one launch, bit for bit the search's
                                                              scores (vbq_amd/ext/vbqx_scores.hip, the second library)
+    compress_to_records_sweep / records_distortion_curve / compress_to_records_quality / test_total_bits
+                                                             (ours) record files at many total_bits from one pass of the budget
+                                                             DP, the distortion at EVERY total_bits, and the smallest file of a
+                                                             distortion target (vbq_amd/budget/vbqb_sweep.hip, the third library)
 """
 from __future__ import annotations
 
@@ -715,6 +719,106 @@ def compress_to_records_budget(means, stds, codepoints, max_bytes, N: int = 10) 
     from . import bitstream as bs
     _, shape, C = _records_args(means, codepoints, N)
     return compress_to_records(means, stds, bs.records_total_bits_within(shape, N, C, max_bytes), codepoints, N)
+
+
+def _records_headers(shape, C, budgets, N):
+    import operator
+    from . import bitstream as bs
+    headers = [bs.RecordsHeader(N=int(N), shape=shape, C=C, total_bits=operator.index(b)) for b in budgets]
+    for h in headers:
+        h.check()
+    return headers
+
+
+def compress_to_records_sweep(means, stds, budgets, codepoints, N: int = 10):
+    """[compress_to_records(means, stds, b, codepoints, N) for b in budgets], byte for byte, with the rows solved at every
+    budget in ONE sweep (vbq_amd.quantize_rows_to_budgets: the candidates scored once, one DP pass at the largest budget), then
+    one pack launch and one device-to-host copy per budget.  `budgets`: ints in any order, repeats allowed."""
+    from . import bitstream as bs, tables
+    from .rows_budget import quantize_rows_to_budgets
+    cp, shape, C = _records_args(means, codepoints, N)
+    headers = _records_headers(shape, C, budgets, N)
+    if not headers:
+        return []
+    R, K = headers[0].n_rows, headers[0].row_length
+    idx, _, _ = quantize_rows_to_budgets(_dev(means).reshape(R, K), _dev(stds).reshape(R, K), [h.total_bits for h in headers],
+                                         table=cp, N=int(N))
+    table = tables.level_major_to_sorted(cp.reshape(C, headers[0].T))
+    files = []
+    for s, h in enumerate(headers):
+        RW = h.record_words
+        buf = torch.zeros(R * RW + 1, dtype=torch.int32, device=idx.device).view(torch.uint32)   # the records, then the status
+        ops.records_pack(idx[s], h.total_bits, h.N, status=buf[-1:], out=buf[:-1].view(R, RW))
+        host = buf.cpu().numpy()
+        if host[-1]:
+            raise _lib.VBQError("compress_to_records: the rank indices of a row do not spell the bit lengths it was given (a code "
+                                "book with equal neighbouring code points has no unique rank index)")
+        files.append(bs.write_records(h, table, host[:-1]))
+    return files
+
+
+def records_distortion_curve(means, stds, codepoints, N: int = 10) -> np.ndarray:
+    """D(b) for b = 0..K N, float64 NumPy [K N + 1]: the mean of ((z_hat - mu) / sigma)^2 over the matrix that the record file
+    compress_to_records(means, stds, b, codepoints, N) has -- with bitstream.records_nbytes, the whole rate-distortion curve of
+    the format.  D(b) = -2 * sum_r objective(r, b) / (R K), the objectives from the curve-only pass of the budget DP
+    (vbq_amd.rows_budget.budget_curve) over chunks of at most rows_budget.CURVE_SCRATCH_BYTES // (8 (K N + 1)) rows, whose f64
+    column sums are added in ascending chunk order: the [R, K N + 1] matrix is never held.  D need not be monotone in b --
+    every row spends exactly b bits."""
+    from . import rows_budget
+    cp, shape, C = _records_args(means, codepoints, N)
+    h = _records_headers(shape, C, [0], N)[0]
+    R, K = h.n_rows, h.row_length
+    mu, sg = _dev(means).reshape(R, K), _dev(stds).reshape(R, K)
+    step = max(1, rows_budget.CURVE_SCRATCH_BYTES // (8 * (K * h.N + 1)))
+    total = None
+    for r0 in range(0, R, step):
+        part = rows_budget.budget_curve(mu[r0:r0 + step], sg[r0:r0 + step], table=cp, N=h.N).sum(dim=0)
+        total = part if total is None else total + part
+    return (-2.0 * total / (R * K)).cpu().numpy()
+
+
+def _smallest_bits_within(curve, max_distortion) -> int:
+    """The smallest b with curve[b] <= max_distortion.  The curve need not be monotone, so every b is looked at (no bisection).
+    ValueError naming the curve's minimum and where it is reached when no b qualifies."""
+    curve = np.asarray(curve, dtype=np.float64)
+    target = float(max_distortion)
+    if target != target:
+        raise ValueError("max_distortion is NaN")
+    ok = np.flatnonzero(curve <= target)
+    if ok.size == 0:
+        best = int(np.nanargmin(curve))
+        raise ValueError(f"no total_bits reaches a distortion of {target!r}: the smallest is {float(curve[best])!r}, "
+                         f"at total_bits = {best}")
+    return int(ok[0])
+
+
+def compress_to_records_quality(means, stds, codepoints, max_distortion, N: int = 10) -> bytes:
+    """`compress_to_records` at the SMALLEST total_bits whose record file has a distortion D(b) <= max_distortion
+    (records_distortion_curve: the mean of ((z_hat - mu) / sigma)^2) -- the dual of compress_to_records_budget.  ValueError
+    naming min_b D(b) and the b it is reached at when no total_bits qualifies."""
+    b = _smallest_bits_within(records_distortion_curve(means, stds, codepoints, N), max_distortion)
+    return compress_to_records(means, stds, b, codepoints, N)
+
+
+def test_total_bits(means, stds, budgets, codepoints, analogies_id):
+    """test_betas for record files: float64 [len(budgets), 4] rows (mrr, acc, hits10, bits) of the matrix quantized row by row
+    to each total_bits of `budgets` -- one budget sweep (vbq_amd.quantize_rows_to_budgets), then one fused rank GEMM per budget
+    on the chosen code points.  `bits` is the file's cost per coordinate, 8 * bitstream.records_nbytes / n."""
+    from . import bitstream as bs
+    from .rows_budget import _rows_sweep
+    N = int(np.log2(np.shape(codepoints)[-1] + 1)) - 1
+    cp, shape, C = _records_args(means, codepoints, N)
+    headers = _records_headers(shape, C, budgets, N)
+    if not headers:
+        return np.zeros((0, 4), dtype=np.float64)
+    R, K = headers[0].n_rows, headers[0].row_length
+    chosen = _rows_sweep("embeddings.test_total_bits", _dev(means).reshape(R, K), _dev(stds).reshape(R, K),
+                         [h.total_bits for h in headers], cp, N)[3]
+    rows = []
+    for s, h in enumerate(headers):
+        ranks = prediction_ranks(chosen[s], analogies_id)
+        rows.append(analogy_metrics(ranks) + (8.0 * bs.records_nbytes(shape, N, h.total_bits, C) / h.n,))
+    return np.array(rows, dtype=np.float64)
 
 
 class RecordEmbeddings:

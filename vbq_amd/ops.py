@@ -639,6 +639,44 @@ def budget_dp(fhat: torch.Tensor, K: int, budget: int, *, status: Optional[torch
     return bits, obj
 
 
+def budget_dp_sweep(fhat: torch.Tensor, K: int, budgets: Sequence[int], *, curve_len: int = 0, status: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None):
+    """vbqb_budget_sweep_f64: budget_dp at every budget of `budgets` (ints, strictly ascending, at most 64 of them, each in
+    [0, K * N]) from ONE forward pass at the largest, and with curve_len > 0 the optimal objective at every budget below
+    curve_len <= K * N + 1 (include/vbq_budget.h, "Budget sweep").  fhat as for budget_dp.  Returns (bits int32 [S, rows, K],
+    objective f64 [S, rows], curve f64 [rows, curve_len] or None); slice s equals budget_dp(fhat, K, budgets[s]) bit for bit and
+    curve[r, n] is the objective budget_dp reports for row r at budget n.  No budgets and a curve is the curve-only pass, which
+    keeps no back-pointers.  `status` and `workspace` as for budget_dp."""
+    import operator
+    from . import _lib_budget
+    fhat = _dev(fhat, torch.float64, "fhat")
+    N, K, curve_len = fhat.shape[0] - 1, int(K), operator.index(curve_len)
+    E = fhat[0].numel() if fhat.shape[0] else 0
+    if K < 1 or E % K:
+        raise ValueError(f"fhat holds {E} elements per level, not a multiple of K={K}")
+    rows = E // K
+    budgets = [operator.index(b) for b in budgets]
+    S = len(budgets)
+    if any(not -(1 << 31) <= b < (1 << 31) for b in budgets) or not 0 <= curve_len < (1 << 31):
+        raise ValueError(f"budgets {budgets} or curve_len {curve_len} outside the int32 range")
+    bits = torch.empty((S, rows, K), dtype=torch.int32, device=fhat.device)
+    obj = torch.empty((S, rows), dtype=torch.float64, device=fhat.device)
+    curve = torch.empty((rows, curve_len), dtype=torch.float64, device=fhat.device) if curve_len else None
+    if status is not None:
+        status = _dev(status, torch.uint32, "status")
+    h = _lib_budget.lib()
+    if workspace is None:
+        wsb = h.vbqb_budget_sweep_workspace_bytes(rows, K, N, max([b + 1 for b in budgets] + [curve_len])) if S else 0
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=fhat.device) if wsb else None
+    else:
+        workspace = _dev(workspace, torch.uint8, "workspace")
+    wsb = workspace.numel() if workspace is not None else 0
+    _lib_budget.check(h.vbqb_budget_sweep_f64(_ptr(fhat), rows, K, N, (C.c_int32 * S)(*budgets), S, _ptr(bits), _ptr(obj),
+                                              _ptr(curve), curve_len, _ptr(status), _ptr(workspace), wsb, _stream(fhat)),
+                      "vbqb_budget_sweep_f64")
+    return bits, obj, curve
+
+
 def budget_patience(fhat: torch.Tensor, lamb: float, patience: int = 3):
     """vbq_budget_patience_f64: per element the scan of utils.encode_mode (utils.py:186-203) over g_b = fhat_b - lamb * b.
     fhat: f64 [N+1, E].  Returns (bits int32 [E], g f64 [E])."""

@@ -5,6 +5,10 @@ most" a budget of the whole tensor, this solves the constrained problem per row:
 coordinates, at most N each, with the largest Gaussian score (the budget DP of img-compression/utils.py:106-160, batched:
 vbq_budget_dp_f64).  Rows of equal cost are fixed-size records, addressable without an entropy coder.
 vbq_amd.embeddings.compress_to_records stores them as such (vbq_amd.bitstream, magic b"VBQr"); RecordEmbeddings looks rows up.
+
+quantize_rows_to_budgets(mu, sigma, budgets) is the same at many budgets, and budget_curve(mu, sigma) the objective of every
+row at EVERY budget, from one forward pass of the DP each (vbqb_budget_sweep_f64, include/vbq_budget.h): the recurrence does
+not depend on the budget it is run for.
 """
 from __future__ import annotations
 
@@ -60,27 +64,13 @@ def quantize_rows_to_budget(mu, sigma, total_bits, *, table, N: int = 10):
     num_bits int32 [R, K] = its bit length (every row sums to its budget), objective f64 [R] = the row's summed score
     -0.5 * ((c - mu) / sigma)**2 in float64, accumulated over ascending k.  The best allocation is exact: no other allocation
     of the same total has a larger objective.  Raises VBQError when a score is NaN or +inf (sigma <= 0, non-finite inputs)."""
-    if not torch.cuda.is_available():
-        raise VBQError("no ROCm device visible: vbq_amd.quantize_rows_to_budget has no CPU implementation")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    mu_t = (torch.from_numpy(np.ascontiguousarray(mu)) if not isinstance(mu, torch.Tensor) else mu).to(dev, torch.float32)
-    sg_t = (torch.from_numpy(np.ascontiguousarray(sigma)) if not isinstance(sigma, torch.Tensor) else sigma).to(dev, torch.float32)
-    if mu_t.dim() != 2 or mu_t.shape != sg_t.shape:
-        raise ValueError(f"mu and sigma must be [R, K] of one shape, got {tuple(mu_t.shape)} and {tuple(sg_t.shape)}")
+    mu_t, sg_t, tab_lm, tab_sorted, C = _rows_args("quantize_rows_to_budget", mu, sigma, table, N)
+    dev = mu_t.device
     R, K = mu_t.shape
-    if K < 1:
-        raise ValueError("K must be at least 1")
-    T = table_size(N)
-    shape = tuple(table.shape)
-    if shape not in ((T,), (1, T), (K, T)):
-        raise ValueError(f"table must be [{T}] or [{K}, {T}] for N={N}, got {shape}")
-    C = K if shape == (K, T) else 1
-    tab_lm, tab_sorted = _device_table(table, C, N, dev, True)
     budgets = torch.as_tensor(np.asarray(total_bits.cpu() if isinstance(total_bits, torch.Tensor) else total_bits)).reshape(-1)
     if budgets.dtype.is_floating_point or budgets.numel() not in (1, R):
         raise ValueError("total_bits must be an int or an int array with one entry per row")
     budgets = budgets.to(torch.int64)
-    mu_t, sg_t = mu_t.contiguous(), sg_t.contiguous()
     num_bits = torch.empty((R, K), dtype=torch.int32, device=dev)
     objective = torch.empty(R, dtype=torch.float64, device=dev)
     if R == 0:
@@ -95,11 +85,124 @@ def quantize_rows_to_budget(mu, sigma, total_bits, *, table, N: int = 10):
             nb, ob = ops.budget_dp(scores[:, rows].contiguous(), K, int(b), status=status)
             num_bits[rows] = nb
             objective[rows] = ob
+    idx, _ = _rank_indices(values, num_bits, tab_sorted, C)
+    _raise_on_status("quantize_rows_to_budget", status)
+    return idx, num_bits, objective
+
+
+def _rows_args(who, mu, sigma, table, N):
+    """The arguments the row calls share, on the current device: (mu f32 [R, K], sigma f32 [R, K], level-major table, sorted
+    table, C = code books)."""
+    if not torch.cuda.is_available():
+        raise VBQError(f"no ROCm device visible: vbq_amd.{who} has no CPU implementation")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mu_t = (torch.from_numpy(np.ascontiguousarray(mu)) if not isinstance(mu, torch.Tensor) else mu).to(dev, torch.float32)
+    sg_t = (torch.from_numpy(np.ascontiguousarray(sigma)) if not isinstance(sigma, torch.Tensor) else sigma).to(dev, torch.float32)
+    if mu_t.dim() != 2 or mu_t.shape != sg_t.shape:
+        raise ValueError(f"mu and sigma must be [R, K] of one shape, got {tuple(mu_t.shape)} and {tuple(sg_t.shape)}")
+    R, K = mu_t.shape
+    if K < 1:
+        raise ValueError("K must be at least 1")
+    T = table_size(N)
+    shape = tuple(table.shape)
+    if shape not in ((T,), (1, T), (K, T)):
+        raise ValueError(f"table must be [{T}] or [{K}, {T}] for N={N}, got {shape}")
+    C = K if shape == (K, T) else 1
+    tab_lm, tab_sorted = _device_table(table, C, N, dev, True)
+    return mu_t.contiguous(), sg_t.contiguous(), tab_lm, tab_sorted, C
+
+
+def _rank_indices(values, num_bits, tab_sorted, C):
+    """num_bits int32 [R, K] -> (rank index uint16 [R, K] of the code point each element chose, the code point f32 [R, K])."""
     chosen = torch.gather(values, 0, num_bits.to(torch.int64)[None])[0]              # [R, K] f32: the code point itself
     if C > 1:
         idx = torch.searchsorted(tab_sorted, chosen.t().contiguous()).t()
     else:
         idx = torch.searchsorted(tab_sorted[0], chosen)
+    return idx.to(torch.uint16).contiguous(), chosen
+
+
+def _raise_on_status(who, status):
     if int(status.cpu().item()) & 1:
-        raise VBQError("quantize_rows_to_budget: a score is NaN or +inf (non-finite mu, or sigma that is not positive)")
-    return idx.to(torch.uint16).contiguous(), num_bits, objective
+        raise VBQError(f"{who}: a score is NaN or +inf (non-finite mu, or sigma that is not positive)")
+
+
+SWEEP_MAX_BUDGETS = 64                       # budgets of one vbqb_budget_sweep_f64 launch
+CURVE_SCRATCH_BYTES = 64 << 20               # embeddings.records_distortion_curve: the f64 curves of one chunk of rows
+
+
+def _budget_list(total_bits, K: int, N: int):
+    import operator
+    if isinstance(total_bits, torch.Tensor):
+        total_bits = total_bits.cpu().tolist()
+    budgets = [operator.index(b) for b in (total_bits.tolist() if isinstance(total_bits, np.ndarray) else total_bits)]
+    for b in budgets:
+        if not 0 <= b <= K * N:
+            raise ValueError(f"budget {b} outside [0, K*N = {K * N}]")
+    return budgets
+
+
+def _sweep_in_order(scores, K: int, budgets, status):
+    """ops.budget_dp_sweep for a budget list in any order and with repeats: the distinct values ascending, 64 to a launch,
+    the slices back in the caller's order.  -> (bits int32 [S, R, K], objective f64 [S, R])."""
+    distinct = sorted(set(budgets))
+    bits, obj = [], []
+    for i in range(0, max(len(distinct), 1), SWEEP_MAX_BUDGETS):
+        b, o, _ = ops.budget_dp_sweep(scores, K, distinct[i:i + SWEEP_MAX_BUDGETS], status=status)
+        bits.append(b)
+        obj.append(o)
+    bits = bits[0] if len(bits) == 1 else torch.cat(bits)
+    obj = obj[0] if len(obj) == 1 else torch.cat(obj)
+    if budgets == distinct:
+        return bits, obj
+    order = torch.tensor([distinct.index(b) for b in budgets], dtype=torch.int64, device=bits.device)
+    return bits[order], obj[order]
+
+
+def _rows_sweep(who, mu, sigma, budgets, table, N):
+    """-> (idx uint16 [S, R, K], num_bits int32 [S, R, K], objective f64 [S, R], code points f32 [S, R, K])."""
+    mu_t, sg_t, tab_lm, tab_sorted, C = _rows_args(who, mu, sigma, table, N)
+    dev = mu_t.device
+    R, K = mu_t.shape
+    budgets = _budget_list(budgets, K, N)
+    S = len(budgets)
+    if R == 0 or S == 0:
+        return (torch.empty((S, R, K), dtype=torch.uint16, device=dev), torch.empty((S, R, K), dtype=torch.int32, device=dev),
+                torch.empty((S, R), dtype=torch.float64, device=dev), torch.empty((S, R, K), dtype=torch.float32, device=dev))
+    scores, values = level_candidates(mu_t, sg_t, tab_lm, N)
+    status = torch.zeros(1, dtype=torch.uint32, device=dev)
+    num_bits, objective = _sweep_in_order(scores, K, budgets, status)
+    idx = torch.empty((S, R, K), dtype=torch.uint16, device=dev)
+    chosen = torch.empty((S, R, K), dtype=torch.float32, device=dev)
+    for s in range(S):
+        idx[s], chosen[s] = _rank_indices(values, num_bits[s], tab_sorted, C)
+    _raise_on_status(who, status)
+    return idx, num_bits, objective, chosen
+
+
+def quantize_rows_to_budgets(mu, sigma, budgets, *, table, N: int = 10):
+    """quantize_rows_to_budget at every budget of `budgets` (ints in [0, K * N], any order, repeats allowed) for the price of
+    about the largest: the candidates are scored once, the budget DP runs ONE forward pass per 64 distinct budgets
+    (ops.budget_dp_sweep) and each budget only walks its own back-pointers.
+    Returns device tensors (idx uint16 [S, R, K], num_bits int32 [S, R, K], objective f64 [S, R]); slice s equals
+    quantize_rows_to_budget(mu, sigma, budgets[s], table=table, N=N) bit for bit."""
+    return _rows_sweep("quantize_rows_to_budgets", mu, sigma, budgets, table, N)[:3]
+
+
+def budget_curve(mu, sigma, *, table, N: int = 10, max_bits=None):
+    """The objective quantize_rows_to_budget reports for every row at EVERY budget: f64 [R, max_bits + 1] on the device, entry
+    [r, b] for row r at total_bits = b (max_bits defaults to K * N).  One curve-only forward pass of the budget DP, which keeps
+    no back-pointers.  A row's curve need not be monotone in b: the budget is spent exactly."""
+    import operator
+    mu_t, sg_t, tab_lm, _, _ = _rows_args("budget_curve", mu, sigma, table, N)
+    R, K = mu_t.shape
+    max_bits = K * N if max_bits is None else operator.index(max_bits)
+    if not 0 <= max_bits <= K * N:
+        raise ValueError(f"max_bits {max_bits} outside [0, K*N = {K * N}]")
+    if R == 0:
+        return torch.empty((0, max_bits + 1), dtype=torch.float64, device=mu_t.device)
+    scores, _ = level_candidates(mu_t, sg_t, tab_lm, N)
+    status = torch.zeros(1, dtype=torch.uint32, device=mu_t.device)
+    curve = ops.budget_dp_sweep(scores, K, [], curve_len=max_bits + 1, status=status)[2]
+    _raise_on_status("budget_curve", status)
+    return curve
