@@ -8,6 +8,8 @@ ROCm device the ops raise.
     vbq_amd.quantize_rows_to_budget(mu, sigma, total_bits) every row at exactly total_bits raw bits (rows_budget.py)
     vbq_amd.quantize_rows_to_budgets(mu, sigma, budgets)   the same at many budgets from one DP pass (include/vbq_budget.h)
     vbq_amd.ChannelwisePriorCDFQuantizer                   img-compression/quantizer.py:13-256
+    vbq_amd.OptimalKmeansQuantizer / ChannelwiseOptimalKmeansWrapper   the k-means baseline fitted exactly on the device: 1-D DP,
+                                                           every level count of every channel in one launch (include/vbq_kmeans.h)
     vbq_amd.utils                                          img-compression/utils.py solvers
     vbq_amd.embeddings                                     word-embeddings notebook cells 25-30; compress_to_bytes / decompress /
                                                            CompressedEmbeddings: the quantized matrix as rANS-coded bytes, rows on demand
@@ -19,9 +21,11 @@ ROCm device the ops raise.
 from ._lib import VBQError, lib, library_path  # noqa: F401
 from . import ops  # noqa: F401
 from .api import gaussian_table, quantize  # noqa: F401
+from .baselines import ChannelwiseOptimalKmeansWrapper, OptimalKmeansQuantizer  # noqa: F401
 from .lazy import LazyArray, device_tensor  # noqa: F401
 from .quantizer import ChannelwisePriorCDFQuantizer  # noqa: F401
 from .rows_budget import quantize_rows_to_budget, quantize_rows_to_budgets  # noqa: F401
 
 __all__ = ["VBQError", "lib", "library_path", "ops", "quantize", "gaussian_table", "ChannelwisePriorCDFQuantizer", "LazyArray",
-           "device_tensor", "quantize_rows_to_budget", "quantize_rows_to_budgets"]
+           "device_tensor", "quantize_rows_to_budget", "quantize_rows_to_budgets",
+           "OptimalKmeansQuantizer", "ChannelwiseOptimalKmeansWrapper"]

@@ -1,7 +1,9 @@
 """Comparison quantizers with the reference's API (img-compression/quantizer.py:259-459):
 UniformQuantizer, KmeansQuantizer, ChannelwiseSimpleQuantizer and its multi-level wrapper.
 The elementwise passes run on the GPU (vbq_baselines.hip); k-means itself is sklearn on the host,
-exactly as in the reference (:309-311).  NumPy in, NumPy out."""
+exactly as in the reference (:309-311).  NumPy in, NumPy out.
+OptimalKmeansQuantizer and ChannelwiseOptimalKmeansWrapper are additions of this package: the same contracts with the k-means
+fit replaced by the exact dynamic programme of include/vbq_kmeans.h on the device (kmeans1d.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -193,6 +195,77 @@ class ChannelwiseSimpleQuantizerWrapper:
             tmp = q.compress_latents(pm)
             for field in output:
                 output[field][l] = tmp[field]
+        Z = np.stack([output["Z_hat"][l] for l in self.quantization_levels])
+        X_hat = np.reshape(_decode(vae, np.reshape(Z, (-1,) + pm.shape[1:]), posterior_means),
+                           (len(self.quantization_levels),) + tuple(np.shape(X)))
+        if clip:
+            X_hat = np.clip(X_hat, 0, 1)
+        output["X_hat"] = {l: X_hat[i] for i, l in enumerate(self.quantization_levels)}
+        return output
+
+
+class OptimalKmeansQuantizer(KmeansQuantizer):
+    """KmeansQuantizer with the fit replaced by the exact one: the code points are the GLOBAL optimum of 1-D k-means (the
+    dynamic programme of include/vbq_kmeans.h, on the device), ascending, deterministic -- no initialisation, no Lloyd
+    iteration.  Same fit(samples, add_n_smoothing=1.) / quantize(samples) contract, so it is a scalar_quantizer_type of
+    ChannelwiseSimpleQuantizer(Wrapper); quantize is KmeansQuantizer's."""
+
+    def fit(self, samples, add_n_smoothing=1.):
+        from . import kmeans1d
+        s = np.asarray(_host(samples) if isinstance(samples, torch.Tensor) else samples)
+        got = kmeans1d.fit_channels(s.reshape((-1, 1)), [self.quantization_levels], add_n_smoothing)[0]
+        self.code_points = got.code_points[0]
+        self.code_lengths = got.code_lengths[0]
+
+
+class ChannelwiseOptimalKmeansWrapper:
+    """ChannelwiseSimpleQuantizerWrapper(OptimalKmeansQuantizer, num_channels, quantization_levels) in two kinds of launch:
+    fit is ONE dynamic programme over all channels and all level counts (kmeans1d.fit_channels), compress one nearest-code
+    launch per level count over all channels.  The dicts compress returns equal that wrapper's, array for array, bit for bit."""
+
+    def __init__(self, num_channels, quantization_levels):
+        self.quantization_levels = quantization_levels
+        self.num_channels = num_channels
+
+    def fit_latents(self, posterior_means, add_n_smoothing):
+        from . import kmeans1d
+        C_ = np.shape(posterior_means)[-1]
+        assert C_ == self.num_channels
+        pm = posterior_means if isinstance(posterior_means, torch.Tensor) else _host(posterior_means)
+        fits = kmeans1d.fit_channels(pm.reshape((-1, C_)), list(self.quantization_levels), add_n_smoothing)
+        self.code_points = {l: f.code_points for l, f in zip(self.quantization_levels, fits)}
+        self.code_lengths = {l: f.code_lengths for l, f in zip(self.quantization_levels, fits)}
+
+    def fit(self, X, vae, add_n_smoothing):
+        posterior_means, _ = vae.encode(X)
+        self.fit_latents(posterior_means, add_n_smoothing)
+
+    def compress_latents(self, posterior_means):
+        """{"Z_hat": {l: ...}, "num_bits": {l: ...}} of latents [..., C], float64 arrays of the latents' shape."""
+        from . import kmeans1d
+        pm = _host(posterior_means)
+        C_ = pm.shape[-1]
+        assert C_ == self.num_channels
+        _require_finite(pm, allow_inf=False)
+        dev = ops.current_device("vbq_amd.baselines")
+        x = ops.upload(pm.reshape((-1, C_)), dev, torch.float32)
+        output = {"Z_hat": {}, "num_bits": {}}
+        channel = torch.arange(C_, dtype=torch.int64, device=dev)[None, :]
+        for l in self.quantization_levels:
+            codes = torch.from_numpy(np.ascontiguousarray(self.code_points[l], dtype=np.float64)).to(dev)
+            lens = torch.from_numpy(np.ascontiguousarray(self.code_lengths[l], dtype=np.float64)).to(dev)
+            I, q = kmeans1d.nearest_code_channels(x, codes)
+            output["Z_hat"][l] = q.cpu().numpy().reshape(pm.shape)
+            # np.take(code_lengths[c], I[:, c]) of every channel as one lookup on the device: the same doubles
+            num_bits = lens.reshape(-1)[I.to(torch.int64) + channel * codes.shape[1]]
+            output["num_bits"][l] = num_bits.cpu().numpy().reshape(pm.shape)
+        return output
+
+    def compress(self, X, vae, quantization_levels, clip=True):
+        assert quantization_levels == self.quantization_levels
+        posterior_means, _ = vae.encode(X)
+        pm = _host(posterior_means)
+        output = self.compress_latents(pm)
         Z = np.stack([output["Z_hat"][l] for l in self.quantization_levels])
         X_hat = np.reshape(_decode(vae, np.reshape(Z, (-1,) + pm.shape[1:]), posterior_means),
                            (len(self.quantization_levels),) + tuple(np.shape(X)))
