@@ -1073,10 +1073,10 @@ def rans_encode_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tenso
         raise ValueError(f"M = {M} slots")
     given = words is not None
     words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words")
+    if not given:
+        words.zero_()
     if sizes is None:
         sizes = torch.zeros(M, dtype=torch.uint32, device=idx.device)
-        if not given:
-            words.zero_()
     else:
         sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes")
     if status is None:
@@ -1163,10 +1163,10 @@ def _map_files_args(idx, classes, files, palettes, items, freq, M, seg, N, canon
     given = words is not None
     if words is not False:
         words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words")
+        if not given:
+            words.zero_()
     if sizes is None:
         sizes = torch.zeros(M, dtype=torch.uint32, device=idx.device)
-        if words is not False and not given:
-            words.zero_()
     else:
         sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes")
     if status is None:
