@@ -864,9 +864,10 @@ int vbq_records_unpack_f32(const uint32_t *d_words, int64_t n_rows, int32_t K, i
  *             any point of vbq_records_topk_f32.
  * One workgroup holds 32 queries in LDS and walks tiles of rows; the records are re-decoded once per block of 32 queries, so
  * these calls are for a few queries -- many-query workloads decode once and use vbq_analogy_ranks_f32 or a GEMM.  The tiles
- * must fit 160 KiB of LDS: every K <= 512 does (n_tables 1 or K, any N and total_bits); above the limit the calls return
- * VBQ_ERR_UNSUPPORTED and name it.  Sizes and pointers are checked before any device work (VBQ_ERR_INVALID_ARGUMENT); Q == 0
- * returns 0; VBQ_ERR_WORKSPACE for a workspace that is too small.
+ * must fit 160 KiB of LDS: every K <= 512 does (n_tables 1 or K, any N and total_bits).  That is a guarantee, not the limit
+ * -- a shorter record leaves room for a longer row, the dense source fits up to K = 624; a call whose smallest tile does not
+ * fit returns VBQ_ERR_UNSUPPORTED and names the limit.  Sizes and pointers are checked before any device work
+ * (VBQ_ERR_INVALID_ARGUMENT); Q == 0 returns 0; VBQ_ERR_WORKSPACE for a workspace that is too small.
  * Added without an ABI version bump: nothing that existed before changed.
  * ---------------------------------------------------------------------------------- */
 size_t vbq_topk_workspace_bytes(int64_t V, int32_t K, int64_t Q, int32_t k, int32_t max_workgroups);
@@ -908,7 +909,8 @@ int vbq_topk_f32(const float *d_emb, int64_t V, int32_t K, const float *d_querie
  * are for many short bags; a few very long bags run serially.  Per bag the kernel keeps the staged record and two sets of K
  * accumulators in LDS, 4 (record_words + 2 K) bytes, and the one code book beside them where it fits and is re-used enough.
  * That must fit 160 KiB: every K <= 16804 does for any (N, total_bits, n_tables) (ceil(14 K / 32) + 2 K <= 40960 words at
- * N = 10, total_bits = 10 K), the dense source up to K = 20480; above, the calls return VBQ_ERR_UNSUPPORTED and name the limit.
+ * N = 10, total_bits = 10 K) -- a guarantee, not the limit: a shorter record leaves room for a longer row, the dense source
+ * fits up to K = 20480; a call whose record and accumulators do not fit returns VBQ_ERR_UNSUPPORTED and names the limit.
  * Sizes, the mode and null pointers are checked before any device work (VBQ_ERR_INVALID_ARGUMENT, also for weights with mode
  * 1 or 2); n_bags == 0 returns 0; n_ids == 0 with n_bags > 0 writes zeros.
  * Added without an ABI version bump: nothing that existed before changed.

@@ -50,8 +50,10 @@ const char *vbqx_last_error(void);
  * code point up as it goes.  A pair is never split and never shares an accumulator, so the result does not depend on how
  * pairs fall into groups.  What hides a record's scan is other waves, so groups are small: G is the largest of 64, 32 and
  * 16 at which tile and staged records stay within 8 KiB, and 8 otherwise (measured: vbqx_scores.hip), which must fit the
- * 160 KiB of a CU: every K <= 3500 does for any (N, total_bits, n_tables); above, the calls return VBQ_ERR_UNSUPPORTED and
- * name the limit.  The grid is one workgroup per group: Q M above 2147483647 G is refused.
+ * 160 KiB of a CU: every K <= 3500 does for any (N, total_bits, n_tables).  That is a guarantee, not the limit -- a shorter
+ * record leaves room for a longer row (N = 10 at the full budget: up to K = 3549; the dense source: up to K = 5103); a call
+ * whose eight pairs do not fit returns VBQ_ERR_UNSUPPORTED and names the limit.  The grid is one workgroup per group: Q M above
+ * 2147483647 G is refused.
  * Sizes, the metric and null pointers are checked before any device work (VBQ_ERR_INVALID_ARGUMENT: K < 1, N outside 1..10,
  * total_bits outside [0, K N], n_tables neither 1 nor K, V < 1, Q < 0, M < 0, a metric other than 0 / 1, Q M above the grid
  * limit, a null pointer other than d_status); Q == 0 or M == 0 returns 0 with no launch.

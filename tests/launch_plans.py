@@ -10,6 +10,16 @@ shapes have to move.
                                                                         vbq_amd/csrc/vbq_reduce.hip
                     launch_hist (k_hist_tiled)                          vbq_amd/csrc/vbq_hist.hip
     solve_kernel    launch_quantize: which solve kernel a lambda chunk takes     vbq_amd/csrc/vbq_quantize.hip, vbq_quantize_fast.hip
+
+and, for tests/test_gpu_wide_rows.py, the rules by which the kernels that size their dynamic LDS from their arguments accept a
+shape, lay the LDS out and refuse one step further:
+
+    record_words    record_check_words                                  vbq_amd/csrc/vbq_records_common.h
+    bag_plan        vbq_bag_f32 / vbq_records_bag_f32 (k_bag)           vbq_amd/csrc/vbq_bag.hip
+    scores_plan     scores_plan (k_scores)                              vbq_amd/ext/vbqx_scores.hip
+    topk_plan       topk_plan (k_topk)                                  vbq_amd/csrc/vbq_topk.hip
+    budget_plan     budget_plan / sweep_plan (k_budget_dp, k_budget_sweep)     vbq_amd/csrc/vbq_budget.hip, vbq_amd/budget/vbqb_sweep.hip
+    widest          the last shape a rule accepts, by bisection
 """
 from collections import namedtuple
 
@@ -51,6 +61,33 @@ FAST_LAMBDA_RANGE = (1.9e-12, 1.8e19)              # fast_ok: every lambda of th
 SWEEP_KEY_SHIFT = 16             # build_sweep_table<16>: a bucket is one value of (f32 bits >> 16)
 SWEEP_KEYS = 2048                # kHullKeys: buckets, 16 octaves of 128
 TILED_MAX_N = 10                 # `else if constexpr (N > 10)`: channel-last with n_ch > 1 is refused above
+# ---- every launcher below: `lds > 64 * 1024` raises hipFuncAttributeMaxDynamicSharedMemorySize before the launch
+LDS_OPT_IN = 64 * 1024
+WAVE = 64                        # kWave (vbq_common.h)
+# ---- vbq_records_common.h
+RECORDS_MAX_N = 10               # kRecordsMaxN
+RECORDS_MAX_WORDS = 8192         # kRecordsMaxWords: 32-bit words of one record
+# ---- vbq_bag.hip
+BAG_WG_PER_CU = 16               # kBagWgPerCu: single-wave workgroups per CU the grid is sized for
+BAG_LDS_TABLE_REUSE = 4          # kBagLdsTableReuse: coordinates decoded per table entry loaded, from which the code book is staged
+BAG_LDS_LIMIT = 160 * 1024       # kBagLdsLimit
+BAG_ALWAYS_K = 16804             # kBagAlwaysK: every K up to here fits whatever N, total_bits and n_tables
+# ---- vbqx_scores.hip
+SCORES_MAX_GROUP = 64            # kScoresMaxGroup = kWave: pairs per wave, halved down to kScoresMinGroup
+SCORES_MIN_GROUP = 8             # kScoresMinGroup (VBQX_SCORES_MIN_GROUP)
+SCORES_LDS_TARGET = 8 * 1024     # kScoresLdsTarget (VBQX_SCORES_LDS_TARGET): what a group above the smallest may take
+SCORES_LDS_LIMIT = 160 * 1024    # kScoresLdsLimit: what the smallest group may take
+SCORES_ALWAYS_K = 3500           # kScoresAlwaysK
+# ---- vbq_topk.hip
+TOPK_Q = 32                      # kTopkQ: queries per workgroup
+TOPK_MAX_E = 8                   # kTopkMaxE: exclusions per query
+TOPK_MIN_ROWS, TOPK_MAX_ROWS = 32, 128       # kTopkMinRows, kTopkMaxRows: rows per tile, halved from the largest
+TOPK_LDS_TWO_PER_CU = 80 * 1024  # kTopkLdsTwoPerCu: the plan first looks for a tile that leaves room for two workgroups per CU
+TOPK_LDS_LIMIT = 160 * 1024      # kTopkLdsLimit
+TOPK_ALWAYS_K = 512              # kTopkAlwaysK
+# ---- vbq_budget.hip, vbqb_sweep.hip
+BUDGET_LDS_BYTES = 160 * 1024    # kBudgetLdsBytes and kSweepLdsBytes
+BUDGET_MAX_N = 52                # kBudgetMaxN and kSweepMaxN
 
 
 def cdiv(a, b):
@@ -252,3 +289,132 @@ def solve_kernels(N, lam, layout, n_ch, **kw):
     """solve_kernel for every chunk of a sweep of any length (the l0 loop of launch_quantize); a per-lambda flag list
     level_len is not needed: the table is given for all chunks or for none."""
     return [solve_kernel(N, list(lam[l0:l0 + MAX_LAMBDA_CHUNK]), layout, n_ch, **kw) for l0 in range(0, len(lam), MAX_LAMBDA_CHUNK)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- wide rows
+def widest(pred, lo, hi):
+    """The largest x in [lo, hi] with pred(x), for a pred that holds up to some x and fails from there on; pred(lo) must hold."""
+    assert pred(lo), lo
+    if pred(hi):
+        return hi
+    while hi - lo > 1:                                       # pred(lo) and not pred(hi)
+        mid = (lo + hi) // 2
+        if pred(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def length_field_bits(N):
+    """length_field_bits of vbq_records_common.h: N.bit_length() for N <= 15."""
+    return 4 if N >= 8 else (3 if N >= 4 else (2 if N >= 2 else 1))
+
+
+def table_size(N):
+    return (2 << N) - 1
+
+
+def record_words(K, N, total_bits):
+    """record_words: K length fields, total_bits of codes, zero padding up to whole 32-bit words."""
+    return (K * length_field_bits(N) + total_bits + 31) // 32
+
+
+def record_fits(K, N, total_bits):
+    """record_check_total_bits and record_check_words: what every entry point that takes records asks first."""
+    return 1 <= N <= RECORDS_MAX_N and 0 <= total_bits <= K * N and record_words(K, N, total_bits) <= RECORDS_MAX_WORDS
+
+
+BagPlan = namedtuple("BagPlan", "lds_bytes table_in_lds")
+
+
+def bag_lds_bytes(K, n_words, table_entries):
+    """bag_lds_bytes: the staged record, the accumulators twice, the one code book."""
+    return 4 * (n_words + 2 * K + table_entries)
+
+
+def bag_plan(K, N, total_bits, n_tables, n_ids, n_bags, cus, records):
+    """vbq_records_bag_f32 (records) / vbq_bag_f32 for n_bags >= 1 bags -> BagPlan, or None where the call is refused."""
+    if records and not record_fits(K, N, total_bits):
+        return None
+    n_words = record_words(K, N, total_bits) if records else 0
+    if bag_lds_bytes(K, n_words, 0) > BAG_LDS_LIMIT:                       # bag_check_lds
+        return None
+    if not records:
+        return BagPlan(bag_lds_bytes(K, 0, 0), False)
+    grid = min(n_bags, cus * BAG_WG_PER_CU)                                # bag_grid
+    per_wg = cdiv(n_ids, grid)
+    T = table_size(N)
+    in_lds = n_tables == 1 and per_wg * K >= BAG_LDS_TABLE_REUSE * T and bag_lds_bytes(K, n_words, T) <= BAG_LDS_LIMIT
+    return BagPlan(bag_lds_bytes(K, n_words, T if in_lds else 0), in_lds)
+
+
+ScoresPlan = namedtuple("ScoresPlan", "G RS lds_bytes")
+
+
+def scores_lds_bytes(G, RS, n_words):
+    """scores_lds_bytes: the ids of the group, the tile [G][RS], the staged records [G][n_words]."""
+    return 8 * WAVE + 4 * (G * RS + G * n_words)
+
+
+def scores_plan(K, N, total_bits, records):
+    """scores_plan: the largest group within the target, else the smallest if it fits at all -> ScoresPlan, or None."""
+    if records and not record_fits(K, N, total_bits):
+        return None
+    n_words = record_words(K, N, total_bits) if records else 0
+    RS = K | 1
+    G = SCORES_MAX_GROUP
+    while G >= SCORES_MIN_GROUP:
+        lds = scores_lds_bytes(G, RS, n_words)
+        if lds <= (SCORES_LDS_TARGET if G > SCORES_MIN_GROUP else SCORES_LDS_LIMIT):
+            return ScoresPlan(G, RS, lds)
+        G >>= 1
+    return None
+
+
+TopkPlan = namedtuple("TopkPlan", "K2 R table_in_lds lds_bytes per_cu")
+
+
+def topk_lds_bytes(K2, R, n_words, table_entries):
+    """topk_lds_bytes: queries [K2][32], B tile [max(K2, 32)][R + 1], thresholds, exclusions, two flags (four words), the staged
+    records, the one code book."""
+    return 4 * (K2 * TOPK_Q + max(K2, TOPK_Q) * (R + 1) + TOPK_Q + TOPK_Q * TOPK_MAX_E + 4 + R * n_words + table_entries)
+
+
+def topk_plan(K, N, total_bits, n_tables, records):
+    """topk_plan: the largest tile that leaves room for two workgroups per CU, else the largest that fits at all; at each tile
+    the one code book in LDS is tried before the code book through L2 -> TopkPlan, or None."""
+    if records and not record_fits(K, N, total_bits):
+        return None
+    n_words = record_words(K, N, total_bits) if records else 0
+    entries = table_size(N) if records and n_tables == 1 else 0
+    K2 = (K + 1) & ~1
+    for limit in (TOPK_LDS_TWO_PER_CU, TOPK_LDS_LIMIT):
+        R = TOPK_MAX_ROWS
+        while R >= TOPK_MIN_ROWS:
+            for in_lds in ((True, False) if entries else (False,)):
+                lds = topk_lds_bytes(K2, R, n_words, entries if in_lds else 0)
+                if lds <= limit:
+                    return TopkPlan(K2, R, in_lds, lds, 2 if lds <= TOPK_LDS_TWO_PER_CU else 1)      # topk_launch: the grid's cap
+            R >>= 1
+    return None
+
+
+BudgetPlan = namedtuple("BudgetPlan", "threads lds_bytes bp_in_lds")
+
+
+def budget_plan(K, N, width):
+    """budget_plan of vbq_budget.hip (width = budget + 1) and sweep_plan of vbqb_sweep.hip with budgets to walk (a curve-only
+    pass keeps no back-pointers and takes the value rows alone) -> BudgetPlan, or None when the two value rows do not fit."""
+    threads = 64 if width <= 64 else (128 if width <= 128 else 256)
+    values = (2 * width + 2 * (N + 1)) * 8 + 16
+    if values > BUDGET_LDS_BYTES:
+        return None
+    bp_row = (K * width + 15) & ~15
+    in_lds = values + bp_row <= BUDGET_LDS_BYTES
+    return BudgetPlan(threads, values + (bp_row if in_lds else 0), in_lds)
+
+
+def budget_bp_row_bytes(K, width):
+    """bp_row_bytes: one row's back-pointers, the size of a workspace slice."""
+    return (K * width + 15) & ~15

@@ -1,7 +1,8 @@
 """tests/launch_plans.py against the sources it restates, without a GPU: every constant a plan depends on is read out of the
 .hip files with a regular expression and compared with the Python copy, and the plan functions are checked on numbers worked
-out by hand for 256 CUs -- the shapes tests/test_gpu_large_paths.py derives on an MI355X.  A failure here after a retuning
-means: move the shapes of that module so that they still reach the paths they are named after."""
+out by hand for 256 CUs -- the shapes tests/test_gpu_large_paths.py derives on an MI355X, and the widest rows
+tests/test_gpu_wide_rows.py derives from the LDS rules.  A failure here after a retuning means: move the shapes of those modules
+so that they still reach the paths they are named after."""
 import os
 import re
 
@@ -10,11 +11,13 @@ import pytest
 import launch_plans as LP
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vbq_amd", "csrc")
+PKG = os.path.dirname(CSRC)
 CUS = 256
 
 
 def _src(name):
-    with open(os.path.join(CSRC, name)) as f:
+    """A file of vbq_amd/csrc, or -- with a directory in the name -- of vbq_amd."""
+    with open(os.path.join(PKG if "/" in name else CSRC, name)) as f:
         return f.read()
 
 
@@ -25,10 +28,11 @@ def _one(pattern, text, what):
 
 
 def _int(expr):
-    """'9 << 14' or '256' -> int."""
-    m = re.fullmatch(r"\s*(\d+)\s*(?:<<\s*(\d+))?\s*", expr)
+    """'9 << 14', '160 * 1024' or '256' -> int."""
+    m = re.fullmatch(r"\s*(\d+)\s*(?:(<<|\*)\s*(\d+))?\s*", expr)
     assert m, expr
-    return int(m.group(1)) << int(m.group(2) or 0)
+    a, b = int(m.group(1)), int(m.group(3) or 0)
+    return a * b if m.group(2) == "*" else a << b
 
 
 def test_lookup_constants_match_the_source():
@@ -167,6 +171,196 @@ def test_solve_kernel_routes():
     assert K(10, [1.0, 1.0, 2.0], "bc", 1, counting=True) == "K1<2>"
     # the eight-lambda sweeps of solve_cases cycled to 33: repeats, so N = 10 stays on K1 for raw lengths as well
     assert LP.solve_kernels(10, [1.0, 8.0] * 16 + [1.0], "cb", 2, elements=4002) == ["K1<0>", "K1p<1>"]
+
+
+# ------------------------------------------------------------------------------------------------ the LDS-planned kernels
+def test_record_constants_match_the_source():
+    s = _src("vbq_records_common.h")
+    assert int(_one(r"constexpr int kRecordsMaxN = (\d+);", s, "kRecordsMaxN")) == LP.RECORDS_MAX_N
+    assert int(_one(r"constexpr int64_t kRecordsMaxWords = (\d+);", s, "kRecordsMaxWords")) == LP.RECORDS_MAX_WORDS
+    _one(r"int length_field_bits\(int N\) \{ return N >= 8 \? 4 : \(N >= 4 \? 3 : \(N >= 2 \? 2 : 1\)\); \}", s, "length_field_bits")
+    _one(r"return \(\(int64_t\)K \* length_field_bits\(N\) \+ total_bits \+ 31\) / 32;", s, "record_words")
+    _one(r"VBQ_REQUIRE\(\*n_words <= kRecordsMaxWords, VBQ_ERR_UNSUPPORTED,", s, "record_check_words")
+    c = _src("vbq_common.h")
+    assert int(_one(r"constexpr int kWave = (\d+);", c, "kWave")) == LP.WAVE
+    _one(r"constexpr int table_size\(int N\) \{ return \(2 << N\) - 1; \}", c, "table_size")
+    assert [LP.length_field_bits(N) for N in range(1, 11)] == [N.bit_length() for N in range(1, 11)]
+    # the LDS of the two record kernels: the image, and the one code book behind it
+    r = _src("vbq_records.hip")
+    _one(r"dim3\(kWave\), \(size_t\)n_words \* 4,\s*reinterpret_cast<hipStream_t>\(stream\), d_idx,", r, "the pack's LDS")
+    _one(r"const size_t lds = \(size_t\)n_words \* 4 \+ \(lds_table \? \(size_t\)T \* 4 : 0\);", r, "the unpack's LDS")
+
+
+def _opt_ins(s):
+    """How often a launcher of the file raises the dynamic LDS limit, each behind the same threshold."""
+    n = len(re.findall(r"hipFuncAttributeMaxDynamicSharedMemorySize", s))
+    assert len(re.findall(r"lds(?:_bytes)? > (\d+) \* 1024 &&\s*hipFuncSetAttribute", s)) == n
+    assert {int(v) * 1024 for v in re.findall(r"lds(?:_bytes)? > (\d+) \* 1024 &&\s*hipFuncSetAttribute", s)} == {LP.LDS_OPT_IN}
+    return n
+
+
+def test_bag_constants_match_the_source():
+    s = _src("vbq_bag.hip")
+    assert int(_one(r"constexpr int kBagWgPerCu = (\d+);", s, "kBagWgPerCu")) == LP.BAG_WG_PER_CU
+    assert int(_one(r"constexpr int64_t kBagLdsTableReuse = (\d+);", s, "kBagLdsTableReuse")) == LP.BAG_LDS_TABLE_REUSE
+    assert _int(_one(r"constexpr size_t kBagLdsLimit = ([^;]+);", s, "kBagLdsLimit")) == LP.BAG_LDS_LIMIT
+    assert int(_one(r"constexpr int kBagAlwaysK = (\d+);", s, "kBagAlwaysK")) == LP.BAG_ALWAYS_K
+    _one(r"return 4 \* \(\(size_t\)n_words \+ 2 \* \(size_t\)K \+ \(size_t\)table_entries\);", s, "bag_lds_bytes")
+    _one(r"const size_t need = bag_lds_bytes\(K, n_words, 0\);\s*VBQ_REQUIRE\(need <= kBagLdsLimit, VBQ_ERR_UNSUPPORTED,", s, "bag_check_lds")
+    _one(r"const int64_t resident = \(int64_t\)num_cus\(\) \* kBagWgPerCu;\s*return \(unsigned\)\(n_bags < resident \? n_bags : resident\);", s,
+         "bag_grid")
+    _one(r"const int64_t per_wg = \(n_ids \+ grid - 1\) / grid;", s, "per_wg")
+    _one(r"const bool lds_table = n_tables == 1 && per_wg \* K >= kBagLdsTableReuse \* T && bag_lds_bytes\(K, n_words, T\) <= kBagLdsLimit;", s,
+         "lds_table")
+    _one(r"bag_launch<false, false>\(who, a, bag_grid\(n_bags\), bag_lds_bytes\(K, 0, 0\),", s, "the dense launch")
+    assert _opt_ins(s) == 1                                  # bag_launch, a template: every instance
+
+
+def test_scores_constants_match_the_source():
+    s = _src("ext/vbqx_scores.hip")
+    assert _int(_one(r"#define VBQX_SCORES_LDS_TARGET \(([^)]+)\)", s, "VBQX_SCORES_LDS_TARGET")) == LP.SCORES_LDS_TARGET
+    assert int(_one(r"#define VBQX_SCORES_MIN_GROUP (\d+)", s, "VBQX_SCORES_MIN_GROUP")) == LP.SCORES_MIN_GROUP
+    _one(r"constexpr int kScoresMaxGroup = kWave, kScoresMinGroup = VBQX_SCORES_MIN_GROUP;", s, "kScoresMaxGroup")
+    assert LP.SCORES_MAX_GROUP == LP.WAVE
+    assert _int(_one(r"constexpr size_t kScoresLdsLimit = ([^;]+);", s, "kScoresLdsLimit")) == LP.SCORES_LDS_LIMIT
+    _one(r"constexpr size_t kScoresLdsTarget = VBQX_SCORES_LDS_TARGET;", s, "kScoresLdsTarget")
+    assert int(_one(r"constexpr int kScoresAlwaysK = (\d+);", s, "kScoresAlwaysK")) == LP.SCORES_ALWAYS_K
+    _one(r"return 8 \* \(size_t\)kWave \+ 4 \* \(\(size_t\)G \* RS \+ \(size_t\)G \* \(size_t\)n_words\);", s, "scores_lds_bytes")
+    _one(r"a\.RS = a\.K \| 1;", s, "RS")
+    _one(r"for \(int G = kScoresMaxGroup; G >= kScoresMinGroup && !a\.G; G >>= 1\) \{", s, "the group loop")
+    _one(r"if \(\*lds <= \(G > kScoresMinGroup \? kScoresLdsTarget : kScoresLdsLimit\)\) a\.G = G;", s, "the group rule")
+    assert _opt_ins(s) == 1                                  # scores_launch_as, a template: every instance
+
+
+def test_topk_constants_match_the_source():
+    s = _src("vbq_topk.hip")
+    assert int(_one(r"constexpr int kTopkQ = (\d+);", s, "kTopkQ")) == LP.TOPK_Q
+    assert int(_one(r"constexpr int kTopkMaxE = (\d+);", s, "kTopkMaxE")) == LP.TOPK_MAX_E
+    lo, hi = _one(r"constexpr int kTopkMinRows = (\d+), kTopkMaxRows = (\d+);", s, "kTopkMinRows")
+    assert (int(lo), int(hi)) == (LP.TOPK_MIN_ROWS, LP.TOPK_MAX_ROWS)
+    assert _int(_one(r"constexpr size_t kTopkLdsLimit = ([^;]+);", s, "kTopkLdsLimit")) == LP.TOPK_LDS_LIMIT
+    assert _int(_one(r"constexpr size_t kTopkLdsTwoPerCu = ([^;]+);", s, "kTopkLdsTwoPerCu")) == LP.TOPK_LDS_TWO_PER_CU
+    assert int(_one(r"constexpr int kTopkAlwaysK = (\d+);", s, "kTopkAlwaysK")) == LP.TOPK_ALWAYS_K
+    _one(r"const size_t bt = \(size_t\)\(K2 > kTopkQ \? K2 : kTopkQ\) \* \(R \+ 1\);\s*return 4 \* \(\(size_t\)K2 \* kTopkQ \+ bt \+ kTopkQ \+ "
+         r"kTopkQ \* kTopkMaxE \+ 4 \+ \(size_t\)R \* n_words \+ table_entries\);", s, "topk_lds_bytes")
+    _one(r"a\.K2 = \(a\.K \+ 1\) & ~1;", s, "K2")
+    _one(r"for \(size_t limit : \{kTopkLdsTwoPerCu, kTopkLdsLimit\}\) \{\s*for \(int R = kTopkMaxRows; R >= kTopkMinRows && !a\.R; R >>= 1\)\s*"
+         r"for \(int in_lds = table_entries \? 1 : 0; in_lds >= 0 && !a\.R; --in_lds\) \{", s, "the plan's loops")
+    _one(r"topk_plan\(who, a, n_words, n_tables == 1 \? table_size\(N\) : 0, &lds\)", s, "the record call's code book")
+    _one(r"topk_lists_cap\(a\.Q, max_workgroups, lds <= kTopkLdsTwoPerCu \? 2 : 1\);", s, "the grid's cap")
+    assert _opt_ins(s) == 1                                  # topk_launch, a template: both instances
+
+
+def test_budget_constants_match_both_sources():
+    """vbq_budget.hip and vbqb_sweep.hip state one rule; budget_plan restates it once."""
+    for name, limit, max_n in (("vbq_budget.hip", "kBudgetLdsBytes", "kBudgetMaxN"), ("budget/vbqb_sweep.hip", "kSweepLdsBytes", "kSweepMaxN")):
+        s = _src(name)
+        assert _int(_one(rf"constexpr size_t {limit} = ([^;]+);", s, limit)) == LP.BUDGET_LDS_BYTES
+        assert int(_one(rf"constexpr int {max_n} = (\d+);", s, max_n)) == LP.BUDGET_MAX_N
+        _one(r"p\.threads = W <= 64 \? 64 : \(W <= 128 \? 128 : 256\);", s, name + ": threads")
+        _one(r"const size_t values = \(2 \* W \+ 2 \* \(size_t\)\(N \+ 1\)\) \* sizeof\(double\) \+ 16;", s, name + ": values")
+        _one(r"p\.bp_row_bytes = \(\(size_t\)K \* W \+ 15\) & ~\(size_t\)15;", s, name + ": bp_row_bytes")
+        _one(rf"p\.ok = values <= {limit};\s*p\.bp_in_lds = p\.ok && values \+ p\.bp_row_bytes <= {limit};", s, name + ": bp_in_lds")
+    b, w = _src("vbq_budget.hip"), _src("budget/vbqb_sweep.hip")
+    _one(r"const size_t W = \(size_t\)budget \+ 1;", b, "the DP's width")
+    _one(r"p\.lds_bytes = values \+ \(p\.bp_in_lds \? p\.bp_row_bytes : 0\);", b, "the DP's LDS")
+    _one(r"const size_t W = \(size_t\)width;", w, "the sweep's width")
+    _one(r"p\.lds_bytes = values \+ \(S > 0 && p\.bp_in_lds \? p\.bp_row_bytes : 0\);", w, "the sweep's LDS")
+    _one(r"const int32_t top = S \? budgets\[S - 1\] \+ 1 : 0;\s*const int32_t width = top > curve_len \? top : curve_len;", w, "width")
+    assert _opt_ins(w) == 1                                  # sweep_launch, a template: every instance
+    assert _opt_ins(b) == 2                                  # k_budget_dp<true> and k_budget_dp<false>
+
+
+def test_widest():
+    assert LP.widest(lambda x: x <= 37, 1, 1000) == 37 and LP.widest(lambda x: x <= 37, 37, 38) == 37
+    assert LP.widest(lambda x: True, 3, 9) == 9 and LP.widest(lambda x: x < 4, 3, 9) == 3
+    with pytest.raises(AssertionError):
+        LP.widest(lambda x: False, 3, 9)
+
+
+def test_record_words_worked_numbers():
+    assert LP.record_words(18724, 10, 187240) == 8192 and LP.record_fits(18724, 10, 187240)
+    assert LP.record_words(18725, 10, 187250) == 8193 and not LP.record_fits(18725, 10, 187250)
+    assert LP.widest(lambda K: LP.record_fits(K, 10, 10 * K), 1, 1 << 20) == 18724
+    assert LP.record_words(12, 10, 41) == 3 and LP.record_words(7, 10, 10) == 2           # tests/test_gpu_records.py
+    assert not LP.record_fits(12, 10, 121) and not LP.record_fits(12, 11, 0) and not LP.record_fits(12, 10, -1)
+
+
+def test_bag_plan_worked_numbers():
+    dense = lambda K: LP.bag_plan(K, 1, 0, 0, 11, 5, CUS, False)                           # noqa: E731
+    assert dense(20480) == (163840, False) and dense(20481) is None
+    assert dense(8192).lds_bytes == 65536 and dense(8193).lds_bytes == 65544               # the first launch that opts in
+    assert LP.widest(lambda K: dense(K) is not None, 1, 1 << 20) == 20480
+    assert dense(300).lds_bytes == 2400                                                    # the widest row tested before
+    full = lambda K, C=1: LP.bag_plan(K, 10, 10 * K, C, 11, 5, CUS, True)                  # noqa: E731
+    assert LP.record_words(16804, 10, 168040) == 7352
+    assert full(16804) == (163840, False) == full(16804, 16804) and full(16805) is None
+    assert LP.widest(lambda K: full(K) is not None, 1, 1 << 20) == 16804 == LP.BAG_ALWAYS_K
+    # the exact fit of the one code book: 6913 + 2 * 16000 + 2047 = 40960 words
+    assert LP.record_words(16000, 10, 157216) == 6913 and LP.record_words(16000, 10, 157217) == 6914
+    assert LP.bag_plan(16000, 10, 157216, 1, 11, 5, CUS, True) == (163840, True)
+    assert LP.bag_plan(16000, 10, 157217, 1, 11, 5, CUS, True) == (155656, False)
+    assert LP.bag_plan(16000, 10, 157216, 16000, 11, 5, CUS, True) == (155652, False)      # per-column code books stay in L2
+    # the reuse rule (tests/test_gpu_bag.py, test_both_sides_of_the_code_book_choice): 9 bags of 150 ids, 11 bags of 410
+    assert not LP.bag_plan(300, 10, 1001, 1, 150, 9, CUS, True).table_in_lds
+    assert LP.bag_plan(300, 10, 1001, 1, 410, 11, CUS, True).table_in_lds and LP.bag_plan(65, 3, 60, 1, 150, 9, CUS, True).table_in_lds
+    for N in range(1, 11):                                                                 # what kBagAlwaysK promises
+        assert all(LP.bag_plan(LP.BAG_ALWAYS_K, N, t, C, 11, 5, CUS, True) for t in (0, N * LP.BAG_ALWAYS_K) for C in (1, LP.BAG_ALWAYS_K))
+
+
+def test_scores_plan_worked_numbers():
+    dense = lambda K: LP.scores_plan(K, 1, 0, False)                                       # noqa: E731
+    assert dense(5103) == (8, 5103, 163808) and dense(5104) is None
+    assert dense(2031) == (8, 2031, 65504) and dense(2032) == (8, 2033, 65568)             # the first launch that opts in
+    assert LP.widest(lambda K: dense(K) is not None, 1, 1 << 20) == 5103
+    assert LP.widest(lambda K: dense(K).lds_bytes <= LP.LDS_OPT_IN, 1, 5103) == 2031
+    full = lambda K: LP.scores_plan(K, 10, 10 * K, True)                                   # noqa: E731
+    assert full(3549) == (8, 3549, 163776) and full(3550) is None
+    assert LP.widest(lambda K: full(K) is not None, 1, 1 << 20) == 3549 >= LP.SCORES_ALWAYS_K
+    # the groups tests/test_gpu_scores.py names: 64 (K = 1, 5), 32 (40), 16 (64, 65, 100), 8 (300, 512, 700)
+    assert [LP.scores_plan(K, 3, K, True).G for K in (1, 5, 40, 64, 65, 100, 300, 512, 700)] == [64, 64, 32, 16, 16, 16, 8, 8, 8]
+    assert LP.scores_plan(700, 3, 701, True).lds_bytes == 8 * 64 + 4 * 8 * (701 + 66)      # "about 32 KB"? 25 056
+    for N in range(1, 11):                                                                 # what kScoresAlwaysK promises
+        assert all(LP.scores_plan(LP.SCORES_ALWAYS_K, N, t, True) for t in (0, N * LP.SCORES_ALWAYS_K))
+
+
+def test_topk_plan_worked_numbers():
+    """The five regimes of the dense source.  K2 = (K + 1) & ~1 is even, so in K they are 1..124, 125..208, 209..310, 311..418
+    and 419..624."""
+    dense = lambda K: LP.topk_plan(K, 1, 0, 0, False)                                      # noqa: E731
+    regime = lambda K: dense(K) and (dense(K).R, dense(K).per_cu)                          # noqa: E731
+    assert [regime(K) for K in (1, 124)] == [(128, 2)] * 2 and dense(124).K2 == 124
+    assert [regime(K) for K in (125, 208)] == [(64, 2)] * 2 and (dense(125).K2, dense(208).K2) == (126, 208)
+    assert [regime(K) for K in (209, 310)] == [(32, 2)] * 2 and (dense(209).K2, dense(310).K2) == (210, 310)
+    assert [regime(K) for K in (311, 418)] == [(64, 1)] * 2 and (dense(311).K2, dense(418).K2) == (312, 418)
+    assert [regime(K) for K in (419, 624)] == [(32, 1)] * 2 and (dense(419).K2, dense(624).K2) == (420, 624)
+    assert dense(624).lds_bytes == 163408 and dense(625) is None
+    assert len({regime(K) for K in range(1, 625)}) == 5
+    assert dense(300) == (300, 32, False, 79168, 2)                                        # the widest row tested before
+    assert dense(310).lds_bytes <= LP.TOPK_LDS_TWO_PER_CU < dense(311).lds_bytes
+    # records
+    assert LP.record_words(512, 10, 5120) == 224
+    assert LP.topk_plan(512, 10, 5120, 1, True) == (512, 32, False, 162960, 1) == LP.topk_plan(512, 10, 5120, 512, True)
+    # kTopkAlwaysK = 512 is a guarantee, not the limit: at N = 10 and the full budget the last K that fits is 514 (225 words)
+    full = lambda K, C=1: LP.topk_plan(K, 10, 10 * K, C, True)                             # noqa: E731
+    assert LP.widest(lambda K: full(K) is not None, 1, 1 << 20) == 514 and full(514) == (514, 32, False, 163608, 1) == full(514, 514)
+    assert full(515) is None
+    # the one code book beside the smallest tile: up to 166 words per record
+    assert LP.topk_plan(512, 10, 3264, 1, True) == (512, 32, True, 163724, 1)
+    assert LP.topk_plan(512, 10, 3265, 1, True) == (512, 32, False, 155664, 1)
+    for N in range(1, 11):                                                                 # what kTopkAlwaysK promises
+        assert all(LP.topk_plan(LP.TOPK_ALWAYS_K, N, t, C, True) for t in (0, N * LP.TOPK_ALWAYS_K) for C in (1, LP.TOPK_ALWAYS_K))
+
+
+def test_budget_plan_worked_numbers():
+    assert LP.budget_plan(1023, 10, 10228) == (256, 163840, False) and LP.budget_plan(1023, 10, 10229) is None
+    assert LP.widest(lambda w: LP.budget_plan(1023, 10, w) is not None, 1, 10231) == 10228
+    assert LP.budget_plan(150, 10, 985) == (256, 163712, True) and LP.budget_plan(150, 10, 986) == (256, 15968, False)
+    assert LP.widest(lambda w: LP.budget_plan(150, 10, w).bp_in_lds, 1, 1501) == 985
+    assert LP.budget_bp_row_bytes(150, 986) == 147904 and LP.budget_bp_row_bytes(1023, 10228) == 10463248
+    assert [LP.budget_plan(7, 10, w).threads for w in (1, 64, 65, 128, 129)] == [64, 64, 128, 128, 256]
+    # tests/test_gpu_budget_dp.py: K = 300, N = 16 at budget 1600 is the workspace path, 4800 value rows above 64 KiB
+    assert not LP.budget_plan(300, 16, 1601).bp_in_lds and LP.budget_plan(300, 16, 4801) == (256, 77104, False)
 
 
 # ------------------------------------------------------------------------------------------------ worked numbers, 256 CUs

@@ -181,6 +181,11 @@ extern "C" int vbq_budget_dp_f64(const double *d_fhat, int64_t n_rows, int32_t K
         const int64_t resident = (int64_t)num_cus() * kBudgetWsWgPerCu;
         if (grid > slices) grid = slices;
         if (grid > resident) grid = resident;
+        // the value rows alone pass 64 KiB from budget + 1 = 4085 (N = 10) on
+        if (p.lds_bytes > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_budget_dp<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)p.lds_bytes) != hipSuccess)
+            (void)hipGetLastError();
         hipLaunchKernelGGL(k_budget_dp<false>, dim3((unsigned)grid), dim3(p.threads), p.lds_bytes, st, d_fhat, (long)n_rows, (int)K,
                            (int)N, (int)budget, d_out_bits, d_out_obj, d_status, static_cast<unsigned char *>(d_workspace),
                            p.bp_row_bytes);
