@@ -10,6 +10,8 @@ ROCm device the ops raise.
     vbq_amd.ChannelwisePriorCDFQuantizer                   img-compression/quantizer.py:13-256
     vbq_amd.OptimalKmeansQuantizer / ChannelwiseOptimalKmeansWrapper   the k-means baseline fitted exactly on the device: 1-D DP,
                                                            every level count of every channel in one launch (include/vbq_kmeans.h)
+    vbq_amd.LatentStore                                    latent files resident on the device: crops from device-side file ids and
+                                                           origins, planned in a kernel, no synchronisation (vbq_amd/store)
     vbq_amd.utils                                          img-compression/utils.py solvers
     vbq_amd.embeddings                                     word-embeddings notebook cells 25-30; compress_to_bytes / decompress /
                                                            CompressedEmbeddings: the quantized matrix as rANS-coded bytes, rows on demand
@@ -28,4 +30,12 @@ from .rows_budget import quantize_rows_to_budget, quantize_rows_to_budgets  # no
 
 __all__ = ["VBQError", "lib", "library_path", "ops", "quantize", "gaussian_table", "ChannelwisePriorCDFQuantizer", "LazyArray",
            "device_tensor", "quantize_rows_to_budget", "quantize_rows_to_budgets",
-           "OptimalKmeansQuantizer", "ChannelwiseOptimalKmeansWrapper"]
+           "OptimalKmeansQuantizer", "ChannelwiseOptimalKmeansWrapper", "LatentStore"]
+
+
+def __getattr__(name):
+    # vbq_amd.LatentStore loads libvbq_store.so (vbq_amd/store) the first time it is asked for, as every library is loaded
+    if name == "LatentStore":
+        from .store import LatentStore
+        return LatentStore
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,6 +1,6 @@
 """Build the HIP extension (and, for tests only, the C oracle) in-tree.
 
-    python -m vbq_amd.build            # libvbq_hip.so, libvbq_ext.so, libvbq_budget.so and libvbq_kmeans.so for gfx950
+    python -m vbq_amd.build            # libvbq_hip.so, libvbq_ext.so, libvbq_budget.so, libvbq_kmeans.so and libvbq_store.so for gfx950
     python -m vbq_amd.build --oracle   # also oracle/_build/libvbq_oracle.so
 
 hipcc cross-compiles gfx950 without a GPU; the resulting .so is git-ignored but travels
@@ -30,6 +30,8 @@ BUDGET = os.path.join(PKG, "budget")
 BUDGET_LIB = os.path.join(LIBDIR, "libvbq_budget.so")
 KMEANS = os.path.join(PKG, "kmeans")
 KMEANS_LIB = os.path.join(LIBDIR, "libvbq_kmeans.so")
+STORE = os.path.join(PKG, "store")
+STORE_LIB = os.path.join(LIBDIR, "libvbq_store.so")
 LINK_LIBS = ["-ldl"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                # every f32/f64 op of the reference is a separately rounded op: never contract a*b+c
@@ -87,7 +89,8 @@ def _build_library(lib, srcs, headers, objdir, flags, force, verbose):
     from concurrent.futures import ThreadPoolExecutor
     extra = extra_flags()
     flags_tag = os.path.join(objdir, "flags.txt")
-    # travels with the library (the object cache does not): flags.txt, vbq_ext.flags.txt, vbq_budget.flags.txt, vbq_kmeans.flags.txt
+    # travels with the library (the object cache does not): flags.txt, vbq_ext.flags.txt, vbq_budget.flags.txt, vbq_kmeans.flags.txt,
+    # vbq_store.flags.txt
     lib_tag = os.path.join(LIBDIR, "flags.txt" if lib == LIB else os.path.basename(lib)[3:-3] + ".flags.txt")
     tag = " ".join(flags + extra)
     # A tree that arrived with its library but without the object cache (the GPU box: vbq_amd/lib/obj is not shipped) is up
@@ -168,6 +171,20 @@ def build_kmeans(force: bool = False, verbose: bool = False) -> str:
                           verbose)
 
 
+def store_sources():
+    import glob
+    return sorted(glob.glob(os.path.join(STORE, "*.hip")))
+
+
+def build_store(force: bool = False, verbose: bool = False) -> str:
+    """libvbq_store.so (vbq_amd/store/vbq_store.h, beside its sources): the sources of vbq_amd/store, built as build_kmeans
+    builds vbq_amd/kmeans -- the headers of vbq_amd/csrc on the include path, hidden visibility.  Objects under
+    vbq_amd/lib/obj/store."""
+    headers = hip_headers() + [os.path.join(STORE, "vbq_store.h")]
+    return _build_library(STORE_LIB, store_sources(), headers, os.path.join(LIBDIR, "obj", "store"), EXT_HIPCC_FLAGS, force,
+                          verbose)
+
+
 def build_oracle(force: bool = False) -> str:
     """gcc build of oracle/vbq_oracle.c (test infrastructure, never loaded by vbq_amd)."""
     odir = os.path.join(ROOT, "oracle")
@@ -182,5 +199,6 @@ if __name__ == "__main__":
     print(build_ext(force="--force" in sys.argv, verbose=True))
     print(build_budget(force="--force" in sys.argv, verbose=True))
     print(build_kmeans(force="--force" in sys.argv, verbose=True))
+    print(build_store(force="--force" in sys.argv, verbose=True))
     if "--oracle" in sys.argv:
         print(build_oracle(force="--force" in sys.argv))
