@@ -56,6 +56,14 @@ enum {
  * outputs, outputs that are "ADDED to", status words and the workspace hold what they held, whichever of the lambdas, the bit
  * depth or an inner step of a composite call the refusal is about.  VBQ_ERR_LAUNCH is a failure of the runtime in mid-call
  * and is exempt: work enqueued before it stays enqueued. */
+/* Buffers.  Every pointer parameter that is not `const` names memory the call writes, of the size and type its comment
+ * states, densely laid out.  Such a buffer must not overlap anything else the call reads or writes -- an input, another output,
+ * the workspace -- unless the function's comment says so: the kernels read through `__restrict__` pointers and work in tiles,
+ * so an overlap gives a silently wrong answer.  What a comment allows is always the buffer's OWN earlier content: state that is
+ * updated in place, counts and totals that are ADDED to, status words that are OR-ed into, slots that keep what they held.  The
+ * library cannot check any of this cheaply and does not; the Python binding does (vbq_amd/ops.py, _out), and
+ * tests/written_buffers.py lists every such parameter with the way a caller reaches it.  The same holds for vbq_ext.h,
+ * vbq_budget.h, vbq_kmeans.h and vbq_store.h. */
 
 enum {
     VBQ_LAYOUT_BC = 0,

@@ -7,6 +7,7 @@
  * vbqb_last_error() gives the text of the calling thread's most recent failure in THIS library (each library keeps one
  * thread-local error string; none sees another's).  A call that returns VBQ_ERR_INVALID_ARGUMENT, VBQ_ERR_UNSUPPORTED or
  * VBQ_ERR_WORKSPACE has enqueued nothing.
+ * What a call writes must overlap nothing else it reads or writes: vbq.h, "Buffers".
  */
 #ifndef VBQ_BUDGET_H_
 #define VBQ_BUDGET_H_

@@ -6,6 +6,7 @@
  * VBQ_OK or a VBQ_ERR_* code of vbq.h, and vbqx_last_error() gives the text of the calling thread's most recent failure
  * in THIS library (the two libraries keep one thread-local error string each; neither sees the other's).  A call that
  * returns VBQ_ERR_INVALID_ARGUMENT or VBQ_ERR_UNSUPPORTED has enqueued nothing.
+ * What a call writes must overlap nothing else it reads or writes: vbq.h, "Buffers".
  */
 #ifndef VBQ_EXT_H_
 #define VBQ_EXT_H_

@@ -8,6 +8,7 @@
  * return value is VBQ_OK or a VBQ_ERR_* code of vbq.h, and vbqk_last_error() gives the text of the calling thread's most
  * recent failure in THIS library (each library keeps one thread-local error string; none sees another's).  A call that returns
  * VBQ_ERR_INVALID_ARGUMENT, VBQ_ERR_UNSUPPORTED or VBQ_ERR_WORKSPACE has enqueued nothing.
+ * What a call writes must overlap nothing else it reads or writes: vbq.h, "Buffers".
  */
 #ifndef VBQ_KMEANS_H_
 #define VBQ_KMEANS_H_

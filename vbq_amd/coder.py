@@ -267,8 +267,8 @@ class RansCodec:
         words = torch.empty((S, nseg, self.segment + 2), dtype=torch.uint16, device=dev)
         out_sizes = torch.empty((S, nseg), dtype=torch.uint32, device=dev)
         offsets = torch.empty(S * nseg, dtype=torch.int64, device=dev)
-        if status is None:
-            status = torch.zeros(1, dtype=torch.uint32, device=dev)
+        status = torch.zeros(1, dtype=torch.uint32, device=dev) if status is None else ops._status(
+            status, 1, dev, (("payload", payload), ("sizes", sizes)))
         check(_lib.lib().vbq_rans_unpack_u16(ops._ptr(payload), payload.numel(), ops._ptr(sizes), S, n, self.segment,
                                              ops._ptr(words), ops._ptr(out_sizes), ops._ptr(offsets), ops._ptr(status),
                                              ops._stream(payload)), "vbq_rans_unpack_u16")

@@ -148,6 +148,7 @@ class CountsAllReduce:
         self.group = group
         fits = max_global_count < PACKED_FIELD_LIMIT and device.type == "cuda"
         self.packed = fits if packed is None else (bool(packed) and device.type == "cuda")
+        self.numel = int(numel)
         self.nw = (numel + 2) // 3
         # word nw carries the overflow flags of all ranks (their sum)
         self.words = torch.zeros(self.nw + 1, dtype=torch.int64, device=device) if self.packed else None
@@ -167,15 +168,17 @@ class CountsAllReduce:
     def start(self, counts: torch.Tensor):
         from . import _lib, ops
         world = self._require_group(self.group)
-        assert counts.dtype == torch.int32 and counts.is_contiguous()
+        if self.packed:                   # wait() unpacks the sums into this tensor: it is checked as any tensor the library writes
+            counts = ops._out(counts, "any", torch.int32, self.words.device, "counts", False, (("words", self.words),))
+            if counts is None or counts.numel() != self.numel:
+                raise ValueError(f"counts: expected a contiguous {torch.int32} device tensor of {self.numel} elements")
+        else:
+            assert counts.dtype == torch.int32 and counts.is_contiguous()
         self._counts = counts
         if self.packed:
-            assert (counts.numel() + 2) // 3 == self.nw
             self.words[self.nw:].zero_()
-            flag_ptr = self.words.data_ptr() + 8 * self.nw
-            import ctypes as C
             _lib.check(_lib.lib().vbq_pack_counts_3x21(ops._ptr(counts), counts.numel(), ops._ptr(self.words), world,
-                                                       C.c_void_p(flag_ptr), ops._stream(counts)), "vbq_pack_counts_3x21")
+                                                       ops._ptr(self.words[self.nw:]), ops._stream(counts)), "vbq_pack_counts_3x21")
             self._work = dist.all_reduce(self.words, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
         else:
             self._work = dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group, async_op=True)

@@ -111,8 +111,9 @@ def kmeans1d_dp(S1: torch.Tensor, S2: torch.Tensor, shift: torch.Tensor, levels:
     codes = torch.empty(total, dtype=torch.float64, device=dev)
     counts = torch.empty(total, dtype=torch.int64, device=dev)
     sse = torch.empty((Cn, Kmax), dtype=torch.float64, device=dev)
+    reads = (("S1", S1), ("S2", S2), ("shift", shift))
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
+        status = ops._status(status, 1, dev, reads)
     h = _lib_kmeans.lib()
     if workspace is None:
         wsb = h.vbqk_kmeans1d_workspace_bytes(n, Cn, Kmax)
@@ -121,7 +122,7 @@ def kmeans1d_dp(S1: torch.Tensor, S2: torch.Tensor, shift: torch.Tensor, levels:
             wsb = max(one, WORKSPACE_CAP_BYTES // one * one)
         workspace = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
     else:
-        workspace = _dev(workspace, torch.uint8, "workspace")
+        workspace = ops._workspace(workspace, 1, dev, 0, reads + (("status", status),))
     wsb = workspace.numel() if workspace is not None else 0
     _lib_kmeans.check(h.vbqk_kmeans1d_f64(_ptr(S1), _ptr(S2), _ptr(shift), n, Cn, (C.c_int32 * S)(*levels), S, _ptr(starts),
                                           _ptr(codes), _ptr(counts), _ptr(sse), _ptr(status), _ptr(workspace), wsb, _stream(S1)),
@@ -144,7 +145,7 @@ def nearest_code_channels(x: torch.Tensor, codes: torch.Tensor, *, counts: Optio
     B, Cn = x.shape
     k = codes.shape[1]
     if counts is not None:
-        counts = ops._out(counts, (Cn, k), torch.int64, x.device, "counts")
+        counts = ops._out(counts, (Cn, k), torch.int64, x.device, "counts", True, (("x", x), ("codes", codes)))
     I = torch.empty((B, Cn), dtype=torch.int32, device=x.device)
     q = torch.empty((B, Cn), dtype=torch.float64, device=x.device)
     _lib_kmeans.check(_lib_kmeans.lib().vbqk_nearest_code_channels_f64(_ptr(x), B, Cn, _ptr(codes), k, _ptr(I), _ptr(q),

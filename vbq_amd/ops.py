@@ -106,20 +106,68 @@ def _per_lambda(t, shape, name):
     return t
 
 
-def _workspace(given, nbytes, device, floor=0):
-    ws = given if given is not None else torch.empty(max(nbytes, floor), dtype=torch.uint8, device=device)
-    if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
+def _laid_out(t):
+    """The strides of `t` are those a new tensor of its shape has: what a kernel that is handed one pointer assumes.  Read from
+    the strides themselves, those of dimensions of size 1 included: is_contiguous() is true for every tensor of at most one
+    element, whatever they are.  (Stricter than density: an [n, 1] view of a [1, n] tensor is refused.)"""
+    want = 1
+    for size, stride in zip(reversed(t.shape), reversed(t.stride())):
+        if stride != want:
+            return False
+        want *= max(size, 1)
+    return True
+
+
+def _apart(name, t, others):
+    """ValueError when the bytes of `t`, a tensor the call writes, intersect those of one of `others`: (name, tensor or None)
+    pairs of what else the call reads or writes, each the tensor whose pointer goes to the library.  Half-open ranges from
+    data_ptr() over numel() * element_size() bytes; an empty tensor intersects nothing."""
+    n = t.numel() * t.element_size()
+    if not n:
+        return
+    a = t.data_ptr()
+    for other, o in others:
+        if o is None:
+            continue
+        m, b = o.numel() * o.element_size(), o.data_ptr()
+        if m and a < b + m and b < a + n:
+            raise ValueError(f"{name} overlaps {other}: a tensor the call writes must share no memory with anything else it "
+                             "reads or writes")
+
+
+def _workspace(given, nbytes, device, floor=0, apart=()):
+    """The caller's scratch, checked (a dense uint8 device tensor of at least `nbytes` bytes that touches nothing in `apart`),
+    or a new one of max(nbytes, floor) bytes."""
+    if given is None:
+        return torch.empty(max(nbytes, floor), dtype=torch.uint8, device=device)
+    if not isinstance(given, torch.Tensor) or given.numel() * given.element_size() < nbytes or not given.is_cuda \
+            or given.device != device:
         raise ValueError(f"workspace must be a device tensor of at least {nbytes} bytes")
-    return ws
+    if given.dtype != torch.uint8 or not _laid_out(given):
+        raise ValueError(f"workspace: expected a contiguous {torch.uint8} device tensor of shape (>= {nbytes},)")
+    _apart("workspace", given, apart)
+    return given
 
 
-def _out(given, shape, dtype, device, name, want=True):
-    """The caller's output tensor, checked (its pointer goes to the library), or a new one (None when not wanted)."""
+def _out(given, shape, dtype, device, name, want=True, apart=()):
+    """The caller's tensor for something the library writes, checked and never copied -- the object that comes back is the one
+    that was given --, or a new one (None when not wanted).  A given tensor lies on `device` (None: on any ROCm device).  shape: the exact shape, or "any" where the call takes the element
+    count from the tensor (such a tensor has to be given); dtype: the dtype, or a tuple of the ones the entry point takes;
+    apart: see _apart."""
     if given is not None:
-        if tuple(given.shape) != shape or given.dtype != dtype or not given.is_cuda or not given.is_contiguous():
+        ok = isinstance(given, torch.Tensor) and given.is_cuda and (device is None or given.device == device) and _laid_out(given)
+        ok = ok and (given.dtype in dtype if isinstance(dtype, tuple) else given.dtype == dtype)
+        if not (ok and (shape == "any" or tuple(given.shape) == shape)):
             raise ValueError(f"{name}: expected a contiguous {dtype} device tensor of shape {shape}")
+        _apart(name, given, apart)
         return given
     return torch.empty(shape, dtype=dtype, device=device) if want else None
+
+
+def _status(given, n, device, apart=()):
+    """A caller's status words, uint32 [n], which the kernels OR their flags into: checked like any written tensor (an empty
+    one has no address: the library would read it as "no status wanted")."""
+    return _out(given, (n,), torch.uint32, device, "status", False, apart)
 
 
 def _solve_inputs(mu, sigma, table_lm, lambdas, N, level_len, layout):
@@ -159,12 +207,13 @@ def quantize(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, lamb
         layout, oshape = LAYOUT_BC_TO_CB, (L, Cc, rows)
     else:
         oshape = (L,) + tuple(mu.shape)
-    idx = _out(out_idx, oshape, torch.uint16, mu.device, "out_idx")
-    zhat = _out(out_zhat, oshape, torch.float32, mu.device, "out_zhat", want_zhat)
-    bits = _out(out_bits, oshape, torch.float32, mu.device, "out_bits", want_bits)
+    reads = (("mu", mu), ("sigma", sigma), ("table_lm", table_lm), ("level_len", level_len))
+    idx = _out(out_idx, oshape, torch.uint16, mu.device, "out_idx", True, reads)
+    zhat = _out(out_zhat, oshape, torch.float32, mu.device, "out_zhat", want_zhat, reads + (("out_idx", idx),))
+    bits = _out(out_bits, oshape, torch.float32, mu.device, "out_bits", want_bits, reads + (("out_idx", idx), ("out_zhat", zhat)))
     want_zhat, want_bits = zhat is not None, bits is not None
     wsb = h.vbq_quantize_workspace_bytes(Cc, L, N)
-    ws = _workspace(workspace, wsb, mu.device)
+    ws = _workspace(workspace, wsb, mu.device, 0, reads + (("out_idx", idx), ("out_zhat", zhat), ("out_bits", bits)))
     if mu.numel() == 0:
         out = (idx,) + ((zhat,) if want_zhat else ()) + ((bits,) if want_bits else ())
         return out if len(out) > 1 else idx
@@ -207,13 +256,14 @@ def level_counts(mu: torch.Tensor, sigma: torch.Tensor, table_lm: torch.Tensor, 
     mu, sigma, rows, Cc, table_lm, L, level_len = _solve_inputs(mu, sigma, table_lm, lambdas, N, level_len, layout)
     if to_planes and mu.dim() == 2 and Cc > 1:
         layout = LAYOUT_BC_TO_CB
+    reads = (("mu", mu), ("sigma", sigma), ("table_lm", table_lm), ("level_len", level_len))
     if out is None:
         out = torch.zeros((L, Cc, N + 1), dtype=torch.int64, device=mu.device)
     else:
-        _out(out, (L, Cc, N + 1), torch.int64, mu.device, "out")
+        out = _out(out, (L, Cc, N + 1), torch.int64, mu.device, "out", True, reads)
     h = _lib.lib()
     wsb = h.vbq_quantize_workspace_bytes(Cc, L, N)
-    ws = _workspace(workspace, wsb, mu.device)
+    ws = _workspace(workspace, wsb, mu.device, 0, reads + (("out", out),))
     if mu.numel():
         check(h.vbq_level_counts_f32(_ptr(mu), _ptr(sigma), rows, Cc, layout, _ptr(table_lm), _ptr(level_len),
                                      _doubles(lambdas), L, N, _ptr(out), _ptr(ws), wsb,
@@ -231,8 +281,10 @@ def code_lengths_from_counts(counts: torch.Tensor, lut: torch.Tensor, *, level_p
         raise ValueError("counts must be int64 or int32")
     counts = _dev(counts, counts.dtype, "counts")
     lut = _dev(lut, torch.float32, "lut")
-    out_len = _out(out_len, tuple(counts.shape), torch.float32, counts.device, "out_len", want_len)
-    out_model = _out(out_model, tuple(counts.shape), torch.float32, counts.device, "out_model", want_model)
+    reads = (("counts", counts), ("lut", lut))
+    out_len = _out(out_len, tuple(counts.shape), torch.float32, counts.device, "out_len", want_len, reads)
+    out_model = _out(out_model, tuple(counts.shape), torch.float32, counts.device, "out_model", want_model,
+                     reads + (("out_len", out_len),))
     check(_lib.lib().vbq_code_lengths_from_counts(_ptr(counts), int(counts.dtype == torch.int32), counts.numel(), _ptr(lut),
                                                   lut.numel(), int(level_period), _ptr(out_len), _ptr(out_model),
                                                   _stream(counts)), "vbq_code_lengths_from_counts")
@@ -253,7 +305,8 @@ def quantize_notebook(means: torch.Tensor, stds: torch.Tensor, codebook_lm: torc
         raise ValueError(f"codebook has {codebook_lm.numel()} entries, expected {table_size(N)}")
     nb = len(betas)
     n = means.numel()
-    idx = _out(out_idx, (nb,) + tuple(means.shape), torch.uint16, means.device, "out_idx")
+    idx = _out(out_idx, (nb,) + tuple(means.shape), torch.uint16, means.device, "out_idx", True,
+               (("means", means), ("stds", stds), ("codebook_lm", codebook_lm)))
     val = torch.empty((nb,) + tuple(means.shape), dtype=torch.float32, device=means.device) if want_values else None
     check(_lib.lib().vbq_quantize_notebook_f64(_ptr(means), _ptr(stds), n, _ptr(codebook_lm), _doubles(betas), nb, N,
                                                _ptr(idx), _ptr(val), _stream(means)), "vbq_quantize_notebook_f64")
@@ -280,7 +333,8 @@ def histogram(idx: torch.Tensor, n_ch: int, *, N: int = 10, layout="bc", out: Op
             raise ValueError("out must be int64 or int32")
         if not out.is_contiguous():
             raise ValueError("out must be contiguous (counts are accumulated in place)")
-        out = _out(_dev(out, out.dtype, "out"), (L, n_ch, T), out.dtype, idx.device, "out")
+        _dev(out, out.dtype, "out")                                       # (the refusals of a host tensor, in their words)
+        out = _out(out, (L, n_ch, T), out.dtype, idx.device, "out", True, (("idx", idx),))
     h = _lib.lib()
     if rows_range is not None:
         check(h.vbq_histogram_rows_u16(_ptr(idx), rows, n_ch, layout, L, N, _ptr(out), int(out.dtype == torch.int32),
@@ -303,12 +357,14 @@ def histogram_models(idx: torch.Tensor, n_ch: int, counts: torch.Tensor, *, N: i
     T = table_size(N)
     if counts.dtype not in (torch.int64, torch.int32):
         raise ValueError(f"counts: expected a contiguous int32 / int64 device tensor of shape {(L, n_ch, T)}")
-    _out(counts, (L, n_ch, T), counts.dtype, idx.device, "counts")
+    counts = _out(counts, (L, n_ch, T), counts.dtype, idx.device, "counts", True, (("idx", idx),))
     if (lut is None) != (models is None):
         raise ValueError("lut and models go together")
     if models is not None:
         lut = _dev(lut, torch.float32, "lut")
-        _out(models, (L, n_ch, T), torch.float32, idx.device, "models")
+        _apart("counts", counts, (("lut", lut),))
+        models = _out(models, (L, n_ch, T), torch.float32, idx.device, "models", True,
+                      (("idx", idx), ("lut", lut), ("counts", counts)))
     check(_lib.lib().vbq_histogram_models_u16(_ptr(idx), rows, n_ch, L, N, _ptr(counts), int(counts.dtype == torch.int32), _ptr(lut),
                                               lut.numel() if lut is not None else 0, _ptr(models), _stream(idx)),
           "vbq_histogram_models_u16")
@@ -331,6 +387,8 @@ def moments(x: torch.Tensor, *, layout="bc", out: Optional[torch.Tensor] = None)
     rows, Cc = _rows_channels(x.shape, layout)
     if out is None:
         out = torch.zeros((Cc, 2), dtype=torch.float64, device=x.device)
+    else:
+        out = _out(out, (Cc, 2), torch.float64, x.device, "out", True, (("x", x),))
     check(_lib.lib().vbq_moments_f32(_ptr(x), rows, Cc, layout, _ptr(out), _stream(x)), "vbq_moments_f32")
     return out
 
@@ -366,8 +424,7 @@ def numpy_row_sums(x: torch.Tensor, workspace: Optional[torch.Tensor] = None) ->
     out = torch.empty(rows, dtype=torch.float32, device=x.device)
     h = _lib.lib()
     wsb = h.vbq_numpy_row_sums_workspace_bytes(rows, n)
-    ws = workspace if workspace is not None and workspace.numel() * workspace.element_size() >= wsb else \
-        torch.empty(max(wsb, 4), dtype=torch.uint8, device=x.device)
+    ws = _workspace(workspace, wsb, x.device, 4, (("x", x),))
     check(h.vbq_numpy_row_sums_f32(_ptr(x), rows, n, _ptr(out), _ptr(ws), wsb, _stream(x)), "vbq_numpy_row_sums_f32")
     return out
 
@@ -416,8 +473,9 @@ def prep_planes(means_bc: torch.Tensor, spread_bc: torch.Tensor, *, spread: str 
     `tf.exp(posterior_logvars) ** 0.5` of quantizer.py:197,202 inside the launch)."""
     means_bc, spread_bc = _pair_bc(means_bc, spread_bc)
     r, c = means_bc.shape
-    out_mu = _out(out_mu, (c, r), torch.float32, means_bc.device, "out_mu")
-    out_sigma = _out(out_sigma, (c, r), torch.float32, means_bc.device, "out_sigma")
+    reads = (("means", means_bc), ("spread", spread_bc))
+    out_mu = _out(out_mu, (c, r), torch.float32, means_bc.device, "out_mu", True, reads)
+    out_sigma = _out(out_sigma, (c, r), torch.float32, means_bc.device, "out_sigma", True, reads + (("out_mu", out_mu),))
     check(_lib.lib().vbq_prep_planes_f32(_ptr(means_bc), _ptr(spread_bc), _spread_kind(spread), r, c, _ptr(out_mu),
                                          _ptr(out_sigma), _stream(means_bc)), "vbq_prep_planes_f32")
     return out_mu, out_sigma
@@ -474,7 +532,8 @@ def compress_latents(means_bc: torch.Tensor, spread_bc: torch.Tensor, table_lm: 
     dev = means_bc.device
     h = _lib.lib()
     wsb = h.vbq_compress_latents_workspace_bytes(B, Cc, L, N)
-    ws = _workspace(workspace, wsb, dev, floor=256)
+    ws = _workspace(workspace, wsb, dev, 256, (("means", means_bc), ("spread", spread_bc), ("table_lm", table_lm),
+                                               ("table_sorted", table_sorted), ("level_len", level_len), ("models", models)))
     z = torch.empty((L, B, Cc), dtype=torch.float32, device=dev)
     raw = torch.empty((L, B, Cc), dtype=torch.int32 if level_len is None else torch.float32, device=dev)
     nb = torch.empty((L, B, Cc), dtype=torch.float32, device=dev) if models is not None else None
@@ -492,7 +551,7 @@ def transpose(x: torch.Tensor, out: Optional[torch.Tensor] = None):
     if x.dim() != 2:
         raise ValueError("transpose expects a 2-D tensor")
     r, c = x.shape
-    out = _out(out, (c, r), torch.float32, x.device, "out")
+    out = _out(out, (c, r), torch.float32, x.device, "out", True, (("x", x),))
     check(_lib.lib().vbq_transpose_f32(_ptr(x), r, c, _ptr(out), _stream(x)), "vbq_transpose_f32")
     return out
 
@@ -521,6 +580,9 @@ def rd_sums(mu: torch.Tensor, sigma: torch.Tensor, idx: torch.Tensor, tab_sorted
             raise ValueError(f"rate shape {tuple(rate.shape)} does not match (L={L}, C={n_ch}, T={T})")
     if out is None:
         out = torch.zeros((L, 2), dtype=torch.float64, device=mu.device)
+    else:
+        out = _out(out, (L, 2), torch.float64, mu.device, "out", True,
+                   (("mu", mu), ("sigma", sigma), ("idx", idx), ("tab_sorted", tab_sorted), ("rate", rate)))
     check(_lib.lib().vbq_rd_sums_u16(_ptr(mu), _ptr(sigma), _ptr(idx), E // n_ch, n_ch, layout, L, N, _ptr(tab_sorted), _ptr(rate),
                                      per_lambda, _ptr(out), _stream(mu)), "vbq_rd_sums_u16")
     return out
@@ -535,7 +597,7 @@ def transpose_planes(x: torch.Tensor, out: Optional[torch.Tensor] = None):
         raise ValueError("transpose_planes expects a 3-D tensor of 2- or 4-byte elements")
     x = x.contiguous()
     b, r, c = x.shape
-    out = _out(out, (b, c, r), x.dtype, x.device, "out")
+    out = _out(out, (b, c, r), x.dtype, x.device, "out", True, (("x", x),))
     check(_lib.lib().vbq_transpose_planes(_ptr(x), b, r, c, x.element_size(), _ptr(out), _stream(x)), "vbq_transpose_planes")
     return out
 
@@ -579,8 +641,27 @@ def bmshj_cdf_pdf(params: torch.Tensor, x: torch.Tensor, *, cdf=True, pdf=True, 
     return tuple(outs)
 
 
+def _icdf_args(params, xi, left, right, mid, flags, flags_shape):
+    """What the two bisection calls check alike: params f32 [C, 43], xi f32 [..., C], the brackets and mid points f32 like xi --
+    state the kernels update where it lies -- and flags u32 (or i32) of `flags_shape`."""
+    params = _dev(params, torch.float32, "params")
+    xi = _dev(xi, torch.float32, "xi")
+    if params.dim() != 2 or params.shape[1] != _lib.BMSHJ_PARAMS_PER_CHANNEL or xi.dim() < 1 or xi.shape[-1] != params.shape[0]:
+        raise ValueError(f"params must be [C, 43] and xi [..., C]; got {tuple(params.shape)}, {tuple(xi.shape)}")
+    reads = (("params", params), ("xi", xi))
+    left = _out(left, tuple(xi.shape), torch.float32, xi.device, "left", False, reads)
+    right = _out(right, tuple(xi.shape), torch.float32, xi.device, "right", False, reads + (("left", left),))
+    mid = _out(mid, tuple(xi.shape), torch.float32, xi.device, "mid", False, reads + (("left", left), ("right", right)))
+    flags = _out(flags, flags_shape, (torch.uint32, torch.int32), xi.device, "flags", False,
+                 reads + (("left", left), ("right", right), ("mid", mid)))
+    if left is None or right is None or mid is None or flags is None:
+        raise ValueError("left, right, mid and flags are the caller's tensors: none may be None")
+    return params, xi, left, right, mid, flags
+
+
 def bmshj_icdf_step(params, xi, left, right, mid, flags):
     """K4 (vbq_bmshj_icdf_step_f32): one in-place bisection update; flags u32[2] must be preset to (0, 0x7f800000)."""
+    params, xi, left, right, mid, flags = _icdf_args(params, xi, left, right, mid, flags, (2,))
     Cc = params.shape[0]
     rows = xi.numel() // Cc
     check(_lib.lib().vbq_bmshj_icdf_step_f32(_ptr(params), _ptr(xi), rows, Cc, _ptr(left), _ptr(right), _ptr(mid),
@@ -590,6 +671,7 @@ def bmshj_icdf_step(params, xi, left, right, mid, flags):
 def bmshj_icdf_chain(params, xi, left, right, mid, flags, n_steps: int, tol: float, first: bool = True):
     """K4 (vbq_bmshj_icdf_chain_f32): n_steps bisection updates enqueued at once, the reference's stopping rule applied on the
     device between them; flags u32 [n_steps + 1, 2] is written (read it after a synchronisation)."""
+    params, xi, left, right, mid, flags = _icdf_args(params, xi, left, right, mid, flags, (int(n_steps) + 1, 2))
     Cc = params.shape[0]
     rows = xi.numel() // Cc
     check(_lib.lib().vbq_bmshj_icdf_chain_f32(_ptr(params), _ptr(xi), rows, Cc, _ptr(left), _ptr(right), _ptr(mid), _ptr(flags),
@@ -606,6 +688,8 @@ def bmshj_nll_grad(params: torch.Tensor, x_cb: torch.Tensor, out: Optional[torch
         raise ValueError(f"params must be [{Cc}, 43], got {tuple(params.shape)}")
     if out is None:
         out = torch.zeros((Cc, 44), dtype=torch.float64, device=x_cb.device)
+    else:
+        out = _out(out, (Cc, 44), torch.float64, x_cb.device, "out", True, (("params", params), ("x_cb", x_cb)))
     check(_lib.lib().vbq_bmshj_nll_grad_f32(_ptr(params), _ptr(x_cb), n, Cc, _ptr(out), _stream(x_cb)),
           "vbq_bmshj_nll_grad_f32")
     return out
@@ -626,13 +710,13 @@ def budget_dp(fhat: torch.Tensor, K: int, budget: int, *, status: Optional[torch
     bits = torch.empty((rows, K), dtype=torch.int32, device=fhat.device)
     obj = torch.empty(rows, dtype=torch.float64, device=fhat.device)
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
+        status = _status(status, 1, fhat.device, (("fhat", fhat),))
     h = _lib.lib()
     if workspace is None:
         wsb = h.vbq_budget_dp_workspace_bytes(rows, K, N, budget)
         workspace = torch.empty(wsb, dtype=torch.uint8, device=fhat.device) if wsb else None
     else:
-        workspace = _dev(workspace, torch.uint8, "workspace")
+        workspace = _workspace(workspace, 1, fhat.device, 0, (("fhat", fhat), ("status", status)))
     wsb = workspace.numel() if workspace is not None else 0
     check(h.vbq_budget_dp_f64(_ptr(fhat), rows, K, N, budget, _ptr(bits), _ptr(obj), _ptr(status), _ptr(workspace), wsb,
                               _stream(fhat)), "vbq_budget_dp_f64")
@@ -663,13 +747,13 @@ def budget_dp_sweep(fhat: torch.Tensor, K: int, budgets: Sequence[int], *, curve
     obj = torch.empty((S, rows), dtype=torch.float64, device=fhat.device)
     curve = torch.empty((rows, curve_len), dtype=torch.float64, device=fhat.device) if curve_len else None
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
+        status = _status(status, 1, fhat.device, (("fhat", fhat),))
     h = _lib_budget.lib()
     if workspace is None:
         wsb = h.vbqb_budget_sweep_workspace_bytes(rows, K, N, max([b + 1 for b in budgets] + [curve_len])) if S else 0
         workspace = torch.empty(wsb, dtype=torch.uint8, device=fhat.device) if wsb else None
     else:
-        workspace = _dev(workspace, torch.uint8, "workspace")
+        workspace = _workspace(workspace, 1, fhat.device, 0, (("fhat", fhat), ("status", status)))
     wsb = workspace.numel() if workspace is not None else 0
     _lib_budget.check(h.vbqb_budget_sweep_f64(_ptr(fhat), rows, K, N, (C.c_int32 * S)(*budgets), S, _ptr(bits), _ptr(obj),
                                               _ptr(curve), curve_len, _ptr(status), _ptr(workspace), wsb, _stream(fhat)),
@@ -708,9 +792,9 @@ def records_pack(idx: torch.Tensor, total_bits: int, N: int, *, status: Optional
     if idx.dim() != 2:
         raise ValueError(f"idx must be [R, K], got shape {tuple(idx.shape)}")
     R, K = idx.shape
-    words = _out(out, (R, records_words(K, N, total_bits)), torch.uint32, idx.device, "out")
+    words = _out(out, (R, records_words(K, N, total_bits)), torch.uint32, idx.device, "out", True, (("idx", idx),))
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
+        status = _status(status, 1, idx.device, (("idx", idx), ("out", words)))
     check(_lib.lib().vbq_records_pack_u16(_ptr(idx), R, K, int(N), int(total_bits), _ptr(words), _ptr(status), _stream(idx)),
           "vbq_records_pack_u16")
     return words
@@ -757,7 +841,7 @@ def records_unpack(words: torch.Tensor, K: int, N: int, total_bits: int, table_s
     values = _out(None, (rows, K), torch.float32, words.device, "values", want_values)
     idx = _out(None, (rows, K), torch.uint16, words.device, "idx", want_idx)
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
+        status = _status(status, 1, words.device, (("words", words), ("table_sorted", table_sorted), ("row_ids", row_ids)))
     check(_lib.lib().vbq_records_unpack_f32(_ptr(words), R, K, N, total_bits, _ptr(table_sorted) if want_values else None,
                                             n_tables, _ptr(row_ids), rows if row_ids is not None else 0, _ptr(values),
                                             _ptr(idx), _ptr(status), _stream(words)), "vbq_records_unpack_f32")
@@ -786,11 +870,11 @@ def _topk_args(queries, K, k, metric, exclude):
     return queries, k, _METRICS[metric], (exclude if E else None), E
 
 
-def _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, device):
+def _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, device, reads):
     ids = torch.empty((Q, k), dtype=torch.int64, device=device)
     scores = torch.empty((Q, k), dtype=torch.float32, device=device)
     nbytes = int(h.vbq_topk_workspace_bytes(V, K, Q, k, int(max_workgroups))) if Q else 0
-    return ids, scores, _workspace(workspace, nbytes, device, floor=1)
+    return ids, scores, _workspace(workspace, nbytes, device, 1, reads)
 
 
 def records_topk(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: torch.Tensor, queries: torch.Tensor,
@@ -805,11 +889,12 @@ def records_topk(words: torch.Tensor, K: int, N: int, total_bits: int, table_sor
     K, N, total_bits = int(K), int(N), int(total_bits)
     n_tables, table_sorted = _records_inputs(words, "V", K, N, total_bits, table_sorted)
     queries, k, metric, exclude, E = _topk_args(queries, K, k, metric, exclude)
+    reads = (("words", words), ("table_sorted", table_sorted), ("queries", queries), ("exclude", exclude))
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
+        status = _status(status, 1, words.device, reads)
     V, Q = words.shape[0], queries.shape[0]
     h = _lib.lib()
-    ids, scores, ws = _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, words.device)
+    ids, scores, ws = _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, words.device, reads + (("status", status),))
     check(h.vbq_records_topk_f32(_ptr(words), V, K, N, total_bits, _ptr(table_sorted), n_tables, _ptr(queries), Q, k, metric,
                                  _ptr(exclude), E, _ptr(ids), _ptr(scores), _ptr(status), int(max_workgroups), _ptr(ws),
                                  ws.numel() * ws.element_size(), _stream(words)), "vbq_records_topk_f32")
@@ -827,7 +912,8 @@ def topk(emb: torch.Tensor, queries: torch.Tensor, k: int = 10, metric="cosine",
     queries, k, metric, exclude, E = _topk_args(queries, K, k, metric, exclude)
     Q = queries.shape[0]
     h = _lib.lib()
-    ids, scores, ws = _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, emb.device)
+    ids, scores, ws = _topk_outputs(h, V, K, Q, k, max_workgroups, workspace, emb.device,
+                                    (("emb", emb), ("queries", queries), ("exclude", exclude)))
     check(h.vbq_topk_f32(_ptr(emb), V, K, _ptr(queries), Q, k, metric, _ptr(exclude), E, _ptr(ids), _ptr(scores),
                          int(max_workgroups), _ptr(ws), ws.numel() * ws.element_size(), _stream(emb)), "vbq_topk_f32")
     return ids, scores
@@ -837,7 +923,7 @@ _BAG_MODES = {"sum": 0, "mean": 1, "max": 2, 0: 0, 1: 1, 2: 2}
 BAG_BAD_ROW, BAG_BAD_OFFSETS = 8, 16             # status bits 3 and 4 of the bag calls (bits 0..2: RECORDS_UNPACK_STATUS)
 
 
-def _bag_args(ids, offsets, weights, mode, status, out, K, device):
+def _bag_args(ids, offsets, weights, mode, status, out, K, device, rows):
     """What records_bag and bag take alike -> (ids [n], offsets [B + 1], weights [n] or None, mode code, status, out [B, K])."""
     ids = _dev(ids, torch.int64, "ids")
     offsets = _dev(offsets, torch.int64, "offsets")
@@ -854,9 +940,11 @@ def _bag_args(ids, offsets, weights, mode, status, out, K, device):
         weights = _dev(weights, torch.float32, "weights")
         if weights.shape != ids.shape:
             raise ValueError(f"weights {tuple(weights.shape)} and ids {tuple(ids.shape)} differ in shape")
+    reads = rows + (("ids", ids), ("offsets", offsets), ("weights", weights))
+    out = _out(out, (offsets.numel() - 1, K), torch.float32, device, "out", True, reads)
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
-    return ids, offsets, weights, mode, status, _out(out, (offsets.numel() - 1, K), torch.float32, device, "out")
+        status = _status(status, 1, device, reads + (("out", out),))
+    return ids, offsets, weights, mode, status, out
 
 
 def records_bag(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: torch.Tensor, ids: torch.Tensor,
@@ -872,7 +960,8 @@ def records_bag(words: torch.Tensor, K: int, N: int, total_bits: int, table_sort
     words = _dev(words, torch.uint32, "words")
     K, N, total_bits = int(K), int(N), int(total_bits)
     n_tables, table_sorted = _records_inputs(words, "V", K, N, total_bits, table_sorted)
-    ids, offsets, weights, mode, status, out = _bag_args(ids, offsets, weights, mode, status, out, K, words.device)
+    ids, offsets, weights, mode, status, out = _bag_args(ids, offsets, weights, mode, status, out, K, words.device,
+                                                         (("words", words), ("table_sorted", table_sorted)))
     check(_lib.lib().vbq_records_bag_f32(_ptr(words), words.shape[0], K, N, total_bits, _ptr(table_sorted), n_tables, _ptr(ids),
                                          ids.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(weights), mode, _ptr(out),
                                          _ptr(status), _stream(words)), "vbq_records_bag_f32")
@@ -887,7 +976,7 @@ def bag(emb: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, *, weights:
     if emb.dim() != 2:
         raise ValueError(f"emb must be [V, K], got shape {tuple(emb.shape)}")
     V, K = emb.shape
-    ids, offsets, weights, mode, status, out = _bag_args(ids, offsets, weights, mode, status, out, K, emb.device)
+    ids, offsets, weights, mode, status, out = _bag_args(ids, offsets, weights, mode, status, out, K, emb.device, (("emb", emb),))
     check(_lib.lib().vbq_bag_f32(_ptr(emb), V, K, _ptr(ids), ids.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(weights), mode,
                                  _ptr(out), _ptr(status), _stream(emb)), "vbq_bag_f32")
     return out
@@ -896,7 +985,7 @@ def bag(emb: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, *, weights:
 SCORES_BAD_ROW = 8                               # status bit 3 of the scores calls (bits 0..2: RECORDS_UNPACK_STATUS)
 
 
-def _scores_args(queries, ids, K, metric, status, out):
+def _scores_args(queries, ids, K, metric, status, out, rows):
     """What records_scores and scores take alike -> (queries [Q, K], ids [Q, M], metric code, status, out [Q, M])."""
     queries = _dev(queries, torch.float32, "queries")
     if queries.dim() != 2 or queries.shape[1] != K:
@@ -906,9 +995,11 @@ def _scores_args(queries, ids, K, metric, status, out):
         raise ValueError(f"ids must be [{queries.shape[0]}, M], got shape {tuple(ids.shape)}")
     if metric not in _METRICS:
         raise ValueError(f"metric {metric!r} is neither 'dot' nor 'cosine'")
+    reads = rows + (("queries", queries), ("ids", ids))
+    out = _out(out, tuple(ids.shape), torch.float32, queries.device, "out", True, reads)
     if status is not None:
-        status = _dev(status, torch.uint32, "status")
-    return queries, ids, _METRICS[metric], status, _out(out, tuple(ids.shape), torch.float32, queries.device, "out")
+        status = _status(status, 1, queries.device, reads + (("out", out),))
+    return queries, ids, _METRICS[metric], status, out
 
 
 def records_scores(words: torch.Tensor, K: int, N: int, total_bits: int, table_sorted: torch.Tensor, queries: torch.Tensor,
@@ -924,7 +1015,8 @@ def records_scores(words: torch.Tensor, K: int, N: int, total_bits: int, table_s
     words = _dev(words, torch.uint32, "words")
     K, N, total_bits = int(K), int(N), int(total_bits)
     n_tables, table_sorted = _records_inputs(words, "V", K, N, total_bits, table_sorted)
-    queries, ids, metric, status, out = _scores_args(queries, ids, K, metric, status, out)
+    queries, ids, metric, status, out = _scores_args(queries, ids, K, metric, status, out,
+                                                     (("words", words), ("table_sorted", table_sorted)))
     _lib_ext.check(_lib_ext.lib().vbqx_records_scores_f32(_ptr(words), words.shape[0], K, N, total_bits, _ptr(table_sorted),
                                                           n_tables, _ptr(queries), ids.shape[0], _ptr(ids), ids.shape[1], metric,
                                                           _ptr(out), _ptr(status), _stream(words)), "vbqx_records_scores_f32")
@@ -940,7 +1032,7 @@ def scores(emb: torch.Tensor, queries: torch.Tensor, ids: torch.Tensor, metric="
     if emb.dim() != 2:
         raise ValueError(f"emb must be [V, K], got shape {tuple(emb.shape)}")
     V, K = emb.shape
-    queries, ids, metric, status, out = _scores_args(queries, ids, K, metric, status, out)
+    queries, ids, metric, status, out = _scores_args(queries, ids, K, metric, status, out, (("emb", emb),))
     _lib_ext.check(_lib_ext.lib().vbqx_scores_f32(_ptr(emb), V, K, _ptr(queries), ids.shape[0], _ptr(ids), ids.shape[1], metric,
                                                   _ptr(out), _ptr(status), _stream(emb)), "vbqx_scores_f32")
     return out
@@ -979,13 +1071,13 @@ def _window_args(payload, sizes, offsets, files, fields, segs, freq, values, box
     box = tuple(int(w) for w in box)
     if len(box) != 3 or min(box) < 0:
         raise ValueError(f"box must be three extents >= 0, got {box}")
+    reads = (("payload", payload), ("sizes", sizes), ("offsets", offsets), ("files", files), ("segs", segs), ("freq", freq),
+             ("values", values), ("channels", channels))
     if status is None:
         status = torch.zeros(F, dtype=torch.uint32, device=payload.device)
     else:
-        status = _dev(status, torch.uint32, "status")
-        if status.numel() != F:
-            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
-    out = _out(out, (F,) + box + (n_ch_sel,), torch.float32, payload.device, "out")
+        status = _status(status, F, payload.device, reads)
+    out = _out(out, (F,) + box + (n_ch_sel,), torch.float32, payload.device, "out", True, reads + (("status", status),))
     return payload, sizes, offsets, files, segs, freq, values, box, channels, status, out, F, n_ch_sel, n_ch, n_tables
 
 
@@ -1024,6 +1116,7 @@ def rans_map_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: 
     cls_base_f -- or None when every file has cls_base = -1; max_classes the largest P of `files`, 1..4.  Everything else, and
     the result (out, status), as rans_decode_window."""
     seg, N, max_classes = int(seg), int(N), int(max_classes)
+    given = [name for name, t in (("out", out), ("status", status)) if t is not None]
     payload, sizes, offsets, files, segs, freq, values, box, channels, status, out, F, n_ch_sel, n_ch, n_tables = _window_args(
         payload, sizes, offsets, files, (16, "seg_base, n, D1, D2, a0, a1, a2, P, table[0..3], cls_base, 0, 0, 0"), segs, freq,
         values, box, seg, N, channels, status, out)
@@ -1031,6 +1124,8 @@ def rans_map_decode_window(payload: torch.Tensor, sizes: torch.Tensor, offsets: 
         classes = _dev(classes, torch.uint8, "classes")
         if classes.dim() != 1:
             raise ValueError(f"classes must be one-dimensional, got shape {tuple(classes.shape)}")
+        for name in given:
+            _apart(name, out if name == "out" else status, (("classes", classes),))
     check(_lib.lib().vbq_rans_map_decode_window_f32(_ptr(payload), payload.numel(), _ptr(sizes), _ptr(offsets), sizes.numel(),
                                                     _ptr(files), F, _ptr(segs), segs.shape[1], _ptr(channels), n_ch_sel, n_ch,
                                                     seg, N, _ptr(freq), n_tables, _ptr(values), _ptr(classes),
@@ -1071,20 +1166,19 @@ def rans_encode_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tenso
             raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
     if M < 0:
         raise ValueError(f"M = {M} slots")
+    reads = (("idx", idx), ("files", files), ("items", items), ("freq", freq), ("canon", canon))
     given = words is not None
-    words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words")
+    words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words", True, reads)
     if not given:
         words.zero_()
     if sizes is None:
         sizes = torch.zeros(M, dtype=torch.uint32, device=idx.device)
     else:
-        sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes")
+        sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes", True, reads + (("words", words),))
     if status is None:
         status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
     else:
-        status = _dev(status, torch.uint32, "status")
-        if status.numel() != F:
-            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+        status = _status(status, F, idx.device, reads + (("words", words), ("sizes", sizes)))
     check(_lib.lib().vbq_rans_encode_files_u16(_ptr(idx), idx.numel(), _ptr(files), F, _ptr(items), items.shape[0], n_ch, seg, N,
                                                _ptr(freq), n_tables, _ptr(canon), _ptr(words), _ptr(sizes), M, _ptr(status),
                                                _stream(idx)), "vbq_rans_encode_files_u16")
@@ -1117,16 +1211,15 @@ def rans_sizes_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Tensor
         canon = _dev(canon, torch.uint16, "canon")
         if tuple(canon.shape) != (n_ch, T):
             raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
+    reads = (("idx", idx), ("files", files), ("items", items), ("freq", freq), ("canon", canon))
     if totals is None:
         totals = torch.zeros((L, F), dtype=torch.int64, device=idx.device).view(torch.uint64)
     else:
-        totals = _out(totals, (L, F), torch.uint64, idx.device, "totals")
+        totals = _out(totals, (L, F), torch.uint64, idx.device, "totals", True, reads)
     if status is None:
         status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
     else:
-        status = _dev(status, torch.uint32, "status")
-        if status.numel() != F:
-            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+        status = _status(status, F, idx.device, reads + (("totals", totals),))
     check(_lib.lib().vbq_rans_sizes_files_u16(_ptr(idx), idx.numel(), lambda_stride, _ptr(files), F, _ptr(items), items.shape[0],
                                               n_ch, seg, N, _ptr(freq), L, _ptr(canon), _ptr(totals), _ptr(status),
                                               _stream(idx)), "vbq_rans_sizes_files_u16")
@@ -1160,21 +1253,22 @@ def _map_files_args(idx, classes, files, palettes, items, freq, M, seg, N, canon
             raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
     if M < 0:
         raise ValueError(f"M = {M} slots")
+    reads = (("idx", idx), ("classes", classes), ("files", files), ("palettes", palettes), ("items", items), ("freq", freq),
+             ("canon", canon))
     given = words is not None
     if words is not False:
-        words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words")
+        words = _out(words, (M, seg + 2), torch.uint16, idx.device, "words", True, reads)
         if not given:
             words.zero_()
+        reads += (("words", words),)
     if sizes is None:
         sizes = torch.zeros(M, dtype=torch.uint32, device=idx.device)
     else:
-        sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes")
+        sizes = _out(sizes, (M,), torch.uint32, idx.device, "sizes", True, reads)
     if status is None:
         status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
     else:
-        status = _dev(status, torch.uint32, "status")
-        if status.numel() != F:
-            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+        status = _status(status, F, idx.device, reads + (("sizes", sizes),))
     return idx, classes, files, palettes, items, freq, canon, words, sizes, status, F, n_tables, n_ch, M, seg, N
 
 
@@ -1248,16 +1342,16 @@ def rans_map_rates_files(idx: torch.Tensor, classes: torch.Tensor, files: torch.
         canon = _dev(canon, torch.uint16, "canon")
         if tuple(canon.shape) != (n_ch, T):
             raise ValueError(f"canon must be [{n_ch}, {T}], got {tuple(canon.shape)}")
+    reads = (("idx", idx), ("classes", classes), ("files", files), ("palettes", palettes), ("items", items), ("freq", freq),
+             ("canon", canon))
     if totals is None:
         totals = torch.zeros((K, F), dtype=torch.int64, device=idx.device).view(torch.uint64)
     else:
-        totals = _out(totals, (K, F), torch.uint64, idx.device, "totals")
+        totals = _out(totals, (K, F), torch.uint64, idx.device, "totals", True, reads)
     if status is None:
         status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
     else:
-        status = _dev(status, torch.uint32, "status")
-        if status.numel() != F:
-            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
+        status = _status(status, F, idx.device, reads + (("totals", totals),))
     check(_lib.lib().vbq_rans_map_rates_files_u16(_ptr(idx), idx.numel(), lambda_stride, _ptr(classes), classes.numel(),
                                                   _ptr(files), F, _ptr(palettes), K, int(max_classes), _ptr(items), items.shape[0],
                                                   n_ch, seg, N, _ptr(freq), L, _ptr(canon), _ptr(totals), _ptr(status),
@@ -1267,8 +1361,8 @@ def rans_map_rates_files(idx: torch.Tensor, classes: torch.Tensor, files: torch.
 
 # ---- batches of compact files (include/vbq.h, "Compact batch"): one wave per (file, part)
 def _il_files_args(idx, files, items, freq, N, status):
-    """What the three compact-batch calls check alike -> (idx, files, items, freq, status, F, n_tables, n_ch)."""
-    idx = _dev(idx, torch.uint16, "idx")
+    """What the four compact-batch calls check alike, `idx` having been checked by the caller (the encoders read it, the decoder
+    writes it) -> (files, items, freq, status, F, n_tables, n_ch)."""
     files = _dev(files, torch.int64, "files")
     items = _dev(items, torch.int32, "items")
     freq = _dev(freq, torch.uint16, "freq")
@@ -1284,10 +1378,8 @@ def _il_files_args(idx, files, items, freq, N, status):
     if status is None:
         status = torch.zeros(F, dtype=torch.uint32, device=idx.device)
     else:
-        status = _dev(status, torch.uint32, "status")
-        if status.numel() != F:
-            raise ValueError(f"status must hold one word per file ({F}), got {status.numel()}")
-    return idx, files, items, freq, status, F, freq.shape[0], freq.shape[1]
+        status = _status(status, F, idx.device, (("idx", idx), ("files", files), ("items", items), ("freq", freq)))
+    return files, items, freq, status, F, freq.shape[0], freq.shape[1]
 
 
 def _il_canon(canon, n_ch, N):
@@ -1307,15 +1399,20 @@ def rans_il_sizes_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Ten
     (bitstream.compact_plan builds both); freq u16 [n_tables, C, T]; canon u16 [C, T] or None.  Returns (sizes u32 [P_all],
     status u32 [F]): entry part_base_f + p is what RansCodec.sizes_interleaved gives for that file alone; entries no item names
     keep what `sizes` held (a new one is zeroed).  `status` is OR-ed into: zeroed here unless given."""
-    idx, files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    idx = _dev(idx, torch.uint16, "idx")
+    given = status is not None
+    files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
     canon = _il_canon(canon, n_ch, N)
+    if given:
+        _apart("status", status, (("canon", canon),))
     P_all = int(P_all)
     if P_all < 0:
         raise ValueError(f"P_all = {P_all} parts")
     if sizes is None:
         sizes = torch.zeros(P_all, dtype=torch.uint32, device=idx.device)
     else:
-        sizes = _out(sizes, (P_all,), torch.uint32, idx.device, "sizes")
+        sizes = _out(sizes, (P_all,), torch.uint32, idx.device, "sizes", True,
+                     (("idx", idx), ("files", files), ("items", items), ("freq", freq), ("canon", canon), ("status", status)))
     check(_lib.lib().vbq_rans_il_sizes_files_u16(_ptr(idx), idx.numel(), _ptr(files), F, _ptr(items), items.shape[0], n_ch,
                                                  int(N), _ptr(freq), n_tables, _ptr(canon), _ptr(sizes), P_all, _ptr(status),
                                                  _stream(idx)), "vbq_rans_il_sizes_files_u16")
@@ -1331,15 +1428,20 @@ def rans_il_rates_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Ten
     [C, T] or None.  Returns (sizes u32 [L, P_all], status u32 [F]): sizes[l] is what rans_il_sizes_files gives on plane l
     with freq[l]; entries no item names keep what `sizes` held (a new one is zeroed).  `status` is OR-ed into: zeroed here
     unless given."""
-    idx, files, items, freq, status, F, L, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    idx = _dev(idx, torch.uint16, "idx")
+    given = status is not None
+    files, items, freq, status, F, L, n_ch = _il_files_args(idx, files, items, freq, N, status)
     canon = _il_canon(canon, n_ch, N)
+    if given:
+        _apart("status", status, (("canon", canon),))
     P_all, lambda_stride = int(P_all), int(lambda_stride)
     if P_all < 0:
         raise ValueError(f"P_all = {P_all} parts")
     if sizes is None:
         sizes = torch.zeros((L, P_all), dtype=torch.uint32, device=idx.device)
     else:
-        sizes = _out(sizes, (L, P_all), torch.uint32, idx.device, "sizes")
+        sizes = _out(sizes, (L, P_all), torch.uint32, idx.device, "sizes", True,
+                     (("idx", idx), ("files", files), ("items", items), ("freq", freq), ("canon", canon), ("status", status)))
     check(_lib.lib().vbq_rans_il_rates_files_u16(_ptr(idx), idx.numel(), lambda_stride, _ptr(files), F, _ptr(items),
                                                  items.shape[0], n_ch, int(N), _ptr(freq), L, _ptr(canon), _ptr(sizes), P_all,
                                                  _ptr(status), _stream(idx)), "vbq_rans_il_rates_files_u16")
@@ -1352,11 +1454,19 @@ def rans_il_encode_files(idx: torch.Tensor, files: torch.Tensor, items: torch.Te
     """vbq_rans_il_encode_files_u16: every listed part into payload u16 [n_words] at offsets int64 [P_all], with sizes u32
     [P_all] from rans_il_sizes_files (the same idx, files, items, freq and canon).  A part's words are those of
     RansCodec.encode_interleaved for its file alone.  Returns (payload, status u32 [F])."""
-    idx, files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    idx = _dev(idx, torch.uint16, "idx")
+    given = status is not None
+    files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
     canon = _il_canon(canon, n_ch, N)
     sizes = _dev(sizes, torch.uint32, "sizes").reshape(-1)
     offsets = _dev(offsets, torch.int64, "offsets").reshape(-1)
-    payload = _dev(payload, torch.uint16, "payload").reshape(-1)
+    more = (("canon", canon), ("sizes", sizes), ("offsets", offsets))
+    if given:
+        _apart("status", status, more)
+    payload = _out(payload, "any", torch.uint16, idx.device, "payload", False,
+                   (("idx", idx), ("files", files), ("items", items), ("freq", freq), ("status", status)) + more)
+    if payload is None:
+        raise ValueError(f"payload: expected a contiguous {torch.uint16} device tensor of shape any")
     if offsets.numel() != sizes.numel():
         raise ValueError(f"{sizes.numel()} sizes and {offsets.numel()} offsets")
     check(_lib.lib().vbq_rans_il_encode_files_u16(_ptr(idx), idx.numel(), _ptr(files), F, _ptr(items), items.shape[0], n_ch,
@@ -1373,10 +1483,19 @@ def rans_il_decode_files(payload: torch.Tensor, sizes: torch.Tensor, offsets: to
     int64 [P_all] -- all UNTRUSTED -- into idx u16 [n_idx] at the positions the descriptors name (files [F, 8] with the word
     fields filled in); positions of no listed part keep what `idx` held.  Returns (idx, status u32 [F]): a part with a status
     bit decoded to zeros (read the words with coder._raise_status)."""
-    idx, files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    idx = _out(idx, "any", torch.uint16, None, "idx", False)
+    if idx is None:
+        raise ValueError(f"idx: expected a contiguous {torch.uint16} device tensor of shape any")
+    given = status is not None
+    files, items, freq, status, F, n_tables, n_ch = _il_files_args(idx, files, items, freq, N, status)
+    if idx.device != files.device:
+        raise ValueError(f"idx: expected a contiguous {torch.uint16} device tensor of shape any")
+    _apart("idx", idx, (("files", files), ("items", items), ("freq", freq)))
     payload = _dev(payload, torch.uint16, "payload").reshape(-1)
     sizes = _dev(sizes, torch.uint32, "sizes").reshape(-1)
     offsets = _dev(offsets, torch.int64, "offsets").reshape(-1)
+    for name, t in (("idx", idx), ("status", status))[:1 + given]:
+        _apart(name, t, (("payload", payload), ("sizes", sizes), ("offsets", offsets)))
     if offsets.numel() != sizes.numel():
         raise ValueError(f"{sizes.numel()} sizes and {offsets.numel()} offsets")
     check(_lib.lib().vbq_rans_il_decode_files_u16(_ptr(payload), payload.numel(), _ptr(sizes), _ptr(offsets), sizes.numel(),

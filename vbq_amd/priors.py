@@ -266,7 +266,7 @@ class BMSHJ2018Prior:
         done, ran = False, 0
         while not done and ran < max_iterations:
             n = min(chain, max_iterations - ran)
-            ops.bmshj_icdf_chain(params, xi_t, left, right, mid, flags, n, float(np.float32(tol)), first=(ran == 0))
+            ops.bmshj_icdf_chain(params, xi_t, left, right, mid, flags[: n + 1], n, float(np.float32(tol)), first=(ran == 0))
             f = flags[: n + 1].cpu().numpy().view(np.uint32)
             widths = f[:, 1].copy().view(np.float32)
             for j in range(1, n + 1):                             # pair j: what step j - 1 of this chain accumulated

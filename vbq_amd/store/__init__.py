@@ -45,12 +45,13 @@ def plan_boxes(table, ids, origins, extents, *, seg, n_sel, desc=None, segs=None
                          f"and {tuple(origins.shape)}")
     S, (F, fields), n_sel = ids.shape[0], table.shape, int(n_sel)
     w0, w1, w2 = (int(w) for w in extents)
-    desc = ops._out(desc, (S, fields), torch.int64, ids.device, "desc")
-    segs = ops._out(segs, (S, n_sel), torch.int32, ids.device, "segs")
+    reads = (("table", table), ("ids", ids), ("origins", origins))
+    desc = ops._out(desc, (S, fields), torch.int64, ids.device, "desc", True, reads)
+    segs = ops._out(segs, (S, n_sel), torch.int32, ids.device, "segs", True, reads + (("desc", desc),))
     if status is None:
         status = torch.zeros(S, dtype=torch.uint32, device=ids.device)
     else:
-        status = ops._out(status, (S,), torch.uint32, ids.device, "status")
+        status = ops._status(status, S, ids.device, reads + (("desc", desc), ("segs", segs)))
     _lib_store.check(_lib_store.lib().vbqs_plan_boxes(ops._ptr(table), F, fields, ops._ptr(ids), ops._ptr(origins), S, w0, w1, w2,
                                                       int(seg), n_sel, ops._ptr(desc), ops._ptr(segs), ops._ptr(status),
                                                       ops._stream(ids)), "vbqs_plan_boxes")
@@ -192,9 +193,9 @@ class LatentStore:
         ids, origins = self._samples(ids, origins, short)
         S, dev = ids.shape[0], ids.device
         shape = (S,) + (box[1:] if short else box) + (C_sel,)
-        out = ops._out(out, shape, torch.float32, dev, "out")
-        status = torch.zeros(S, dtype=torch.uint32, device=dev) if status is None else ops._out(status, (S,), torch.uint32, dev,
-                                                                                                   "status")
+        out = ops._out(out, shape, torch.float32, dev, "out", True, (("ids", ids), ("origins", origins)))
+        status = torch.zeros(S, dtype=torch.uint32, device=dev) if status is None else ops._status(
+            status, S, dev, (("ids", ids), ("origins", origins), ("out", out)))
         if S == 0 or C_sel == 0 or 0 in box:
             return out, status
         n_sel = self._n_sel(box)

@@ -5,6 +5,7 @@
  * (a hipStream_t passed as void*; NULL = the default stream) and returns without synchronising, nothing is allocated or copied
  * inside a call, the return value is VBQ_OK or a VBQ_ERR_* code of vbq.h, and vbqs_last_error() gives the text of the calling
  * thread's most recent failure in THIS library.  A call that returns VBQ_ERR_INVALID_ARGUMENT has enqueued nothing.
+ * What a call writes must overlap nothing else it reads or writes: vbq.h, "Buffers".
  * The header lives beside its sources (vbq_amd/store): the directory `include` holds the headers of the first four libraries.
  */
 #ifndef VBQ_STORE_H_
