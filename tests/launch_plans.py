@@ -10,6 +10,8 @@ shapes have to move.
                                                                         vbq_amd/csrc/vbq_reduce.hip
                     launch_hist (k_hist_tiled)                          vbq_amd/csrc/vbq_hist.hip
     solve_kernel    launch_quantize: which solve kernel a lambda chunk takes     vbq_amd/csrc/vbq_quantize.hip, vbq_quantize_fast.hip
+    notebook_kernel launch_notebook: which notebook kernel a beta chunk takes   vbq_amd/csrc/vbq_notebook.hip
+    transpose_kernel, gather_kernel, np_sums_first_kernel               vbq_amd/csrc/vbq_transpose.hip, vbq_latents.hip, vbq_reduce.hip
 
 and, for tests/test_gpu_wide_rows.py, the rules by which the kernels that size their dynamic LDS from their arguments accept a
 shape, lay the LDS out and refuse one step further:
@@ -61,6 +63,16 @@ FAST_LAMBDA_RANGE = (1.9e-12, 1.8e19)              # fast_ok: every lambda of th
 SWEEP_KEY_SHIFT = 16             # build_sweep_table<16>: a bucket is one value of (f32 bits >> 16)
 SWEEP_KEYS = 2048                # kHullKeys: buckets, 16 octaves of 128
 TILED_MAX_N = 10                 # `else if constexpr (N > 10)`: channel-last with n_ch > 1 is refused above
+# ---- vbq_notebook.hip, vbq_sweep_host.h: the notebook solve
+NB_MAX_BETA_CHUNK = 64           # kMaxBetaChunk: betas per launch
+NB_PRUNED_MAX_L = 2              # `nonneg && Lc <= 2`: the pruned descent
+NB_HULL_MIN_L = 6                # `fast_ok && N == 10 && Lc >= 6`: K1nt from this many betas
+NB_FAST_RANGE = (1e-12, 1e18)    # fast_ok: every beta of the chunk inside, as doubles
+NB_SWEEP_RANGE = (2e-12, 2e18)   # build_sweep_table<kNbKeyShift>(b, Lc, 2e-12f, 2e18f, sw) on b = (float)(2 beta)
+NB_KEY_SHIFT = 17                # kNbKeyShift
+NB_KEYS = 1536                   # kNbKeys: 24 octaves of 64 buckets
+# ---- vbq_reduce.hip: the NumPy-order sums
+NP_BLOCK = 8192                  # kNpBlock: elements per k_np_block_sums workgroup
 # ---- every launcher below: `lds > 64 * 1024` raises hipFuncAttributeMaxDynamicSharedMemorySize before the launch
 LDS_OPT_IN = 64 * 1024
 WAVE = 64                        # kWave (vbq_common.h)
@@ -289,6 +301,59 @@ def solve_kernels(N, lam, layout, n_ch, **kw):
     """solve_kernel for every chunk of a sweep of any length (the l0 loop of launch_quantize); a per-lambda flag list
     level_len is not needed: the table is given for all chunks or for none."""
     return [solve_kernel(N, list(lam[l0:l0 + MAX_LAMBDA_CHUNK]), layout, n_ch, **kw) for l0 in range(0, len(lam), MAX_LAMBDA_CHUNK)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- other routes
+def _f32(x):
+    import struct
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def sweep_table_ok(values, max_l, shift, keys, lo, hi):
+    """build_sweep_table<shift> (vbq_sweep_host.h) on f32 `values`: between 1 and max_l of them, each inside [lo, hi] (as f32),
+    no two in one bucket of key = bits >> shift (equal ones among them), last key - first key + 2 <= keys."""
+    import struct
+    if not 1 <= len(values) <= max_l:
+        return False
+    v = sorted(_f32(x) for x in values)
+    if not all(_f32(lo) <= x <= _f32(hi) for x in v):
+        return False
+    k = [struct.unpack("I", struct.pack("f", x))[0] >> shift for x in v]
+    return all(b > a for a, b in zip(k, k[1:])) and k[-1] - k[0] + 2 <= keys
+
+
+def notebook_kernel(N, betas):
+    """launch_notebook for ONE chunk of betas (at most 64 doubles) -> the kernel it launches:
+        "pruned<L>"  k_quant_notebook_pruned   one or two betas, none negative
+        "hull"       k_quant_notebook_hull     N = 10, six or more betas in the fast range whose sweep table can be built
+        "fast"       k_quant_notebook_fast     every beta in the fast range
+        "literal"    k_quant_notebook          the rest: a negative beta, a beta outside the fast range"""
+    L = len(betas)
+    assert 1 <= L <= NB_MAX_BETA_CHUNK
+    if all(b >= 0.0 for b in betas) and L <= NB_PRUNED_MAX_L:
+        return f"pruned<{L}>"
+    fast_ok = all(NB_FAST_RANGE[0] <= b <= NB_FAST_RANGE[1] for b in betas)
+    if fast_ok and N == 10 and L >= NB_HULL_MIN_L and \
+            sweep_table_ok([_f32(2.0 * b) for b in betas], NB_MAX_BETA_CHUNK, NB_KEY_SHIFT, NB_KEYS, *NB_SWEEP_RANGE):
+        return "hull"
+    return "fast" if fast_ok else "literal"
+
+
+def transpose_kernel(rows, cols, elem_bytes, aligned=True):
+    """launch_transpose_batched / vbq_transpose_f32 -> "vec" (k_transpose_batched_vec: rows and cols multiples of the 16-byte
+    vector, 16-byte aligned bases; a whole number of vectors per plane follows) or "scalar" (k_transpose_batched)."""
+    V = 16 // elem_bytes
+    return "vec" if rows % V == 0 and cols % V == 0 and aligned else "scalar"
+
+
+def gather_kernel(n_ch, layout, out_layout):
+    """vbq_gather_f32 -> "k_gather_transpose" where the output's layout differs from the input's (C > 1), else "k_gather"."""
+    return "k_gather_transpose" if n_ch > 1 and layout != out_layout else "k_gather"
+
+
+def np_sums_first_kernel(n):
+    """launch_np_sums: the first launch of vbq_numpy_sum_sq_f32 / vbq_numpy_row_sums_f32 on rows of n elements."""
+    return "k_np_block_sums" if n // NP_BLOCK > 0 else "k_np_finish"
 
 
 # ---------------------------------------------------------------------------------------------------------------- wide rows
