@@ -57,7 +57,7 @@ THREADS = 256                    # workgroup size of the reductions and scans
 SOLVE_DEPTHS = (12, 11, 10, 9, 8, 7, 6, 5, 4)      # VBQ_FOR_EACH_N: the bit depths the solve kernels are built for
 MAX_LAMBDA_CHUNK = 32            # kMaxLambdaChunk: lambdas per launch
 PRUNED_MAX_L = 2                 # kPrunedMaxL: lambdas up to which the pruned descent K1p takes an indices-only call
-PRUNED_BUILT_L = (1, 2, 3, 4)    # VBQ_PRUNED_CASE: the K1p instances that are compiled (3 and 4 are not reached)
+PRUNED_BUILT_L = (1, 2)          # VBQ_PRUNED_CASE: the K1p instances that are compiled, all of them reached
 HULL_IDX_MIN_L = 16              # `if (L < 16) return 1;` of launch_quant_hull_idx10: K1e from this many lambdas
 FAST_LAMBDA_RANGE = (1.9e-12, 1.8e19)              # fast_ok: every lambda of the chunk inside, as doubles
 SWEEP_KEY_SHIFT = 16             # build_sweep_table<16>: a bucket is one value of (f32 bits >> 16)

@@ -160,3 +160,67 @@ def test_library_reads_no_environment_but_the_test_hook():
     for f in sorted(os.listdir(pkg)):
         if f.endswith(".py"):
             assert "VBQ_PYTHON_HOST_STAGE" not in open(os.path.join(pkg, f)).read(), f
+
+
+_INT_DEFAULT = re.compile(r"-?\d+|\([\d\s+\-*/%<>()]*\d[\d\s+\-*/%<>()]*\)")
+
+
+def unsettled_conditionals(root):
+    """["file:line: why", ...]: the preprocessor conditionals under vbq_amd/ and include/ that are none of an include guard,
+    `#ifdef __cplusplus`, a VBQ_ONLY_N10 block, or `#ifndef NAME` / `#define NAME <integer>` / `#endif` on three lines."""
+    bad = []
+    for top in ("vbq_amd", "include"):
+        for d, _, files in sorted(os.walk(os.path.join(root, top))):
+            for f in sorted(files):
+                if f.endswith((".hip", ".h")):
+                    bad += _unsettled_in(os.path.join(d, f), os.path.relpath(os.path.join(d, f), root))
+    return bad
+
+
+def _unsettled_in(path, name):
+    text = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), open(path, errors="replace").read(), flags=re.S)
+    lines = [ln.split("//", 1)[0].strip() for ln in text.splitlines()]
+    directives = [(i, re.match(r"#\s*(\w+)\s*(.*)", ln)) for i, ln in enumerate(lines) if ln.startswith("#")]
+    directives = [(i, m.group(1), m.group(2).strip()) for i, m in directives if m]
+    last = directives[-1][0] if directives else -1
+    bad, stack = [], []                                         # stack: (kind, line) of every open conditional
+    for i, word, rest in directives:
+        at = f"{name}:{i + 1}"
+        if word in ("if", "ifdef", "ifndef"):
+            define = re.fullmatch(r"#\s*define\s+(\w+)\s*(.*)", lines[i + 1]) if i + 1 < len(lines) else None
+            mine = define is not None and word == "ifndef" and define.group(1) == rest
+            if word == "ifdef" and rest == "__cplusplus":
+                kind = "c++"
+            elif word in ("ifdef", "ifndef") and rest == "VBQ_ONLY_N10":
+                kind = "N10"
+            elif mine and define.group(2) == "":
+                kind = "guard"                                  # must close on the file's last directive: checked at its #endif
+            elif mine and i + 2 < len(lines) and re.fullmatch(r"#\s*endif", lines[i + 2]):
+                kind = "default"
+                if not _INT_DEFAULT.fullmatch(define.group(2)):
+                    bad.append(f"{at}: the guarded default of {rest} is not a number: {define.group(2)!r}")
+            else:
+                kind = "other"
+                bad.append(f"{at}: #{word} {rest} selects code: a build flag nobody sets chooses between two forms")
+            stack.append((kind, i))
+        elif word in ("else", "elif"):
+            if not stack or stack[-1][0] not in ("guard", "c++", "N10"):
+                bad.append(f"{at}: #{word} keeps a second form of the code")
+        elif word == "endif":
+            if not stack:
+                bad.append(f"{at}: #endif without an #if")
+                continue
+            kind, opened = stack.pop()
+            if kind == "guard" and i != last:
+                bad.append(f"{name}:{opened + 1}: #ifndef with an empty #define that is not the file's include guard")
+    bad += [f"{name}:{opened + 1}: conditional never closed" for _, opened in stack]
+    return bad
+
+
+def test_no_build_flag_selects_between_two_forms_of_the_code():
+    """Every line of the native sources is compiled by the one build there is: the only preprocessor conditionals are include
+    guards, `#ifdef __cplusplus`, the VBQ_ONLY_N10 blocks (fewer instances of the same code) and numeric tuning defaults
+    (`#ifndef NAME` / `#define NAME <integer>` / `#endif`, the values tools/build_variants.py builds).  A flag that picks a
+    second code path (`#if NAME`, `#else`, a default that is not a number) leaves a form nobody builds, tests or times."""
+    bad = unsettled_conditionals(ROOT)
+    assert not bad, "\n".join(bad)

@@ -6,7 +6,7 @@ scores also equal the exhaustive maximum over every code point (oracle/rd_f64.py
 
 Before every launch tests/launch_plans.solve_kernel says which kernel the call takes, and the test asserts that it is the
 instance the case is named after.  Three things follow from the dispatch and are asserted rather than assumed:
-  * k_quant_pruned<N, 3> and <N, 4> are compiled but never launched: launch_quant_pruned hands calls with more than
+  * k_quant_pruned is built for one and two lambdas only: launch_quant_pruned hands calls with more than
     kPrunedMaxL = 2 lambdas on, and indices-only calls with three or four lambdas take k_quant_fast<N, 0>.  They are run
     here all the same -- as K1<0> launches with three and four lambdas.
   * at N = 10 a raw-length counting call with an eligible sweep takes K1t and a raw-length indices-only sweep of 16 or

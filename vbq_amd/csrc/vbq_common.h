@@ -56,12 +56,9 @@ __device__ __forceinline__ void set_issue_priority(unsigned int p) {
 // The wave's slot on its SIMD (HW_ID[3:0]): distinct for the waves that compete for one SIMD's issue cycles.
 __device__ __forceinline__ unsigned int wave_slot() { return __builtin_amdgcn_s_getreg((3 << 11) | 4); }
 // One step of the rotation, at the top of a kernel's element loop: `rot` starts at wave_slot() and walks 3, 2, 1, 0, 3, ...
-// (-DVBQ_NO_ISSUE_ROTATION builds the kernels without it, for A/B timing).
 __device__ __forceinline__ void rotate_issue_priority(unsigned int &rot) {
-#ifndef VBQ_NO_ISSUE_ROTATION
     set_issue_priority(rot);
     rot += 3u;
-#endif
 }
 
 constexpr int kWave = 64;
@@ -124,7 +121,7 @@ int quantize_kernel_refusal(const char *who, int32_t n_ch, int32_t layout, const
                             int32_t mode, bool counting, bool idx_only, int32_t wg_per_cu);
 int pruned_max_lambdas();                            // kPrunedMaxL of vbq_quantize_fast.hip: the most lambdas K1p takes per call
 
-// K1p (vbq_quantize_fast.hip): one to four lambdas per call with exact pruning of the descent; indices only.  Returns 1 when the
+// K1p (vbq_quantize_fast.hip): one or two lambdas per call with exact pruning of the descent; indices only.  Returns 1 when the
 // call is not of that kind (the caller takes launch_quant_fast).  Valid for ANY penalties (literal comparisons only).
 template <int N>
 int launch_quant_pruned(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch, const float *table,

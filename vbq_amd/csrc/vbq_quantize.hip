@@ -489,7 +489,7 @@ int launch_quantize(const float *mu, const float *sg, int64_t n_rows, int32_t n_
                 }
             }
             if constexpr (sizeof(PenT) == 4) {
-                // one to four lambdas, indices only: the descent with exact pruning (literal comparisons: any penalties)
+                // one or two lambdas, indices only: the descent with exact pruning (literal comparisons: any penalties)
                 if (!lc_out && oi && !oz && !ob && wg_per_cu == 0) {
                     const int r = launch_quant_pruned<N>(mu_r, sg_r, n_per_ch, ch_stride, n_ch, table, l32, len_c, Lc, oi, E,
                                                          vec2_ok | (bc_to_cb ? 2 : 0), st);

@@ -14,6 +14,11 @@
 //  * phase B (per lambda): 11 adds of the penalties, a v_min3 tree for the best cost S, then
 //    sign(S - c_n) shifted into a bit mask (v_alignbit) -- two ops per level, no VCC traffic --
 //    gives the set of levels that attain S.  One LDS read fetches the packed word of the first.
+//  * a lane solves TWO elements, level by level side by side.  Per lambda the loop keeps only what the answers need: the
+//    penalty row comes in as 16-byte LDS reads from an address held in a vector register; one compare tests both elements
+//    for a cross-level tie (their mask counts summed; a lane with a non-number distortion is sent to the literal scan up
+//    front); where indices are the only output the packed word goes out unmasked -- the rank is its low half -- and both
+//    halves leave as one v_perm_b32 word, through a buffer descriptor when the planes end within 4 GB of the first.
 //  * instruction costs measured on gfx950 (tools/ubench.hip): v_add/sub/mul_f32, and/or/xor,
 //    add/sub_u32, lshrrev run at 2 cycles per wave64; fma, min/max/min3, alignbit, cmp, cndmask,
 //    ffbl, bcnt, lshl_add and ANY op with an SGPR source run at 4.  Hence the penalties are
@@ -43,22 +48,12 @@ namespace vbq {
 namespace {
 
 constexpr int kFastThreads = 256;
-#ifndef VBQ_FAST_NE
-#define VBQ_FAST_NE 2
-#endif
 #ifndef VBQ_FAST_WAVES
 #define VBQ_FAST_WAVES 4
 #endif
-#ifndef VBQ_SLOW_INLINE
-#define VBQ_SLOW_INLINE __noinline__
-#endif
-constexpr int kFastNE = VBQ_FAST_NE;      // elements per thread: 4 (16-B loads) or 2 (8-B loads)
-// 1: the lambda loop of k_quant_fast without six instructions the answers do not need (an address copy, a 64-bit pointer add, a
-// second tie compare, two masks and a shift-or: see its phase B; two elements per thread only); 0: the loop as it was
-#ifndef VBQ_K1_TRIM
-#define VBQ_K1_TRIM 1
-#endif
-constexpr bool kK1Trim = VBQ_K1_TRIM != 0 && VBQ_FAST_NE == 2;
+// Elements per thread (8-byte loads, one 4-byte index store per lambda).  The merged tie test and the v_perm pair of
+// k_quant_fast's phase B are written for exactly two.
+constexpr int kFastNE = 2;
 
 // Correctly rounded f32 quotient d / sigma without an f32 division: RN32(RN64(d * RN64(1/sigma))).
 // The f64 product is within 2^-52 (relative) of the true quotient, and a quotient of two f32 numbers
@@ -146,7 +141,7 @@ __device__ __forceinline__ LevelInfo<N> descend(const float *tb, int n, float z,
 
 // Literal restatement of the reference scan for ONE element and ONE lambda (slow path).
 template <int N>
-__device__ VBQ_SLOW_INLINE uint32_t exact_rank_scan(const float *tb, float z, float sigma, const float *pen) {
+__device__ __noinline__ uint32_t exact_rank_scan(const float *tb, float z, float sigma, const float *pen) {
     const double sg = __ddiv_rn(1.0, (double)sigma);
     uint32_t g = 0;
     float bestL = 0.f, bestR = 0.f;
@@ -182,6 +177,7 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
     constexpr int T = table_size(N);
     constexpr int N1 = N + 1;
     constexpr int NE = kFastNE;
+    static_assert(NE == 2, "the pair loads, the merged tie test and the v_perm pair take two elements per lane");
     constexpr bool EXTRA = MODE == 1;
     constexpr bool COUNT = MODE == 2;
     // dbg (tests only, VBQ_FAST_DEBUG): 1 = send every solve through the literal scan,
@@ -218,17 +214,10 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
     auto load_group = [&](long q, float (&m)[NE], float (&sv)[NE]) {
         const long i0 = q * NE;
         if (!(vec_ok & 2) && (vec_ok & 1) && (i0 + NE <= n_per_ch)) {
-            if constexpr (NE == 4) {
-                const float4 mv = *reinterpret_cast<const float4 *>(mu + base + i0);
-                const float4 s4v = *reinterpret_cast<const float4 *>(sg + base + i0);
-                m[0] = mv.x; m[1] = mv.y; m[2] = mv.z; m[3] = mv.w;
-                sv[0] = s4v.x; sv[1] = s4v.y; sv[2] = s4v.z; sv[3] = s4v.w;
-            } else {
-                const float2 mv = *reinterpret_cast<const float2 *>(mu + base + i0);
-                const float2 s2v = *reinterpret_cast<const float2 *>(sg + base + i0);
-                m[0] = mv.x; m[1] = mv.y;
-                sv[0] = s2v.x; sv[1] = s2v.y;
-            }
+            const float2 mv = *reinterpret_cast<const float2 *>(mu + base + i0);
+            const float2 s2v = *reinterpret_cast<const float2 *>(sg + base + i0);
+            m[0] = mv.x; m[1] = mv.y;
+            sv[0] = s2v.x; sv[1] = s2v.y;
         } else {
 #pragma unroll
             for (int k = 0; k < NE; ++k) {
@@ -247,7 +236,7 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
     const bool resident = (vec_ok & 4) != 0;                // the launcher sized the grid to the resident workgroups
     unsigned int rot = wave_slot();
     // The penalty row's LDS address lives in a vector register and advances by the row pitch (a 2-cycle add): as a function of
-    // the scalar loop counter it was copied into one with a 4-cycle v_mov from an SGPR at every lambda.
+    // the scalar loop counter it would be copied into one with a 4-cycle v_mov from an SGPR at every lambda.
     uint32_t prow0 = 0;
     asm volatile("" : "+v"(prow0));
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(out_idx, 0, -1 /* 4 GB */, 0x00020000);
@@ -328,21 +317,16 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
         // could hide a neighbour's tie from that count.
         uint64_t nan0[NE];
 #pragma unroll
-        for (int k = 0; k < NE; ++k) nan0[k] = kK1Trim ? __builtin_amdgcn_ballot_w64(du[k][0] != du[k][0]) : 0ull;
+        for (int k = 0; k < NE; ++k) nan0[k] = __builtin_amdgcn_ballot_w64(du[k][0] != du[k][0]);
         uint32_t prow = prow0, plane_off = 0;
         for (int l = 0; l < L; ++l, prow += 4u * PS, plane_off += plane_bytes) {
-            if constexpr (kK1Trim) asm volatile("" : "+v"(prow));      // stays a register of its own: not l * pitch again
-            const float *pp = kK1Trim ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(penl) + prow) : penl + l * PS;
+            asm volatile("" : "+v"(prow));                      // stays a register of its own: not l * pitch again
+            const float *pp = reinterpret_cast<const float *>(reinterpret_cast<const char *>(penl) + prow);
             float p[PS];
-            if constexpr (kK1Trim) {                           // rows are whole 16-byte reads, which the opaque offset no longer shows
 #pragma unroll
-                for (int n = 0; n < PS; n += 4) {
-                    const float4 v = *reinterpret_cast<const float4 *>(pp + n);
-                    p[n] = v.x; p[n + 1] = v.y; p[n + 2] = v.z; p[n + 3] = v.w;
-                }
-            } else {
-#pragma unroll
-                for (int n = 0; n < N1; ++n) p[n] = pp[n];
+            for (int n = 0; n < PS; n += 4) {                   // rows are whole 16-byte reads, which the opaque offset does not show
+                const float4 v = *reinterpret_cast<const float4 *>(pp + n);
+                p[n] = v.x; p[n + 1] = v.y; p[n + 2] = v.z; p[n + 3] = v.w;
             }
             uint32_t rank[NE];
             // The NE solves are written level-by-level across elements so that neighbouring
@@ -371,12 +355,12 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
                 // reference's L-before-R order decides: literal scan).  Which SIDE wins never changes the level.
                 uint64_t any_multi = 0;
                 uint32_t lvl[NE];
-                uint64_t multi2 = 0;                            // either element of the lane: see the index modes below
-                if constexpr (kK1Trim) multi2 = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[0]) + (uint32_t)__popc(ne[NE - 1]), 2u * N, 33);
+                // either element of the lane: see the index modes below
+                const uint64_t multi2 = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[0]) + (uint32_t)__popc(ne[NE - 1]), 2u * N, 33);
 #pragma unroll
                 for (int k = 0; k < NE; ++k) {
                     lvl[k] = (uint32_t)__builtin_ctz(~ne[k]);
-                    const uint64_t multi = kK1Trim ? (multi2 | nan0[k]) : __builtin_amdgcn_uicmp((uint32_t)__popc(ne[k]), (uint32_t)N, 33);
+                    const uint64_t multi = multi2 | nan0[k];
                     fmk[k] = never_flag ? 0ull : (force_slow ? ~0ull : multi);
                     any_multi |= fmk[k];
                 }
@@ -406,12 +390,10 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
             // More than one level attains S in EITHER element of the lane: every mask has at most N bits (the level that
             // attains S clears its own, unless no cost is a number: nan0), so the two counts sum to 2 N exactly when both are N
             // -- v_bcnt accumulates, one compare instead of two.  The partner of a tie is re-solved with it: the same answer.
-            uint64_t multi2 = 0;
-            if constexpr (kK1Trim) multi2 = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[0]) + (uint32_t)__popc(ne[NE - 1]), 2u * N, 33);
+            const uint64_t multi2 = __builtin_amdgcn_uicmp((uint32_t)__popc(ne[0]) + (uint32_t)__popc(ne[NE - 1]), 2u * N, 33);
 #pragma unroll
             for (int k = 0; k < NE; ++k) {
-                // more than one level attains S
-                const uint64_t multi = kK1Trim ? (multi2 | nan0[k]) : __builtin_amdgcn_uicmp((uint32_t)__popc(ne[k]), (uint32_t)N, 33);
+                const uint64_t multi = multi2 | nan0[k];
                 // The gap sits at the float's own bit positions [31:21]: compare bit patterns directly.
                 // fl(dL + pen) can meet fl(dR + pen) only if dL - dR <= ulp(S) <= 2^-22 S.  The test
                 // (word & 0xffe00000) <= bits(2^-20 S) is implied by word <= bits(2^-19 S) without the mask
@@ -420,7 +402,7 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
                 const uint64_t lr_close = __builtin_amdgcn_uicmp(pk[k], thr, 37);
                 // ranks need N + 1 <= 13 bits, the gap sits above bit 21 and bits 15 .. N + 1 are zero: where only the low
                 // half of the word leaves (the index stores below) the mask is not needed
-                rank[k] = (kK1Trim && !EXTRA) ? pk[k] : pk[k] & ((2u << N) - 1u);
+                rank[k] = !EXTRA ? pk[k] : pk[k] & ((2u << N) - 1u);
                 fm[k] = never_flag ? 0ull : (force_slow ? ~0ull : (multi | lr_close));
             }
             uint64_t any_flag = 0;
@@ -446,29 +428,17 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
                 }
             }
             if (full) {
-                if constexpr (NE == 4) {
-                    uint2 pk2;
-                    pk2.x = rank[0] | (rank[1] << 16);
-                    pk2.y = rank[2] | (rank[3] << 16);
-                    *reinterpret_cast<uint2 *>(out_idx + o) = pk2;
-                    if (EXTRA) {
-                        if (out_zhat) *reinterpret_cast<float4 *>(out_zhat + o) = make_float4(zh[0], zh[1], zh[2], zh[3]);
-                        if (out_bits) *reinterpret_cast<float4 *>(out_bits + o) = make_float4(bt[0], bt[1], bt[2], bt[3]);
-                    }
+                if constexpr (!EXTRA) {
+                    // the low halves of both words as one: v_perm_b32 (bytes 0, 1 of rank[0]; 4, 5 = bytes 0, 1 of rank[1])
+                    const uint32_t two = __builtin_amdgcn_perm(rank[NE - 1], rank[0], 0x05040100u);
+                    if constexpr (BUF)
+                        __builtin_amdgcn_raw_buffer_store_b32(two, orsrc, (uint32_t)(2 * (base + i0)), plane_off, 0);
+                    else
+                        store_idx2<false>(reinterpret_cast<uint32_t *>(out_idx + o), two);
                 } else {
-                    if constexpr (kK1Trim && !EXTRA) {
-                        // the low halves of both words as one: v_perm_b32 (bytes 0, 1 of rank[0]; 4, 5 = bytes 0, 1 of rank[1])
-                        const uint32_t two = __builtin_amdgcn_perm(rank[NE - 1], rank[0], 0x05040100u);
-                        if constexpr (BUF)
-                            __builtin_amdgcn_raw_buffer_store_b32(two, orsrc, (uint32_t)(2 * (base + i0)), plane_off, 0);
-                        else
-                            store_idx2<false>(reinterpret_cast<uint32_t *>(out_idx + o), two);
-                    } else
                     store_idx2<false>(reinterpret_cast<uint32_t *>(out_idx + o), rank[0] | (rank[1] << 16));
-                    if (EXTRA) {
-                        if (out_zhat) *reinterpret_cast<float2 *>(out_zhat + o) = make_float2(zh[0], zh[1]);
-                        if (out_bits) *reinterpret_cast<float2 *>(out_bits + o) = make_float2(bt[0], bt[1]);
-                    }
+                    if (out_zhat) *reinterpret_cast<float2 *>(out_zhat + o) = make_float2(zh[0], zh[1]);
+                    if (out_bits) *reinterpret_cast<float2 *>(out_bits + o) = make_float2(bt[0], bt[1]);
                 }
             } else {
 #pragma unroll
@@ -476,10 +446,10 @@ k_quant_fast(const float *__restrict__ mu, const float *__restrict__ sg, long n_
                     if (i0 + k < n_per_ch) {
                         // BUF: the short store through the descriptor as well -- a plain one keeps a 64-bit pointer per lane
                         // alive that every lambda advances, whether a lane stores through it or not
-                        if constexpr (kK1Trim && !EXTRA && BUF)
+                        if constexpr (!EXTRA && BUF)
                             __builtin_amdgcn_raw_buffer_store_b16((uint16_t)rank[k], orsrc, (uint32_t)(2 * (base + i0 + k)), plane_off, 0);
                         else
-                        out_idx[o + k] = (uint16_t)rank[k];
+                            out_idx[o + k] = (uint16_t)rank[k];
                         if (EXTRA) {
                             if (out_zhat) out_zhat[o + k] = zh[k];
                             if (out_bits) out_bits[o + k] = bt[k];
@@ -541,10 +511,11 @@ constexpr int kHullThreads = VBQ_HULL_THREADS;
 #define VBQ_HULL_COPIES 16
 #endif
 // Records in flight per stage of K1t's position phase (10: all of an element's at once; 2, 5 and 10 measured alike, 113 us
-// against 118 us for 0, one position after the other as sweep_position has it)
+// against 118 us for one position after the other as sweep_position has it)
 #ifndef VBQ_K1T_STAGE
 #define VBQ_K1T_STAGE 10
 #endif
+static_assert(VBQ_K1T_STAGE >= 1, "K1t's stage loop advances by VBQ_K1T_STAGE records: 0 would never end");
 constexpr int kHullKeys = 2048;         // 16 octaves of 128 buckets
 constexpr int kFixQueue = 192;          // K1t: deferred fix-ups per workgroup (about ten are expected per 2 300 elements)
 struct HullSweep : SweepTable<32, kHullKeys> {};     // keys = float bits >> 16: sign, exponent, 7 mantissa bits
@@ -749,11 +720,10 @@ k_level_counts_hull(const float *__restrict__ mu, const float *__restrict__ sg, 
             float Tn[N];
             sweep_thresholds<N>(du[k], Tn);
             fix[k] = __builtin_amdgcn_ballot_w64(!(sweep_max_du<N>(du[k]) < kSweepBig)) | (force_slow ? ~0ull : 0ull);
-#if VBQ_K1T_STAGE
             // The positions in stages (sweep_position taken apart, as K1e does): all ten bucket reads, then the records
             // VBQ_K1T_STAGE at a time, the compares and bands behind them, the ten counter updates last -- LDS returns in
-            // order, so a read issued behind an atomic waits for it, and one position after the other drained the counter at
-            // every read.
+            // order, so a read issued behind an atomic waits for it, and one position after the other would drain the
+            // counter at every read.
             uint32_t apos[N];
 #pragma unroll
             for (int n = 0; n < N; ++n) apos[n] = lut[sweep_bucket<16>(Tn[n], key0, nkeys)];
@@ -775,17 +745,6 @@ k_level_counts_hull(const float *__restrict__ mu, const float *__restrict__ sg, 
             }
 #pragma unroll
             for (int n = 0; n < N; ++n) atomicAdd(&H[((uint32_t)n * LB + apos[n]) * (unsigned)KC + copy], vinc);
-#else
-#pragma unroll
-            for (int n = 0; n < N; ++n) {
-                float4 nb;
-                const uint32_t a = sweep_position<16>(Tn[n], key0, nkeys, lut, rec, nb);
-                const float G = sweep_band(Tn[n], n, du[k][n]);
-                const float dist = sweep_distance(Tn[n], nb);
-                fix[k] |= __builtin_amdgcn_ballot_w64(dist <= G);
-                atomicAdd(&H[((uint32_t)n * LB + a) * (unsigned)KC + copy], vinc);
-            }
-#endif
             fix[k] &= __builtin_amdgcn_ballot_w64(valid);      // lane masks are scalars: no branch inside the block
         }
         uint64_t any_fix = 0;
@@ -1223,7 +1182,7 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
 
 
 // =====================================================================================================================
-// K1p: the solve for ONE to FOUR lambdas per call -- the literal signature quantize(mu, sigma, lmbda) -- with exact pruning.
+// K1p: the solve for ONE or TWO lambdas per call -- the literal signature quantize(mu, sigma, lmbda) -- with exact pruning.
 //
 // Per bit level only the NEARER neighbour's distortion is formed (one exact quotient: the cost is monotone in |P - z| and the
 // two sides of a level share their penalty, so min(cost L_n, cost R_n) = fl(min(dL, dR) + pen_n)); per lambda the running
@@ -1234,7 +1193,9 @@ k_quant_hull_idx(const float *__restrict__ mu, const float *__restrict__ sg, lon
 // keeps the level unless fl(dR + pen) < fl(dL + pen)), and the lanes in which several levels attained S -- the
 // reference's candidate order [L_0..L_N, R_1..R_N] decides there -- take the literal scan.  No tie certificate, no
 // precondition on the penalties: every comparison is one the reference makes.
-constexpr int kPrunedMaxL = 2;                       // measured: 1 lambda 15-43 % faster than k_quant_fast, 2 equal, 4 slower (142 against 112 us)
+// One or two lambdas: the instances launch_quant_pruned builds.  Measured: 1 lambda 15-43 % faster than k_quant_fast, 2 equal,
+// 4 slower (142 against 112 us).
+constexpr int kPrunedMaxL = 2;
 template <int N, int LL>
 __global__ void __launch_bounds__(256, 4)
 k_quant_pruned(const float *__restrict__ mu, const float *__restrict__ sg, long n_per_ch, long ch_stride, int C,
@@ -1406,13 +1367,13 @@ k_quant_pruned(const float *__restrict__ mu, const float *__restrict__ sg, long 
 void quant_fast_grid(int64_t n_per_ch, int32_t n_ch, int wg_per_cu, int reserved, bool counting, int64_t *out_gx, bool *out_resident) {
     const int64_t nquads = (n_per_ch + kFastNE - 1) / kFastNE;
     int64_t gx = (nquads + kFastThreads - 1) / kFastThreads;
-    // A RESIDENT grid: 4 workgroups per CU (110 VGPRs: four waves per SIMD; 3 with NE=4) that stay from start to end, every
+    // A RESIDENT grid: 4 workgroups per CU (110 VGPRs: four waves per SIMD) that stay from start to end, every
     // channel's share balanced, the issue priority rotating over them (vbq_common.h) -- 335 us on Kodak-24 against 358 us
     // for 18 short-lived workgroups per channel and 394 us for the same resident grid without the rotation.
     // wg_per_cu < 4 leaves LDS and wave slots for a kernel of another stream (K2 overlapping this launch); 5 is taken as 4
     // (a fifth workgroup per CU would only wait for a slot: 444 us).
     const bool explicit_wgs = wg_per_cu >= 1 && wg_per_cu <= 5;
-    const int fit = kFastNE == 4 ? 3 : 4;
+    const int fit = 4;
     // Slots the caller reserves for a kernel of another stream (`reserved_workgroups` of the entry points: the overlapped
     // all-reduce of a sharded build).
     // A resident workgroup that finds its slot taken starts only when another one has FINISHED ALL its iterations -- up to twice
@@ -1470,7 +1431,7 @@ int launch_quant_fast(const float *mu, const float *sg, int64_t n_per_ch, int64_
     else if (out_zhat || out_bits)
         hipLaunchKernelGGL((k_quant_fast<N, 1>), grid, block, 0, st, mu, sg, (long)n_per_ch, (long)ch_stride, (int)n_ch, table,
                            lam, len, (int)L, out_idx, out_zhat, out_bits, (long)E, vec_ok, dbg, level_counts);
-    else if (kK1Trim && index_planes_within_4gb(L, E))
+    else if (index_planes_within_4gb(L, E))
         hipLaunchKernelGGL((k_quant_fast<N, 0, true>), grid, block, 0, st, mu, sg, (long)n_per_ch, (long)ch_stride, (int)n_ch, table,
                            lam, len, (int)L, out_idx, out_zhat, out_bits, (long)E, vec_ok, dbg, level_counts);
     else
@@ -1482,7 +1443,7 @@ int launch_quant_fast(const float *mu, const float *sg, int64_t n_per_ch, int64_
 
 int pruned_max_lambdas() { return kPrunedMaxL; }
 
-// Host side of K1p: one to four lambdas, indices the only output.  Returns 1 when the call is not its kind.
+// Host side of K1p: one or two lambdas, indices the only output.  Returns 1 when the call is not its kind.
 template <int N>
 int launch_quant_pruned(const float *mu, const float *sg, int64_t n_per_ch, int64_t ch_stride, int32_t n_ch, const float *table,
                         const Lambdas32 &lam, const float *len, int32_t L, uint16_t *out_idx, int64_t E, int vec_ok, hipStream_t st) {
@@ -1501,7 +1462,7 @@ int launch_quant_pruned(const float *mu, const float *sg, int64_t n_per_ch, int6
                            table, lam, len, out_idx, (long)E, vec_ok, dbg);                                            \
         break;
     switch (L) {
-        VBQ_PRUNED_CASE(1) VBQ_PRUNED_CASE(2) VBQ_PRUNED_CASE(3) VBQ_PRUNED_CASE(4)
+        VBQ_PRUNED_CASE(1) VBQ_PRUNED_CASE(2)
         default: return 1;
     }
 #undef VBQ_PRUNED_CASE

@@ -71,21 +71,14 @@ __device__ __forceinline__ float sweep_max_du(const float (&du)[N + 1]) {
 // Bucket of a threshold: its bit pattern shifted (an arithmetic shift keeps T <= 0 negative, so one median clamps "below the
 // sweep", "above it" and the table range).
 // The median is written out: min(max(x, 0), nkeys - 1) only folds into one when the compiler can prove 0 <= nkeys - 1, and
-// from a kernel argument it cannot (it emitted v_max_i32 and v_min_i32, three 4-cycle instructions with the subtraction).
+// from a kernel argument it cannot (it emits v_max_i32 and v_min_i32, three 4-cycle instructions with the subtraction).
 // nkeys >= 2 on every table build_sweep_table accepts (vbq_sweep_host.h), so the median of { x, 0, nkeys - 1 } is the clamp.
-#ifndef VBQ_SWEEP_MED3
-#define VBQ_SWEEP_MED3 1
-#endif
 template <int SHIFT>
 __device__ __forceinline__ int sweep_bucket(float t, int key0, int nkeys) {
     const int x = ((int)__float_as_uint(t) >> SHIFT) - key0;
-#if VBQ_SWEEP_MED3
     int r;
     asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(nkeys - 1));
     return r;
-#else
-    return min(max(x, 0), nkeys - 1);
-#endif
 }
 
 // Position of a threshold in the sorted sweep, a = #{ l : val_(l) < T }: the count of sweep points below its bucket, then the
