@@ -162,6 +162,7 @@ class Inputs:
         self.ladder = bitstream.palette_ladder(ls, (0, 1))
         self.given = None
         self.form = "numpy"
+        self.image_form = None
 
     def _copy(self):
         new = object.__new__(Inputs)
@@ -175,6 +176,39 @@ class Inputs:
         new.files = [(torch.from_numpy(m).cuda(), torch.from_numpy(lv).cuda()) for m, lv in self.files]
         new.form, new.tag = "device", self.tag + "/device"
         return new
+
+    def in_form(self, form, which, values_only=False):
+        """The same inputs with one group of arrays in a form of tests/input_forms.py: `which` is "files" (the latents), "cls2",
+        "cls3", "X" (the image the WITH_VAE probes encode) or "all".  values_only: the PLAIN form (C-contiguous NumPy; device
+        tensors when these inputs are on the device) of form.values(a) -- what the answer under the form is held against.
+        The budgets, lambdas and palettes stay as they are."""
+        import input_forms as IF
+        assert which in ("files", "cls2", "cls3", "X", "all"), which
+        plain = IF.DEV_PLAIN if self.form == "device" else IF.NP_PLAIN
+
+        def host(a):
+            return np.asarray(a.detach().cpu() if hasattr(a, "detach") else a)
+
+        def to(a, base=plain):
+            a = host(a)
+            if not form.applies(a):
+                return base.make(a)
+            return base.make(form.values(a)) if values_only else form.make(a)
+        new = self._copy()
+        if which in ("files", "all"):
+            new.files = [(to(m), to(lv)) for m, lv in self.files]
+        for name in ("cls2", "cls3"):
+            if which in (name, "all"):
+                setattr(new, name, [to(c, IF.NP_PLAIN) for c in getattr(self, name)])
+        if which in ("X", "all") and form.family != "device":
+            new.image_form = (lambda a: IF.NP_PLAIN.make(form.values(a))) if values_only else \
+                (lambda a: form.make(a) if form.applies(a) else a)
+        new.tag = f"{self.tag}/{form.name}:{which}" + ("/values" if values_only else "")
+        return new
+
+    def image(self, X):
+        """The image a WITH_VAE probe encodes, in the form in_form(form, "X") asked for."""
+        return X if self.image_form is None else self.image_form(np.asarray(X))
 
     def reading(self, given, tag):
         """The same inputs for the reader probes, with the files they read given."""
@@ -225,7 +259,10 @@ class StubVAE:
 
     def encode(self, X):
         import torch
-        X = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.asarray(X, np.float32)).cuda()
+        # (an image in any form -- a strided or reversed array, a list, a CPU tensor -- as one dense f32 device tensor, so that
+        # the mean is the same reduction whatever the form)
+        X = X.detach() if isinstance(X, torch.Tensor) else torch.from_numpy(np.array(X, np.float32, order="C"))
+        X = X.to("cuda", torch.float32).contiguous()
         return self.means + X.mean(), self.logvars
 
     def decode(self, Z):
@@ -282,13 +319,18 @@ def _one(i):
 
 def _flat(i):
     """File 0 as rows [B, C] of means and standard deviations, NumPy."""
-    m, lv = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in _one(i))
+    m, lv = (np.asarray(a.detach().cpu() if hasattr(a, "cpu") else a) for a in _one(i))
     return m.reshape(-1, C), np.exp(0.5 * lv.reshape(-1, C).astype(np.float64)).astype(np.float32)
+
+
+def _lead(a):
+    """`a` with a leading axis of one (a nested list gets it as a list)."""
+    return [a] if isinstance(a, list) else a[None]
 
 
 def p_latents(q, i):
     m, lv = _one(i)
-    out = q.compress_latents(m[None], lv[None], i.lambs)
+    out = q.compress_latents(_lead(m), _lead(lv), i.lambs)
     return tuple(np.asarray(out[k][l]) for k in ("Z_hat", "raw_num_bits", "num_bits_cl", "num_bits") for l in out[k])
 
 
@@ -498,7 +540,7 @@ def v_replay(q, i, shape=IMAGE_SHAPES[0]):
     X, vae = _image_probe(shape)
     outs = []
     for x in (X, 0.5 * X):                                        # the capture, then a replay of it with another image
-        out, (sums, sums_cl, u8) = q.compress_replay(x, vae, i.lambs)
+        out, (sums, sums_cl, u8) = q.compress_replay(i.image(x), vae, i.lambs)
         outs.append((tuple(np.array(out[k][l]) for k in ("Z_hat", "raw_num_bits", "num_bits_cl", "num_bits", "X_hat") for l in out[k]),
                      sums, sums_cl, u8))
     return tuple(outs)
@@ -506,13 +548,13 @@ def v_replay(q, i, shape=IMAGE_SHAPES[0]):
 
 def v_compress(q, i, shape=IMAGE_SHAPES[0]):
     X, vae = _image_probe(shape)
-    out = q.compress(X, vae, i.lambs)
+    out = q.compress(i.image(X), vae, i.lambs)
     return tuple(np.asarray(out[k][l]) for k in ("Z_hat", "raw_num_bits", "num_bits_cl", "num_bits", "X_hat") for l in out[k])
 
 
 def v_bytes(q, i, shape=IMAGE_SHAPES[0]):
     X, vae = _image_probe(shape)
-    data = q.compress_to_bytes(X, vae, i.lamb, segment=SEGMENT)
+    data = q.compress_to_bytes(i.image(X), vae, i.lamb, segment=SEGMENT)
     return data, q.decompress(data, vae)
 
 

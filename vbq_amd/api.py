@@ -23,7 +23,11 @@ def gaussian_table(scale, N: int = 10, loc=0.0) -> np.ndarray:
 
 # Tables already on the device (level-major and rank order), with the verdict of the monotonicity check: a sweep calls quantize()
 # many times with ONE table, and preparing it costs an upload, and the check a pass over it.
-#   torch tensor   keyed by identity, storage pointer and version counter: an in-place edit or a new tensor is prepared again.
+#   device tensor  nothing of its content is kept: the rank-order copy is gathered from the tensor on every call (one launch, no
+#                  synchronisation).  The version counter does not see an edit through .data, a DLPack alias or a kernel's raw
+#                  pointer, so it cannot vouch for a copy; it only keys the VERDICT of the check (identity, storage pointer,
+#                  version, shape, strides), and is never read on an inference tensor, which has none.
+#   CPU tensor     taken as the NumPy array that shares its memory (an edit of that array moves no version counter either).
 #   NumPy array    has no version counter -- an edit in place is invisible to any identity key.  Keyed by (data pointer, shape,
 #                  dtype); on a key hit a strided 256-element sample is compared first and then the WHOLE content against what was
 #                  uploaded (xxh3 digest when xxhash is importable, else np.array_equal against a kept host copy: 0.1-0.2 ms for
@@ -71,32 +75,53 @@ def _check_monotone(host: np.ndarray, C: int, T: int):
         raise ValueError("table is not monotone in xi")
 
 
-def _upload(table, C: int, N: int, dev):
+_SLOTS = {}
+
+
+def _slot_of_rank(N: int, dev) -> torch.Tensor:
+    """int64 [T] on `dev`: the level-major slot of every rank.  Constant per (N, device) and kept, so that a call with a device
+    table uploads nothing."""
+    key = (N, str(dev))
+    if key not in _SLOTS:
+        _SLOTS[key] = torch.from_numpy(np.argsort(rank_of_slot(N))).to(dev)
+    return _SLOTS[key]
+
+
+def _upload(table: np.ndarray, C: int, N: int, dev):
     T = table_size(N)
-    tab_t = (torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32)) if not isinstance(table, torch.Tensor) else table)
-    tab_t = tab_t.to(dev, torch.float32).reshape(C, T).contiguous()
-    slot_of_rank = torch.from_numpy(np.argsort(rank_of_slot(N))).to(dev)
-    return tab_t, tab_t[:, slot_of_rank].contiguous()        # rank order == sorted order for a monotone table
+    tab_t = ops.host_tensor(np.asarray(table, dtype=np.float32)).to(dev).reshape(C, T).contiguous()
+    return tab_t, tab_t.index_select(1, _slot_of_rank(N, tab_t.device))        # rank order == sorted order for a monotone table
 
 
 def _device_table(table, C: int, N: int, dev, validate: bool):
-    """(level-major, rank-order) f32 [C, T] copies on `dev`; raises ValueError unless every channel is non-decreasing in xi
-    (tf.searchsorted is undefined otherwise, quantizer.py:135).  Uploaded once per table tensor / table content, checked once
-    when `validate` asks for it."""
+    """(level-major, rank-order) f32 [C, T] tensors on `dev`; raises ValueError unless every channel is non-decreasing in xi
+    (tf.searchsorted is undefined otherwise, quantizer.py:135).  The pair follows the table's CONTENT on every call: a NumPy
+    array or CPU tensor is uploaded once per content (compared on every call), a device tensor is gathered anew.  The check runs
+    once per content (host tables) or once per (tensor, version counter) (device tables) when `validate` asks for it."""
     T = table_size(N)
     meta = (C, N, str(dev))
     if len(_CHECKED) > 64:
         _CHECKED.clear()
-    if isinstance(table, torch.Tensor):
-        key = ("t", id(table), table.data_ptr(), table._version, tuple(table.shape), str(table.device))
-        hit = _CHECKED.get(key)
-        if hit is not None and hit[0]() is table and hit[2] == meta and (hit[3] or not validate):
-            return hit[1]
-        pair = hit[1] if hit is not None and hit[0]() is table and hit[2] == meta else _upload(table, C, N, dev)
+    if isinstance(table, torch.Tensor) and table.device.type != "cpu":
+        # The level-major copy is the caller's tensor itself when that is f32 and dense; the rank-order copy is gathered from
+        # it again on EVERY call -- one launch on the current stream, no synchronisation -- so the pair always holds what the
+        # tensor holds now.  Only the verdict of the monotonicity check is kept.  An inference tensor has no version counter
+        # (reading it raises) and cannot be edited in place outside inference mode: it is keyed without one.
+        t = table.detach()
+        tab_t = t.to(dev, torch.float32).reshape(C, T).contiguous()
+        pair = (tab_t, tab_t.index_select(1, _slot_of_rank(N, tab_t.device)))
         if validate:
-            _check_monotone(pair[0].cpu().numpy(), C, T)
-        _CHECKED[key] = (weakref.ref(table), pair, meta, bool(validate))
+            version = None if table.is_inference() else table._version
+            key = ("t", id(table), table.data_ptr(), version, tuple(table.shape), str(table.device), tuple(table.stride()))
+            hit = _CHECKED.get(key)
+            if not (hit is not None and hit[0]() is table and hit[1] == meta):
+                _check_monotone(tab_t.cpu().numpy(), C, T)
+                _CHECKED[key] = (weakref.ref(table), meta)
         return pair
+    if isinstance(table, torch.Tensor):
+        # a CPU tensor takes the content path of a NumPy array: the array shares the tensor's memory and no version counter is read
+        t = table.detach()
+        table = (t if t.dtype in (torch.float32, torch.float64, torch.float16) else t.to(torch.float32)).numpy()
     table = np.asarray(table)
     if not table.flags.c_contiguous:
         table = np.ascontiguousarray(table)                  # (a fresh array per call: takes the content check, never the identity path)
@@ -146,7 +171,12 @@ def quantize(mu, sigma, lmbda: Union[float, Sequence[float]], *, table=None, pri
                 layout -- what the kernels write; a caller that goes on to a histogram, a lookup or the entropy coder (all of
                 which take planes) saves the transpose back, half the time of a channel-last sweep.
     return_indices=False with return_values / return_bits: only those are produced (and returned).
-    validate  : check (once per table tensor / table content) that the table is monotone in xi; False skips the check.
+    validate  : check that the table is monotone in xi; False skips the check.  The table's values are those it holds at the
+                call, whatever wrote them.  The check runs once per content for a NumPy array or CPU tensor, and once per
+                (tensor, version counter) for a device tensor: an edit the counter cannot see (through .data, a DLPack alias,
+                a kernel writing through the raw pointer) is re-read but not re-validated.
+    mu, sigma, table and lengths may have any layout (slices, transposes, reversed or read-only arrays) and any real dtype
+    (they are converted to f32); tensors that require grad are detached.
     Returns rank indices (uint16; position in the sorted table) with the lambda axis in front and, if asked, the code-point
     values / code lengths (f32).  Torch in -> device tensors out; NumPy in -> NumPy out.
 
@@ -168,8 +198,8 @@ def quantize(mu, sigma, lmbda: Union[float, Sequence[float]], *, table=None, pri
         raise ValueError("nothing to return")
     dev = torch.device("cuda", torch.cuda.current_device())
     was_np = not isinstance(mu, torch.Tensor)
-    mu_t = (torch.from_numpy(np.ascontiguousarray(mu)) if was_np else mu).to(dev, torch.float32)
-    sg_t = (torch.from_numpy(np.ascontiguousarray(sigma)) if not isinstance(sigma, torch.Tensor) else sigma).to(dev, torch.float32)
+    mu_t = (ops.host_tensor(mu) if was_np else mu.detach()).to(dev, torch.float32)
+    sg_t = (ops.host_tensor(sigma) if not isinstance(sigma, torch.Tensor) else sigma.detach()).to(dev, torch.float32)
     if mu_t.shape != sg_t.shape:
         raise ValueError(f"mu {tuple(mu_t.shape)} and sigma {tuple(sg_t.shape)} differ in shape")
     C = 1 if mu_t.dim() == 1 else (mu_t.shape[1] if layout == "bc" else mu_t.shape[0])
@@ -183,8 +213,7 @@ def quantize(mu, sigma, lmbda: Union[float, Sequence[float]], *, table=None, pri
     tab_t, srt_t = _device_table(table, C, N, dev, validate)
     len_t = None
     if lengths is not None:
-        len_t = (torch.from_numpy(np.ascontiguousarray(lengths)) if not isinstance(lengths, torch.Tensor) else lengths)
-        len_t = len_t.to(dev, torch.float32)
+        len_t = (ops.host_tensor(lengths) if not isinstance(lengths, torch.Tensor) else lengths.detach()).to(dev, torch.float32)
     L = len(lambdas)
     channel_last = layout == "bc" and mu_t.dim() == 2 and C > 1 and mu_t.shape[0] > 0
     if channel_last:

@@ -31,6 +31,14 @@ def _host(a):
     return _to_numpy(a)
 
 
+def _host_samples(samples):
+    """The samples of a `fit` on the host, in the dtype the kernels bin them in: a list (of Python floats) and float16 become
+    float32 as _dev_f32 makes them, so that min, max and delta are computed on the values that are binned; float64 stays (and is
+    refused there)."""
+    s = _host(samples)
+    return s.astype(np.float32) if isinstance(samples, (list, tuple)) or s.dtype == np.float16 else s
+
+
 def _decode(vae, Z, like):
     """`vae.decode` of NumPy latents -> NumPy; a VAE whose encoder returned torch tensors gets them back on that device."""
     return _host(vae.decode(torch.from_numpy(np.ascontiguousarray(Z)).to(like.device) if isinstance(like, torch.Tensor) else Z))
@@ -76,7 +84,7 @@ class UniformQuantizer:
 
     def fit(self, samples, add_n_smoothing=1.):
         _require_finite(samples, allow_inf=True)
-        s = np.asarray(samples)
+        s = _host_samples(samples)
         mn, mx = np.min(s), np.max(s)
         N = self.quantization_levels
         delta = (mx - mn) / N
@@ -140,7 +148,7 @@ class ChannelwiseSimpleQuantizer:
     def fit_latents(self, posterior_means, add_n_smoothing):
         C_ = np.shape(posterior_means)[-1]
         assert C_ == self.num_channels
-        means = np.reshape(_host(posterior_means), (-1, C_))
+        means = np.reshape(_host_samples(posterior_means), (-1, C_))
         for c, q in enumerate(self._quantizers):
             q.fit(means[:, c], add_n_smoothing)
         self.code_points = np.array([q.code_points for q in self._quantizers])
@@ -151,7 +159,7 @@ class ChannelwiseSimpleQuantizer:
         self.fit_latents(posterior_means, add_n_smoothing)
 
     def compress_latents(self, posterior_means):
-        pm = _host(posterior_means)
+        pm = _host_samples(posterior_means)
         C_ = pm.shape[-1]
         assert C_ == self.num_channels
         means = np.reshape(pm, (-1, C_))
@@ -189,7 +197,7 @@ class ChannelwiseSimpleQuantizerWrapper:
     def compress(self, X, vae, quantization_levels, clip=True):
         assert quantization_levels == self.quantization_levels
         posterior_means, _ = vae.encode(X)
-        pm = _host(posterior_means)
+        pm = _host_samples(posterior_means)
         output = {"Z_hat": {}, "num_bits": {}}
         for l, q in zip(self.quantization_levels, self._quantizers):
             tmp = q.compress_latents(pm)
@@ -212,7 +220,7 @@ class OptimalKmeansQuantizer(KmeansQuantizer):
 
     def fit(self, samples, add_n_smoothing=1.):
         from . import kmeans1d
-        s = np.asarray(_host(samples) if isinstance(samples, torch.Tensor) else samples)
+        s = _host_samples(samples)
         got = kmeans1d.fit_channels(s.reshape((-1, 1)), [self.quantization_levels], add_n_smoothing)[0]
         self.code_points = got.code_points[0]
         self.code_lengths = got.code_lengths[0]
@@ -231,7 +239,7 @@ class ChannelwiseOptimalKmeansWrapper:
         from . import kmeans1d
         C_ = np.shape(posterior_means)[-1]
         assert C_ == self.num_channels
-        pm = posterior_means if isinstance(posterior_means, torch.Tensor) else _host(posterior_means)
+        pm = posterior_means if isinstance(posterior_means, torch.Tensor) else _host_samples(posterior_means)
         fits = kmeans1d.fit_channels(pm.reshape((-1, C_)), list(self.quantization_levels), add_n_smoothing)
         self.code_points = {l: f.code_points for l, f in zip(self.quantization_levels, fits)}
         self.code_lengths = {l: f.code_lengths for l, f in zip(self.quantization_levels, fits)}

@@ -130,9 +130,9 @@ class RansCodec:
         """allow_zero=True accepts zero entries (`exact_frequencies`: a table fitted to the data it codes).  Such a table
         codes only symbols whose entry is nonzero; every entry must then stay below 2**15.  segment=None: a codec for the
         interleaved layout alone (the calls that cut streams into segments then raise ValueError)."""
-        f = freq if isinstance(freq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(freq, dtype=np.uint16)))
         T = ops.table_size(N)
-        self.freq_host = f.cpu().reshape(-1, T)
+        # the codec's own copy: a later edit of `freq` is not its table (the device copy is made once)
+        self.freq_host = _freq_host(freq).reshape(-1, T).clone()
         sums = self.freq_host.to(torch.int64).sum(dim=1)
         if allow_zero:
             if not bool(torch.all(sums == (1 << PROB_BITS))) or int(self.freq_host.to(torch.int64).max()) >= (1 << PROB_BITS):
@@ -372,7 +372,7 @@ class MappedRansCodec(RansCodec):
     freq[cls[i], s].  Words and sizes have the layout of RansCodec, so its pack / unpack calls serve unchanged."""
 
     def __init__(self, freq, N: int = 10, segment: int = DEFAULT_SEGMENT):
-        f = freq if isinstance(freq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(freq, dtype=np.uint16)))
+        f = _freq_host(freq)
         if f.dim() != 3 or not 1 <= f.shape[0] <= MAX_CLASSES or f.shape[2] != ops.table_size(N):
             raise ValueError(f"freq must be [P, S, {ops.table_size(N)}] with 1 <= P <= {MAX_CLASSES}, got {tuple(f.shape)}")
         super().__init__(f, N=N, segment=int(segment))                   # (rows checked there; freq_host is [P * S, T])
@@ -460,3 +460,15 @@ class MappedRansCodec(RansCodec):
     def decode_packed(self, payload, sizes, cls, n: int) -> torch.Tensor:
         """vbq_rans_unpack_u16 + the mapped decoder, one status word for both: u16 indices [S, n]."""
         return super().decode_packed(payload, sizes, int(n), _cls=cls)
+
+
+def _freq_host(freq) -> torch.Tensor:
+    """A frequency table -- tensor on any device, NumPy array of any layout or integer dtype, nested lists -- as a u16 CPU
+    tensor; ValueError for entries that are not integers in [0, 65535]."""
+    f = freq.detach().cpu() if isinstance(freq, torch.Tensor) else ops.host_tensor(np.asarray(freq))
+    if f.dtype != torch.uint16:
+        wide = f.to(torch.int64)
+        if f.dtype.is_floating_point or f.dtype == torch.bool or bool(((wide < 0) | (wide > 0xFFFF)).any()):
+            raise ValueError(f"frequencies must be integers in [0, 65535], got {f.dtype}")
+        f = wide.to(torch.uint16)
+    return f

@@ -138,7 +138,7 @@ def prediction_ranks(emb, analogies_id):
     V, K = e.shape
     if an_np.size and (an_np.min() < 0 or an_np.max() >= V):
         raise IndexError("analogy word id out of range")          # NumPy fancy indexing raises too
-    an = torch.from_numpy(np.ascontiguousarray(an_np, dtype=np.int32)).to(e.device)
+    an = ops.host_tensor(np.asarray(an_np, dtype=np.int32)).to(e.device)
     Q = an.shape[0]
     out = torch.empty(Q, dtype=torch.int64, device=e.device)
     if Q == 0:
@@ -231,7 +231,7 @@ def default_segment(row_length: int) -> int:
 def _file_args(means, codepoints, segment):
     """(code book f64 [T], N, shape, n coordinates, segment) of a compressed file, validated."""
     from . import bitstream as bs, tables
-    cp = np.asarray(codepoints, dtype=np.float64).reshape(-1)
+    cp = np.asarray(_host_array(codepoints), dtype=np.float64).reshape(-1)
     N = int(np.log2(cp.size + 1)) - 1
     if not 1 <= N <= bs.MAX_N or cp.size != tables.table_size(N):
         raise ValueError(f"a code book of {cp.size} points: need 2^(N+1) - 1 of them with N in 1..{bs.MAX_N}")
@@ -321,14 +321,14 @@ def compress_to_budget(means, stds, codepoints, max_bytes, *, betas=None, segmen
 def _row_ids(ids, V: int) -> np.ndarray:
     """The ids of a `rows` call as int64 [n] on the host: ValueError unless one-dimensional, IndexError for ids that are not
     integers or lie outside [0, V)."""
-    ids = np.asarray(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids)
+    ids = _host_array(ids)
     if ids.ndim != 1:
         raise ValueError(f"ids must be one-dimensional, got shape {ids.shape}")
     if ids.size and ids.dtype.kind not in "iu":
         raise IndexError(f"row ids must be integers, got {ids.dtype}")
-    ids = ids.astype(np.int64)
-    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= V):
-        raise IndexError(f"row {int(ids[(ids < 0) | (ids >= V)][0])} outside [0, {V})")
+    # (the range is checked on the dtype the ids came in, before the cast to int64: a uint64 id of 2**63 or more would turn
+    # negative in it)
+    ids = _int64_ids(ids, V, padding=False)
     return ids
 
 
@@ -482,6 +482,11 @@ def most_similar(emb, queries, k: int = 10, metric: str = "cosine", exclude=None
     return ops.topk(e, q, k, metric, exclude)
 
 
+def _host_array(a) -> np.ndarray:
+    """A tensor (any device, also one that requires grad), NumPy array or sequence as a NumPy array on the host."""
+    return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
+
+
 # ------------------------------------------------------------------------ pooled rows (vbq_bag.hip)
 _BAG_MODES = ("sum", "mean", "max")
 
@@ -492,8 +497,7 @@ def _bag_args(ids, offsets, weights, mode, V: int):
     the last bag runs to the end), or 2-D [B, L] without (row b is bag b); negative ids are padding in both forms.  ValueError
     for an unknown mode, weights with a mode other than "sum", weights that are not finite or not shaped like ids, and offsets
     that do not start at 0, decrease or exceed len(ids); IndexError for ids that are not integers or reach V."""
-    def host(a):
-        return np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+    host = _host_array
     if mode not in _BAG_MODES:
         raise ValueError(f"mode {mode!r} is none of 'sum', 'mean', 'max'")
     if weights is not None and mode != "sum":
@@ -523,16 +527,15 @@ def _bag_args(ids, offsets, weights, mode, V: int):
         offsets = np.concatenate([offsets.astype(np.int64), np.array([ids.size], np.int64)])
         if offsets[0] != 0 or (np.diff(offsets) < 0).any():
             raise ValueError(f"offsets must start at 0, never decrease and stay within len(ids) = {ids.size}")
-    ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
-    if ids.size and int(ids.max()) >= V:
-        raise IndexError(f"row {int(ids[ids >= V][0])} outside [0, {V}) (negative ids are padding)")
+    # (range before cast, as in _row_ids: an id that wrapped to a negative one would be pooled as padding)
+    ids = _int64_ids(ids, V, padding=True).reshape(-1)
     return ids, offsets, weights
 
 
 def _bag_call(call, device, args, mode, tail):
     """Uploads of `args` (what _bag_args returned), the one launch `call(ids, offsets, weights=, mode=, status=)` and the look
     at the status word -> f32 [B, *tail]."""
-    ids, offsets, weights = (None if a is None else torch.from_numpy(a).to(device) for a in args)
+    ids, offsets, weights = (None if a is None else ops.host_tensor(a).to(device) for a in args)
     status = torch.zeros(1, dtype=torch.uint32, device=device)
     out = call(ids, offsets, weights=weights, mode=mode, status=status)
     assert int(status.cpu().item()) == 0, "ids and offsets checked on the host, records validated at load: no status bit is due"
@@ -569,13 +572,10 @@ def _listed_ids(queries, ids, V: int):
             raise IndexError(f"row ids must be integers, got {ids.dtype}")
         t = ids.to(torch.int64)
     else:
-        a = np.asarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids)
+        a = _host_array(ids)
         if a.size and a.dtype.kind not in "iu":
             raise IndexError(f"row ids must be integers, got {a.dtype}")
-        a = np.ascontiguousarray(a, dtype=np.int64)
-        if a.size and int(a.max()) >= V:
-            raise IndexError(f"row {int(a[a >= V][0])} outside [0, {V}) (negative ids are padding)")
-        t = torch.from_numpy(a)
+        t = ops.host_tensor(_int64_ids(a, V, padding=True))
     qs = tuple(np.shape(queries))
     Q = 1 if len(qs) == 1 else (int(qs[0]) if qs else 0)
     if t.dim() == 1 and Q == 1:
@@ -602,7 +602,7 @@ def _scores_call(call, queries, listed, K: int, V: int, metric, device):
 def _pair_ids(a, b, V: int):
     """The ids of a `similarity` call as two int64 host arrays [P] and their common shape; IndexError unless every id is an
     integer in [0, V), ValueError for two shapes.  Needs no device."""
-    a, b = (np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x) for x in (a, b))
+    a, b = (_host_array(x) for x in (a, b))
     if a.shape != b.shape:
         raise ValueError(f"a {a.shape} and b {b.shape} differ in shape")
     return _row_ids(a.reshape(-1), V), _row_ids(b.reshape(-1), V), a.shape
@@ -662,8 +662,8 @@ def similarity(emb, a, b, metric: str = "cosine"):
     shape = _dense_shape(emb)
     a, b, out_shape = _pair_ids(a, b, shape[0])
     e = _dev(emb)
-    queries = e.index_select(0, torch.from_numpy(a).to(e.device))
-    return _dense_scores(e, shape, queries, (torch.from_numpy(b)[:, None], True), metric)[0].view(out_shape)
+    queries = e.index_select(0, ops.host_tensor(a).to(e.device))
+    return _dense_scores(e, shape, queries, (ops.host_tensor(b)[:, None], True), metric)[0].view(out_shape)
 
 
 def rerank(emb, queries, ids, k=None, metric: str = "cosine"):
@@ -683,7 +683,7 @@ def _records_args(means, codepoints, N):
     shape = tuple(int(d) for d in np.shape(means)) or (1,)
     if int(np.prod(shape)) == 0:
         raise ValueError("an empty matrix has no compressed form")
-    cp = np.asarray(codepoints.cpu().numpy() if isinstance(codepoints, torch.Tensor) else codepoints, dtype=np.float32)
+    cp = np.asarray(_host_array(codepoints), dtype=np.float32)
     K = int(np.prod(shape[1:]))
     C = K if cp.shape == (K, table_size(N)) else 1
     return cp, shape, C
@@ -872,7 +872,7 @@ class RecordEmbeddings:
         out_shape = (ids.size,) + tuple(h.shape[1:])
         if ids.size == 0:
             return torch.empty(out_shape, dtype=torch.float32, device=self.device)
-        return self._decode(torch.from_numpy(ids).to(self.device)).view(out_shape)
+        return self._decode(ops.host_tensor(ids).to(self.device)).view(out_shape)
 
     def most_similar(self, queries=None, *, ids=None, k: int = 10, metric: str = "cosine", exclude=None):
         """The k rows nearest to each query -> (ids int64 [Q, k], scores f32 [Q, k]) device tensors, as the module's
@@ -892,7 +892,7 @@ class RecordEmbeddings:
             queries = self.rows(own).reshape(own.size, K)
         q, k, exclude = _search_args(queries, K, k, metric, exclude, self.device)
         if ids is not None:
-            own = torch.from_numpy(own).to(self.device)[:, None]
+            own = ops.host_tensor(own).to(self.device)[:, None]
             exclude = own if exclude is None else torch.cat([own, exclude], dim=1)
             if exclude.shape[1] > 8:
                 raise ValueError("with ids, exclude holds at most 7 columns (the query's own row is the eighth)")
@@ -938,7 +938,7 @@ class RecordEmbeddings:
         h = self.header
         a, b, out_shape = _pair_ids(a, b, h.n_rows)
         queries = self.rows(a).reshape(a.size, h.row_length)
-        return self._scores(queries, (torch.from_numpy(b)[:, None], True), metric)[0].view(out_shape)
+        return self._scores(queries, (ops.host_tensor(b)[:, None], True), metric)[0].view(out_shape)
 
     def rerank(self, queries, ids, k=None, metric: str = "cosine"):
         """`scores(queries, ids, metric)` put into most_similar's order -> (ids int64 [Q, k or M], scores f32 [Q, k or M]) device
@@ -948,3 +948,13 @@ class RecordEmbeddings:
         listed = _listed_ids(queries, ids, self.header.n_rows)
         k = _rerank_k(k, listed[0].shape[1])
         return _rerank(*self._scores(queries, listed, metric), k)
+
+
+def _int64_ids(ids: np.ndarray, V: int, padding: bool) -> np.ndarray:
+    """Integer ids of any width as a C-contiguous int64 array, their range checked ON THE DTYPE THEY CAME IN: a uint64 id of
+    2**63 or more would turn negative in the cast -- padding where negative ids are padding.  IndexError for an id that
+    reaches V, and, unless negative ids are `padding`, for one below 0."""
+    if ids.size and (int(ids.max()) >= V or (not padding and int(ids.min()) < 0)):
+        bad = ids[(ids >= V) | (ids < 0)] if not padding else ids[ids >= V]
+        raise IndexError(f"row {int(bad.reshape(-1)[0])} outside [0, {V})" + (" (negative ids are padding)" if padding else ""))
+    return np.ascontiguousarray(ids, dtype=np.int64)

@@ -21,7 +21,7 @@ def _on_device(x):
 
 def _check_pair(img1, img2):
     """NumPy arrays -- or, for callers that already hold the images on the device, torch tensors there (no PCIe)."""
-    a, b = (x if _on_device(x) else np.asarray(x) for x in (img1, img2))
+    a, b = (x.detach() if _on_device(x) else np.asarray(x.detach() if isinstance(x, torch.Tensor) else x) for x in (img1, img2))
     if tuple(a.shape) != tuple(b.shape):
         raise RuntimeError("Input images must have the same shape (%s vs. %s)." % (tuple(a.shape), tuple(b.shape)))
     if a.ndim != 4:
@@ -42,8 +42,8 @@ def _as_f64_device(a):
     else:
         dev = ops.current_device("vbq_amd.metrics")
         if a.dtype != np.uint8:
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        u = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            return ops.host_tensor(np.asarray(a, dtype=np.float64)).to(dev)
+        u = ops.host_tensor(a).to(dev)
     out = torch.empty(u.shape, dtype=torch.float64, device=u.device)
     check(_lib.lib().vbq_u8_to_f64(ops._ptr(u), u.numel(), ops._ptr(out), ops._stream(u)), "vbq_u8_to_f64")
     return out
@@ -53,7 +53,7 @@ def mse(img1, img2):
     """img_comparison_metrics.py:6-16: mean squared difference over (H, W, C), float64 [B]."""
     a, b = _check_pair(img1, img2)
     if _is_u8(a) and _is_u8(b):
-        ta, tb = (x.contiguous() if _on_device(x) else torch.from_numpy(np.ascontiguousarray(x)).to(ops.current_device("vbq_amd.metrics")) for x in (a, b))
+        ta, tb = (x.contiguous() if _on_device(x) else ops.host_tensor(x).to(ops.current_device("vbq_amd.metrics")) for x in (a, b))
         out = torch.empty(a.shape[0], dtype=torch.int64, device=ta.device)
         n = int(np.prod(tuple(a.shape[1:])))
         check(_lib.lib().vbq_image_sqerr_u8(ops._ptr(ta), ops._ptr(tb), a.shape[0], n, ops._ptr(out), ops._stream(ta)),

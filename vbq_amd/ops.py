@@ -35,9 +35,19 @@ def current_device(who: str) -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def host_tensor(a) -> torch.Tensor:
+    """A NumPy array or sequence -> CPU tensor of the same values and dtype, whatever the array's layout: a C-contiguous
+    writable array is shared, every other one (a slice, a transpose, a reversed or a read-only array -- torch.from_numpy refuses
+    negative strides and warns about memory it may not write) is copied.  The tensor is only ever read."""
+    a = np.asarray(a)
+    if not (a.flags.c_contiguous and a.flags.writeable):
+        a = np.array(a, order="C")
+    return torch.from_numpy(a)
+
+
 def upload(a, device, dtype) -> torch.Tensor:
     """A tensor, NumPy array or sequence -> contiguous tensor of `dtype` on `device`."""
-    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+    t = a.detach() if isinstance(a, torch.Tensor) else host_tensor(a)
     return t.to(device, dtype).contiguous()
 
 

@@ -140,8 +140,7 @@ class BMSHJ2018Prior:
 
     # ---- evaluation (learned_prior.py:109-171, 235-334) ---------------------------------------
     def _x(self, inputs):
-        t = inputs if isinstance(inputs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(inputs)))
-        t = t.to(_device(), torch.float32).contiguous()
+        t = ops.upload(inputs, _device(), torch.float32)          # any layout or real dtype; a tensor that requires grad is detached
         assert t.shape[-1] == self._channels, \
             "Innermost dimension of inputs = %d, does not match number of channels = %d" % (t.shape[-1], self._channels)
         return t
@@ -196,8 +195,7 @@ class BMSHJ2018Prior:
         The reference tests |prev_loss - loss| / |loss| < tol after every step (:427) but never
         assigns prev_loss (it stays inf, :421), so its loop always runs all `its` iterations.
         That behaviour is the default here; early_stop=True applies the evidently intended rule."""
-        x = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(data)))
-        x = x.to(_device(), torch.float32).reshape(-1, self._channels).contiguous()
+        x = ops.upload(data, _device(), torch.float32).reshape(-1, self._channels).contiguous()
         x_cb = ops.transpose(x)
         beta1, beta2, eps = 0.9, 0.999, 1e-8                                     # tf.train.AdamOptimizer defaults
         weights = [w.copy() for w in self.get_weights()]
@@ -234,7 +232,7 @@ class BMSHJ2018Prior:
         # The bracket doubling below never ends for an xi outside (0, 1) (or NaN) after the float32 cast: check on the host,
         # before anything goes to the device.
         xi32 = xi.detach().to(torch.float32) if isinstance(xi, torch.Tensor) else \
-            torch.from_numpy(np.asarray(xi, dtype=np.float32))
+            ops.host_tensor(np.asarray(xi, dtype=np.float32))
         if not bool(torch.all((xi32 > 0) & (xi32 < 1))):
             raise ValueError("inverse_cdf: every xi must be finite and lie in (0, 1) as a float32")
         xi_t = self._x(xi)

@@ -413,7 +413,7 @@ class ChannelwisePriorCDFQuantizer:
 
     def _f32_dev(self, a) -> torch.Tensor:
         """A NumPy array (or anything _to_numpy takes) or a tensor as an f32 tensor on the device."""
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(_to_numpy(a))
+        t = a if isinstance(a, torch.Tensor) else ops.host_tensor(_to_numpy(a))     # any layout, read-only too: as api.quantize
         return t.to(self.device, torch.float32)
 
     def _batch_dev(self, batch_means, batch_stds):
@@ -595,7 +595,7 @@ class ChannelwisePriorCDFQuantizer:
         The dict's arrays live in the graph's static tensors: valid until the next call with the same shape.  Falls back to
         `compress` + `utils.evaluation_reads` when the VAE cannot be captured (NumPy VAEs, decoders that synchronise)."""
         from .replay import CompressReplay
-        X = np.asarray(X) if not isinstance(X, np.ndarray) else X
+        X = _to_numpy(X) if not isinstance(X, np.ndarray) else X      # (a tensor on any device, also one that requires grad)
         lambs = list(lambs)                                       # an ndarray, a tuple, ...: `list == ndarray` below would be an array
         cache = self._dev_cache.setdefault("_replays", {})
         last = self._dev_cache.get("_replay_last")                # the loop's common case: the same shape, settings and VAE as last time

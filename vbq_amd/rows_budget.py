@@ -23,10 +23,10 @@ from .tables import table_size
 
 def level_candidates(mu_t: torch.Tensor, sg_t: torch.Tensor, tab_lm: torch.Tensor, N: int):
     """Per level n = 0..N and element (r, k): the better of the two n-bit neighbours of mu (vbq_n_bit_intervals_f32) under the
-    score -0.5 * ((c - mu) / sigma)**2, float64 on the upcast float32 values; the right neighbour only when strictly better;
-    level 0 is the root table[..., 0].  Returns (scores f64 [N+1, R, K], values f32 [N+1, R, K])."""
-    R, K = mu_t.shape
-    C = tab_lm.shape[0]
+    score -0.5 * ((c - mu) / sigma)**2 in f64; the right neighbour only when strictly better; level 0 is the root table[..., 0].
+    mu_t, sg_t [R, K] and tab_lm [C, T] are f32 device tensors (ValueError for another dtype).  -> (scores f64, values f32) [N+1, R, K]."""
+    mu_t, sg_t, tab_lm = (ops._dev(t, torch.float32, name) for t, name in ((mu_t, "mu_t"), (sg_t, "sg_t"), (tab_lm, "tab_lm")))
+    (R, K), C = mu_t.shape, tab_lm.shape[0]
     z_cb = ops.transpose(mu_t) if C > 1 else mu_t.reshape(1, R * K)                  # [K, R] planes, or one plane of R*K
     B = z_cb.shape[1]
     left = torch.empty((C, N + 1, B), dtype=torch.float32, device=mu_t.device)
@@ -67,7 +67,7 @@ def quantize_rows_to_budget(mu, sigma, total_bits, *, table, N: int = 10):
     mu_t, sg_t, tab_lm, tab_sorted, C = _rows_args("quantize_rows_to_budget", mu, sigma, table, N)
     dev = mu_t.device
     R, K = mu_t.shape
-    budgets = torch.as_tensor(np.asarray(total_bits.cpu() if isinstance(total_bits, torch.Tensor) else total_bits)).reshape(-1)
+    budgets = (total_bits.detach().cpu() if isinstance(total_bits, torch.Tensor) else ops.host_tensor(total_bits)).reshape(-1)
     if budgets.dtype.is_floating_point or budgets.numel() not in (1, R):
         raise ValueError("total_bits must be an int or an int array with one entry per row")
     budgets = budgets.to(torch.int64)
@@ -96,15 +96,15 @@ def _rows_args(who, mu, sigma, table, N):
     if not torch.cuda.is_available():
         raise VBQError(f"no ROCm device visible: vbq_amd.{who} has no CPU implementation")
     dev = torch.device("cuda", torch.cuda.current_device())
-    mu_t = (torch.from_numpy(np.ascontiguousarray(mu)) if not isinstance(mu, torch.Tensor) else mu).to(dev, torch.float32)
-    sg_t = (torch.from_numpy(np.ascontiguousarray(sigma)) if not isinstance(sigma, torch.Tensor) else sigma).to(dev, torch.float32)
+    mu_t = (ops.host_tensor(mu) if not isinstance(mu, torch.Tensor) else mu.detach()).to(dev, torch.float32)
+    sg_t = (ops.host_tensor(sigma) if not isinstance(sigma, torch.Tensor) else sigma.detach()).to(dev, torch.float32)
     if mu_t.dim() != 2 or mu_t.shape != sg_t.shape:
         raise ValueError(f"mu and sigma must be [R, K] of one shape, got {tuple(mu_t.shape)} and {tuple(sg_t.shape)}")
     R, K = mu_t.shape
     if K < 1:
         raise ValueError("K must be at least 1")
     T = table_size(N)
-    shape = tuple(table.shape)
+    shape = tuple(int(d) for d in np.shape(table))
     if shape not in ((T,), (1, T), (K, T)):
         raise ValueError(f"table must be [{T}] or [{K}, {T}] for N={N}, got {shape}")
     C = K if shape == (K, T) else 1
